@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --config loop                           (the reference's redraw loop: controller + uniform + render per frame)
+    python bench.py --full [--dump-outputs DIR]             (every figure below; outputs of the last timed step)
 
 A "step" is one frame of the reference's render loop (clear + 2 sphere passes +
 mesh pass, /root/reference/src/lib.rs:1024-1184) through the C ABI of
@@ -15,7 +16,11 @@ to rank 0 (north_star), issued by the library itself (rwr_dist_gather_strips_rgb
 only carries the communicator id and the barriers, over gloo) — total work is fixed, so
 "scaling" is "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step and the run's
+configuration.  A plain run does nothing else: setup, W warm-up steps, K timed steps, the line.
+--dump-outputs DIR writes the frame of the last timed step as DIR/<name>.npy (float32, see dump_outputs).
+--full adds the measurements that take runs of their own and the checks (frames one at a time, the redraw
+loop's host cost, the render-only share and the gathered-frame check with a gather), and to the line:
   roofline     — dominant kernel against BOTH roofs: the binding one (VALU issue: the
                  kernel's SQ_ACTIVE_INST_VALU from the committed PMC pass x 4 cycles /
                  SIMDs / the shader clock measured live in this run) and HBM (algorithmic
@@ -41,6 +46,7 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 FP32_PEAK_TFLOPS = 157.3    # vector FP32 spec
 ALGO_BYTES_PER_PIXEL = 8    # 4 B RGBA8 + 4 B R32F depth, each pixel stored once
+DUMP_MAX_PIXELS = 1 << 21   # larger frames are dumped as a fixed, seeded sample of this many pixels (< 64 MB of .npy files)
 
 CONFIGS = {
     # BASELINE.json configs[1]: the configuration the metric is quoted on
@@ -106,6 +112,25 @@ def cpu_baseline(cfg, budget_s: float) -> dict:
     }
 
 
+def dump_outputs(out_dir: str, frame: dict) -> None:
+    """Writes what the caller of the timed path receives for its last frame — rwr_readback's RGBA8 colour (H, W, 4) and R32F
+    depth (H, W), framebuffer row 0 = the bottom image row; after a gather rank 0's gathered colour only — as
+    out_dir/<name>.npy in float32 (the bytes' values, exact).  A frame of more than DUMP_MAX_PIXELS pixels is written as the
+    same seeded sample of pixels in every run: (n, 4) and (n,) arrays in the order of pixel_index.npy (row-major indices)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    h, w = frame["color"].shape[:2]
+    idx = None
+    if h * w > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(0).choice(h * w, DUMP_MAX_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    for name, a in frame.items():
+        if idx is not None:
+            a = a.reshape((h * w,) + a.shape[2:])[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.astype(np.float32))
+
+
 def spawn_ranks(n: int, argv: list[str]) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks as FRESH child processes (this parent has made no
     GPU call and imports neither torch nor the library), one per GPU, with the environment torch.distributed.run would give
@@ -145,7 +170,11 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the CPU baseline and the measurements and checks outside the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget with --full (0 disables)")
     ap.add_argument("--frames-in-flight", type=int, default=None,
                     help="frame slots (targets, per-frame records, stream, gather buffers) the context alternates between; default 2 for the "
                          "reference frame, 3 with a gather and for the wavefront configurations")
@@ -163,6 +192,8 @@ def main() -> int:
         args.steps = cfg.get("steps", 4000)
     if args.warmup is None:
         args.warmup = cfg.get("warmup", 1000)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import __graft_entry__ as graft
@@ -253,7 +284,8 @@ def main() -> int:
             dist.barrier()
 
     # Shader clock and VALU issue cost under load, for the VALU roof (about 15 ms of arithmetic on every CU).  It runs
-    # here, before the warm-up steps, like the scene upload and the BVH build: setup, not a step.
+    # here, before the warm-up steps, like the scene upload and the BVH build: setup, not a step.  Plain runs keep it too
+    # (only --full reports it): it also brings the clock up, and without it a short run's steps (--warmup 5) take ~10 % longer.
     clk = ctx.measure_valu_clock(8)
 
     for _ in range(args.warmup):   # (wavefront configs: at least one frame per slot, or a slot's queues are allocated inside the timed region)
@@ -276,22 +308,27 @@ def main() -> int:
     barrier()
 
     # ---- everything below is OUTSIDE the timed region --------------------------------------------
+    # the frame of the last timed step, before any other frame is rendered
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"color": ctx.dist_readback()} if use_dist else ctx.readback())
     # (a) duration of the dominant kernel's own dispatches (start/stop timestamps of the dispatch, as a
     #     profiler reports them) while frames are pipelined exactly as in the timed region
-    n_probe = max(64, min(512, args.steps)) if primary_only else max(2, min(8, args.steps))
-    ctx.set_kernel_timing(4 if primary_only else 1)
-    probe_us = int(max(200.0, min(50000.0, 0.6 * n_probe * dev_ms * 1e3 / args.steps)))
-    if rank == 0:
-        ctx.clock_probe_start(probe_us)   # one idle wave on a side stream: the shader clock WHILE these frames render
-    for _ in range(n_probe):
-        step()
-    kernel_us, kernel_samples = ctx.kernel_timing_stats()
-    ctx.set_kernel_timing(0)
-    workload_mhz = ctx.clock_probe_read() if rank == 0 else None
+    kernel_us, kernel_samples, workload_mhz = None, 0, None
+    if args.full:
+        n_probe = max(64, min(512, args.steps)) if primary_only else max(2, min(8, args.steps))
+        ctx.set_kernel_timing(4 if primary_only else 1)
+        probe_us = int(max(200.0, min(50000.0, 0.6 * n_probe * dev_ms * 1e3 / args.steps)))
+        if rank == 0:
+            ctx.clock_probe_start(probe_us)   # one idle wave on a side stream: the shader clock WHILE these frames render
+        for _ in range(n_probe):
+            step()
+        kernel_us, kernel_samples = ctx.kernel_timing_stats()
+        ctx.set_kernel_timing(0)
+        workload_mhz = ctx.clock_probe_read() if rank == 0 else None
     # (b) the same frames one at a time (no overlap between frames): the latency of a frame and the
     #     duration of a lone kernel launch
     serial_ms_per_frame, serial_kernel_us = None, None
-    if fif > 1 and not args.skip_serial:
+    if args.full and fif > 1 and not args.skip_serial:
         ctx.set_frames_in_flight(1)
         n_serial = max(50, min(500, args.steps // 4)) if primary_only else max(3, min(20, args.steps))
         for _ in range(10 if primary_only else 1):
@@ -304,7 +341,7 @@ def main() -> int:
         serial_kernel_us, _ = ctx.kernel_timing_stats()
         ctx.set_kernel_timing(0)
     loop_stats = None
-    if loop_keys:
+    if args.full and loop_keys:
         # the host side of a frame alone (controller update + inverse uniform, no render), and what a frame costs the host
         # thread when it only enqueues (K frames issued back to back, the device drained before and after)
         ctx.set_frames_in_flight(fif)
@@ -328,16 +365,19 @@ def main() -> int:
                               "(update + uniform + rwr_render's launches); ms_per_step is the device-side frame rate with a new uniform every frame"}
     render_only_ms = None
     if use_dist:
-        # outside the timed region: the same share WITHOUT the gather, so that the line shows how the frame's time
-        # splits between rendering (which scales with the rank count) and the single collective (which does not)
-        n_ro = max(20, min(300, args.steps // 4))
-        ctx.timer_begin()
-        for _ in range(n_ro):
-            render()
-        render_only_ms = ctx.timer_end() / n_ro
-        t = torch.tensor([elapsed, dev_ms, render_only_ms], dtype=torch.float64)
+        if args.full:
+            # outside the timed region: the same share WITHOUT the gather, so that the line shows how the frame's time
+            # splits between rendering (which scales with the rank count) and the single collective (which does not)
+            n_ro = max(20, min(300, args.steps // 4))
+            ctx.timer_begin()
+            for _ in range(n_ro):
+                render()
+            render_only_ms = ctx.timer_end() / n_ro
+        t = torch.tensor([elapsed, dev_ms, render_only_ms or 0.0], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, dev_ms, render_only_ms = float(t[0]), float(t[1]), float(t[2])
+        elapsed, dev_ms = float(t[0]), float(t[1])
+        if args.full:
+            render_only_ms = float(t[2])
 
     # path segments actually traced: W*H*spp primary rays + the bounce rays the queue carried
     primary_rays, bounce_rays = ctx.last_render_stats()
@@ -349,13 +389,22 @@ def main() -> int:
     value = rays_per_frame / (elapsed / args.steps) / 1e6
 
     gathered_ok = None
-    if use_dist and rank == 0:
+    if args.full and use_dist and rank == 0:
         # the gathered frame must equal what a single GPU renders (checked once, outside the timed region)
         got = ctx.dist_readback()                        # waits for the last gather
         ctx.render(cam_inv, params)                      # the whole frame on this rank alone
         gathered_ok = bool((got == ctx.readback()["color"]).all())
     out = None
     if rank == 0:
+        out = {
+            "metric": "Mray/s", "value": round(value, 2), "unit": "Mray/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5), "ms_per_frame": round(ms_per_step, 5),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": cfg["label"], "width": w, "height": h, "spp": cfg["spp"], "bounces": cfg["bounces"],
+                       "faces": int(len(model["faces"])), "partition": f"{world} interleaved sets of 8-row strips + 1 RCCL gather" if world > 1 else "single GPU",
+                       "frames_in_flight": fif, "device": info["name"]},
+        }
+    if rank == 0 and args.full:
         # Average duration of one launch of the dominant kernel(s) over the timed region: HIP events on the launch
         # stream(s) around exactly K steps / K.  With two frames in flight the dispatches overlap, so a single
         # dispatch's own start-to-stop time (launch_us_pipelined, what a kernel trace lists) is LONGER than this;
@@ -456,15 +505,7 @@ def main() -> int:
         })
         if serial_kernel_us:
             roofline["launch_us_serial"] = round(serial_kernel_us, 3)
-        out = {
-            "metric": "Mray/s", "value": round(value, 2), "unit": "Mray/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5), "ms_per_frame": round(ms_per_step, 5),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": cfg["label"], "width": w, "height": h, "spp": cfg["spp"], "bounces": cfg["bounces"],
-                       "faces": int(len(model["faces"])), "partition": f"{world} interleaved sets of 8-row strips + 1 RCCL gather" if world > 1 else "single GPU",
-                       "frames_in_flight": fif, "device": info["name"]},
-            "roofline": roofline,
-        }
+        out["roofline"] = roofline
         if serial_ms_per_frame is not None:
             out["ms_per_frame_one_in_flight"] = round(serial_ms_per_frame, 5)   # frame latency: each frame waits for the previous
         if render_only_ms is not None:
@@ -479,10 +520,11 @@ def main() -> int:
     if use_dist:
         dist.destroy_process_group()
     if rank == 0:
-        if world == 1 and args.cpu_seconds > 0:
-            out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            if world == 1 and args.cpu_seconds > 0:
+                out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     return 0
 

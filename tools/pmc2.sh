@@ -15,6 +15,6 @@ G[lds]="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_IN
 G[thr]="SQ_THREAD_CYCLES_VALU SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_VALU SQ_INSTS_VALU"
 for g in "$@"; do
   echo "pass $g"
-  timeout -k 5 280 rocprofv3 --kernel-trace --pmc ${G[$g]} --output-format csv -d "$OUT/$g" -- python3 bench.py --cpu-seconds 0 $BENCH_ARGS > "$OUT/$g.log" 2>&1 || { echo "pass $g failed"; tail -5 "$OUT/$g.log"; }
+  timeout -k 5 280 rocprofv3 --kernel-trace --pmc ${G[$g]} --output-format csv -d "$OUT/$g" -- python3 bench.py --full --cpu-seconds 0 $BENCH_ARGS > "$OUT/$g.log" 2>&1 || { echo "pass $g failed"; tail -5 "$OUT/$g.log"; }
 done
 python3 tools/pmc_summary.py "$OUT"

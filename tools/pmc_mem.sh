@@ -4,7 +4,7 @@
 OUT=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
-run() { name=$1; shift; echo "pass $name"; timeout -k 5 120 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -- python3 bench.py --cpu-seconds 0 --steps 100 --warmup 10 $BENCH_ARGS > "$OUT/$name.log" 2>&1 || echo "pass $name failed (see $OUT/$name.log)"; }
+run() { name=$1; shift; echo "pass $name"; timeout -k 5 120 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -- python3 bench.py --full --cpu-seconds 0 --steps 100 --warmup 10 $BENCH_ARGS > "$OUT/$name.log" 2>&1 || echo "pass $name failed (see $OUT/$name.log)"; }
 BENCH_ARGS="$*"
 run ta1  TA_TA_BUSY_sum TA_TOTAL_WAVEFRONTS_sum
 run ta2  TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum

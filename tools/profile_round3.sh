@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 #        tools/profile_round3.sh bench      (the bench lines, which quote the counters just collected)
 O=gpurun_out/profile_r03; mkdir -p $O
 if [ "$1" = "bench" ]; then
-b() { name=$1; shift; python3 bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err; tail -c 400 $O/bench_$name.json | head -c 200; echo; }
+b() { name=$1; shift; python3 bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err; tail -c 400 $O/bench_$name.json | head -c 200; echo; }
 b default
 b driver_cmd --gpus 1 --steps 20 --warmup 5
 b cfg2b --cpu-seconds 0 --config cfg2b
@@ -22,7 +22,7 @@ b loop_fif1 --cpu-seconds 0 --config loop --frames-in-flight 1
 ls $O | head -50
 exit 0
 fi
-k() { name=$1; shift; timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$name -- python3 bench.py --cpu-seconds 0 "$@" > $O/trace_$name.log 2>&1; cp $O/trace_$name/*/*kernel_stats.csv $O/kernel_stats_$name.csv; }
+k() { name=$1; shift; timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$name -- python3 bench.py --full --cpu-seconds 0 "$@" > $O/trace_$name.log 2>&1; cp $O/trace_$name/*/*kernel_stats.csv $O/kernel_stats_$name.csv; }
 k cfg2 --steps 500 --warmup 100
 k cfg2_one_in_flight --steps 500 --warmup 100 --frames-in-flight 1
 k cfg4_one_in_flight --config cfg4 --steps 20 --warmup 4 --frames-in-flight 1

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r03_first; mkdir -p $O
 timeout -k 10 600 python3 -m pytest tests/test_gpu_dist.py -x -q -m gpu > $O/pytest_dist.log 2>&1; echo "dist rc=$?"; tail -5 $O/pytest_dist.log
-b() { name=$1; shift; timeout -k 10 300 python3 bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err; echo "$name rc=$?"; python3 - $O/bench_$name.json <<'P'
+b() { name=$1; shift; timeout -k 10 300 python3 bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err; echo "$name rc=$?"; python3 - $O/bench_$name.json <<'P'
 import json,sys
 try:
     d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
