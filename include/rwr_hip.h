@@ -144,12 +144,30 @@ enum {
                                        in all three shaders: triangle_list/compute.wgsl:166-174): origin =
                                        camera.origin + (5 x_nds, 5 y_nds, 0), direction (0, 0, -1).  Reference
                                        frame only (spp 1, no bounce, no RWR_FLAG_USE_BVH) */
-    RWR_FLAG_NORMAL_MAP  = 1u << 4  /* extension: mesh hits are shaded with the normal of their part's normal map
+    RWR_FLAG_NORMAL_MAP  = 1u << 4, /* extension: mesh hits are shaded with the normal of their part's normal map
                                        (rwr_scene_set_normal_map; res/cube.mtl:13 `map_Bump`, which the reference parses
                                        nowhere: resources.rs:187-213 loads the diffuse texture only and compute.wgsl:226-229
                                        shades with the flat face normal).  Without the flag — the default — the frame is
                                        the reference's.  Visibility never changes; bounce rays still leave along the
                                        geometric normal */
+    RWR_FLAG_ACCUMULATE  = 1u << 5  /* extension: progressive accumulation across frames (rwr_accum_reset, rwr_accum_samples).
+                                       The frame traces global samples [N, N + spp), N = the samples the context's accumulation
+                                       holds, and shows the mean of all N + spp: after frames of s1, s2, ... sK samples with an
+                                       unchanged key, every plane (color, depth, and with RWR_FLAG_AUX_OUTPUTS color_f32, obj_id,
+                                       hit_t) is, byte for byte, ONE frame without the flag of spp = s1 + ... + sK and the same
+                                       seed, whenever that sum is >= 2 (depth / id / t report global sample 0 on every frame; spp
+                                       may change from frame to frame).  Always the integrator, samples always jittered: a first
+                                       accumulated frame of spp 1 is a jittered one-sample estimate, not the reference frame.
+                                       KEY — the accumulation goes on only while all of these stay as they were: the camera
+                                       uniform's 144 bytes, the screen size, the rows (rwr_render_rows / rwr_render_strips
+                                       arguments), max_bounces, seed, flags but this bit, frames in flight, and the scene (any
+                                       rwr_scene_* call that changes it, uploads included).  Any change starts over at N = 0, as
+                                       do rwr_accum_reset and any frame rendered without the flag.  CAP: at most 2^24 samples
+                                       per pixel (environment RWR_ACCUM_MAX_SAMPLES, read by rwr_ctx_create, lowers it); a
+                                       frame that would go past it traces nothing and shows the image held; a first frame of
+                                       more samples than the cap is RWR_ERR_INVALID_ARGUMENT.  With RWR_FLAG_ORTHO_RAYS,
+                                       RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED.  Frames in flight and
+                                       row bands / strips keep the contract (the sums are keyed by global pixel) */
 };
 
 #define RWR_MAX_SPHERES 8
@@ -358,8 +376,15 @@ RWR_API int rwr_ctx_set_kernel_timing(rwr_context *ctx, uint32_t every_n);
 RWR_API int rwr_kernel_timing_stats(rwr_context *ctx, double *mean_us, uint32_t *count);
 
 /* Segments (rays) traced by the last render call, for Mray/s accounting:
- * W*rows*spp primary + bounce rays actually emitted. */
+ * W*rows*spp primary + bounce rays actually emitted (an accumulating frame: its own spp; 0 past the cap). */
 RWR_API int rwr_last_render_stats(rwr_context *ctx, uint64_t *primary_rays, uint64_t *bounce_rays);
+
+/* Progressive accumulation (RWR_FLAG_ACCUMULATE).  One context holds one accumulation.
+ * rwr_accum_reset: the next accumulating frame starts over at N = 0 (host-side only, nothing waits).
+ * rwr_accum_samples: samples per pixel held by the image of the frame rendered last — N + spp, or the N it showed past the
+ * cap — and 0 when that frame did not accumulate.  Host-side, does not wait.  NULL ctx or samples: RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_accum_reset(rwr_context *ctx);
+RWR_API int rwr_accum_samples(rwr_context *ctx, uint64_t *samples);
 
 /* Self-test of the kernels' short exact forms ("Numerics"): the frame kernel replaces the
  * shader's  ((1/d) - (1/kNear)) / ((1/kFar) - (1/kNear))  (compute.wgsl:78-80) and the three divisions

@@ -43,6 +43,7 @@ FLAG_AUX_OUTPUTS, FLAG_NO_CULL, FLAG_USE_BVH = 1, 2, 4
 # internal debug flags (csrc/rwr_internal.h, not part of include/rwr_hip.h)
 FLAG_ORTHO_RAYS = 1 << 3
 FLAG_NORMAL_MAP = 1 << 4
+FLAG_ACCUMULATE = 1 << 5
 FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
 KEY_FORWARD, KEY_BACKWARD, KEY_LEFT, KEY_RIGHT, KEY_UP, KEY_DOWN = 1, 2, 4, 8, 16, 32
 OK, ERR_INVALID_ARGUMENT, ERR_HIP, ERR_NOT_READY, ERR_IO, ERR_PARSE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
@@ -104,6 +105,7 @@ def lib() -> C.CDLL:
         "rwr_resize": [vp, vp], "rwr_render": [vp, vp, vp], "rwr_render_rows": [vp, vp, vp, u32, u32], "rwr_render_strips": [vp, vp, vp, u32, u32],
         "rwr_synchronize": [vp], "rwr_readback": [vp, vp, vp, vp, vp, vp], "rwr_get_device_targets": [vp, vp, vp],
         "rwr_timer_begin": [vp], "rwr_timer_end": [vp, vp], "rwr_timer_stop": [vp], "rwr_timer_elapsed": [vp, vp], "rwr_last_render_stats": [vp, vp, vp],
+        "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
         "rwr_load_model_compute": [C.c_char_p, C.c_char_p, vp], "rwr_model_free": [vp],
         "rwr_model_info": [vp, vp, vp, vp, vp, vp, vp], "rwr_scene_upload_model": [vp, vp],
@@ -570,6 +572,16 @@ class Context:
         a, b = C.c_uint64(), C.c_uint64()
         _check(lib().rwr_last_render_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def accum_reset(self):
+        """The next FLAG_ACCUMULATE frame starts a new accumulation."""
+        _check(lib().rwr_accum_reset(self._h))
+
+    def accum_samples(self) -> int:
+        """Samples per pixel held by the image of the frame rendered last (0: it did not accumulate)."""
+        n = C.c_uint64()
+        _check(lib().rwr_accum_samples(self._h, C.byref(n)))
+        return n.value
 
 
 def csrc_tree() -> str:

@@ -196,6 +196,27 @@ struct rwr_context {
     } wf_state[kMaxFramesInFlight];
     uint32_t last_spp = 0;
     bool last_had_bounce = false;
+    // Progressive accumulation (RWR_FLAG_ACCUMULATE): ONE accumulation per context.  Its sums and the first frame's sample-0 planes
+    // are context-wide (global pixel index, whatever the slot), allocated by the first accumulating frame; `key` is everything a
+    // frame must share with the one before for the accumulation to go on (accum_key), empty when the next frame starts over.
+    struct Accum {
+        DeviceBuffer<unsigned long long> d_hist;   // 4 planes of W*H, 2^-26 fixed point (AccumBuffers::hist)
+        DeviceBuffer<float> d_depth;
+        DeviceBuffer<int32_t> d_obj_id;
+        DeviceBuffer<float> d_hit_t;
+        std::vector<unsigned char> key;
+        uint64_t samples = 0;              // samples per pixel the history holds
+        hipEvent_t done = nullptr;         // recorded after every accumulating resolve: the next one waits for it (frames in flight)
+        bool done_recorded = false;
+        void release()
+        {
+            d_hist.release(); d_depth.release(); d_obj_id.release(); d_hit_t.release();
+            key.clear(); samples = 0;
+        }
+    } accum;
+    uint64_t accum_max = 1u << 24;         // samples per pixel at most (f32 holds the divisor exactly); RWR_ACCUM_MAX_SAMPLES lowers it
+    uint64_t last_accum_samples = 0;       // rwr_accum_samples: of the frame rendered last, 0 when it did not accumulate
+    uint64_t scene_generation = 0;         // bumped by every change of the scene (an accumulation does not survive one)
     // one decoded texture per scene part (texels decoded to linear f32 at upload, Rgba8UnormSrgb semantics)
     std::vector<DeviceBuffer<float4>> d_texs;
     DeviceBuffer<uint32_t> d_face_mat;      // per face: index of its part's material
@@ -566,6 +587,8 @@ int rwr_ctx_create(int device_id, rwr_context **out_ctx)
     if (const char *e7 = std::getenv("RWR_WF_PACKET_FILL")) ctx->wf_packet_fill = (float)std::atof(e7);
     if (const char *e11 = std::getenv("RWR_BIN_CAPACITY")) ctx->bin_min_capacity = (uint32_t)std::strtoul(e11, nullptr, 10);
     if (const char *e3 = std::getenv("RWR_BIN_MIN_FACES")) ctx->bin_min_faces = (uint32_t)std::strtoul(e3, nullptr, 10);
+    if (const char *e21 = std::getenv("RWR_ACCUM_MAX_SAMPLES"))
+        ctx->accum_max = std::min<uint64_t>(1u << 24, std::max<uint64_t>(1u, std::strtoull(e21, nullptr, 10)));
     *out_ctx = ctx;
     return RWR_OK;
 }
@@ -587,6 +610,8 @@ void rwr_ctx_destroy(rwr_context *ctx)
     for (auto &t : ctx->d_nmaps) t.release();
     ctx->d_bvh_nodes.release(); ctx->d_bvh_leaf_faces.release();
     for (auto &w : ctx->wf_state) w.release();
+    ctx->accum.release();
+    if (ctx->accum.done) (void)hipEventDestroy(ctx->accum.done);
     if (ctx->h_wf_live) { (void)hipHostFree(ctx->h_wf_live); ctx->h_wf_live = nullptr; } for (auto &t : ctx->d_texs) t.release();
     ctx->d_face_mat.release(); ctx->d_materials.release();
     for (FrameSlot &sl : ctx->slots) {
@@ -632,6 +657,7 @@ void *rwr_ctx_get_stream(rwr_context *ctx) { return ctx ? reinterpret_cast<void 
 int rwr_scene_clear(rwr_context *ctx)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    ctx->scene_generation++;
     DeviceGuard g(ctx->device);
     RWR_HIP_CHECK(sync_all(ctx));
     ctx->st_verts.clear(); ctx->st_faces.clear(); ctx->st_face_mat.clear(); ctx->st_materials.clear();
@@ -649,6 +675,7 @@ int rwr_scene_add_mesh(rwr_context *ctx, const rwr_model_vertex_small *verts, ui
                        const uint8_t *rgba8_srgb, uint32_t tex_w, uint32_t tex_h)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    ctx->scene_generation++;
     if (n_faces == 0) return RWR_OK;  // nothing to add
     if (!verts || !faces || !material || !rgba8_srgb)
         return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL mesh array with n_faces = %u", n_faces);
@@ -706,6 +733,7 @@ int rwr_scene_add_mesh(rwr_context *ctx, const rwr_model_vertex_small *verts, ui
 int rwr_scene_commit(rwr_context *ctx)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    ctx->scene_generation++;
     DeviceGuard g(ctx->device);
     RWR_HIP_CHECK(sync_all(ctx));
     ctx->n_faces = (uint32_t)ctx->st_faces.size();
@@ -743,6 +771,7 @@ int rwr_scene_part_count(rwr_context *ctx, uint32_t *n_parts)
 int rwr_scene_set_normal_map(rwr_context *ctx, uint32_t part, const uint8_t *rgba8_linear, uint32_t tex_w, uint32_t tex_h)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    ctx->scene_generation++;
     if (part >= ctx->st_materials.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->st_materials.size());
     if (rgba8_linear && (tex_w == 0 || tex_h == 0)) return set_error(RWR_ERR_INVALID_ARGUMENT, "empty normal map");
     if (tex_w > kMaxTextureDim || tex_h > kMaxTextureDim)
@@ -782,6 +811,7 @@ int rwr_scene_upload_mesh(rwr_context *ctx, const rwr_model_vertex_small *verts,
 int rwr_scene_set_spheres(rwr_context *ctx, const rwr_sphere_buffer_data *spheres, uint32_t n)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    ctx->scene_generation++;
     if (n > RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "at most %d spheres", RWR_MAX_SPHERES);
     if (n && !spheres) return set_error(RWR_ERR_INVALID_ARGUMENT, "spheres is NULL");
     for (uint32_t i = 0; i < n; i++) ctx->spheres[i] = spheres[i];
@@ -792,6 +822,7 @@ int rwr_scene_set_spheres(rwr_context *ctx, const rwr_sphere_buffer_data *sphere
 int rwr_scene_set_triangles(rwr_context *ctx, const rwr_triangle_buffer_data *triangles, uint32_t n)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    ctx->scene_generation++;
     if (n > RWR_MAX_TRIANGLES) return set_error(RWR_ERR_INVALID_ARGUMENT, "at most %d single triangles", RWR_MAX_TRIANGLES);
     if (n && !triangles) return set_error(RWR_ERR_INVALID_ARGUMENT, "triangles is NULL with n = %u", n);
     for (uint32_t i = 0; i < n; i++) ctx->triangles[i] = triangles[i];   // passed by value with every launch
@@ -802,6 +833,7 @@ int rwr_scene_set_triangles(rwr_context *ctx, const rwr_triangle_buffer_data *tr
 int rwr_scene_set_instances(rwr_context *ctx, const rwr_instance_raw *instances, uint32_t n)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    ctx->scene_generation++;
     if (n && !instances) return set_error(RWR_ERR_INVALID_ARGUMENT, "instances is NULL");
     if ((uint64_t)ctx->n_faces * (n ? n : 1u) > 0x7fffffffull) return set_error(RWR_ERR_INVALID_ARGUMENT, "too many faces");
     DeviceGuard g(ctx->device);
@@ -827,6 +859,7 @@ int rwr_resize(rwr_context *ctx, const rwr_screen *screen)
     DeviceGuard g(ctx->device);
     RWR_HIP_CHECK(sync_all(ctx));
     ctx->screen = *screen;
+    ctx->accum.release();   // (the key holds the screen size too)
     for (uint32_t i = 0; i < ctx->n_slots; i++) {
         RWR_HIP_CHECK(ensure_slot_targets(ctx, i));
         ctx->slots[i].aux_valid = false;
@@ -834,6 +867,20 @@ int rwr_resize(rwr_context *ctx, const rwr_screen *screen)
     for (rwr_context::GatherSet &gs : ctx->gather) gs.valid = false;   // a frame gathered at the old size is gone
     RWR_HIP_CHECK(ensure_frame_buffers(ctx));
     return RWR_OK;
+}
+
+// What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
+// camera uniform's bytes, the screen, the rows, bounces, seed, flags but the ACCUMULATE bit, frames in flight and the scene.
+static std::vector<unsigned char> accum_key_of(const rwr_context *ctx, const rwr_camera_inv_uniform &cam, const rwr_render_params &rp,
+                                               uint32_t row_begin, uint32_t row_end, uint32_t row_pitch)
+{
+    const uint32_t words[9] = {ctx->screen.width, ctx->screen.height, row_begin, row_end, row_pitch, rp.max_bounces, rp.seed,
+                               rp.flags & ~(uint32_t)RWR_FLAG_ACCUMULATE, ctx->n_slots};
+    std::vector<unsigned char> key(sizeof cam + sizeof words + sizeof ctx->scene_generation);
+    std::memcpy(key.data(), &cam, sizeof cam);
+    std::memcpy(key.data() + sizeof cam, words, sizeof words);
+    std::memcpy(key.data() + sizeof cam + sizeof words, &ctx->scene_generation, sizeof ctx->scene_generation);
+    return key;
 }
 
 // One frame — rows [row_begin, row_end) in strips of 8 rows, strip k starting at row_begin + k * row_pitch (row_pitch 8: the
@@ -854,11 +901,36 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
     if ((rp.flags & RWR_FLAG_USE_BVH) && (rp.spp != 1 || rp.max_bounces != 0))
         return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_USE_BVH applies to the reference frame (spp 1, no bounce); bounce rays always use the BVH");
     if (rp.spp > 4096) return set_error(RWR_ERR_INVALID_ARGUMENT, "spp must be <= 4096");
-    const bool wavefront = rp.spp != 1 || rp.max_bounces != 0;
+    const bool accumulate = (rp.flags & RWR_FLAG_ACCUMULATE) != 0;
+    if (accumulate && ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0))
+        return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_ACCUMULATE: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
+    // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1)
+    const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate;
     // the reference's dormant parts (single-triangle passes, orthographic rays) have their own plain kernel
     const bool dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;
     if (dormant && (wavefront || (rp.flags & RWR_FLAG_USE_BVH)))
         return set_error(RWR_ERR_UNSUPPORTED, "single-triangle passes and RWR_FLAG_ORTHO_RAYS apply to the reference frame (spp 1, no bounce, no RWR_FLAG_USE_BVH)");
+
+    // Progressive accumulation: does this frame go on with the context's accumulation (same key, room below the cap), start a
+    // new one, or only show it (past the cap)?  A frame without the flag ends it.  Committed once the frame is enqueued.
+    std::vector<unsigned char> accum_key;
+    AccumMode accum_mode = AccumMode::kFirst;
+    uint64_t accum_before = 0;   // samples the history holds before this frame
+    if (accumulate) {
+        accum_key = accum_key_of(ctx, *camera, rp, row_begin, row_end, row_pitch);
+        if (accum_key == ctx->accum.key && ctx->accum.samples != 0) {
+            accum_before = ctx->accum.samples;
+            accum_mode = accum_before + rp.spp > ctx->accum_max ? AccumMode::kShow : AccumMode::kAdd;
+        } else if (rp.spp > ctx->accum_max) {
+            return set_error(RWR_ERR_INVALID_ARGUMENT, "spp %u is more than the %llu samples an accumulation may hold (RWR_ACCUM_MAX_SAMPLES)",
+                             rp.spp, (unsigned long long)ctx->accum_max);
+        }
+    } else {
+        ctx->accum.key.clear();
+        ctx->accum.samples = 0;
+        ctx->last_accum_samples = 0;
+    }
+    const uint32_t trace_spp = accum_mode == AccumMode::kShow ? 0u : rp.spp;   // samples this frame traces
 
     DeviceGuard g(ctx->device);
     const size_t n = (size_t)ctx->screen.width * ctx->screen.height;
@@ -932,6 +1004,7 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
         fp.mesh_px[k] = (int32_t)std::fmax(-1e9, std::fmin(1e9, v));   // +-inf -> +-1e9
     }
     fp.spp = rp.spp;
+    fp.jitter_spp = accumulate ? std::max(rp.spp, 2u) : rp.spp;
     fp.seed = rp.seed;
     fp.bounces = rp.max_bounces;
     // Per-frame records and tables (k_frame_setup): they depend on the camera, so they are rebuilt
@@ -947,7 +1020,7 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
     so.ftris = sl.d_ftris.ptr; so.tnum = sl.d_tnum.ptr;
     so.ray_colp = sl.d_ray_colp.ptr; so.ray_row = sl.d_ray_row.ptr;
     fp.ray_colp = so.ray_colp; fp.ray_row = so.ray_row; fp.tnum = so.tnum;
-    if (rp.spp != 1 || rp.max_bounces != 0) {
+    if (wavefront) {
         // the wavefront integrator's per-tile ray counts and live-tile count start every frame from zero: k_frame_setup zeroes them
         rwr_context::WfState &W0 = ctx->wf_state[ctx->n_slots > 1u ? ctx->cur : 0u];
         fp.row_begin = row_begin; fp.row_end = row_end; fp.row_pitch = row_pitch;
@@ -958,7 +1031,7 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
         so.zero_b = W0.d_tiles.ptr + 2u * n_tiles0; so.n_zero_b = 1u;   // live_count (below)
     }
     // A/B (RWR_FRAME_GRAPH=1): the plain reference frame — records + frame kernel, nothing else on the stream — as one graph launch
-    const bool as_graph = ctx->frame_graph_mode != 0u && !(rp.spp != 1 || rp.max_bounces != 0) && !aux && ctx->n_triangles == 0 &&
+    const bool as_graph = ctx->frame_graph_mode != 0u && !wavefront && !aux && ctx->n_triangles == 0 &&
                           !(rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH | RWR_FLAG_NO_CULL | RWR_FLAG_ONE_PIXEL_PER_LANE)) &&
                           !ctx->force_one_pixel && ctx->n_tris != 0 && ctx->n_tris <= ctx->bin_min_faces && !ctx->timing_every;
     if (as_graph) {
@@ -1004,7 +1077,7 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
     // launches.  RWR_FUSED_SETUP=1 forces the fused form wherever it is possible (tests), 0 switches it off.
     const uint32_t render_groups = ((ctx->screen.width + 63u) / 64u) * ((row_end - row_begin + row_pitch - 1u) / std::max(1u, row_pitch));
     const bool fused_pays = ctx->fused_setup_force || (ctx->n_slots > 1u && render_groups <= 1200u);
-    const bool fused = ctx->fused_setup && fused_pays && !(rp.spp != 1 || rp.max_bounces != 0) && !aux && ctx->n_triangles == 0 &&
+    const bool fused = ctx->fused_setup && fused_pays && !wavefront && !aux && ctx->n_triangles == 0 &&
                        !(rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH | RWR_FLAG_NO_CULL | RWR_FLAG_ONE_PIXEL_PER_LANE | RWR_FLAG_NORMAL_MAP)) &&
                        !ctx->force_one_pixel && ctx->n_tris != 0 && ctx->n_tris <= ctx->bin_min_faces && !ctx->timing_every &&
                        row_end > row_begin;
@@ -1212,11 +1285,13 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
             for (size_t q = 1; q < n_queues; q++) RWR_HIP_CHECK(hipStreamWaitEvent(W.streams[q], W.fork, 0));
         }
         const uint32_t *last_counters = nullptr;
-        for (uint32_t s0 = 0, g = 0; s0 < rp.spp; s0 += group, g++) {
+        // (global sample indices: an accumulating frame traces [accum_before, accum_before + spp), keyed like one frame of them all)
+        for (uint32_t s0 = 0, g = 0; s0 < trace_spp; s0 += group, g++) {
             const uint32_t cnt = std::min(group, rp.spp - s0);
             const size_t q = g % n_queues;
             hipStream_t gs = q ? W.streams[q] : stream;
-            RWR_HIP_CHECK(launch_wf_primary(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg, wfq[q], s0, cnt, z_split));
+            RWR_HIP_CHECK(launch_wf_primary(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg, wfq[q],
+                                            (uint32_t)accum_before + s0, cnt, z_split));
             if (rp.max_bounces) {
                 RWR_HIP_CHECK(launch_wf_bounce(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh, tex0, wfq[q], n_tiles, cnt,
                                                (uint32_t)std::fmax(1.0f, std::ceil(ctx->wf_packet_fill * (float)(cnt * kWfTilePixels))),
@@ -1231,7 +1306,28 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
         // (the resolve also hands the last group's live pool counts to the host: a store to pinned memory, no copy command.  The
         // same store at the top of the per-lane trace kernel made THAT kernel twice as slow, 453 -> 840 us at configs[3], with the
         // pointer null and the instruction mix unchanged; here it costs nothing measurable.)
-        RWR_HIP_CHECK(launch_wf_resolve(stream, fp, tg, wfq[0], last_counters, last_counters ? ctx->h_wf_live : nullptr));
+        if (!accumulate) {
+            RWR_HIP_CHECK(launch_wf_resolve(stream, fp, tg, wfq[0], last_counters, last_counters ? ctx->h_wf_live : nullptr));
+        } else {
+            // The history is the context's, not the slot's: frames in flight trace side by side, their resolves run in frame order
+            rwr_context::Accum &A = ctx->accum;
+            if (accum_mode == AccumMode::kFirst) {
+                RWR_HIP_CHECK(A.d_hist.ensure(4u * n));
+                RWR_HIP_CHECK(A.d_depth.ensure(n));
+                if (aux) { RWR_HIP_CHECK(A.d_obj_id.ensure(n)); RWR_HIP_CHECK(A.d_hit_t.ensure(n)); }
+            }
+            if (!A.done) RWR_HIP_CHECK(hipEventCreateWithFlags(&A.done, hipEventDisableTiming));
+            if (A.done_recorded) RWR_HIP_CHECK(hipStreamWaitEvent(stream, A.done, 0));
+            const AccumBuffers ab{A.d_hist.ptr, A.d_depth.ptr, aux ? A.d_obj_id.ptr : nullptr, aux ? A.d_hit_t.ptr : nullptr};
+            const uint64_t total = accum_mode == AccumMode::kShow ? accum_before : accum_before + rp.spp;
+            RWR_HIP_CHECK(launch_wf_resolve_accum(stream, fp, tg, wfq[0], ab, accum_mode, (uint32_t)total, last_counters,
+                                                  last_counters ? ctx->h_wf_live : nullptr));
+            RWR_HIP_CHECK(hipEventRecord(A.done, stream));
+            A.done_recorded = true;
+            A.key.swap(accum_key);
+            A.samples = total;
+            ctx->last_accum_samples = total;
+        }
         W.fix_clean = true;   // (the resolve zeroes what it reads; rows outside the band were never touched)
         ctx->last_spp = rp.spp;
         ctx->last_segments = n_tiles;
@@ -1245,7 +1341,7 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
     sl.aux_valid = aux;
     uint64_t rows_rendered = 0;   // the strips' rows inside [row_begin, row_end)
     for (uint32_t y0 = row_begin; y0 < row_end; y0 += row_pitch) rows_rendered += std::min(kStripRows, row_end - y0);
-    ctx->last_primary = (uint64_t)ctx->screen.width * rows_rendered * rp.spp;
+    ctx->last_primary = (uint64_t)ctx->screen.width * rows_rendered * trace_spp;
     ctx->last_bounce = 0;  // filled in lazily by rwr_last_render_stats from the pass counters
     return RWR_OK;
 }
@@ -1537,6 +1633,21 @@ int rwr_last_render_stats(rwr_context *ctx, uint64_t *primary_rays, uint64_t *bo
     }
     if (primary_rays) *primary_rays = ctx->last_primary;
     if (bounce_rays) *bounce_rays = ctx->last_bounce;
+    return RWR_OK;
+}
+
+int rwr_accum_reset(rwr_context *ctx)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    ctx->accum.key.clear();
+    ctx->accum.samples = 0;
+    return RWR_OK;
+}
+
+int rwr_accum_samples(rwr_context *ctx, uint64_t *samples)
+{
+    if (!ctx || !samples) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *samples = ctx->last_accum_samples;
     return RWR_OK;
 }
 

@@ -137,6 +137,72 @@ hipError_t launch_wf_resolve(hipStream_t s, const FrameParams &fp, const Targets
     return hipGetLastError();
 }
 
+// The resolve of an accumulating frame (RWR_FLAG_ACCUMULATE): the frame traced global samples [N, N + spp) into its slot's sums;
+// they are added to the context's history (kFirst: stored — no memset) and left zeroed, and the pixel shows history / total in the
+// f32 arithmetic of k_wf_resolve — with integer sums, the bytes of ONE frame of `total` samples.  Sample 0's planes (depth; id and
+// t with AUX) were written by the first frame alone: kFirst keeps a copy, later frames write it back into their own slot's targets.
+// Same workgroup shape as k_wf_resolve.  Frames in other slots may still be tracing: only these resolves are ordered (context.cpp).
+template <bool AUX, AccumMode MODE>
+__global__ void __launch_bounds__(256)
+k_wf_resolve_accum(const FrameParams p, const Targets tg, WfBuffers wf, const AccumBuffers ac, float total,
+                   const uint32_t *__restrict__ live_counters, uint32_t *__restrict__ host_live)
+{
+    if (host_live && (blockIdx.x | blockIdx.y) == 0u && threadIdx.x < 2u) host_live[threadIdx.x] = live_counters[threadIdx.x];
+    const uint32_t strip = blockIdx.y >> 1, in_strip = (blockIdx.y & 1u) * 4u + (threadIdx.x >> 6);
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = p.row_begin + strip * p.row_pitch + in_strip;
+    if (x >= p.width || y >= p.row_end) return;
+    const uint32_t pixel = y * p.width + x;
+    const size_t plane = (size_t)p.width * p.height;
+    // this frame's sums: none past the cap, none in a piece of a tile nothing can be seen through (never touched: zero)
+    bool live = MODE != AccumMode::kShow;
+    if (live && wf.tile_live) {
+        const uint32_t bits = wf.tile_live[strip * wf.tiles_x + blockIdx.x];
+        live = (bits >> ((blockIdx.y & 1u) * 2u + ((threadIdx.x >> 5) & 1u))) & 1u;
+    }
+    // (a pixel this frame added nothing to — a background pixel — leaves its slot sums and its history as they are: half the bytes)
+    unsigned long long s[4] = {0ull, 0ull, 0ull, 0ull};
+    if (live)
+        for (uint32_t c = 0; c < 4u; c++) s[c] = wf.fix[c * plane + pixel];
+    const bool added = (s[0] | s[1] | s[2] | s[3]) != 0ull;
+    if (added)
+        for (uint32_t c = 0; c < 4u; c++) wf.fix[c * plane + pixel] = 0ull;
+    if (MODE == AccumMode::kFirst) {
+        for (uint32_t c = 0; c < 4u; c++) ac.hist[c * plane + pixel] = s[c];
+    } else {
+        for (uint32_t c = 0; c < 4u; c++) s[c] += ac.hist[c * plane + pixel];
+        if (MODE == AccumMode::kAdd && added)
+            for (uint32_t c = 0; c < 4u; c++) ac.hist[c * plane + pixel] = s[c];
+    }
+    const float unit = 1.0f / kWfFixedScale, fs = total;
+    const float r = (float)s[0] * unit / fs, g = (float)s[1] * unit / fs, b = (float)s[2] * unit / fs, a = (float)s[3] * unit / fs;
+    reinterpret_cast<uint32_t *>(tg.color)[pixel] = pack_rgba8(r, g, b, a);
+    if (AUX) reinterpret_cast<float4 *>(tg.color_f32)[pixel] = make_float4(r, g, b, a);
+    if (MODE == AccumMode::kFirst) {
+        ac.depth[pixel] = tg.depth[pixel];
+        if (AUX) { ac.obj_id[pixel] = tg.obj_id[pixel]; ac.hit_t[pixel] = tg.hit_t[pixel]; }
+    } else {
+        tg.depth[pixel] = ac.depth[pixel];
+        if (AUX) { tg.obj_id[pixel] = ac.obj_id[pixel]; tg.hit_t[pixel] = ac.hit_t[pixel]; }
+    }
+}
+
+hipError_t launch_wf_resolve_accum(hipStream_t s, const FrameParams &fp, const Targets &tg, const WfBuffers &wf, const AccumBuffers &ac,
+                                   AccumMode mode, uint32_t total_samples, const uint32_t *live_counters, uint32_t *host_live)
+{
+    if (fp.row_end <= fp.row_begin || fp.width == 0) return hipSuccess;
+    const dim3 grid((fp.width + 63u) / 64u, 2u * band_strips(fp));
+    const float total = (float)total_samples;   // exact: at most 2^24 (RWR_ACCUM_MAX_SAMPLES)
+#define RWR_ACCUM_LAUNCH(A, M) hipLaunchKernelGGL((k_wf_resolve_accum<A, M>), grid, dim3(256), 0, s, fp, tg, wf, ac, total, live_counters, host_live)
+    const bool aux = (fp.flags & RWR_FLAG_AUX_OUTPUTS) != 0;
+    switch (mode) {
+    case AccumMode::kFirst: if (aux) RWR_ACCUM_LAUNCH(true, AccumMode::kFirst); else RWR_ACCUM_LAUNCH(false, AccumMode::kFirst); break;
+    case AccumMode::kAdd: if (aux) RWR_ACCUM_LAUNCH(true, AccumMode::kAdd); else RWR_ACCUM_LAUNCH(false, AccumMode::kAdd); break;
+    case AccumMode::kShow: if (aux) RWR_ACCUM_LAUNCH(true, AccumMode::kShow); else RWR_ACCUM_LAUNCH(false, AccumMode::kShow); break;
+    }
+#undef RWR_ACCUM_LAUNCH
+    return hipGetLastError();
+}
+
 hipError_t preload_kernels_wavefront()
 {
     hipFuncAttributes attr;

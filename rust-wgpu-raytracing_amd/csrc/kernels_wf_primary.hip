@@ -233,11 +233,11 @@ k_wf_primary(const WfPrimaryArgs a)
 
     for (uint32_t sidx = z; sidx < (empty_tile ? 0u : sample_count); sidx += z_split) {
         const uint32_t sample = sample_begin + sidx;
-        // -- the sample's ray: pixel centre at spp = 1, else two uniforms of the counter-based RNG ---------------
-        kernarg<WfPrimaryArgs> *const qr = wf_args_again(ka);   // this phase's kernel arguments: seed, spp, the camera
+        // -- the sample's ray: pixel centre at spp = 1, else (and in every accumulating frame) two uniforms of the counter-based RNG
+        kernarg<WfPrimaryArgs> *const qr = wf_args_again(ka);   // this phase's kernel arguments: seed, jitter rule, the camera
         const u2 base = u2{rng_base(pix0, sample, qr->p.seed), rng_base(pix0 + 1u, sample, qr->p.seed)};
         f2 jx = splat(0.5f), jy = splat(0.5f);
-        if (qr->p.spp > 1u) {
+        if (qr->p.jitter_spp > 1u) {
             jx = f2{rng_dim(base.x, 0u), rng_dim(base.y, 0u)};
             jy = f2{rng_dim(base.x, 1u), rng_dim(base.y, 1u)};
         }

@@ -150,8 +150,9 @@ struct FrameParams {
     float tex_wmax, tex_hmax;     // (float)(tex_w - 1), (float)(tex_h - 1) of material 0
     uint32_t flags;
     uint32_t wave_cull_min;   // run the per-wave (8x8 tile) cull only for block lists longer than this
-    // wavefront integrator (extension): sample being traced, samples per pixel, RNG seed, bounces
-    uint32_t sample, spp, seed, bounces;
+    // wavefront integrator (extension): samples per pixel of this frame; the count the jitter rule looks at (jittered when > 1:
+    // the frame's spp, at least 2 in an accumulating frame, RWR_FLAG_ACCUMULATE); RNG seed; bounces
+    uint32_t spp, jitter_spp, seed, bounces;
     rwr_sphere_buffer_data spheres[RWR_MAX_SPHERES];
     // conservative pixel-space bounds {x0, y0, x1, y1} of each sphere's silhouette
     // (host-computed per frame, context.cpp); a tile outside them skips the sphere
@@ -271,6 +272,21 @@ hipError_t launch_primary_bvh(hipStream_t s, const FrameParams &fp, const TriRec
 // live_counters / host_live: the last launch group's counters (kernels_wf_bounce.hip) and the pinned words the host reads them from
 hipError_t launch_wf_resolve(hipStream_t s, const FrameParams &fp, const Targets &tg, const WfBuffers &wf, const uint32_t *live_counters = nullptr,
                              uint32_t *host_live = nullptr);
+// Progressive accumulation (RWR_FLAG_ACCUMULATE): the context's sums over every frame of the accumulation so far, 4 planes of
+// W*H u64 in the 2^-26 units of WfBuffers::fix (global pixel index), and the first frame's sample-0 planes (aux: id and t too).
+struct AccumBuffers {
+    unsigned long long *hist;
+    float *depth;
+    int32_t *obj_id;
+    float *hit_t;
+};
+// How a frame's resolve treats the history: the first frame of an accumulation stores its sums and copies its sample-0 planes
+// out; a later frame adds its sums and copies the planes back in; a frame past the cap traced nothing and only shows the history.
+enum class AccumMode { kFirst, kAdd, kShow };
+// k_wf_resolve for an accumulating frame: the slot's sums (left zeroed) go into the history, colour = history / total_samples
+hipError_t launch_wf_resolve_accum(hipStream_t s, const FrameParams &fp, const Targets &tg, const WfBuffers &wf, const AccumBuffers &ac,
+                                   AccumMode mode, uint32_t total_samples, const uint32_t *live_counters = nullptr,
+                                   uint32_t *host_live = nullptr);
 
 // per-frame records and tables (kernels_primary.hip): FrameTri + tnum per face, ray tables per column pair / row
 struct FrameSetupOut {

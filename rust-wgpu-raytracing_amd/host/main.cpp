@@ -3,14 +3,16 @@
 // input* -> update -> render, with key events taken from a script instead of a window.
 //
 //   rwr_render --res DIR [--scene suzanne_lowpoly.obj] [--size 600x600] [--keys "S*15,D*4"]
-//              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--out frame.png] [--time]
+//              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
 // (KEY in W A S D Up Down Left Right Space LShift, or '-' for no key).  After the script,
 // --frames more frames are rendered with no key held.  The window default is 600x600
 // (lib.rs:1248-1251).  --resize WxH@FRAME (repeatable): a WindowEvent::Resized delivered before frame FRAME
 // (0-based, counted over the whole run) -> State::resize (lib.rs:772-989, 1323-1330), including its quirk: the
-// camera's aspect is recomputed from the size BEFORE the resize.
+// camera's aspect is recomputed from the size BEFORE the resize.  --accumulate (extension): every frame sets
+// RWR_FLAG_ACCUMULATE, so the image converges while the camera rests (any change starts over); the program prints
+// `samples N` for the final frame.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -41,7 +43,7 @@ int main(int argc, char **argv)
 {
     std::string res, scene = "suzanne_lowpoly.obj", out, keys;
     uint32_t w = 600, h = 600, frames = 1, spp = 1, bounces = 0;
-    bool timing = false;
+    bool timing = false, accumulate = false;
     struct Resize { uint64_t frame; uint32_t w, h; };
     std::vector<Resize> resizes;
     for (int i = 1; i < argc; i++) {
@@ -58,6 +60,7 @@ int main(int argc, char **argv)
         else if (a == "--spp") spp = (uint32_t)std::atoi(next());
         else if (a == "--bounces") bounces = (uint32_t)std::atoi(next());
         else if (a == "--time") timing = true;
+        else if (a == "--accumulate") accumulate = true;
         else if (a == "--resize") {
             Resize r{0, 0, 0};
             unsigned long long f = 0;
@@ -69,7 +72,9 @@ int main(int argc, char **argv)
             if (std::sscanf(next(), "%ux%u", &w, &h) != 2) { std::fprintf(stderr, "--size WxH\n"); return 2; }
         } else if (a == "--help" || a == "-h") {
             std::printf("usage: rwr_render --res DIR [--scene F.obj] [--size WxH] [--keys \"S*15,D*4\"] [--frames N] "
-                        "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--out frame.png] [--time]\n");
+                        "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--out frame.png] [--time]\n"
+                        "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
+                        "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n");
             return 0;
         } else {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
@@ -95,7 +100,7 @@ int main(int argc, char **argv)
 
     try {
         State state(w, h, res, scene);
-        const rwr_render_params params{spp, bounces, 0u, 0u};
+        const rwr_render_params params{spp, bounces, 0u, accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u};
         uint64_t rendered = 0;
         const auto t0 = std::chrono::steady_clock::now();
         auto frame = [&]() {  // [Resized: resize()] then RedrawRequested: update() then render() (lib.rs:1323-1337)
@@ -116,6 +121,7 @@ int main(int argc, char **argv)
         const Camera &c = state.camera();
         std::printf("frames %llu  eye (%.6f, %.6f, %.6f)  target (%.6f, %.6f, %.6f)  size %ux%u  aspect %.9g\n", (unsigned long long)rendered,
                     c.eye.x, c.eye.y, c.eye.z, c.target.x, c.target.y, c.target.z, state.size().width, state.size().height, (double)c.aspect);
+        if (accumulate) std::printf("samples %llu\n", (unsigned long long)state.accumulated_samples());
         if (timing) std::printf("%.3f ms/frame over %llu frames (update + render, host wall clock)\n", sec * 1e3 / (double)rendered,
                                 (unsigned long long)rendered);
         if (!out.empty()) {

@@ -128,6 +128,13 @@ public:
         if (!camera_inv_uniform_.update_view_proj(camera_)) throw RwrFailure(RWR_ERR_INVALID_ARGUMENT, "singular camera");
     }
     void render(const rwr_render_params *params = nullptr) { check(rwr_render(ctx_, &camera_inv_uniform_, params)); }  // lib.rs:1012-1230
+    // extension (RWR_FLAG_ACCUMULATE): samples per pixel the frame rendered last holds, 0 when it did not accumulate
+    uint64_t accumulated_samples()
+    {
+        uint64_t n = 0;
+        check(rwr_accum_samples(ctx_, &n));
+        return n;
+    }
 
     // the blit's job (screenquad.wgsl + sRGB swapchain, lib.rs:1186-1224): framebuffer -> PNG
     void present(const std::string &png_path)
