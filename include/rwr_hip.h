@@ -124,10 +124,18 @@ typedef struct rwr_camera {
  * [0, 16], albedo * E(h1) to [0, 64], NaN counting as 0 — so that the sums have a fixed range (they are added as fixed
  * point, in any order, and the frame is bit-reproducible).  The reference's materials (components <= 1) come nowhere near;
  * a material with Ka = 20 is clamped, in the oracle's or_render_path as here.  spp 1 / max_bounces 0 is the reference frame:
- * nothing is clamped before the rgba8unorm store. */
+ * nothing is clamped before the rgba8unorm store.
+ * Deeper paths (RWR_FLAG_MULTI_BOUNCE, max_bounces = B <= RWR_MAX_BOUNCES): a sample adds, for k = 1 ... B, the term
+ * T(k-1) * E(hk) clamped per channel to [0, 64] (NaN counting as 0), with T0 = albedo(h0) and Tk = T(k-1) * albedo(hk).  Ray k
+ * starts at P(k-1) + 1e-4 n(k-1) (P = origin + t * direction; n = the face normal flipped towards the ray, or the sphere's
+ * outward normal; normal maps never change it) and leaves in the cosine-distributed direction about n(k-1) drawn from RNG
+ * dimensions 2 + 16 (k-1) ... 17 + 16 (k-1) of (global pixel, global sample, seed): for k = 1 the one-bounce ray.  hk is its
+ * nearest hit, spheres in order then faces, ties to the earlier candidate; a miss ends the path.  Depth, id and t planes
+ * report primary sample 0 whatever B is, and a path of B bounces is a prefix of the path of B + 1. */
 typedef struct rwr_render_params {
     uint32_t spp;          /* >= 1.  1 = the reference's single centre sample        */
-    uint32_t max_bounces;  /* 0 = reference (primary rays only); 1 = one diffuse bounce */
+    uint32_t max_bounces;  /* 0 = reference (primary rays only); 1 = one diffuse bounce; up to
+                              RWR_MAX_BOUNCES with RWR_FLAG_MULTI_BOUNCE (else > 1 is RWR_ERR_UNSUPPORTED) */
     uint32_t seed;         /* RNG stream key; results do not depend on GPU count     */
     uint32_t flags;        /* RWR_FLAG_*                                              */
 } rwr_render_params;
@@ -150,7 +158,7 @@ enum {
                                        shades with the flat face normal).  Without the flag — the default — the frame is
                                        the reference's.  Visibility never changes; bounce rays still leave along the
                                        geometric normal */
-    RWR_FLAG_ACCUMULATE  = 1u << 5  /* extension: progressive accumulation across frames (rwr_accum_reset, rwr_accum_samples).
+    RWR_FLAG_ACCUMULATE  = 1u << 5, /* extension: progressive accumulation across frames (rwr_accum_reset, rwr_accum_samples).
                                        The frame traces global samples [N, N + spp), N = the samples the context's accumulation
                                        holds, and shows the mean of all N + spp: after frames of s1, s2, ... sK samples with an
                                        unchanged key, every plane (color, depth, and with RWR_FLAG_AUX_OUTPUTS color_f32, obj_id,
@@ -168,7 +176,14 @@ enum {
                                        more samples than the cap is RWR_ERR_INVALID_ARGUMENT.  With RWR_FLAG_ORTHO_RAYS,
                                        RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED.  Frames in flight and
                                        row bands / strips keep the contract (the sums are keyed by global pixel) */
+    RWR_FLAG_MULTI_BOUNCE = 1u << 6 /* extension: max_bounces may be 0 ... RWR_MAX_BOUNCES (diffuse paths of that many bounces,
+                                       rwr_render_params); more is RWR_ERR_INVALID_ARGUMENT.  With max_bounces <= 1 every plane
+                                       is the frame without the flag, byte for byte.  RWR_FLAG_USE_BVH, RWR_FLAG_ORTHO_RAYS and
+                                       single-triangle passes stay reference-frame only.  rwr_last_render_stats' bounce_rays
+                                       counts the rays of every bounce */
 };
+
+#define RWR_MAX_BOUNCES 8u
 
 #define RWR_MAX_SPHERES 8
 #define RWR_MAX_TRIANGLES 8
@@ -376,7 +391,8 @@ RWR_API int rwr_ctx_set_kernel_timing(rwr_context *ctx, uint32_t every_n);
 RWR_API int rwr_kernel_timing_stats(rwr_context *ctx, double *mean_us, uint32_t *count);
 
 /* Segments (rays) traced by the last render call, for Mray/s accounting:
- * W*rows*spp primary + bounce rays actually emitted (an accumulating frame: its own spp; 0 past the cap). */
+ * W*rows*spp primary + bounce rays actually emitted, of every generation with RWR_FLAG_MULTI_BOUNCE (an accumulating frame:
+ * its own spp; 0 past the cap). */
 RWR_API int rwr_last_render_stats(rwr_context *ctx, uint64_t *primary_rays, uint64_t *bounce_rays);
 
 /* Progressive accumulation (RWR_FLAG_ACCUMULATE).  One context holds one accumulation.

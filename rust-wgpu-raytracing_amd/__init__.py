@@ -44,6 +44,8 @@ FLAG_AUX_OUTPUTS, FLAG_NO_CULL, FLAG_USE_BVH = 1, 2, 4
 FLAG_ORTHO_RAYS = 1 << 3
 FLAG_NORMAL_MAP = 1 << 4
 FLAG_ACCUMULATE = 1 << 5
+FLAG_MULTI_BOUNCE = 1 << 6   # max_bounces up to MAX_BOUNCES (include/rwr_hip.h)
+MAX_BOUNCES = 8
 FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
 KEY_FORWARD, KEY_BACKWARD, KEY_LEFT, KEY_RIGHT, KEY_UP, KEY_DOWN = 1, 2, 4, 8, 16, 32
 OK, ERR_INVALID_ARGUMENT, ERR_HIP, ERR_NOT_READY, ERR_IO, ERR_PARSE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6

@@ -171,6 +171,7 @@ struct rwr_context {
         DeviceBuffer<float4> d_rays;
         bool fix_clean = false;         // the fixed-point planes are all zero (k_wf_resolve leaves them so)
         DeviceBuffer<unsigned long long> d_masks;
+        DeviceBuffer<unsigned long long> d_masks_next;   // deeper paths: the ballots of the generation being written (swapped with d_masks)
         DeviceBuffer<uint16_t> d_sorted, d_bins;
         DeviceBuffer<uint32_t> d_wave_total;
         DeviceBuffer<unsigned long long> d_fix;   // the frame's fixed-point sums, 4 planes
@@ -189,7 +190,7 @@ struct rwr_context {
                 if (join[q]) { (void)hipEventDestroy(join[q]); join[q] = nullptr; }
             }
             if (fork) { (void)hipEventDestroy(fork); fork = nullptr; }
-            d_rays.release(); d_masks.release(); d_sorted.release(); d_bins.release(); d_wave_total.release(); d_fix.release();
+            d_rays.release(); d_masks.release(); d_masks_next.release(); d_sorted.release(); d_bins.release(); d_wave_total.release(); d_fix.release();
             d_pool_info.release(); d_live.release(); d_pool_list.release(); d_tiles.release();
             fix_clean = false;
         }
@@ -897,7 +898,10 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
     rwr_render_params rp = {1, 0, 0, 0};
     if (params) rp = *params;
     if (rp.spp == 0) return set_error(RWR_ERR_INVALID_ARGUMENT, "spp must be >= 1");
-    if (rp.max_bounces > 1) return set_error(RWR_ERR_UNSUPPORTED, "max_bounces > 1 is not supported");
+    if ((rp.flags & RWR_FLAG_MULTI_BOUNCE) && rp.max_bounces > RWR_MAX_BOUNCES)
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "max_bounces %u is more than RWR_MAX_BOUNCES (%u)", rp.max_bounces, RWR_MAX_BOUNCES);
+    if (rp.max_bounces > 1 && !(rp.flags & RWR_FLAG_MULTI_BOUNCE))
+        return set_error(RWR_ERR_UNSUPPORTED, "max_bounces > 1 is not supported without RWR_FLAG_MULTI_BOUNCE");
     if ((rp.flags & RWR_FLAG_USE_BVH) && (rp.spp != 1 || rp.max_bounces != 0))
         return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_USE_BVH applies to the reference frame (spp 1, no bounce); bounce rays always use the BVH");
     if (rp.spp > 4096) return set_error(RWR_ERR_INVALID_ARGUMENT, "spp must be <= 4096");
@@ -1211,6 +1215,7 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
             RWR_HIP_CHECK(W.d_sorted.ensure(n_queues * slots));
             RWR_HIP_CHECK(W.d_bins.ensure(n_queues * slots));
             RWR_HIP_CHECK(W.d_masks.ensure(n_queues * n_tiles * group * 8u));
+            if (rp.max_bounces > 1u) RWR_HIP_CHECK(W.d_masks_next.ensure(n_queues * n_tiles * group * 8u));
             RWR_HIP_CHECK(W.d_pool_info.ensure(n_queues * n_tiles * wf_pool_info_bytes()));
             RWR_HIP_CHECK(W.d_pool_list.ensure(n_queues * 2u * (size_t)n_tiles));
             if (overlap && !W.fork) RWR_HIP_CHECK(hipEventCreateWithFlags(&W.fork, hipEventDisableTiming));
@@ -1292,12 +1297,24 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
             hipStream_t gs = q ? W.streams[q] : stream;
             RWR_HIP_CHECK(launch_wf_primary(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg, wfq[q],
                                             (uint32_t)accum_before + s0, cnt, z_split));
-            if (rp.max_bounces) {
-                RWR_HIP_CHECK(launch_wf_bounce(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh, tex0, wfq[q], n_tiles, cnt,
+            // the bounce stage: one generation of rays per bounce (RWR_FLAG_MULTI_BOUNCE: up to RWR_MAX_BOUNCES).  Generation k traces
+            // ray k of every path that is still alive — the sort and trace kernels run again over the same fixed slots — and, unless
+            // it is the last, writes ray k + 1 back into the slot of every hit, with its bit in the other ballot array.
+            WfBuffers wg = wfq[q];
+            unsigned long long *masks_next = W.d_masks_next.ptr ? W.d_masks_next.ptr + q * n_tiles * group * 8u : nullptr;
+            for (uint32_t gen = 1; gen <= rp.max_bounces; gen++) {
+                if (gen > 1u)   // the sort counts this generation's live pools from zero (the primary stage zeroed the set of four for the first)
+                    RWR_HIP_CHECK(hipMemsetAsync(wg.counters, 0, 4u * sizeof(uint32_t), gs));
+                const bool emit = gen < rp.max_bounces;
+                const WfEmit em{masks_next, 2u + 16u * gen, (uint32_t)accum_before + s0};
+                if (emit) RWR_HIP_CHECK(hipMemsetAsync(masks_next, 0, (size_t)n_tiles * group * 8u * sizeof(unsigned long long), gs));
+                RWR_HIP_CHECK(launch_wf_bounce(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh, tex0, wg, n_tiles, cnt,
                                                (uint32_t)std::fmax(1.0f, std::ceil(ctx->wf_packet_fill * (float)(cnt * kWfTilePixels))),
-                                               W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles));
-                if (s0 + group >= rp.spp) last_counters = wfq[q].counters;   // the last group's live-pool counts, for the next frame's split
+                                               W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles,
+                                               emit ? &em : nullptr));
+                if (emit) std::swap(wg.masks, masks_next);
             }
+            if (rp.max_bounces && s0 + group >= rp.spp) last_counters = wfq[q].counters;   // the last group's live-pool counts, for the next frame's split
         }
         for (size_t q = 1; q < n_queues; q++) {
             RWR_HIP_CHECK(hipEventRecord(W.join[q], W.streams[q]));

@@ -28,6 +28,11 @@
 //                     be adding to the same pixels at the same time — the sums are the same bits.
 // On frames that show little the sort strides over the live tiles k_wf_classify listed instead of visiting every pool.
 //
+// Deeper paths (RWR_FLAG_MULTI_BOUNCE, max_bounces B >= 2): the host runs the sort and the trace kernels once per GENERATION
+// of rays, B times per launch group.  Every generation but the last uses the trace kernels' EMIT forms: besides adding the
+// term T * E(h) a hit writes the path's next ray back into ITS OWN fixed slot (a slot's pixel never changes, so the sums and
+// their flush stay as they are), with its direction bin, and sets the slot's bit in the next generation's ballots
+// (WfEmit::masks_out, cleared before, swapped with WfBuffers::masks after the generation).  The last generation runs the plain forms.
 // Nothing here decides what the first hit shows; bounce rays are the oracle's rays bit for bit (first stage) and
 // their nearest hits are exact, so the stage's output differs from the oracle's only by the fixed-point rounding
 // of the terms and of the throughput (tolerance 1e-4).
@@ -297,6 +302,34 @@ RWR_DEV void flush_pool(TraceShared &sh, const FrameParams &p, const WfBuffers &
     }
 }
 
+// EMIT forms: the next ray of the path whose ray hit (obj, t) — from P + 1e-4 n (P = O + t D, n = the face's normal flipped
+// towards the ray or the sphere's outward normal, as the first stage builds the first bounce ray), in the cosine-distributed
+// direction of RNG dimensions em.next_dim ... keyed by the slot's global pixel and sample, throughput thr — goes back into slot
+// e of the tile's pool; the slot's bit is set in the next generation's ballots.
+RWR_DEV void emit_next_ray(const FrameParams &p, const WfBuffers &wf, const WfEmit &em, const TriRecord *__restrict__ tris, uint32_t tile,
+                           uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr)
+{
+    const f3 P = along(O, t, D);
+    f3 n;
+    if (obj >= 0) {
+        n = ld3(tris[obj].nhat);
+        if (ndotd > 0.0f) n = neg3(n);   // compute.wgsl:140-142
+    } else {
+        n = normalize3(sub3(P, ld3(p.spheres[-2 - obj].center)));
+    }
+    const f3 O1 = mk3(P.x + n.x * 1e-4f, P.y + n.y * 1e-4f, P.z + n.z * 1e-4f);
+    // the slot's pixel (as add_contribution maps it) and sample
+    const uint32_t r = e & (kWfTilePixels - 1u), w = r >> 7, k = (r >> 6) & 1u, l = r & 63u;
+    const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (w & 1u) * 32u + 2u * (l & 15u) + k;
+    const uint32_t py = p.row_begin + (tile / wf.tiles_x) * p.row_pitch + (w >> 1) * 4u + (l >> 4);
+    const f3 D1 = bounce_direction(n, py * p.width + px, em.sample_base + e / kWfTilePixels, p.seed, em.next_dim);
+    const size_t slot = (size_t)tile * wf.group * kWfTilePixels + e;
+    wf.rays[2u * slot] = make_float4(O1.x, O1.y, O1.z, wf_pack_unorm16x2(thr.x, thr.y));
+    wf.rays[2u * slot + 1u] = make_float4(D1.x, D1.y, D1.z, wf_pack_unorm16x2(thr.z, 0.0f));
+    wf.bins[slot] = (uint16_t)wf_direction_bin(D1);
+    atomicOr(&em.masks_out[(size_t)tile * wf.group * 8u + (e >> 6)], 1ull << (e & 63u));
+}
+
 // The trace kernels are PERSISTENT: kWfTraceGroups workgroups pull work items — (pool of the class, share of it)
 // — from a device counter until the class's live x split items are handed out.  Returns false when none are left.
 // Contains barriers; uniform over the workgroup.
@@ -339,11 +372,12 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // WIDE: a workgroup of 1 024 threads that shares ONE copy of the nodelets in LDS (a BVH too large for four 256-thread
 // workgroups per CU to hold a copy each — 508 nodes = 65 KB at configs[3] — but small enough for one per CU): every node fetch
 // of the traversal then comes from LDS instead of through the vector memory pipe, 64 different 16-byte pieces per load.
-template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false>
+// EMIT: a generation of a deeper path that is not its last (emit_next_ray).
+template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false>
 __global__ void __launch_bounds__(WIDE ? 1024 : 256)
 k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                 const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
-                uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles)
+                uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em)
 {
     __shared__ TraceShared sh;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
@@ -405,8 +439,16 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                 if (mh.have && (!have || mh.t < best_t)) { have = true; best_t = mh.t; obj = (int32_t)mh.idx; }
             }
             if (have) {
-                const f3 e1 = shade_winner<NMAP>(p, obj, best_t, mh.u, mh.v, mh.ndotd, shade, tex, O, D).colour;
+                const Shaded s1 = shade_winner<NMAP>(p, obj, best_t, mh.u, mh.v, mh.ndotd, shade, tex, O, D);
+                const f3 e1 = s1.colour;
                 add_contribution(sh, e, thr.x * e1.x, thr.y * e1.y, thr.z * e1.z);
+                if (EMIT)
+                    emit_next_ray(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd,
+                                  mk3(thr.x * s1.albedo.x, thr.y * s1.albedo.y, thr.z * s1.albedo.z));
+            }
+            if (EMIT) {   // rays written for the next generation (lanes past the pool's end have left the iteration)
+                const unsigned long long em = __ballot(have);
+                if (em && (tid & 63u) == (uint32_t)__builtin_ctzll(em)) atomicAdd(&wf.wave_total[tile * 4u], (uint32_t)__popcll(em));
             }
         }
         __syncthreads();
@@ -493,11 +535,11 @@ RWR_DEV i2 sphere_pair_intersect_t(f3 center, float radius, v3 O, v3 D, f2 &t_ou
 #ifndef RWR_PACKET_OCC
 #define RWR_PACKET_OCC 4
 #endif
-template <bool NMAP>
+template <bool NMAP, bool EMIT = false>   // EMIT: see k_wf_trace_lane
 __global__ void __launch_bounds__(256, RWR_PACKET_OCC)
 k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
-                  uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles)
+                  uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em)
 {
     __shared__ TraceShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -664,12 +706,19 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
         // -- shade the second hit, add albedo(h0) * E(h1) to the pixel's sums --------------------------------------
         if (__any(any2(have))) {
             f2 er = splat(0.0f), eg = splat(0.0f), eb = splat(0.0f);
+            f2 ar = splat(0.0f), ag = splat(0.0f), ab = splat(0.0f);   // albedo (EMIT)
             const i2 is_mesh = have & (obj >= 0);
             if (__any(any2(is_mesh))) {   // mesh winners: both rays of a lane at once (packed arithmetic, rwr_shade_p2.h)
                 const ShadeRec none = {};
-                if (NMAP) shade_mesh_pair<true, false, true>(p, shade, tex, obj, none, best, R.D, er, eg, eb);
-                else if (p.n_materials > 1u) shade_mesh_pair<true, false>(p, shade, tex, obj, none, best, R.D, er, eg, eb);
-                else shade_mesh_pair<false, false>(p, shade, tex, obj, none, best, R.D, er, eg, eb);
+                if (EMIT) {
+                    if (NMAP) shade_mesh_pair<true, false, true>(p, shade, tex, obj, none, best, R.D, er, eg, eb, ar, ag, ab);
+                    else if (p.n_materials > 1u) shade_mesh_pair<true, false>(p, shade, tex, obj, none, best, R.D, er, eg, eb, ar, ag, ab);
+                    else shade_mesh_pair<false, false>(p, shade, tex, obj, none, best, R.D, er, eg, eb, ar, ag, ab);
+                } else {
+                    if (NMAP) shade_mesh_pair<true, false, true>(p, shade, tex, obj, none, best, R.D, er, eg, eb);
+                    else if (p.n_materials > 1u) shade_mesh_pair<true, false>(p, shade, tex, obj, none, best, R.D, er, eg, eb);
+                    else shade_mesh_pair<false, false>(p, shade, tex, obj, none, best, R.D, er, eg, eb);
+                }
             }
             if (__any(any2(have & (obj < -1)))) {   // sphere winners (rare): one ray at a time
 #pragma unroll
@@ -679,12 +728,23 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
                         const f3 Ok = lane3(R.O, k), Dk = lane3(R.D, k);
                         const f3 ek = shade_winner<false>(p, o, k ? best_t.y : best_t.x, 0.0f, 0.0f, 0.0f, shade, tex, Ok, Dk).colour;
                         if (k) { er.y = ek.x; eg.y = ek.y; eb.y = ek.z; } else { er.x = ek.x; eg.x = ek.y; eb.x = ek.z; }
+                        if (EMIT) { if (k) { ar.y = 1.0f; ag.y = 0.0f; ab.y = 0.0f; } else { ar.x = 1.0f; ag.x = 0.0f; ab.x = 0.0f; } }
                     }
                 }
             }
             const f2 cr = thr.x * er, cg = thr.y * eg, cb = thr.z * eb;
             if (have.x) add_contribution(sh, e0, cr.x, cg.x, cb.x);
             if (have.y) add_contribution(sh, e1, cr.y, cg.y, cb.y);
+            if (EMIT) {   // every hit's next ray, one ray of the lane after the other
+                const f2 nr = thr.x * ar, ng = thr.y * ag, nb = thr.z * ab;
+#pragma unroll
+                for (int k = 0; k < 2; k++)
+                    if (k ? have.y : have.x)
+                        emit_next_ray(p, wf, em, tris, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), k ? obj.y : obj.x, k ? best_t.y : best_t.x,
+                                      k ? best.ndotd.y : best.ndotd.x, k ? mk3(nr.y, ng.y, nb.y) : mk3(nr.x, ng.x, nb.x));
+                const uint32_t n_emit = (uint32_t)__popcll(__ballot(have.x != 0)) + (uint32_t)__popcll(__ballot(have.y != 0));
+                if (lane == 0u) atomicAdd(&wf.wave_total[tile * 4u], n_emit);
+            }
         }
     }
     __syncthreads();
@@ -694,8 +754,9 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
 
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf, uint32_t n_tiles,
-                            uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list)
+                            uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list, const WfEmit *emit)
 {
+    const WfEmit em = emit ? *emit : WfEmit{nullptr, 0u, 0u};
     if (n_tiles == 0 || sample_count == 0) return hipSuccess;
     uint32_t *counters = wf.counters;   // this queue's set, zeroed by the primary stage that filled the queue
     PoolInfo *info = static_cast<PoolInfo *>(pool_info);
@@ -724,37 +785,49 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
                            sample_count, packets ? packet_min_rays : 0xffffffffu, bvh.packet_extent, bvh.packet_dense_rays);
     const dim3 grid(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit));
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
-    if (packets) {
-        if (nmap) hipLaunchKernelGGL((k_wf_trace_packet<true>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles);
-        else hipLaunchKernelGGL((k_wf_trace_packet<false>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles);
+    if (packets && emit) {
+        if (nmap) hipLaunchKernelGGL((k_wf_trace_packet<true, true>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em);
+        else hipLaunchKernelGGL((k_wf_trace_packet<false, true>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em);
+    } else if (packets) {
+        if (nmap) hipLaunchKernelGGL((k_wf_trace_packet<true>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em);
+        else hipLaunchKernelGGL((k_wf_trace_packet<false>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em);
     }
     const bool stack16 = bvh.n_nodes <= 0x7fffu && fp.n_tris <= 4095u;   // node indices and leaf links (first << 3 | count - 1) in 15 bits
     const size_t fixed = (size_t)bvh.stack_depth * 256u * (stack16 ? 2u : 4u);
     const size_t node_bytes = (size_t)bvh.n_nodes * sizeof(BvhNode4);
     // nodelets go to LDS when the workgroup then still fits a CU at least four times (160 KiB LDS, 12 KiB static)
-#define RWR_LANE_LAUNCH(L, N, S16, BYTES) hipLaunchKernelGGL((k_wf_trace_lane<L, N, S16>), grid, dim3(256), BYTES, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles)
-#define RWR_LANE_LAUNCH2(L, BYTES) \
-    if (nmap) { if (stack16) RWR_LANE_LAUNCH(L, true, true, BYTES); else RWR_LANE_LAUNCH(L, true, false, BYTES); } \
-    else { if (stack16) RWR_LANE_LAUNCH(L, false, true, BYTES); else RWR_LANE_LAUNCH(L, false, false, BYTES); }
+#define RWR_LANE_LAUNCH(L, N, S16, E, BYTES) hipLaunchKernelGGL((k_wf_trace_lane<L, N, S16, false, E>), grid, dim3(256), BYTES, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em)
+#define RWR_LANE_LAUNCH1(L, E, BYTES) \
+    if (nmap) { if (stack16) RWR_LANE_LAUNCH(L, true, true, E, BYTES); else RWR_LANE_LAUNCH(L, true, false, E, BYTES); } \
+    else { if (stack16) RWR_LANE_LAUNCH(L, false, true, E, BYTES); else RWR_LANE_LAUNCH(L, false, false, E, BYTES); }
+#define RWR_LANE_LAUNCH2(L, BYTES) if (emit) { RWR_LANE_LAUNCH1(L, true, BYTES) } else { RWR_LANE_LAUNCH1(L, false, BYTES) }
     const size_t fixed_wide = 4u * fixed, wide_bytes = node_bytes + fixed_wide;
     if (node_bytes + fixed <= 28u * 1024u) { RWR_LANE_LAUNCH2(true, node_bytes + fixed) }
     else if (bvh.wide_lane && !nmap && stack16 && wide_bytes + 14u * 1024u <= 160u * 1024u) {
         // a BVH too large for a copy per 256-thread workgroup, small enough for one copy per CU: 1 024-thread workgroups
-        static std::atomic<uint64_t> wide_raised_on{0};
+        static std::atomic<uint64_t> wide_raised_on{0}, wide_emit_raised_on{0};
+        std::atomic<uint64_t> &raised = emit ? wide_emit_raised_on : wide_raised_on;
+        const void *kernel = emit ? reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, true>)
+                                  : reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true>);
         int dev = 0;
         hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) return e;
         const uint64_t bit = 1ull << (dev & 63);
-        if (!(wide_raised_on.load(std::memory_order_acquire) & bit)) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 146 * 1024);
+        if (!(raised.load(std::memory_order_acquire) & bit)) {
+            e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 146 * 1024);
             if (e != hipSuccess) return e;
-            wide_raised_on.fetch_or(bit, std::memory_order_release);
+            raised.fetch_or(bit, std::memory_order_release);
         }
-        hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, fp, tris, shade, bvh, tex,
-                           wf, info, counters, pool_list, n_tiles);
+        if (emit)
+            hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true, true>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, fp, tris,
+                               shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em);
+        else
+            hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, fp, tris, shade, bvh, tex,
+                               wf, info, counters, pool_list, n_tiles, em);
     }
     else { RWR_LANE_LAUNCH2(false, fixed) }
 #undef RWR_LANE_LAUNCH2
+#undef RWR_LANE_LAUNCH1
 #undef RWR_LANE_LAUNCH
     return hipGetLastError();
 }

@@ -419,12 +419,14 @@ RWR_DEV float rng_uniform(uint32_t pixel, uint32_t sample, uint32_t dim, uint32_
     return (float)(rng_hash(pixel, sample, dim, seed) >> 8) * (1.0f / 16777216.0f);
 }
 
-RWR_DEV f3 bounce_direction(f3 n, uint32_t pixel, uint32_t sample, uint32_t seed)
+// dim0: the first of the 16 RNG dimensions the direction reads (2 for the first bounce; ray k of a deeper path,
+// RWR_FLAG_MULTI_BOUNCE: 2 + 16 (k - 1))
+RWR_DEV f3 bounce_direction(f3 n, uint32_t pixel, uint32_t sample, uint32_t seed, uint32_t dim0 = 2u)
 {
     float a = 0.0f, b = 0.0f;
     for (uint32_t k = 0; k < 8u; k++) {  // rejection-sample the unit disk
-        const float ua = 2.0f * rng_uniform(pixel, sample, 2u + 2u * k, seed) - 1.0f;
-        const float ub = 2.0f * rng_uniform(pixel, sample, 3u + 2u * k, seed) - 1.0f;
+        const float ua = 2.0f * rng_uniform(pixel, sample, dim0 + 2u * k, seed) - 1.0f;
+        const float ub = 2.0f * rng_uniform(pixel, sample, dim0 + 1u + 2u * k, seed) - 1.0f;
         if (ua * ua + ub * ub <= 1.0f) { a = ua; b = ub; break; }
     }
     const float dz = sqrtf(fmaxf(0.0f, 1.0f - a * a - b * b));

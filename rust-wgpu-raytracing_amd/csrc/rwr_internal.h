@@ -238,6 +238,15 @@ struct WfBuffers {
     const uint32_t *live_count;
     const uint32_t *tile_live;
 };
+// Deeper paths (RWR_FLAG_MULTI_BOUNCE; the EMIT forms of the trace kernels, kernels_wf_bounce.hip): the next generation's ballots
+// (same layout as WfBuffers::masks, cleared before the generation), the RNG dimension its rays start from (2 + 16 k for ray
+// k + 1), and the global sample index of the launch group's first sample (accumulation base + group base).  A kernel argument
+// of its own behind the others, so that the kernels which end a path keep their argument layout and their code.
+struct WfEmit {
+    unsigned long long *masks_out;
+    uint32_t next_dim;
+    uint32_t sample_base;
+};
 struct BvhNode4;
 struct BvhDevice {
     const BvhNode4 *nodes;
@@ -263,9 +272,12 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
 // once per frame, ahead of the primary stage, when the frame is expected to show little: fills live_list / live_count / tile_live
 hipError_t launch_wf_classify(hipStream_t s, const FrameParams &fp, const FrameTri *ftris, const Targets &tg, uint32_t tiles_x,
                               uint32_t *live_list, uint32_t *live_count, uint32_t *tile_live);
+// emit: one generation of a deeper path that is not its last — the trace kernels' EMIT forms write every hit's next ray back
+// into its slot; null: the kernels that end the path
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf,
-                            uint32_t n_tiles, uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list);
+                            uint32_t n_tiles, uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list,
+                            const WfEmit *emit = nullptr);
 size_t wf_pool_info_bytes();
 hipError_t launch_primary_bvh(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                               const BvhDevice &bvh, const float4 *tex, const Targets &tg);

@@ -100,7 +100,8 @@ int main(int argc, char **argv)
 
     try {
         State state(w, h, res, scene);
-        const rwr_render_params params{spp, bounces, 0u, accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u};
+        // more than one bounce: the deeper paths of RWR_FLAG_MULTI_BOUNCE
+        const rwr_render_params params{spp, bounces, 0u, (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u)};
         uint64_t rendered = 0;
         const auto t0 = std::chrono::steady_clock::now();
         auto frame = [&]() {  // [Resized: resize()] then RedrawRequested: update() then render() (lib.rs:1323-1337)

@@ -1,0 +1,96 @@
+"""The tests' CPU reference of the deeper paths (path_ref.c, which includes the oracle): built once per session into a pytest
+temporary directory with the oracle's own compiler flags, called like oracle.render_path."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SOURCE = os.path.join(HERE, "path_ref.c")
+
+_lib = None
+
+
+def compiler() -> str:
+    """$CC, else gcc, else ROCm's clang."""
+    cc = os.environ.get("CC")
+    if cc:
+        return cc
+    if shutil.which("gcc"):
+        return "gcc"
+    return "/opt/rocm/llvm/bin/clang"
+
+
+def oracle_cflags() -> list:
+    """CFLAGS exactly as oracle/Makefile sets them (continuation lines joined)."""
+    text = open(os.path.join(ROOT, "oracle", "Makefile")).read().replace("\\\n", " ")
+    m = re.search(r"^CFLAGS\s*\?=\s*(.*)$", text, re.M)
+    return m.group(1).split()
+
+
+def lib(tmp_path_factory) -> C.CDLL:
+    """Compiles path_ref.c on first use (one build per session) and loads it."""
+    global _lib
+    if _lib is None:
+        out = os.path.join(str(tmp_path_factory.mktemp("path_ref")), "libpath_ref.so")
+        cmd = [compiler()] + oracle_cflags() + ["-shared", "-o", out, SOURCE, "-lm"]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("path_ref.c build failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)
+        lib_ = C.CDLL(out)
+        lib_.pr_render_path_nm.restype = C.c_int
+        lib_.pr_bounce_direction.restype = None
+        lib_.pr_bounce_direction.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        _lib = lib_
+    return _lib
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def bounce_direction(L, n, pixel: int, sample: int, seed: int, dim0: int) -> np.ndarray:
+    n = np.ascontiguousarray(n, dtype=np.float32)
+    out = np.zeros(3, np.float32)
+    L.pr_bounce_direction(_p(n), pixel, sample, seed, dim0, _p(out))
+    return out
+
+
+def render_path(L, orc, cam_inv, screen, params, spheres, model, instances=None, rows=None) -> dict:
+    """pr_render_path_nm with oracle.render_path's arguments (one model dict or a list of parts); the result has the planes
+    and "rays": the rays traced beyond the primary ones."""
+    scene = orc.concat_parts(list(model) if isinstance(model, (list, tuple)) else [model])
+    w, h = int(screen["width"][0]), int(screen["height"][0])
+    r0, r1 = rows if rows is not None else (0, h)
+    color = np.zeros((h, w, 4), np.uint8)
+    depth = np.zeros((h, w), np.float32)
+    color_f = np.zeros((h, w, 4), np.float32)
+    obj_id = np.full((h, w), -1, np.int32)
+    hit_t = np.zeros((h, w), np.float32)
+    texs = scene["textures"]
+    n_mat = len(texs)
+    ptrs = (C.c_void_p * n_mat)(*[t.ctypes.data for t in texs])
+    ws = np.array([t.shape[1] for t in texs], np.uint32)
+    hs = np.array([t.shape[0] for t in texs], np.uint32)
+    n_inst = 0 if instances is None else len(instances)
+    inst = None if n_inst == 0 else np.ascontiguousarray(instances, dtype=orc.INSTANCE_DTYPE)
+    mats = np.ascontiguousarray(scene["materials"])
+    fmat = np.ascontiguousarray(scene["face_material"], dtype=np.uint32)
+    nts = scene.get("normal_textures") or [None] * n_mat
+    nptrs = (C.c_void_p * n_mat)(*[None if t is None else t.ctypes.data for t in nts])
+    nws = np.array([0 if t is None else t.shape[1] for t in nts], np.uint32)
+    nhs = np.array([0 if t is None else t.shape[0] for t in nts], np.uint32)
+    rays = np.zeros(1, np.uint64)
+    rc = L.pr_render_path_nm(_p(cam_inv), _p(screen), _p(params), _p(spheres), C.c_uint32(len(spheres)),
+                             _p(scene["vertices"]), C.c_uint32(len(scene["vertices"])), _p(scene["faces"]), C.c_uint32(len(scene["faces"])),
+                             _p(inst), C.c_uint32(n_inst), _p(mats), C.c_uint32(n_mat), _p(fmat), ptrs, _p(ws), _p(hs), nptrs, _p(nws), _p(nhs),
+                             C.c_uint32(r0), C.c_uint32(r1), _p(color), _p(depth), _p(color_f), _p(obj_id), _p(hit_t), _p(rays))
+    if rc != 0:
+        raise MemoryError("pr_render_path_nm")
+    return {"color": color, "depth": depth, "color_f32": color_f, "obj_id": obj_id, "hit_t": hit_t, "rays": int(rays[0])}
