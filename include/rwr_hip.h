@@ -364,6 +364,11 @@ RWR_API int rwr_dist_strip_layout(uint32_t rank, uint32_t world, uint32_t height
 RWR_API int rwr_dist_host_pack_strips(uint32_t rank, uint32_t world, uint32_t width, uint32_t height,
                                       const uint8_t *frame_rgba8, uint8_t *message);
 RWR_API int rwr_dist_host_deal_strips(uint32_t world, uint32_t width, uint32_t height, const uint8_t *recv, uint8_t *frame_rgba8);
+/* The frame kernel's form of a diffuse texture, computed on the HOST (for inspection and tests; the library builds it at
+ * upload): (tex_w + 1) * (tex_h + 1) records of 4 uint32, row pitch tex_w + 1.  Record (px, py) holds the texels
+ * (px-1, py-1), (px, py-1), (px-1, py), (px, py), each coordinate clamped to the texture, as r << 2 | g << 12 | b << 22 of
+ * its sRGB bytes (alpha is not kept). */
+RWR_API int rwr_host_texture_quads(const uint8_t *rgba8_srgb, uint32_t tex_w, uint32_t tex_h, uint32_t *out);
 /* Self-test of the gather's own stages on ONE GPU for any world size, no communicator: the context plays every rank in
  * turn.  After rendering rank's share (rwr_render_strips(ctx, ..., rank, world), or rwr_render_rows of rwr_dist_band
  * with strips = 0) _deposit runs that rank's side of the gather on the frame just rendered — the same pack launch, message

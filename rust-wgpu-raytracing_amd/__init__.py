@@ -120,7 +120,7 @@ def lib() -> C.CDLL:
         "rwr_dist_gather_rgba8": [vp, i32], "rwr_dist_gather_strips_rgba8": [vp, i32], "rwr_dist_frame": [vp, vp], "rwr_dist_readback": [vp, vp],
         "rwr_dist_barrier": [vp], "rwr_dist_destroy": [vp],
         "rwr_dist_strip_layout": [u32, u32, u32, vp], "rwr_dist_host_pack_strips": [u32, u32, u32, u32, vp, vp],
-        "rwr_dist_host_deal_strips": [u32, u32, u32, vp, vp],
+        "rwr_dist_host_deal_strips": [u32, u32, u32, vp, vp], "rwr_host_texture_quads": [vp, u32, u32, vp],
         "rwr_dist_loopback_deposit": [vp, u32, u32, i32], "rwr_dist_loopback_finish": [vp, u32, i32],
         "rwr_measure_valu_clock": [vp, u32, vp], "rwr_clock_probe_start": [vp, u32], "rwr_clock_probe_read": [vp, vp],
     }
@@ -309,6 +309,15 @@ def dist_host_pack_strips(rank: int, world: int, frame: np.ndarray) -> np.ndarra
     msg = np.zeros((max(1, lay["strips"] * STRIP_ROWS), w, 4), np.uint8)
     _check(lib().rwr_dist_host_pack_strips(rank, world, w, h, _p(frame), _p(msg)))
     return msg[:lay["rows"]]
+
+
+def host_texture_quads(rgba8: np.ndarray) -> np.ndarray:
+    """The frame kernel's quad records of an (H, W, 4) uint8 sRGB texture, built on the host: (H + 1, W + 1, 4) uint32."""
+    rgba8 = np.ascontiguousarray(rgba8, np.uint8)
+    h, w = rgba8.shape[:2]
+    out = np.zeros((h + 1, w + 1, 4), np.uint32)
+    _check(lib().rwr_host_texture_quads(_p(rgba8), w, h, _p(out)))
+    return out
 
 
 def dist_host_deal_strips(world: int, recv: np.ndarray, height: int) -> np.ndarray:

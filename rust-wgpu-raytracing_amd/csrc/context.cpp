@@ -65,9 +65,38 @@ struct DeviceBuffer {
     }
 };
 
+// Quad records of a w x h RGBA8 sRGB texture (rwr_internal.h QuadTex): record (px, py) of the (w + 1) x (h + 1) grid holds the
+// four ClampToEdge texels of the footprint whose top-left tap is (px - 1, py - 1).
+void build_tex_quads(const uint8_t *rgba8, uint32_t w, uint32_t h, uint32_t *out)
+{
+    auto texel = [&](int64_t x, int64_t y) {
+        x = std::min<int64_t>(std::max<int64_t>(x, 0), (int64_t)w - 1);
+        y = std::min<int64_t>(std::max<int64_t>(y, 0), (int64_t)h - 1);
+        const uint8_t *t = rgba8 + 4u * ((size_t)y * w + (size_t)x);
+        return (uint32_t)t[0] << 2 | (uint32_t)t[1] << 12 | (uint32_t)t[2] << 22;
+    };
+    for (uint32_t py = 0; py <= h; py++)
+        for (uint32_t px = 0; px <= w; px++) {
+            uint32_t *r = out + 4u * ((size_t)py * (w + 1u) + px);
+            r[0] = texel((int64_t)px - 1, (int64_t)py - 1);
+            r[1] = texel(px, (int64_t)py - 1);
+            r[2] = texel((int64_t)px - 1, py);
+            r[3] = texel(px, py);
+        }
+}
+
 }  // namespace rwr
 
 using namespace rwr;
+
+int rwr_host_texture_quads(const uint8_t *rgba8_srgb, uint32_t tex_w, uint32_t tex_h, uint32_t *out)
+{
+    if (!rgba8_srgb || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (tex_w == 0 || tex_h == 0 || tex_w > kMaxTextureDim || tex_h > kMaxTextureDim)
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "texture %ux%u outside 1..%u", tex_w, tex_h, kMaxTextureDim);
+    build_tex_quads(rgba8_srgb, tex_w, tex_h, out);
+    return RWR_OK;
+}
 
 // Everything one frame in flight owns: its stream, its targets and the per-frame records / tables.
 // Frames alternate between slots (rwr_ctx_set_frames_in_flight), so the ramp-up of one frame's kernel
@@ -220,6 +249,9 @@ struct rwr_context {
     uint64_t scene_generation = 0;         // bumped by every change of the scene (an accumulation does not survive one)
     // one decoded texture per scene part (texels decoded to linear f32 at upload, Rgba8UnormSrgb semantics)
     std::vector<DeviceBuffer<float4>> d_texs;
+    std::vector<DeviceBuffer<uint4>> d_quads;   // the same textures as quad records (rwr_internal.h QuadTex): the frame kernel's
+    DeviceBuffer<const uint4 *> d_mat_quads;    // per material: its d_quads entry
+    DeviceBuffer<float> d_srgb_lut;             // build_srgb_lut's table
     DeviceBuffer<uint32_t> d_face_mat;      // per face: index of its part's material
     DeviceBuffer<MaterialRec> d_materials;
     // host staging of the scene being assembled (rwr_scene_clear / add_mesh / commit)
@@ -566,6 +598,14 @@ int rwr_ctx_create(int device_id, rwr_context **out_ctx)
         rwr_ctx_destroy(ctx);
         return set_error(RWR_ERR_HIP, "stream/event creation failed: %s", hipGetErrorString(e));
     }
+    {   // the sRGB decode table of the frame kernel's quad texels (every frame kernel reads it, with or without a mesh)
+        float lut[256];
+        build_srgb_lut(lut);
+        if ((e = ctx->d_srgb_lut.ensure(256)) != hipSuccess || (e = hipMemcpy(ctx->d_srgb_lut.ptr, lut, sizeof lut, hipMemcpyHostToDevice)) != hipSuccess) {
+            rwr_ctx_destroy(ctx);
+            return set_error(RWR_ERR_HIP, "sRGB table upload failed: %s", hipGetErrorString(e));
+        }
+    }
     ctx->stream = ctx->own_stream;
     ctx->slots[0].stream = ctx->stream;
     (void)preload_kernels();   // have the code objects on the device before the first frame asks for them
@@ -614,6 +654,8 @@ void rwr_ctx_destroy(rwr_context *ctx)
     ctx->accum.release();
     if (ctx->accum.done) (void)hipEventDestroy(ctx->accum.done);
     if (ctx->h_wf_live) { (void)hipHostFree(ctx->h_wf_live); ctx->h_wf_live = nullptr; } for (auto &t : ctx->d_texs) t.release();
+    for (auto &t : ctx->d_quads) t.release();
+    ctx->d_mat_quads.release(); ctx->d_srgb_lut.release();
     ctx->d_face_mat.release(); ctx->d_materials.release();
     for (FrameSlot &sl : ctx->slots) {
         sl.release_buffers();
@@ -664,6 +706,8 @@ int rwr_scene_clear(rwr_context *ctx)
     ctx->st_verts.clear(); ctx->st_faces.clear(); ctx->st_face_mat.clear(); ctx->st_materials.clear();
     for (auto &t : ctx->d_texs) t.release();
     ctx->d_texs.clear();
+    for (auto &t : ctx->d_quads) t.release();
+    ctx->d_quads.clear();
     for (auto &t : ctx->d_nmaps) t.release();
     ctx->d_nmaps.clear();
     ctx->have_mesh = false;
@@ -707,9 +751,20 @@ int rwr_scene_add_mesh(rwr_context *ctx, const rwr_model_vertex_small *verts, ui
                                  (float)rgba8_srgb[4 * i + 3] / 255.0f);  // alpha is linear in sRGB formats
         e = hipMemcpy(tex.ptr, lin.data(), lin.size() * sizeof(float4), hipMemcpyHostToDevice);
     }
+    // ... and as quad records (the frame kernel's form)
+    ctx->d_quads.emplace_back();
+    DeviceBuffer<uint4> &quad = ctx->d_quads.back();
+    if (e == hipSuccess) e = quad.ensure((size_t)(tex_w + 1u) * (tex_h + 1u));
+    if (e == hipSuccess) {
+        std::vector<uint4> q((size_t)(tex_w + 1u) * (tex_h + 1u));
+        build_tex_quads(rgba8_srgb, tex_w, tex_h, reinterpret_cast<uint32_t *>(q.data()));
+        e = hipMemcpy(quad.ptr, q.data(), q.size() * sizeof(uint4), hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) {
         ctx->d_texs.back().release();
         ctx->d_texs.pop_back();
+        ctx->d_quads.back().release();
+        ctx->d_quads.pop_back();
         return set_error(RWR_ERR_HIP, "texture upload failed: %s", hipGetErrorString(e));
     }
     const uint32_t vbase = (uint32_t)ctx->st_verts.size(), mid = (uint32_t)ctx->st_materials.size();
@@ -753,6 +808,12 @@ int rwr_scene_commit(rwr_context *ctx)
     RWR_HIP_CHECK(hipMemcpy(ctx->d_faces.ptr, ctx->st_faces.data(), ctx->st_faces.size() * sizeof(rwr_model_face_small), hipMemcpyHostToDevice));
     RWR_HIP_CHECK(hipMemcpy(ctx->d_face_mat.ptr, ctx->st_face_mat.data(), ctx->st_face_mat.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     RWR_HIP_CHECK(hipMemcpy(ctx->d_materials.ptr, ctx->st_materials.data(), ctx->st_materials.size() * sizeof(MaterialRec), hipMemcpyHostToDevice));
+    {
+        std::vector<const uint4 *> mq(ctx->d_quads.size());
+        for (size_t i = 0; i < mq.size(); i++) mq[i] = ctx->d_quads[i].ptr;
+        RWR_HIP_CHECK(ctx->d_mat_quads.ensure(mq.size()));
+        RWR_HIP_CHECK(hipMemcpy(ctx->d_mat_quads.ptr, mq.data(), mq.size() * sizeof(const uint4 *), hipMemcpyHostToDevice));
+    }
     ctx->tex_w = ctx->st_materials[0].tex_w;
     ctx->tex_h = ctx->st_materials[0].tex_h;
     ctx->tris_dirty = true;
@@ -987,6 +1048,7 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
     fp.n_materials = (uint32_t)ctx->st_materials.size();
     fp.tangents = ctx->d_tangent.ptr;
     const float4 *tex0 = ctx->d_texs.empty() ? nullptr : ctx->d_texs[0].ptr;
+    const QuadTex quad_tex{ctx->d_quads.empty() ? nullptr : ctx->d_quads[0].ptr, ctx->d_mat_quads.ptr, ctx->d_srgb_lut.ptr};
     Targets tg{sl.d_color.ptr, sl.d_depth.ptr, aux ? sl.d_color_f32.ptr : nullptr,
                aux ? sl.d_obj_id.ptr : nullptr, aux ? sl.d_hit_t.ptr : nullptr};
     CullConsts cc;
@@ -1046,7 +1108,7 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
             hipGraph_t g = nullptr;
             RWR_HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
             hipError_t e = launch_frame_setup(stream, cc, *camera, ctx->screen.width, ctx->screen.height, ctx->d_cull.ptr, ctx->d_tris.ptr, ctx->n_tris, so);
-            if (e == hipSuccess) e = launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg);
+            if (e == hipSuccess) e = launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, quad_tex, tg);
             const hipError_t e2 = hipStreamEndCapture(stream, &g);
             RWR_HIP_CHECK(e);
             RWR_HIP_CHECK(e2);
@@ -1104,7 +1166,7 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
         fs.flag_base = sl.fused_count;
         sl.fused_count += fs.n_blocks;   // (modulo 2^32, like the device's count)
         sl.fused_used = true;
-        RWR_HIP_CHECK(launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg, nullptr, nullptr, &fs));
+        RWR_HIP_CHECK(launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, quad_tex, tg, nullptr, nullptr, &fs));
         sl.aux_valid = false;
         ctx->last_spp = 0;
         ctx->last_had_bounce = false;
@@ -1175,7 +1237,7 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
         if ((rp.flags & RWR_FLAG_ONE_PIXEL_PER_LANE) || ctx->force_one_pixel)
             RWR_HIP_CHECK(launch_primary(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg));
         else
-            RWR_HIP_CHECK(launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg,
+            RWR_HIP_CHECK(launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, quad_tex, tg,
                                             dispatch_timed ? ctx->timing_events[2 * ctx->timing_pairs] : nullptr,
                                             dispatch_timed ? ctx->timing_events[2 * ctx->timing_pairs + 1] : nullptr));
         ctx->last_spp = 0;

@@ -4,9 +4,11 @@
 // as the one-pixel-per-lane form (RWR_FLAG_ONE_PIXEL_PER_LANE and the wavefront integrator's first stage).
 //   wave64 = 32x4 pixel tile, lane l owns pixels (2*(l&15), l>>4) and (2*(l&15)+1, l>>4);
 //   workgroup (4 waves, 2x2 tiles) = 64x8 pixels = one screen-bin column (kBinW).
-//   Each wave culls the faces for its own tile, 64 at a time, one per lane, from the per-frame
-//   records of k_frame_setup, and runs the exact test on the survivors in ascending face order with
-//   the face record in scalar registers.  No LDS, no barrier.
+//   The workgroup loads the per-frame culling records of k_frame_setup for its (bin's) face list once,
+//   256 at a time, into LDS; each wave culls them for its own tile, 64 at a time, one per lane, and runs
+//   the exact test on the survivors in ascending face order with the face record in scalar registers.
+//   The diffuse texture is read as one quad record per pixel (rwr_internal.h QuadTex) decoded through an
+//   LDS copy of the sRGB table: one vector-memory instruction per pixel instead of four.
 #include <hip/hip_ext.h>
 
 #include "rwr_frame_setup.h"
@@ -40,7 +42,7 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
              uint32_t n_tris, uint32_t row_begin, uint32_t bins_enabled, uint32_t row_pitch,
              int32_t mesh_x0, int32_t mesh_y0, int32_t mesh_x1, int32_t mesh_y1,
              const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
-             const float4 *__restrict__ tex, const Targets tg, const FusedSetup fs)
+             const QuadTex tex, const Targets tg, const FusedSetup fs)
 {
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     uint32_t by = blockIdx.y;
@@ -100,34 +102,60 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
     constexpr float kTileWf = 16.0f, kTileHf = 8.0f;
 #endif
 
-    // -- candidate faces of this wave's tile: the first 64 culling records are requested before anything
-    // else, so that their latency hides behind the ray generation ------------------------------
-    uint32_t n_src = n_tris;
+    // -- candidate faces of the workgroup: its bin's list (binned scenes) or the whole scene.  The four tiles lie in one
+    // bin (a workgroup's 8 rows start on a multiple of 8 rows from row_begin: launch_primary_p2 checks row_pitch), so
+    // the list is the same for all four waves, and its culling records are loaded once per workgroup: wave w
+    // requests entries [64 w, 64 w + 64) of each round of 256 before anything else, so that their latency hides
+    // behind the ray generation, and puts them in LDS, where every wave reads the ones it culls against ------------
+    const uint32_t wu = __builtin_amdgcn_readfirstlane(wave);
+    uint32_t n_list = n_tris;
     const uint32_t *__restrict__ src = nullptr;
-    if (CULL && bins_enabled) {
-        const uint32_t bin = ((tile_y0 - row_begin) / kBinH) * p.bins.bins_x + blk_x0 / kBinW;
-        const uint32_t off = p.bins.offsets[bin];
-        if (off != kBinNoList) {   // (kBinNoList: this frame's lists did not fit; walk the whole scene)
-            n_src = p.bins.counts[bin];
-            src = p.bins.lists + off;
+    bool live = true;   // (wave-uniform) this wave's tile overlaps the screen rectangle of the whole mesh
+    if (CULL) {
+        if (bins_enabled) {
+            const uint32_t bin = ((by * row_pitch) / kBinH) * p.bins.bins_x + blk_x0 / kBinW;
+            const uint32_t off = p.bins.offsets[bin];
+            if (off != kBinNoList) {   // (kBinNoList: this frame's lists did not fit; walk the whole scene)
+                n_list = p.bins.counts[bin];
+                src = p.bins.lists + off;
+            }
         }
-    }
-    n_src = __builtin_amdgcn_readfirstlane(n_src);
-    if (CULL) {  // the tile lies outside the screen rectangle of the whole mesh: scalar integer compares
-        const int32_t wu = __builtin_amdgcn_readfirstlane((int32_t)wave);
+        // scalar integer compares against the mesh rectangle: the wave's tile, and the workgroup's (no wave has work
+        // when the workgroup's rectangle is outside, and then no record is loaded)
+        const int32_t bx0 = (int32_t)blk_x0, by0 = (int32_t)(row_begin + by * row_pitch);
 #if RWR_P2_TILE_32x4
-        const int32_t sx0 = (int32_t)blk_x0 + (wu & 1) * 32, sy0 = (int32_t)(row_begin + by * row_pitch) + (wu >> 1) * 4;
+        const int32_t sx0 = bx0 + (int32_t)(wu & 1u) * 32, sy0 = by0 + (int32_t)(wu >> 1) * 4;
         const int32_t sx1 = sx0 + 32, sy1 = sy0 + 4;
 #else
-        const int32_t sx0 = (int32_t)blk_x0 + wu * 16, sy0 = (int32_t)(row_begin + by * row_pitch);
+        const int32_t sx0 = bx0 + (int32_t)wu * 16, sy0 = by0;
         const int32_t sx1 = sx0 + 16, sy1 = sy0 + 8;
 #endif
-        if (sx1 < mesh_x0 || sx0 > mesh_x1 || sy1 < mesh_y0 || sy0 > mesh_y1) n_src = 0u;
+        if (sx1 < mesh_x0 || sx0 > mesh_x1 || sy1 < mesh_y0 || sy0 > mesh_y1) live = false;
+        if (bx0 + 64 < mesh_x0 || bx0 > mesh_x1 || by0 + 8 < mesh_y0 || by0 > mesh_y1) n_list = 0u;
     }
-    bool valid = lane < n_src;
-    uint32_t face = (valid && src) ? src[lane] : lane;
-    FrameTri cur;
-    if (CULL && valid) cur = ftris[face];
+    n_list = __builtin_amdgcn_readfirstlane(n_list);
+    __shared__ float4 s_rec[CULL ? 4 : 1][CULL ? 256 : 1];   // round's culling records, one plane per 16 B of FrameTri
+    __shared__ uint32_t s_face[CULL ? 256 : 1];              // ... and their face indices
+    __shared__ float s_lut[256];                             // sRGB decode table of the quad texels (rwr_internal.h QuadTex)
+    // The records and the table go from memory to LDS without passing through registers (LDS DMA: lane l of wave w
+    // writes 16 / 4 bytes at M0 + 16 l / 4 l); rwait() waits for them before the barrier that publishes them.
+    const uint32_t slot = 64u * wu + lane;
+    auto load_round = [&](uint32_t base) {   // wave w: entries [base + 64 w, base + 64 w + 64) of the list
+        const uint32_t e = base + slot;
+        if (e < n_list) {
+            const uint32_t f = src ? src[e] : e;
+            s_face[slot] = f;
+            const char *r = reinterpret_cast<const char *>(ftris + f);
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)(r + 16 * k),
+                                                 (__attribute__((address_space(3))) void *)&s_rec[k][64u * wu], 16, 0, 0);
+        }
+    };
+    auto rwait = []() { __builtin_amdgcn_s_waitcnt(0xF70); };   // vmcnt(0)
+    if constexpr (CULL) load_round(0u);
+    __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)(tex.lut + threadIdx.x),
+                                     (__attribute__((address_space(3))) void *)&s_lut[64u * wu], 4, 0, 0);
 
     const f3 O = ld3(p.cam.origin);
     const v3 D = pixel_pair_ray_dir_tab(p.cam, ray_colp, ray_row, px0, py);
@@ -162,33 +190,65 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
     uint32_t dbg_listed = 0, dbg_tested = 0;
     uint32_t n_tested = 0;  // wave-uniform
     ShadeRec last_shade = {};  // of the face tested last (scalar registers)
-    {
-        // Each wave culls for its own tile, 64 faces at a time, one per lane (rwr_cull.h), and walks
-        // the survivors in ascending face order: no LDS, no barrier.  The next 64 records are requested
-        // before the exact tests of the current ones.
+    if constexpr (CULL) {
+        // Each wave culls the round's records for its own tile, 64 at a time, one per lane (rwr_cull.h), and walks the
+        // survivors in ascending face order.  Every wave reaches every barrier: n_list is the workgroup's (a wave
+        // outside the mesh rectangle loads its share and keeps no face).
         const TileRect tile_rect = {tx0, ty0, tx0 + kTileWf, ty0 + kTileHf};
-        for (uint32_t base = 0; base < n_src; base += 64u) {
-            bool keep = valid;
-            if (CULL && keep) keep = !rect_culls(cur, tile_rect);
-            unsigned long long m = __ballot(keep);
-            const uint32_t my_face = face;
-            const uint32_t e = base + 64u + lane;
-            valid = e < n_src;
-            face = (valid && src) ? src[e] : e;
-            if (CULL && valid) cur = ftris[face];
+        for (uint32_t base = 0; base < n_list; base += 256u) {
+            if (base) {   // lists of more than 256 faces: every wave is done with the previous round
+                __syncthreads();
+                load_round(base);
+            }
+            rwait();
+            __syncthreads();
+            const uint32_t n_round = min(n_list - base, 256u);
+            for (uint32_t b = 0; b < n_round; b += 64u) {
+                const uint32_t i = b + lane;
+                bool keep = live && i < n_round;
+                uint32_t my_face = 0u;
+                if (keep) {
+                    const float4 q0 = s_rec[0][i], q1 = s_rec[1][i], q2 = s_rec[2][i], q3 = s_rec[3][i];
+                    const FrameTri rec = {q0.x, q0.y, q0.z, q0.w, {q1.x, q1.y, q1.z}, q1.w,
+                                          {q2.x, q2.y, q2.z}, q2.w, {q3.x, q3.y, q3.z}, q3.w};
+                    my_face = s_face[i];
+                    keep = !rect_culls(rec, tile_rect);
+                }
+                unsigned long long m = __ballot(keep);
+                if (AUX) dbg_listed += (uint32_t)__popcll(m);
+                while (m) {
+                    const uint32_t bit = (uint32_t)__builtin_ctzll(m);
+                    m &= m - 1ull;
+                    // wave-uniform face index: the record comes in through scalar loads
+                    const uint32_t idx = (uint32_t)__builtin_amdgcn_readlane((int)my_face, (int)bit);
+                    if (FUSED) {
+                        intersect_and_select(load_tri_record(tris_c + idx), tnum_c[idx], idx, O, D, best);
+                        last_shade = load_shade_record(shade_c + idx);
+                    } else {
+                        intersect_and_select(tris[idx], p.tnum[idx], idx, O, D, best);
+                        last_shade = shade[idx];
+                    }
+                    n_tested++;
+                    if (AUX) dbg_tested++;
+                }
+            }
+        }
+        if (n_list == 0u) {   // (the table's barrier when no round ran)
+            rwait();
+            __syncthreads();
+        }
+    } else {
+        rwait();   // (the table's)
+        __syncthreads();
+        // no culling: every face, in ascending order
+        for (uint32_t base = 0; base < n_list; base += 64u) {
+            unsigned long long m = __ballot(base + lane < n_list);
             if (AUX) dbg_listed += (uint32_t)__popcll(m);
             while (m) {
-                const uint32_t b = (uint32_t)__builtin_ctzll(m);
+                const uint32_t idx = base + (uint32_t)__builtin_ctzll(m);
                 m &= m - 1ull;
-                // wave-uniform face index: the record comes in through scalar loads
-                const uint32_t idx = (uint32_t)__builtin_amdgcn_readlane((int)my_face, (int)b);
-                if (FUSED) {
-                    intersect_and_select(load_tri_record(tris_c + idx), tnum_c[idx], idx, O, D, best);
-                    last_shade = load_shade_record(shade_c + idx);
-                } else {
-                    intersect_and_select(tris[idx], p.tnum[idx], idx, O, D, best);
-                    last_shade = shade[idx];
-                }
+                intersect_and_select(tris[idx], p.tnum[idx], idx, O, D, best);
+                last_shade = shade[idx];
                 n_tested++;
                 if (AUX) dbg_tested++;
             }
@@ -244,10 +304,12 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
     }
     if (__any(any2(obj >= 0))) {  // wave-uniform; lanes without a mesh winner shade face 0 and drop the result
         f2 cr, cg, cb;
-        if (NMAP) shade_mesh_pair<true, false, true>(p, shade, tex, obj, last_shade, best, D, cr, cg, cb);   // (per-face material path)
-        else if (p.n_materials > 1u) shade_mesh_pair<true, false>(p, shade, tex, obj, last_shade, best, D, cr, cg, cb);
-        else if (n_tested == 1u) shade_mesh_pair<false, true>(p, shade, tex, obj, last_shade, best, D, cr, cg, cb);
-        else shade_mesh_pair<false, false>(p, shade, tex, obj, last_shade, best, D, cr, cg, cb);
+        QuadTex qt = tex;
+        qt.lut = s_lut;   // the decode table in LDS (filled above, behind the barriers of the mesh pass)
+        if (NMAP) shade_mesh_pair<true, false, true, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);   // (per-face material path)
+        else if (p.n_materials > 1u) shade_mesh_pair<true, false, false, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);
+        else if (n_tested == 1u) shade_mesh_pair<false, true, false, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);
+        else shade_mesh_pair<false, false, false, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);
         // rgba8unorm conversion of both pixels (rwr_device.h); alpha 2.0 -> 255
         const f2 sr = cr * 255.0f, sg = cg * 255.0f, sb = cb * 255.0f;
         const uint32_t m0 = pack_rgba8_scaled(sr.x, sg.x, sb.x, 0xff000000u);
@@ -288,10 +350,12 @@ uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks)
 }
 
 hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
-                             const FrameTri *ftris, const float4 *tex, const Targets &tg, hipEvent_t ev_start,
+                             const FrameTri *ftris, const QuadTex &tex, const Targets &tg, hipEvent_t ev_start,
                              hipEvent_t ev_stop, const FusedSetup *fused)
 {
     if (fp.row_end <= fp.row_begin || fp.width == 0) return hipSuccess;
+    if (fp.row_pitch % kStripRows != 0u) return hipErrorInvalidValue;   // a workgroup's four tiles must share a screen bin
+    if (!tex.lut) return hipErrorInvalidValue;
     const dim3 grid((fp.width + 63u) / 64u, band_strips(fp) + (fused ? fused->extra_rows : 0u));
     const dim3 block(256);
     const bool aux = (fp.flags & RWR_FLAG_AUX_OUTPUTS) != 0;

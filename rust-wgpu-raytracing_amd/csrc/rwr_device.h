@@ -230,6 +230,17 @@ RWR_DEV TexTaps tex_taps(uint32_t pitch, float wmax, float hmax, f2 fxy)
     t.a = fxy - f0;
     return t;
 }
+// the bilinear blend of the four taps' (r, g, b) at fractional position a: tex_filter's operations (quad_filter's)
+RWR_DEV f3 tex_blend(const float4 &t00, const float4 &t10, const float4 &t01, const float4 &t11, f2 a)
+{
+    const f2 b = 1.0f - a;
+    const float w00 = b.x * b.y, w10 = a.x * b.y, w01 = b.x * a.y, w11 = a.x * a.y;
+    // (r, g) as a pair (adjacent in the loaded texel), b alone
+    const f2 rg = fma2(f2{t11.x, t11.y}, splat(w11), fma2(f2{t01.x, t01.y}, splat(w01),
+                  fma2(f2{t10.x, t10.y}, splat(w10), f2{t00.x, t00.y} * w00)));
+    const float bl = __builtin_fmaf(t11.z, w11, __builtin_fmaf(t01.z, w01, __builtin_fmaf(t10.z, w10, t00.z * w00)));
+    return mk3(rg.x, rg.y, bl);
+}
 RWR_DEV f3 tex_filter(const float4 *__restrict__ tex, const TexTaps &t)
 {
     const char *base = reinterpret_cast<const char *>(tex);
@@ -248,6 +259,35 @@ RWR_DEV f3 tex_filter(const float4 *__restrict__ tex, const TexTaps &t)
 RWR_DEV f3 tex_sample_bilinear(const float4 *__restrict__ tex, uint32_t pitch, float wmax, float hmax, f2 fxy)
 {
     return tex_filter(tex, tex_taps(pitch, wmax, hmax, fxy));
+}
+
+// The same fetch and filter from the quad form of the texture (rwr_internal.h QuadTex): the 2x2 footprint is the one
+// record at p = (med3(f0.x, -1, wmax) + 1, med3(f0.y, -1, hmax) + 1), f0 = floor(fxy), which holds exactly the taps
+// tex_taps picks (a NaN position: v_med3 returns one of its finite operands, so p stays inside the (w+1) x (h+1) grid).
+// Its texels' channels are byte offsets into the decode table `lut` (in LDS): the same floats as the float4 texels, and the
+// same blend.  qw = w + 1 (<= kMaxTextureDim + 1, so py * qw + px < 2^29 is a v_mul_u32_u24 + add; the byte offset of
+// the record is formed in 64 bits).
+struct QuadTap { uint32_t idx; f2 a; };
+RWR_DEV QuadTap quad_tap(uint32_t qw, float wmax, float hmax, f2 fxy)
+{
+    const f2 f0 = f2{floorf(fxy.x), floorf(fxy.y)};
+    const uint32_t px = (uint32_t)(__builtin_amdgcn_fmed3f(f0.x, -1.0f, wmax) + 1.0f);
+    const uint32_t py = (uint32_t)(__builtin_amdgcn_fmed3f(f0.y, -1.0f, hmax) + 1.0f);
+    QuadTap t;
+    t.idx = __umul24(py, qw) + px;
+    t.a = fxy - f0;
+    return t;
+}
+RWR_DEV float4 quad_texel(const float *lut, uint32_t w)
+{
+    const char *l = reinterpret_cast<const char *>(lut);
+    return make_float4(*reinterpret_cast<const float *>(l + (w & 0x3fcu)), *reinterpret_cast<const float *>(l + ((w >> 10) & 0x3fcu)),
+                       *reinterpret_cast<const float *>(l + (w >> 20)), 0.0f);
+}
+RWR_DEV f3 quad_filter(const uint4 *__restrict__ quad, const float *lut, const QuadTap &t)
+{
+    const uint4 q = quad[t.idx];
+    return tex_blend(quad_texel(lut, q.x), quad_texel(lut, q.y), quad_texel(lut, q.z), quad_texel(lut, q.w), t.a);
 }
 
 // Mesh shading, triangle_list/compute.wgsl:217-234 (colour path: see the header), in three steps

@@ -68,6 +68,20 @@ struct alignas(16) MaterialRec {
 };
 static_assert(sizeof(MaterialRec) == 64, "MaterialRec is 64 B");
 
+// The frame kernel's (k_primary_p2) form of the diffuse textures: one 16-byte "quad" record per bilinear footprint, so that
+// a pixel's four taps are ONE vector-memory instruction (the texture addresser's cost is per instruction, not per byte).
+// Record (px, py), px in [0, w], py in [0, h], row pitch w + 1, holds the texels (cx(px-1), cy(py-1)), (cx(px), cy(py-1)),
+// (cx(px-1), cy(py)), (cx(px), cy(py)) with cx / cy ClampToEdge on [0, w-1] / [0, h-1].  A texel is one dword
+// r << 2 | g << 12 | b << 22 of its sRGB bytes: each channel's byte offset into the 256-float decode table
+// (build_srgb_lut), which the kernel keeps in LDS.  Alpha is not stored: shading never reads it.
+struct QuadTex {
+    const uint4 *quad0;         // material 0
+    const uint4 *const *mats;   // per material (n_materials > 1)
+    const float *lut;           // build_srgb_lut's table (device memory; the kernel copies it to LDS)
+};
+// host: the (w + 1) * (h + 1) records of a w x h RGBA8 image, 4 dwords each
+void build_tex_quads(const uint8_t *rgba8, uint32_t w, uint32_t h, uint32_t *out);
+
 // Per-face tangent frame for normal-mapped shading (extension; 32 B, made by k_prebake in double and rounded once):
 // t = normalize(dP/du - n (n . dP/du)), b = +-cross(n, t) towards -dP/dv' (v' = 1 - v: the sampling space of
 // compute.wgsl:224; the map's green axis points up the image); zeros for degenerate texture coordinates.
@@ -262,7 +276,7 @@ struct BvhDevice {
 
 struct FusedSetup;
 hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
-                             const FrameTri *ftris, const float4 *tex, const Targets &tg, hipEvent_t ev_start = nullptr,
+                             const FrameTri *ftris, const QuadTex &tex, const Targets &tg, hipEvent_t ev_start = nullptr,
                              hipEvent_t ev_stop = nullptr, const FusedSetup *fused = nullptr);
 // grid rows the fused form puts in front of the frame's strips for `n_blocks` record-making workgroups
 uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks);
