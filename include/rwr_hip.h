@@ -415,6 +415,13 @@ RWR_API int rwr_accum_samples(rwr_context *ctx, uint64_t *samples);
  * mismatches}.  A non-zero mismatch count is a bug. */
 RWR_API int rwr_selftest_exact_math(rwr_context *ctx, uint32_t normalize_count, uint32_t seed, uint64_t out4[4]);
 
+/* Self-test of the frame kernel's short exact form of the hit test's plane distance t = tnum / ndotd (compute.wgsl:99-102):
+ * `count` rounds of pseudo-random operand pairs, a wave-uniform numerator per wave as in the hit test, plus the edges of
+ * the form's domain.  out4 = {in-domain quotients compared with the IEEE division, mismatches, quotients the hit test
+ * takes (|ndotd| >= kEpsilon or NaN) compared through the kernel's choice of short form or IEEE division, mismatches}.
+ * A non-zero mismatch count is a bug. */
+RWR_API int rwr_selftest_exact_div(rwr_context *ctx, uint32_t count, uint32_t seed, uint64_t out4[4]);
+
 /* Measurement aid for roofline accounting (bench.py): runs a short f32 VALU loop with `waves_per_simd` (1..8)
  * waves on every SIMD and stamps the shader cycle counter against the constant 100 MHz counter.
  * out4 = {shader clock in MHz under v_fma_f32 load, shader cycles a SIMD spends per wave64 v_fma_f32,

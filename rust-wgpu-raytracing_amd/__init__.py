@@ -115,7 +115,7 @@ def lib() -> C.CDLL:
         "rwr_make_instance_grid": [u32, f32, vp],
         "rwr_write_png_rgba8": [C.c_char_p, vp, u32, u32, i32, i32],
         "rwr_ctx_set_kernel_timing": [vp, u32], "rwr_kernel_timing_stats": [vp, vp, vp],
-        "rwr_selftest_exact_math": [vp, u32, u32, vp], "rwr_ctx_set_frames_in_flight": [vp, u32],
+        "rwr_selftest_exact_math": [vp, u32, u32, vp], "rwr_selftest_exact_div": [vp, u32, u32, vp], "rwr_ctx_set_frames_in_flight": [vp, u32],
         "rwr_dist_get_unique_id": [vp], "rwr_dist_init": [vp, i32, i32, vp], "rwr_dist_band": [u32, u32, u32, vp, vp],
         "rwr_dist_gather_rgba8": [vp, i32], "rwr_dist_gather_strips_rgba8": [vp, i32], "rwr_dist_frame": [vp, vp], "rwr_dist_readback": [vp, vp],
         "rwr_dist_barrier": [vp], "rwr_dist_destroy": [vp],
@@ -525,6 +525,11 @@ class Context:
     def selftest_exact_math(self, normalize_count: int = 1 << 30, seed: int = 1) -> tuple[int, int, int, int]:
         out = (C.c_uint64 * 4)()
         _check(lib().rwr_selftest_exact_math(self._h, normalize_count, seed, out))
+        return tuple(int(v) for v in out)
+
+    def selftest_exact_div(self, count: int = 1 << 30, seed: int = 1) -> tuple[int, int, int, int]:
+        out = (C.c_uint64 * 4)()
+        _check(lib().rwr_selftest_exact_div(self._h, count, seed, out))
         return tuple(int(v) for v in out)
 
     def measure_valu_clock(self, waves_per_simd: int = 8) -> dict:

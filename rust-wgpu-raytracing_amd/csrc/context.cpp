@@ -1633,6 +1633,25 @@ int rwr_selftest_exact_math(rwr_context *ctx, uint32_t normalize_count, uint32_t
     return RWR_OK;
 }
 
+int rwr_selftest_exact_div(rwr_context *ctx, uint32_t count, uint32_t seed, uint64_t out4[4])
+{
+    if (!ctx || !out4) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    DeviceGuard g(ctx->device);
+    struct Scoped {
+        DeviceBuffer<unsigned long long> b;
+        ~Scoped() { b.release(); }
+    } scoped;
+    DeviceBuffer<unsigned long long> &d_out = scoped.b;
+    RWR_HIP_CHECK(d_out.ensure(4));
+    RWR_HIP_CHECK(hipMemsetAsync(d_out.ptr, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    RWR_HIP_CHECK(launch_selftest_exact_div(ctx->stream, d_out.ptr, count, seed));
+    unsigned long long h[4];
+    RWR_HIP_CHECK(hipMemcpyAsync(h, d_out.ptr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    RWR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 4; k++) out4[k] = h[k];
+    return RWR_OK;
+}
+
 int rwr_measure_valu_clock(rwr_context *ctx, uint32_t waves_per_simd, double out4[4])
 {
     if (!ctx || !out4) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");

@@ -189,7 +189,9 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
     best.idx = u2{0u, 0u};
     uint32_t dbg_listed = 0, dbg_tested = 0;
     uint32_t n_tested = 0;  // wave-uniform
-    ShadeRec last_shade = {};  // of the face tested last (scalar registers)
+    uint32_t last_idx = 0;  // (wave-uniform) the face tested last: a wave that tested exactly one face loads its shading
+                            // record for the shading step, into scalar registers (carried through the loop, the record's
+                            // 11 dwords lived in vector registers)
     if constexpr (CULL) {
         // Each wave culls the round's records for its own tile, 64 at a time, one per lane (rwr_cull.h), and walks the
         // survivors in ascending face order.  Every wave reaches every barrier: n_list is the workgroup's (a wave
@@ -204,30 +206,23 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
             __syncthreads();
             const uint32_t n_round = min(n_list - base, 256u);
             for (uint32_t b = 0; b < n_round; b += 64u) {
+                // every lane reads and culls its slot (i < 256: inside the arrays), the slots past the round's end are
+                // dropped by the ballot: no branch, and the lane mask comes straight from the compares
                 const uint32_t i = b + lane;
-                bool keep = live && i < n_round;
-                uint32_t my_face = 0u;
-                if (keep) {
-                    const float4 q0 = s_rec[0][i], q1 = s_rec[1][i], q2 = s_rec[2][i], q3 = s_rec[3][i];
-                    const FrameTri rec = {q0.x, q0.y, q0.z, q0.w, {q1.x, q1.y, q1.z}, q1.w,
-                                          {q2.x, q2.y, q2.z}, q2.w, {q3.x, q3.y, q3.z}, q3.w};
-                    my_face = s_face[i];
-                    keep = !rect_culls(rec, tile_rect);
-                }
-                unsigned long long m = __ballot(keep);
+                const float4 q0 = s_rec[0][i], q1 = s_rec[1][i], q2 = s_rec[2][i], q3 = s_rec[3][i];
+                const FrameTri rec = {q0.x, q0.y, q0.z, q0.w, {q1.x, q1.y, q1.z}, q1.w,
+                                      {q2.x, q2.y, q2.z}, q2.w, {q3.x, q3.y, q3.z}, q3.w};
+                const uint32_t my_face = s_face[i];
+                unsigned long long m = live ? __builtin_amdgcn_ballot_w64(i < n_round && !rect_culls(rec, tile_rect)) : 0ull;
                 if (AUX) dbg_listed += (uint32_t)__popcll(m);
                 while (m) {
                     const uint32_t bit = (uint32_t)__builtin_ctzll(m);
                     m &= m - 1ull;
                     // wave-uniform face index: the record comes in through scalar loads
                     const uint32_t idx = (uint32_t)__builtin_amdgcn_readlane((int)my_face, (int)bit);
-                    if (FUSED) {
-                        intersect_and_select(load_tri_record(tris_c + idx), tnum_c[idx], idx, O, D, best);
-                        last_shade = load_shade_record(shade_c + idx);
-                    } else {
-                        intersect_and_select(tris[idx], p.tnum[idx], idx, O, D, best);
-                        last_shade = shade[idx];
-                    }
+                    if (FUSED) intersect_and_select(load_tri_record(tris_c + idx), tnum_c[idx], idx, O, D, best);
+                    else intersect_and_select(tris[idx], to_const_space(p.tnum)[idx], idx, O, D, best);
+                    last_idx = idx;
                     n_tested++;
                     if (AUX) dbg_tested++;
                 }
@@ -247,8 +242,8 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
             while (m) {
                 const uint32_t idx = base + (uint32_t)__builtin_ctzll(m);
                 m &= m - 1ull;
-                intersect_and_select(tris[idx], p.tnum[idx], idx, O, D, best);
-                last_shade = shade[idx];
+                intersect_and_select(tris[idx], to_const_space(p.tnum)[idx], idx, O, D, best);
+                last_idx = idx;
                 n_tested++;
                 if (AUX) dbg_tested++;
             }
@@ -306,10 +301,14 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
         f2 cr, cg, cb;
         QuadTex qt = tex;
         qt.lut = s_lut;   // the decode table in LDS (filled above, behind the barriers of the mesh pass)
-        if (NMAP) shade_mesh_pair<true, false, true, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);   // (per-face material path)
-        else if (p.n_materials > 1u) shade_mesh_pair<true, false, false, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);
-        else if (n_tested == 1u) shade_mesh_pair<false, true, false, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);
-        else shade_mesh_pair<false, false, false, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);
+        const ShadeRec unused = {};   // (the per-pixel paths load their records themselves)
+        if (NMAP) shade_mesh_pair<true, false, true, FrameParams, QuadTex>(p, shade, qt, obj, unused, best, D, cr, cg, cb);   // (per-face material path)
+        else if (p.n_materials > 1u) shade_mesh_pair<true, false, false, FrameParams, QuadTex>(p, shade, qt, obj, unused, best, D, cr, cg, cb);
+        else if (n_tested == 1u) {
+            // the one face the wave tested (so the scene has faces and the record array exists): every mesh winner shows it
+            const ShadeRec last_shade = FUSED ? load_shade_record(shade_c + last_idx) : shade[last_idx];
+            shade_mesh_pair<false, true, false, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);
+        } else shade_mesh_pair<false, false, false, FrameParams, QuadTex>(p, shade, qt, obj, unused, best, D, cr, cg, cb);
         // rgba8unorm conversion of both pixels (rwr_device.h); alpha 2.0 -> 255
         const f2 sr = cr * 255.0f, sg = cg * 255.0f, sb = cb * 255.0f;
         const uint32_t m0 = pack_rgba8_scaled(sr.x, sg.x, sb.x, 0xff000000u);

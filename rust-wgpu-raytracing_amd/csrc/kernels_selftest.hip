@@ -5,8 +5,10 @@
 //   * normalize3_fast vs normalize3: 2^30 pseudo-random vectors spread over the whole domain of
 //     normalize_fast_domain and a little beyond it (exponents 2^-44 .. 2^43 per component, all sign combinations;
 //     vectors outside the domain are skipped, as the kernel skips them), plus the
-//     two-wide form.
-// Run through rwr_selftest_exact_math() by tests/test_gpu_exact_math.py.
+//     two-wide form;
+//   * the hit test's t = tnum / ndotd (rwr_device_p2.h hit_t): 2^30 rounds of pseudo-random pairs and the domain edges.
+// Run through rwr_selftest_exact_math() by tests/test_gpu_exact_math.py and rwr_selftest_exact_div() by
+// tests/test_gpu_exact_div.py.
 #include "rwr_device_p2.h"
 
 namespace rwr {
@@ -47,8 +49,9 @@ __global__ void __launch_bounds__(256)
 k_selftest_normalize(unsigned long long *out, uint32_t count, uint32_t seed)  // out[2] compared, out[3] mismatches
 {
     unsigned long long n = 0, bad = 0;
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;   // (64-bit: a count near 2^32 must not wrap the loop)
+    for (uint64_t i64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i64 < count; i64 += stride) {
+        const uint32_t i = (uint32_t)i64;
         f3 a = mk3(selftest_component(i, 0u, seed), selftest_component(i, 1u, seed), selftest_component(i, 2u, seed));
         if ((i & 7u) == 0u) {  // every eighth vector: comparable magnitudes (what a camera produces)
             const float s = __builtin_fabsf(a.x);
@@ -69,6 +72,75 @@ k_selftest_normalize(unsigned long long *out, uint32_t count, uint32_t seed)  //
     }
     atomicAdd(&out[2], n);
     atomicAdd(&out[3], bad);
+}
+
+// arbitrary float: sign, exponent in [emin, emin + span), 23 random mantissa bits
+RWR_DEV float selftest_float(uint32_t i, uint32_t k, uint32_t seed, int emin, uint32_t span)
+{
+    const uint32_t h = rng_hash(i, k, 0u, seed), g = rng_hash(i, k, 1u, seed);
+    const uint32_t expo = (uint32_t)(127 + emin) + g % span;
+    return __uint_as_float((h & 0x80000000u) | (expo << 23) | (h & 0x007fffffu));
+}
+
+// operands at and just beyond the edges of hit_t's domain, and the special values
+__constant__ const float kDivEdgeNum[] = {0x1p-40f, -0x1p-40f, 0x1.fffffep-41f, -0x1.fffffep-41f, 0x1p40f, -0x1p40f, 0x1.000002p40f,
+                                          -0x1.000002p40f, 0.0f, -0.0f, 0x1p-126f, 0x1p-149f, -0x1p-140f, __builtin_inff(), -__builtin_inff(),
+                                          __builtin_nanf(""), 1.0f, -3.0f, 0x1.234566p-20f, 0x1.fffffep39f};
+__constant__ const float kDivEdgeDen[] = {kEpsilon, -kEpsilon, 0x1.0c6f7ap-20f, -0x1.0c6f7ap-20f, 0x1p40f, -0x1p40f, 0x1.000002p40f,
+                                          -0x1.000002p40f, 0x1p-40f, 0.0f, -0.0f, 0x1p-149f, -0x1p-126f, __builtin_inff(), -__builtin_inff(),
+                                          __builtin_nanf(""), 1.0f, -1.0f, 0x1.fffffep-1f, 0x1p-19f};
+constexpr uint32_t kDivEdges = sizeof(kDivEdgeNum) / sizeof(float);
+static_assert(sizeof(kDivEdgeDen) == sizeof(kDivEdgeNum), "edge lists");
+
+// hit_t (rwr_device_p2.h) against the IEEE quotient tnum / ndotd.  Every round: a wave-uniform numerator (as the face's
+// is in the hit test) and a pair of denominators per lane, exponents 2^-44 .. 2^43 and 2^-24 .. 2^43 (so that some waves
+// leave the domain).  out[0] / out[1]: in-domain elements compared through div_fast / mismatches; out[2] / out[3]: elements
+// with |ndotd| >= kEpsilon or NaN (those whose t the hit test takes) compared through hit_t, the wave-uniform choice of
+// short form or IEEE division / mismatches of t's bits or of its t < 0 mask.  Every eighth round puts edge operands in
+// the numerator and in a quarter of the lanes; three rounds in eight draw every operand of the wave inside the domain
+// (exponents 2^-40 .. 2^39 and 2^-19 .. 2^39), so that hit_t's own choice takes the short form there.
+__global__ void __launch_bounds__(256)
+k_selftest_div(unsigned long long *out, uint32_t count, uint32_t seed)
+{
+    unsigned long long n = 0, bad = 0, n_sel = 0, bad_sel = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;   // (64-bit: a count near 2^32 must not wrap the loop)
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < count; i0 += stride) {   // (wave-uniform loop)
+        const bool spare = i0 + threadIdx.x >= count;
+        const uint32_t i = (uint32_t)(i0 + threadIdx.x);
+        const uint32_t w = __builtin_amdgcn_readfirstlane(i >> 6);
+        const bool inside = (w & 7u) >= 1u && (w & 7u) <= 3u;
+        float tnum = inside ? selftest_float(w, 0u, seed, -40, 80u) : selftest_float(w, 0u, seed, -44, 88u);
+        f2 d = inside ? f2{selftest_float(i, 1u, seed, -19, 59u), selftest_float(i, 2u, seed, -19, 59u)}
+                      : f2{selftest_float(i, 1u, seed, -24, 68u), selftest_float(i, 2u, seed, -24, 68u)};
+        if ((w & 7u) == 0u) {
+            const uint32_t r = w >> 3;
+            tnum = kDivEdgeNum[r % kDivEdges];
+            if ((lane & 3u) == 0u) d = f2{kDivEdgeDen[(r / kDivEdges + lane) % kDivEdges], kDivEdgeDen[(r + lane / 4u) % kDivEdges]};
+        }
+        if (spare) d = splat(1.0f);   // (the last round's spare lanes: in the domain, not counted)
+        const f2 q = div_fast(splat(tnum), d);
+        const f2 t = hit_t(tnum, d, abs2(d));
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const float dk = k ? d.y : d.x, want = tnum / dk;
+            if (spare) continue;
+            const float ad = __builtin_fabsf(dk);
+            if (hit_div_num_domain(tnum) && ad >= kEpsilon && ad <= 0x1p40f) {
+                n++;
+                bad += !same_bits(k ? q.y : q.x, want);
+            }
+            if (!(ad < kEpsilon)) {
+                const float got = k ? t.y : t.x;
+                n_sel++;
+                bad_sel += !same_bits(got, want) || ((got < 0.0f) != (want < 0.0f));
+            }
+        }
+    }
+    atomicAdd(&out[0], n);
+    atomicAdd(&out[1], bad);
+    atomicAdd(&out[2], n_sel);
+    atomicAdd(&out[3], bad_sel);
 }
 
 // Shader clock and f32 VALU issue rate under load, for the roofline accounting of bench.py: every wave runs
@@ -122,6 +194,12 @@ k_clock_probe(ulonglong2 *out, uint32_t ticks)
     const uint64_t c1 = __builtin_amdgcn_s_memtime();
     r1 = __builtin_amdgcn_s_memrealtime();
     if (threadIdx.x == 0) out[0] = make_ulonglong2(c1 - c0, r1 - r0);
+}
+
+hipError_t launch_selftest_exact_div(hipStream_t s, unsigned long long *d_out4, uint32_t count, uint32_t seed)
+{
+    hipLaunchKernelGGL(k_selftest_div, dim3(8192), dim3(256), 0, s, d_out4, count, seed);
+    return hipGetLastError();
 }
 
 hipError_t launch_clock_probe(hipStream_t s, ulonglong2 *d_out, uint32_t ticks)

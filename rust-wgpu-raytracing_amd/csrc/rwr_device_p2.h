@@ -44,6 +44,15 @@ RWR_DEV bool normalize_fast_domain(v3 a)
 {
     return normalize_fast_domain(mk3(a.x.x, a.y.x, a.z.x)) && normalize_fast_domain(mk3(a.x.y, a.y.y, a.z.y));
 }
+// (wave-uniform) every active lane's pair in the domain: compares combined without branches, one lane mask per element
+RWR_DEV bool normalize_fast_domain_all(v3 a)
+{
+    const f2 x = abs2(a.x), y = abs2(a.y), z = abs2(a.z);
+    const float lo0 = __builtin_fminf(__builtin_fminf(x.x, y.x), z.x), hi0 = __builtin_fmaxf(__builtin_fmaxf(x.x, y.x), z.x);
+    const float lo1 = __builtin_fminf(__builtin_fminf(x.y, y.y), z.y), hi1 = __builtin_fmaxf(__builtin_fmaxf(x.y, y.y), z.y);
+    return (__builtin_amdgcn_ballot_w64(lo0 >= 0x1p-40f) & __builtin_amdgcn_ballot_w64(hi0 <= 0x1p40f) &
+            __builtin_amdgcn_ballot_w64(lo1 >= 0x1p-40f) & __builtin_amdgcn_ballot_w64(hi1 <= 0x1p40f)) == __builtin_amdgcn_read_exec();
+}
 RWR_DEV f2 div_shared_rcp(f2 n, f2 d, f2 r)
 {
     const f2 q0 = n * r;
@@ -62,6 +71,31 @@ RWR_DEV v3 normalize3_fast(v3 a)
     f2 r = f2{__builtin_amdgcn_rcpf(len.x), __builtin_amdgcn_rcpf(len.y)};
     r = fma2(fma2(-len, r, splat(1.0f)), r, r);
     return v3{div_shared_rcp(a.x, len, r), div_shared_rcp(a.y, len, r), div_shared_rcp(a.z, len, r)};
+}
+
+// The plane distance t = tnum / ndotd of the hit test (compute.wgsl:99-102) in 9 instead of 22 VALU instructions, the
+// same bits, when |tnum| lies in [2^-40, 2^40] (tnum is the face's, wave-uniform: a scalar test) and every active lane
+// with |ndotd| >= kEpsilon has |ndotd| <= 2^40: the compiler's IEEE expansion with its v_div_scale / v_div_fmas /
+// v_div_fixup left out, which are the identity on such operands (numerator above 2^-103, quotient in [2^-80, 2^60],
+// exponent difference below 96; cf. normalize3_fast).  A lane with |ndotd| < kEpsilon never takes its t (:94), so its
+// value is free; a NaN ndotd fails the test.  rwr_selftest_exact_div() compares it with the quotient on 2^30 in-domain
+// pairs and the domain edges (tests/test_gpu_exact_div.py).
+RWR_DEV bool hit_div_num_domain(float tnum) { return (__float_as_uint(tnum) & 0x7fffffffu) - 0x2b800000u <= 0x28000000u; }
+RWR_DEV bool hit_div_lanes_in_domain(f2 abs_ndotd)   // (wave-uniform) one compare and one lane mask per element
+{
+    return (__builtin_amdgcn_ballot_w64(abs_ndotd.x <= 0x1p40f) & __builtin_amdgcn_ballot_w64(abs_ndotd.y <= 0x1p40f)) ==
+           __builtin_amdgcn_read_exec();
+}
+RWR_DEV f2 div_fast(f2 n, f2 d)
+{
+    f2 r = f2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+    r = fma2(fma2(-d, r, splat(1.0f)), r, r);
+    return div_shared_rcp(n, d, r);
+}
+RWR_DEV f2 hit_t(float tnum, f2 ndotd, f2 abs_ndotd)
+{
+    if (hit_div_num_domain(tnum) && hit_div_lanes_in_domain(abs_ndotd)) return div_fast(splat(tnum), ndotd);
+    return tnum / ndotd;
 }
 
 // compute.wgsl:78-80
@@ -125,7 +159,7 @@ RWR_DEV v3 pixel_pair_ray_dir_tab(const rwr_camera_inv_uniform &cam, const float
     w.z = m[0][2] * vx + m[1][2] * vy + m[2][2] * vz + m[3][2] * vw;
     // same bits either way (rwr_device.h normalize3_fast); a wave with an axis-parallel or absurdly
     // scaled ray takes the compiler's division
-    if (__all(normalize_fast_domain(w))) return normalize3_fast(w);
+    if (normalize_fast_domain_all(w)) return normalize3_fast(w);
     return normalize3(w);
 }
 
@@ -163,8 +197,9 @@ RWR_DEV void intersect_and_select(const TriRecord &T, float tnum, uint32_t idx, 
     const f3 N1 = ld3(T.N);
     const v3 N = splat3(N1);
     const f2 ndotd = dot3(N, D);
-    i2 hit = ~(abs2(ndotd) < kEpsilon);                       // :94
-    const f2 t = tnum / ndotd;                                // :99-102
+    const f2 abs_ndotd = abs2(ndotd);
+    i2 hit = ~(abs_ndotd < kEpsilon);                         // :94
+    const f2 t = hit_t(tnum, ndotd, abs_ndotd);               // :99-102, same bits as tnum / ndotd
     hit &= ~(t < 0.0f);                                       // :105
     const v3 P = along(splat3(O), t, D);                      // :110
     v3 C = cross3(splat3(ld3(T.e0)), sub3(P, splat3(ld3(T.p0))));
