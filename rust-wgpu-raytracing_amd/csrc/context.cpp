@@ -113,6 +113,7 @@ struct FrameSlot {
     DeviceBuffer<FrameTri> d_ftris;
     DeviceBuffer<float> d_tnum;                  // per frame: plane-distance numerator per face
     DeviceBuffer<float4> d_ray_colp, d_ray_row;  // per frame: ray tables (FrameParams::ray_colp / ray_row)
+    DeviceBuffer<uint32_t> d_tile_lists;         // per frame: the two-pixel frame kernel's per-tile face sets (FrameParams::tile_lists)
     DeviceBuffer<uint32_t> d_bin_lists, d_bin_counts, d_bin_offsets, d_bin_total;   // per-frame screen bins (large scenes)
     uint32_t *h_bin_total = nullptr;   // pinned: entries the last binned frame of this slot needed (read a frame late, never waited for)
     bool aux_valid = false;
@@ -131,7 +132,7 @@ struct FrameSlot {
         frame_graph_key.clear();
         d_fused.release(); fused_count = 0; fused_blocks = 0; fused_used = false;
         d_color.release(); d_depth.release(); d_color_f32.release(); d_obj_id.release(); d_hit_t.release();
-        d_ftris.release(); d_tnum.release(); d_ray_colp.release(); d_ray_row.release();
+        d_ftris.release(); d_tnum.release(); d_ray_colp.release(); d_ray_row.release(); d_tile_lists.release();
         d_bin_lists.release(); d_bin_counts.release(); d_bin_offsets.release(); d_bin_total.release();
         if (h_bin_total) { (void)hipHostFree(h_bin_total); h_bin_total = nullptr; }
     }
@@ -162,6 +163,7 @@ struct rwr_context {
     uint32_t frame_graph_mode = 0;                      // A/B: RWR_FRAME_GRAPH=1 (hipGraph replay / update of the reference frame's launches)
     bool fused_setup = true;                            // one launch per small reference frame (k_primary_p2<FUSED>); RWR_FUSED_SETUP=0: two
     bool fused_setup_force = false;                     // RWR_FUSED_SETUP=1: wherever the fused form is possible
+    bool tile_lists = true;                             // per-tile face sets from k_frame_setup for the two-pixel kernel; RWR_TILE_LISTS=0: it culls itself
     // BVH over the (flattened) world-space faces, for bounce rays
     DeviceBuffer<BvhNode4> d_bvh_nodes;
     DeviceBuffer<uint32_t> d_bvh_leaf_faces;
@@ -613,6 +615,7 @@ int rwr_ctx_create(int device_id, rwr_context **out_ctx)
     if (const char *e4 = std::getenv("RWR_ONE_PIXEL_PER_LANE")) ctx->force_one_pixel = std::atoi(e4) != 0;
     if (const char *e14 = std::getenv("RWR_FRAME_GRAPH")) ctx->frame_graph_mode = (uint32_t)std::atoi(e14);
     if (const char *e16 = std::getenv("RWR_FUSED_SETUP")) { ctx->fused_setup = std::atoi(e16) != 0; ctx->fused_setup_force = ctx->fused_setup; }
+    if (const char *e22 = std::getenv("RWR_TILE_LISTS")) ctx->tile_lists = std::atoi(e22) != 0;
     if (const char *e5 = std::getenv("RWR_AUTO_BVH_FACE_PX")) ctx->auto_bvh_face_px = (float)std::atof(e5);
     if (const char *e6 = std::getenv("RWR_WF_GROUP")) ctx->wf_group = std::min(kWfMaxGroup, std::max(1u, (uint32_t)std::strtoul(e6, nullptr, 10)));
     if (const char *e9 = std::getenv("RWR_WF_STATS")) {
@@ -1095,6 +1098,24 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
         RWR_HIP_CHECK(W0.d_tiles.ensure(2u * n_tiles0 + 1u));
         so.zero_a = W0.d_wave_total.ptr; so.n_zero_a = (uint32_t)(n_tiles0 * 4u);
         so.zero_b = W0.d_tiles.ptr + 2u * n_tiles0; so.n_zero_b = 1u;   // live_count (below)
+    }
+    // Unbinned scenes in the two-pixel frame kernel with culling: k_frame_setup's last blocks make every tile's face set
+    // (rwr_frame_setup.h frame_tile_lists_block), one wave per region of 4x4 of the kernel's workgroups (recomputing the faces'
+    // records per block is the blocks' fixed cost; one region per wave keeps the launch short: it delays this slot's frame kernel).
+    // (The fused form ignores them: its record makers run in the frame kernel's own launch.)
+    const bool tile_lists = ctx->tile_lists && !wavefront && !dormant && ctx->n_tris != 0 && ctx->n_tris <= std::min(ctx->bin_min_faces, kTileListMaxFaces) &&
+                            !(rp.flags & (RWR_FLAG_USE_BVH | RWR_FLAG_NO_CULL | RWR_FLAG_ONE_PIXEL_PER_LANE)) && !ctx->force_one_pixel &&
+                            row_end > row_begin;
+    if (tile_lists) {
+        so.list_gx = (ctx->screen.width + 63u) / 64u;
+        so.list_gy = band_strips(fp);
+        so.list_row_begin = fp.row_begin;
+        so.list_row_pitch = fp.row_pitch;
+        const uint32_t regions = ((so.list_gx + kListRegionWgs - 1u) / kListRegionWgs) * ((so.list_gy + kListRegionWgs - 1u) / kListRegionWgs);
+        so.list_blocks = (regions + 4u * kListRegionsPerWave - 1u) / (4u * kListRegionsPerWave);
+        RWR_HIP_CHECK(sl.d_tile_lists.ensure((size_t)so.list_gx * so.list_gy * 4u * kTileListWords));
+        so.tile_lists = sl.d_tile_lists.ptr;
+        fp.tile_lists = so.tile_lists;
     }
     // A/B (RWR_FRAME_GRAPH=1): the plain reference frame — records + frame kernel, nothing else on the stream — as one graph launch
     const bool as_graph = ctx->frame_graph_mode != 0u && !wavefront && !aux && ctx->n_triangles == 0 &&

@@ -134,6 +134,17 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
         if (bx0 + 64 < mesh_x0 || bx0 > mesh_x1 || by0 + 8 < mesh_y0 || by0 > mesh_y1) n_list = 0u;
     }
     n_list = __builtin_amdgcn_readfirstlane(n_list);
+    // Unbinned scenes of at most kTileListMaxFaces faces come with this frame's per-tile face sets (k_frame_setup,
+    // rwr_frame_setup.h): the wave loads its tile's set with scalar loads now, behind the ray generation, and walks it instead
+    // of culling the records itself (no record copy to LDS, no culling batch).
+    const bool lists = CULL && !FUSED && p.tile_lists != nullptr;   // (uniform)
+    uint32_t set[kTileListWords] = {};
+    if (lists) {
+        const const_ptr<uint32_t> rec = to_const_space(p.tile_lists) + ((by * gridDim.x + blockIdx.x) * 4u + wu) * kTileListWords;
+#pragma unroll
+        for (uint32_t k = 0; k < kTileListWords; k++) set[k] = rec[k];
+        n_list = 0u;
+    }
     __shared__ float4 s_rec[CULL ? 4 : 1][CULL ? 256 : 1];   // round's culling records, one plane per 16 B of FrameTri
     __shared__ uint32_t s_face[CULL ? 256 : 1];              // ... and their face indices
     __shared__ float s_lut[256];                             // sRGB decode table of the quad texels (rwr_internal.h QuadTex)
@@ -153,7 +164,7 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
         }
     };
     auto rwait = []() { __builtin_amdgcn_s_waitcnt(0xF70); };   // vmcnt(0)
-    if constexpr (CULL) load_round(0u);
+    if (CULL && !lists) load_round(0u);
     __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)(tex.lut + threadIdx.x),
                                      (__attribute__((address_space(3))) void *)&s_lut[64u * wu], 4, 0, 0);
 
@@ -197,6 +208,23 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
         // survivors in ascending face order.  Every wave reaches every barrier: n_list is the workgroup's (a wave
         // outside the mesh rectangle loads its share and keeps no face).
         const TileRect tile_rect = {tx0, ty0, tx0 + kTileWf, ty0 + kTileHf};
+        if (lists) {   // the tile's set, 64 faces at a time, ascending
+            rwait();   // (the table's barrier)
+            __syncthreads();
+#pragma unroll
+            for (uint32_t k = 0; k < kTileListWords / 2u; k++) {
+                unsigned long long m = live ? ((unsigned long long)set[2u * k + 1u] << 32 | set[2u * k]) : 0ull;
+                if (AUX) dbg_listed += (uint32_t)__popcll(m);
+                while (m) {
+                    const uint32_t idx = 64u * k + (uint32_t)__builtin_ctzll(m);
+                    m &= m - 1ull;
+                    intersect_and_select(tris[idx], to_const_space(p.tnum)[idx], idx, O, D, best);
+                    last_idx = idx;
+                    n_tested++;
+                    if (AUX) dbg_tested++;
+                }
+            }
+        }
         for (uint32_t base = 0; base < n_list; base += 256u) {
             if (base) {   // lists of more than 256 faces: every wave is done with the previous round
                 __syncthreads();
@@ -228,7 +256,7 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
                 }
             }
         }
-        if (n_list == 0u) {   // (the table's barrier when no round ran)
+        if (n_list == 0u && !lists) {   // (the table's barrier when no round ran)
             rwait();
             __syncthreads();
         }

@@ -150,6 +150,10 @@ struct BinGrid {
 };
 constexpr uint32_t kBinNoList = 0xffffffffu;
 constexpr uint32_t kStripRows = 8;   // rows of a strip = of every render kernel's workgroup tile (RWR_STRIP_ROWS)
+// Per-tile face sets (FrameParams::tile_lists): a 256-bit set per 32x4 tile, for scenes of at most kTileListMaxFaces faces
+// (made by waves of k_frame_setup that cover kListRegionsPerWave regions of kListRegionWgs x kListRegionWgs workgroups each)
+constexpr uint32_t kTileListMaxFaces = 256, kTileListWords = kTileListMaxFaces / 32;
+constexpr uint32_t kListRegionWgs = 4, kListRegionsPerWave = 1;
 
 struct FrameParams {
     rwr_camera_inv_uniform cam;
@@ -192,6 +196,9 @@ struct FrameParams {
     uint32_t n_materials;
     uint32_t pad_m;
     const TangentRec *tangents;   // per face (RWR_FLAG_NORMAL_MAP)
+    // Per-tile face sets of the two-pixel frame kernel, made by k_frame_setup (rwr_frame_setup.h frame_tile_lists_block):
+    // kTileListWords words per 32x4 tile, bit f set = face f survives the tile's culling.  Null: the kernel culls itself.
+    const uint32_t *tile_lists;
 };
 // 8-row strips a launch renders (the y extent of every render kernel's grid)
 inline uint32_t band_strips(const FrameParams &fp) { return fp.row_end > fp.row_begin ? (fp.row_end - fp.row_begin + fp.row_pitch - 1u) / fp.row_pitch : 0u; }
@@ -325,6 +332,10 @@ struct FrameSetupOut {
     // done here instead of by memset commands of their own on the stream (4-5 us each on a frame of a few hundred)
     uint32_t *zero_a, *zero_b;
     uint32_t n_zero_a, n_zero_b;
+    // the two-pixel frame kernel's per-tile face sets (FrameParams::tile_lists; null: none this frame), for the kernel's grid of
+    // list_gx x list_gy workgroups at row_begin + by * row_pitch; list_blocks blocks of the launch make them
+    uint32_t *tile_lists;
+    uint32_t list_gx, list_gy, list_row_begin, list_row_pitch, list_blocks;
 };
 // The frame kernel's FUSED form (one launch per frame, kernels_primary_p2.hip): the grid's first rows are workgroups that make
 // the frame's records and tables (the work of k_frame_setup), the others wait until all of them have finished.
