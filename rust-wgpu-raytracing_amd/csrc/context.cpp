@@ -419,6 +419,13 @@ void compute_cull_consts(const rwr_camera_inv_uniform &cam, uint32_t width, uint
     double vxa = 0.0, vya = 0.0;
     for (int k = 0; k < 3; k++) { vxa += sx * Vx[k] * A[k]; vya += sy * Vy[k] * A[k]; }
     cc.vxa = (float)vxa; cc.vya = (float)vya;
+    // World-magnitude terms of rwr_cull.h ("World magnitude"): |O|_1; the pixel shift per unit of rho
+    // anywhere on the screen, |Ux + x Vx|_1 max|dir|_1 / |vxa| with 0 <= x <= width (+1); and |Vx|_1 max|dir|_1 / |vxa|
+    // (likewise for y), which bounds the shift's denominator: rho times it <= 1/2 at most doubles the shift.
+    cc.origin[3] = (float)((std::fabs((double)cam.origin[0]) + std::fabs((double)cam.origin[1]) + std::fabs((double)cam.origin[2])) * 1.001);
+    cc.A[3] = (float)(1.001 * (l1[0] + ((double)width + 1.0) * l1[1]) * max_dir_l1 / std::fabs(vxa));
+    cc.Bx[3] = (float)(1.001 * (l1[2] + ((double)height + 1.0) * l1[3]) * max_dir_l1 / std::fabs(vya));
+    cc.By[3] = (float)(1.001 * std::fmax(l1[1] / std::fabs(vxa), l1[3] / std::fabs(vya)) * max_dir_l1);
     // a pinhole camera has both determinants well away from 0; a singular or non-finite
     // uniform simply disables culling (the exact test then sees every face)
     const double bx1 = std::fabs(Bx[0]) + std::fabs(Bx[1]) + std::fabs(Bx[2]);
@@ -449,6 +456,20 @@ bool mesh_screen_rect(const CullConsts &cc, const float lo[3], const float hi[3]
     }
     rect[0] = x0; rect[1] = y0; rect[2] = x1; rect[3] = y1;
     return true;
+}
+
+// rho (rwr_cull.h world_rho) for every face of the mesh at once: the magnitude from the box's corners, the distance
+// from the box; +inf when the origin is too close to the box for the bound.
+double mesh_world_rho(const CullConsts &cc, const float lo[3], const float hi[3])
+{
+    double mag = 0.0, dist = 0.0;
+    for (int k = 0; k < 3; k++) {
+        mag += std::fmax(std::fabs((double)lo[k]), std::fabs((double)hi[k]));
+        dist = std::fmax(dist, std::fmax((double)lo[k] - (double)cc.origin[k], (double)cc.origin[k] - (double)hi[k]));
+    }
+    const double delta = 12.0 * 5.9604645e-8 * ((double)cc.origin[3] + mag);   // kCullWorld (rwr_cull.h)
+    dist *= 0.999;
+    return dist > 2.0 * delta ? delta / (dist - delta) : INFINITY;
 }
 
 // Average projected area, in pixels, of a face of the mesh: the area of that rectangle (clipped to the
@@ -1062,11 +1083,13 @@ static int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, 
     const bool have_mesh_rect = ctx->n_tris != 0 && mesh_screen_rect(cc, ctx->aabb_lo, ctx->aabb_hi, mesh_rect);
     const float inf = std::numeric_limits<float>::infinity();
     fp.mesh_rect[0] = fp.mesh_rect[1] = -inf; fp.mesh_rect[2] = fp.mesh_rect[3] = inf;
-    if (have_mesh_rect) {
-        fp.mesh_rect[0] = (float)(mesh_rect[0] - 1.0 - 1e-4 * std::fabs(mesh_rect[0]));
-        fp.mesh_rect[1] = (float)(mesh_rect[1] - 1.0 - 1e-4 * std::fabs(mesh_rect[1]));
-        fp.mesh_rect[2] = (float)(mesh_rect[2] + 1.0 + 1e-4 * std::fabs(mesh_rect[2]));
-        fp.mesh_rect[3] = (float)(mesh_rect[3] + 1.0 + 1e-4 * std::fabs(mesh_rect[3]));
+    const double mesh_rho = have_mesh_rect ? mesh_world_rho(cc, ctx->aabb_lo, ctx->aabb_hi) : INFINITY;
+    if (have_mesh_rect && mesh_rho * cc.By[3] <= 0.5) {
+        const double wx = 2.0 * mesh_rho * cc.A[3], wy = 2.0 * mesh_rho * cc.Bx[3];   // world-magnitude stray (rwr_cull.h)
+        fp.mesh_rect[0] = (float)(mesh_rect[0] - 1.0 - wx - 1e-4 * std::fabs(mesh_rect[0]));
+        fp.mesh_rect[1] = (float)(mesh_rect[1] - 1.0 - wy - 1e-4 * std::fabs(mesh_rect[1]));
+        fp.mesh_rect[2] = (float)(mesh_rect[2] + 1.0 + wx + 1e-4 * std::fabs(mesh_rect[2]));
+        fp.mesh_rect[3] = (float)(mesh_rect[3] + 1.0 + wy + 1e-4 * std::fabs(mesh_rect[3]));
     }
     for (int k = 0; k < 4; k++) {
         const double v = k < 2 ? std::floor((double)fp.mesh_rect[k]) : std::ceil((double)fp.mesh_rect[k]);

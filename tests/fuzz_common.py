@@ -1,7 +1,8 @@
 """Randomised parity against the CPU oracle (test infrastructure): random triangle soups and the real meshes,
 cameras (fields of view from 1 to 175 degrees), up to 8 spheres, frame sizes from 1x1, 1-3 frames in flight, a
 quarter of the frames path-traced (some with rigid instances or a second part with its own material), a tenth with
-single-triangle passes / orthographic rays.  Every frame must match the oracle bit for bit in object ids, hit
+single-triangle passes / orthographic rays; optionally (far=True) every scene moved up to 1e5 from the world origin, and
+(plain=True) every primary frame rendered again without AUX outputs.  Every frame must match the oracle bit for bit in object ids, hit
 distances and depth, and within 1e-4 in colour.  Used by tests/test_gpu_fuzz.py (bounded, in the driver's -m gpu
 run) and tools/fuzz_parity.py (as long as you like).  What this validates above all: the conservative culling
 margins (csrc/rwr_cull.h) and the BVH / packet traversal never change which surface a ray sees."""
@@ -22,8 +23,19 @@ def soup(ref_loader, rng, n_faces, extent, tri_size, tex):
     return {"vertices": verts, "faces": faces, "material": mat, "texture": tex}
 
 
-def run(r, orc, ref_loader, ctx, seed, seconds, path_fraction=0.25, many_samples=False, verbose=False):
-    """r: the product package; ctx: an r.Context.  Returns (frames, path-traced frames, dormant frames, worst colour difference)."""
+def _moved(model, offset):
+    m = dict(model)
+    v = model["vertices"].copy()
+    v["position"] = (v["position"].astype(np.float64) + offset).astype(np.float32)
+    m["vertices"] = v
+    return m
+
+
+def run(r, orc, ref_loader, ctx, seed, seconds, path_fraction=0.25, many_samples=False, verbose=False, far=False, plain=False):
+    """r: the product package; ctx: an r.Context.  Returns (frames, path-traced frames, dormant frames, worst colour difference).
+    far: each frame's scene (mesh, second part, spheres, camera) moved by an offset of up to 1e5 on random axes (no rigid
+    instances or single-triangle passes then); plain: each primary frame rendered again without AUX outputs, its RGBA8
+    compared with the AUX frame's and its depth with the oracle's.  Neither changes the random stream when off."""
     _soup = soup
     t_end = time.time() + seconds
     rng = np.random.default_rng(seed)
@@ -41,14 +53,22 @@ def run(r, orc, ref_loader, ctx, seed, seconds, path_fraction=0.25, many_samples
             model = meshes[int(rng.integers(0, len(meshes)))]
             n_faces = len(model["faces"])
         w, h = int(rng.integers(1, 260)), int(rng.integers(1, 150))
-        cam = r.make_camera(eye=rng.uniform(-4, 4, 3) * float(rng.choice([0.1, 1.0, 1.0, 6.0])), target=rng.uniform(-1, 1, 3), aspect=w / h,
+        offset = np.zeros(3)
+        if far:
+            axes = rng.random(3) < 0.6
+            axes[int(rng.integers(0, 3))] = True
+            offset = np.where(axes, rng.choice([-1.0, 1.0], 3) * 10.0 ** rng.uniform(0.0, 5.0, 3), 0.0)
+            model = _moved(model, offset)
+        cam = r.make_camera(eye=tuple(rng.uniform(-4, 4, 3) * float(rng.choice([0.1, 1.0, 1.0, 6.0])) + offset), target=tuple(rng.uniform(-1, 1, 3) + offset), aspect=w / h,
                             fovy=float(rng.choice([rng.uniform(15, 110), rng.uniform(1, 15), rng.uniform(110, 175)])))
         ci = r.camera_build_inv_uniform(cam)
-        spheres = r.make_spheres([(tuple(rng.uniform(-3, 3, 3)), float(rng.uniform(0.05, 1.5))) for _ in range(int(rng.integers(0, 9)))])
+        spheres = r.make_spheres([(tuple(rng.uniform(-3, 3, 3) + offset), float(rng.uniform(0.05, 1.5))) for _ in range(int(rng.integers(0, 9)))])
         parts = None
         if kind < 0.5 and rng.random() < 0.3 and n_faces < 400:   # a second part with its own material and texture
             tex2 = rng.integers(0, 256, (int(rng.integers(1, 40)), int(rng.integers(1, 40)), 4), dtype=np.uint8)
             other = _soup(ref_loader, rng, int(rng.integers(1, 200)), extent=2.0, tri_size=0.5, tex=tex2)
+            if far:
+                other = _moved(other, offset)
             other["material"]["ambient"], other["material"]["specular"] = rng.uniform(0, 0.3, 3), rng.uniform(0, 1, 3)
             parts = [model, other]
             ctx.upload_parts(parts)
@@ -59,9 +79,9 @@ def run(r, orc, ref_loader, ctx, seed, seconds, path_fraction=0.25, many_samples
         path = (rng.random() < path_fraction or parts is not None) and w * h * n_faces < 4e6   # several parts: the oracle's path renderer
         if parts is not None and not path:
             ctx.upload_model(model); parts = None
-        dormant = (not path) and rng.random() < 0.12 and w * h * n_faces < 2e7
+        dormant = (not path) and (not far) and rng.random() < 0.12 and w * h * n_faces < 2e7
         inst = None
-        if path and rng.random() < 0.4 and n_faces < 400:   # rigid instances: rotation about y + translation
+        if path and (not far) and rng.random() < 0.4 and n_faces < 400:   # rigid instances: rotation about y + translation
             k = int(rng.integers(2, 6))
             inst = np.zeros(k, dtype=r.INSTANCE_DTYPE)
             for i in range(k):
@@ -93,7 +113,7 @@ def run(r, orc, ref_loader, ctx, seed, seconds, path_fraction=0.25, many_samples
             ctx.render(ci, r.make_params(flags=r.FLAG_AUX_OUTPUTS))
             want = orc.render_frame(ci.view(orc.CAMERA_INV_DTYPE), orc.make_screen(w, h), spheres.view(orc.SPHERE_DTYPE), model)
         got = ctx.readback(aux=True)
-        tag = (seed, n_frames, n_faces, w, h, path, dormant, None if inst is None else len(inst))
+        tag = (seed, n_frames, n_faces, w, h, path, dormant, None if inst is None else len(inst), tuple(offset))
         assert np.array_equal(got["obj_id"], want["obj_id"]), tag
         assert np.array_equal(got["hit_t"].view(np.uint32), want["hit_t"].view(np.uint32)), tag
         assert np.array_equal(got["depth"].view(np.uint32), want["depth"].view(np.uint32)), tag
@@ -108,6 +128,11 @@ def run(r, orc, ref_loader, ctx, seed, seconds, path_fraction=0.25, many_samples
             assert float(rel[big].max() if big.any() else 0.0) <= 5e-3, tag
             d = float(np.abs(got["color_f32"] - want["color_f32"])[~big].max()) if (~big).any() else 0.0
         assert d <= 1e-4, tag + (d,)
+        if plain and not path and not dormant:
+            ctx.render(ci, r.make_params())
+            p = ctx.readback()
+            assert np.array_equal(p["color"], got["color"]), tag + ("plain rgba8",)
+            assert np.array_equal(p["depth"].view(np.uint32), want["depth"].view(np.uint32)), tag + ("plain depth",)
         worst = max(worst, d)
         n_frames += 1
         if verbose and time.time() - t_note > 30.0:
