@@ -1,0 +1,103 @@
+// Self-tests and clock measurements behind the C ABI.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "rwr_context.h"
+
+using namespace rwr;
+
+// out4 += what one of the self-test kernels counted (kernels_selftest.hip)
+template <typename Launch>
+static int run_selftest(rwr_context *ctx, uint64_t out4[4], Launch launch)
+{
+    if (!ctx || !out4) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    DeviceGuard g(ctx->device);
+    DeviceBuffer<unsigned long long> d_out;
+    RWR_HIP_CHECK(d_out.ensure(4));
+    RWR_HIP_CHECK(hipMemsetAsync(d_out.ptr, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    RWR_HIP_CHECK(launch(d_out.ptr));
+    unsigned long long h[4];
+    RWR_HIP_CHECK(hipMemcpyAsync(h, d_out.ptr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    RWR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 4; k++) out4[k] = h[k];
+    return RWR_OK;
+}
+
+extern "C" {
+
+int rwr_selftest_exact_math(rwr_context *ctx, uint32_t normalize_count, uint32_t seed, uint64_t out4[4])
+{
+    return run_selftest(ctx, out4, [&](unsigned long long *d) { return launch_selftest_exact_math(ctx->stream, d, normalize_count, seed); });
+}
+
+int rwr_selftest_exact_div(rwr_context *ctx, uint32_t count, uint32_t seed, uint64_t out4[4])
+{
+    return run_selftest(ctx, out4, [&](unsigned long long *d) { return launch_selftest_exact_div(ctx->stream, d, count, seed); });
+}
+
+int rwr_measure_valu_clock(rwr_context *ctx, uint32_t waves_per_simd, double out4[4])
+{
+    if (!ctx || !out4) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (waves_per_simd < 1u || waves_per_simd > 8u) return set_error(RWR_ERR_INVALID_ARGUMENT, "waves_per_simd must be 1..8");
+    DeviceGuard g(ctx->device);
+    hipDeviceProp_t prop;
+    RWR_HIP_CHECK(hipGetDeviceProperties(&prop, ctx->device));
+    const uint32_t n_wg = (uint32_t)prop.multiProcessorCount * waves_per_simd, n_waves = n_wg * 4u, iters = 1u << 15;
+    DeviceBuffer<ulonglong2> d_out;
+    OwnedEvent e0, e1;
+    RWR_HIP_CHECK(d_out.ensure(n_waves));
+    RWR_HIP_CHECK(hipEventCreate(&e0.h));
+    RWR_HIP_CHECK(hipEventCreate(&e1.h));
+    std::vector<ulonglong2> h(n_waves);
+    RWR_HIP_CHECK(sync_all(ctx));
+    for (int mode = 0; mode < 2; mode++) {
+        // an untimed launch first: the stamped one then starts on a busy, clocked-up chip
+        RWR_HIP_CHECK(launch_measure_valu(ctx->stream, mode, d_out.ptr, n_wg, iters));
+        RWR_HIP_CHECK(hipEventRecord(e0, ctx->stream));
+        RWR_HIP_CHECK(launch_measure_valu(ctx->stream, mode, d_out.ptr, n_wg, iters));
+        RWR_HIP_CHECK(hipEventRecord(e1, ctx->stream));
+        RWR_HIP_CHECK(hipMemcpyAsync(h.data(), d_out.ptr, n_waves * sizeof(ulonglong2), hipMemcpyDeviceToHost, ctx->stream));
+        RWR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        float ms = 0.0f;
+        RWR_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        std::vector<double> mhz(n_waves);
+        for (uint32_t i = 0; i < n_waves; i++) mhz[i] = h[i].y ? (double)h[i].x / (double)h[i].y * 100.0 : 0.0;
+        std::nth_element(mhz.begin(), mhz.begin() + n_waves / 2, mhz.end());
+        const double clock_mhz = mhz[n_waves / 2];
+        // every SIMD issued (waves on it) * iters * 8 wave instructions during the launch (HIP events around it);
+        // cycles = elapsed time x the in-kernel clock
+        const double instr_per_simd = (double)n_waves / (4.0 * prop.multiProcessorCount) * iters * 8.0;
+        const double per_instr = (double)ms * 1e-3 * clock_mhz * 1e6 / instr_per_simd;
+        if (mode == 0) { out4[0] = clock_mhz; out4[1] = per_instr; }
+        else { out4[2] = per_instr; out4[3] = clock_mhz; }
+    }
+    return RWR_OK;
+}
+
+int rwr_clock_probe_start(rwr_context *ctx, uint32_t micros)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (micros == 0u || micros > 100000u) return set_error(RWR_ERR_INVALID_ARGUMENT, "probe duration must be 1..100000 us");
+    DeviceGuard g(ctx->device);
+    if (!ctx->probe_stream) RWR_HIP_CHECK(hipStreamCreateWithFlags(&ctx->probe_stream.h, hipStreamNonBlocking));
+    RWR_HIP_CHECK(ctx->d_probe.ensure(1));
+    RWR_HIP_CHECK(hipStreamSynchronize(ctx->probe_stream));
+    RWR_HIP_CHECK(launch_clock_probe(ctx->probe_stream, ctx->d_probe.ptr, micros * 100u));
+    return RWR_OK;
+}
+
+int rwr_clock_probe_read(rwr_context *ctx, double *shader_mhz)
+{
+    if (!ctx || !shader_mhz) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!ctx->probe_stream) return set_error(RWR_ERR_NOT_READY, "rwr_clock_probe_start has not been called");
+    DeviceGuard g(ctx->device);
+    ulonglong2 h{0, 0};
+    RWR_HIP_CHECK(hipMemcpyAsync(&h, ctx->d_probe.ptr, sizeof h, hipMemcpyDeviceToHost, ctx->probe_stream));
+    RWR_HIP_CHECK(hipStreamSynchronize(ctx->probe_stream));
+    *shader_mhz = h.y ? (double)h.x / (double)h.y * 100.0 : 0.0;
+    return RWR_OK;
+}
+
+}  // extern "C"

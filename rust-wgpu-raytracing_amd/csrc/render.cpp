@@ -1,0 +1,613 @@
+// One frame behind the C ABI: what was asked, which kernel renders it, and the commands it puts on the slot's stream.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "rwr_context.h"
+
+using namespace rwr;
+
+namespace {
+
+// A render call, validated.
+struct FrameRequest {
+    rwr_render_params rp;
+    uint32_t row_begin, row_end, row_pitch;
+    bool aux, accumulate;
+    bool wavefront;   // the wavefront integrator renders it (several samples, a bounce, or an accumulation)
+    bool dormant;     // the reference's dormant parts (single-triangle passes, orthographic rays) have their own plain kernel
+};
+
+// Progressive accumulation: what this frame does with the context's history.
+struct AccumPlan {
+    std::vector<unsigned char> key;
+    AccumMode mode = AccumMode::kFirst;
+    uint64_t before = 0;      // samples the history holds before this frame
+    uint32_t trace_spp = 0;   // samples this frame traces
+};
+
+// The kernel that renders a frame.  Decided once (choose_kernel); every other question about the frame's form is asked of it.
+enum class FrameKernel { kDormant, kBvh, kOnePixel, kTwoPixel, kWavefront };
+
+// The frame's timing pair (rwr_ctx_set_kernel_timing): the two-pixel frame kernel is timed by its own dispatch timestamps,
+// everything else by stream events around it.
+struct FrameTiming {
+    bool on = false, dispatch = false;
+};
+
+int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_render_params *params, uint32_t row_begin,
+             uint32_t row_end, uint32_t row_pitch, FrameRequest &rq)
+{
+    if (!ctx || !camera) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (ctx->screen.width == 0) return set_error(RWR_ERR_NOT_READY, "rwr_resize has not been called");
+    if (!ctx->have_mesh) return set_error(RWR_ERR_NOT_READY, "rwr_scene_upload_mesh has not been called");
+    if (row_begin > row_end || row_end > ctx->screen.height)
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "row band [%u,%u) outside the %u-row frame", row_begin, row_end,
+                         ctx->screen.height);
+    rwr_render_params rp = {1, 0, 0, 0};
+    if (params) rp = *params;
+    if (rp.spp == 0) return set_error(RWR_ERR_INVALID_ARGUMENT, "spp must be >= 1");
+    if ((rp.flags & RWR_FLAG_MULTI_BOUNCE) && rp.max_bounces > RWR_MAX_BOUNCES)
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "max_bounces %u is more than RWR_MAX_BOUNCES (%u)", rp.max_bounces, RWR_MAX_BOUNCES);
+    if (rp.max_bounces > 1 && !(rp.flags & RWR_FLAG_MULTI_BOUNCE))
+        return set_error(RWR_ERR_UNSUPPORTED, "max_bounces > 1 is not supported without RWR_FLAG_MULTI_BOUNCE");
+    if ((rp.flags & RWR_FLAG_USE_BVH) && (rp.spp != 1 || rp.max_bounces != 0))
+        return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_USE_BVH applies to the reference frame (spp 1, no bounce); bounce rays always use the BVH");
+    if (rp.spp > 4096) return set_error(RWR_ERR_INVALID_ARGUMENT, "spp must be <= 4096");
+    const bool accumulate = (rp.flags & RWR_FLAG_ACCUMULATE) != 0;
+    if (accumulate && ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0))
+        return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_ACCUMULATE: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
+    // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1)
+    const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate;
+    const bool dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;
+    if (dormant && (wavefront || (rp.flags & RWR_FLAG_USE_BVH)))
+        return set_error(RWR_ERR_UNSUPPORTED, "single-triangle passes and RWR_FLAG_ORTHO_RAYS apply to the reference frame (spp 1, no bounce, no RWR_FLAG_USE_BVH)");
+    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, wavefront, dormant};
+    return RWR_OK;
+}
+
+// What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
+// camera uniform's bytes, the screen, the rows, bounces, seed, flags but the ACCUMULATE bit, frames in flight and the scene.
+std::vector<unsigned char> accum_key_of(const rwr_context *ctx, const rwr_camera_inv_uniform &cam, const FrameRequest &rq)
+{
+    const uint32_t words[9] = {ctx->screen.width, ctx->screen.height, rq.row_begin, rq.row_end, rq.row_pitch, rq.rp.max_bounces, rq.rp.seed,
+                               rq.rp.flags & ~(uint32_t)RWR_FLAG_ACCUMULATE, ctx->n_slots};
+    std::vector<unsigned char> key(sizeof cam + sizeof words + sizeof ctx->scene_generation);
+    std::memcpy(key.data(), &cam, sizeof cam);
+    std::memcpy(key.data() + sizeof cam, words, sizeof words);
+    std::memcpy(key.data() + sizeof cam + sizeof words, &ctx->scene_generation, sizeof ctx->scene_generation);
+    return key;
+}
+
+// Progressive accumulation: does this frame go on with the context's accumulation (same key, room below the cap), start a
+// new one, or only show it (past the cap)?  A frame without the flag ends it.  Committed once the frame is enqueued.
+int plan_accumulation(rwr_context *ctx, const rwr_camera_inv_uniform &cam, const FrameRequest &rq, AccumPlan &ap)
+{
+    if (rq.accumulate) {
+        ap.key = accum_key_of(ctx, cam, rq);
+        if (ap.key == ctx->accum.key && ctx->accum.samples != 0) {
+            ap.before = ctx->accum.samples;
+            ap.mode = ap.before + rq.rp.spp > ctx->accum_max ? AccumMode::kShow : AccumMode::kAdd;
+        } else if (rq.rp.spp > ctx->accum_max) {
+            return set_error(RWR_ERR_INVALID_ARGUMENT, "spp %u is more than the %llu samples an accumulation may hold (RWR_ACCUM_MAX_SAMPLES)",
+                             rq.rp.spp, (unsigned long long)ctx->accum_max);
+        }
+    } else {
+        ctx->accum.key.clear();
+        ctx->accum.samples = 0;
+        ctx->last_accum_samples = 0;
+    }
+    ap.trace_spp = ap.mode == AccumMode::kShow ? 0u : rq.rp.spp;
+    return RWR_OK;
+}
+
+FrameKernel choose_kernel(const rwr_context *ctx, const FrameRequest &rq, const FrameConsts &fc)
+{
+    if (rq.dormant) return FrameKernel::kDormant;
+    if (rq.wavefront) return FrameKernel::kWavefront;
+    const bool one_pixel = (rq.rp.flags & RWR_FLAG_ONE_PIXEL_PER_LANE) || ctx->force_one_pixel;
+    // faces much smaller than a tile: the per-ray BVH kernel is the faster way to the same frame (frame_consts.cpp mean_face_pixels)
+    const bool auto_bvh = !(rq.rp.flags & RWR_FLAG_NO_CULL) && !one_pixel && ctx->n_tris > ctx->bin_min_faces &&
+                          ctx->auto_bvh_face_px > 0.0f && fc.mean_face_px < (double)ctx->auto_bvh_face_px;
+    if ((rq.rp.flags & RWR_FLAG_USE_BVH) || auto_bvh) return FrameKernel::kBvh;
+    return one_pixel ? FrameKernel::kOnePixel : FrameKernel::kTwoPixel;
+}
+
+// The plain reference frame of a small scene: the two-pixel kernel, all faces in one 256-wide batch (no bins), culled.  What its
+// special forms — per-tile face sets, the fused launch, the graph — have in common; each adds its own terms.
+bool small_culled_frame(const rwr_context *ctx, const FrameRequest &rq, FrameKernel kernel)
+{
+    return kernel == FrameKernel::kTwoPixel && ctx->n_tris != 0 && ctx->n_tris <= ctx->bin_min_faces && !(rq.rp.flags & RWR_FLAG_NO_CULL);
+}
+
+// rows a launch renders: its strips' rows inside [row_begin, row_end) — band_strips with the last strip clipped
+uint64_t band_rows(const FrameParams &fp)
+{
+    const uint32_t strips = band_strips(fp);
+    if (strips == 0u) return 0u;
+    const uint32_t last = fp.row_begin + (strips - 1u) * fp.row_pitch;
+    return (uint64_t)(strips - 1u) * kStripRows + std::min(kStripRows, fp.row_end - last);
+}
+
+const float4 *tex0_of(const rwr_context *ctx) { return ctx->d_texs.empty() ? nullptr : ctx->d_texs[0].ptr; }
+
+// Per-frame records and tables (k_frame_setup): they depend on the camera, so they are rebuilt
+// every frame, on the render stream just ahead of the render kernel.  (Running this small
+// kernel on a side stream, double-buffered so that it overlaps the previous frame, was
+// measured 4-10 us SLOWER per frame than the 3 us it hides: cross-stream event waits cost
+// more than the kernel.)  Here: where they go.
+int frame_tables(rwr_context *ctx, FrameSlot &sl, FrameParams &fp, FrameSetupOut &so)
+{
+    so.ray_pairs = ((ctx->screen.width + 63u) / 64u) * 32u;  // whole 64-pixel workgroup columns
+    so.ray_rows = ctx->screen.height + 8u;                   // whole 8-row tiles below any band
+    RWR_HIP_CHECK(sl.d_ray_colp.ensure(2u * (size_t)so.ray_pairs));
+    RWR_HIP_CHECK(sl.d_ray_row.ensure(so.ray_rows));
+    so.ftris = sl.d_ftris.ptr; so.tnum = sl.d_tnum.ptr;
+    so.ray_colp = sl.d_ray_colp.ptr; so.ray_row = sl.d_ray_row.ptr;
+    fp.ray_colp = so.ray_colp; fp.ray_row = so.ray_row; fp.tnum = so.tnum;
+    return RWR_OK;
+}
+
+// k_frame_setup, the screen bins of a large scene, and the start of the frame's timing pair.
+int enqueue_records(rwr_context *ctx, FrameSlot &sl, FrameKernel kernel, FrameConsts &fc, const FrameSetupOut &so, FrameTiming &timing)
+{
+    FrameParams &fp = fc.fp;
+    const hipStream_t stream = sl.stream;
+    RWR_HIP_CHECK(launch_frame_setup(stream, fc.cc, fp.cam, fp.width, fp.height, ctx->d_cull.ptr, ctx->d_tris.ptr, ctx->n_tris, so));
+    if (ctx->n_tris > ctx->bin_min_faces && !(fp.flags & RWR_FLAG_NO_CULL)) {
+        // more faces than one 256-wide batch: bin them per 64x32-pixel screen region, once per frame.  The lists
+        // are sized by a count pass on the device; the buffer keeps what the previous frames needed (read back a
+        // frame late through pinned memory, never waited for) with headroom, and a frame whose lists do not fit
+        // walks the whole scene instead — the same pixels — while the buffer grows for the next one.
+        const uint32_t bins_x = (fp.width + kBinW - 1) / kBinW, bins_y = (fp.row_end - fp.row_begin + kBinH - 1) / kBinH;
+        const size_t n_bins = (size_t)bins_x * bins_y;
+        if (!sl.h_bin_total) {
+            RWR_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&sl.h_bin_total.h), sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));   // fine-grained: kernels store to it, the host reads it without a synchronisation
+            *sl.h_bin_total = 0u;
+        }
+        const uint64_t needed = *sl.h_bin_total;
+        uint64_t capacity = std::max<uint64_t>(sl.d_bin_lists.count, std::max<uint64_t>(ctx->bin_min_capacity, ctx->bin_min_capacity >= 65536u ? 8ull * ctx->n_tris : 0ull));
+        if (needed > capacity || needed + needed / 4u > capacity) capacity = std::max<uint64_t>(capacity, needed + needed / 2u);
+        capacity = std::min<uint64_t>(capacity, 0xfffffff0ull);
+        if (capacity > sl.d_bin_lists.count) RWR_HIP_CHECK(hipStreamSynchronize(stream));   // the old buffer may still be read
+        RWR_HIP_CHECK(sl.d_bin_lists.ensure((size_t)capacity));
+        RWR_HIP_CHECK(sl.d_bin_counts.ensure(5u * (size_t)n_bins));   // four wave counts per bin, then the bins' own counts (launch_bin_faces)
+        RWR_HIP_CHECK(sl.d_bin_offsets.ensure(n_bins));
+        RWR_HIP_CHECK(sl.d_bin_total.ensure(1));
+        RWR_HIP_CHECK(launch_bin_faces(stream, sl.d_ftris.ptr, ctx->n_tris, fp.row_begin, sl.d_bin_lists.ptr, sl.d_bin_counts.ptr,
+                                       sl.d_bin_offsets.ptr, sl.d_bin_total.ptr, bins_x, bins_y, (uint32_t)sl.d_bin_lists.count, fp.mesh_px,
+                                       sl.h_bin_total));   // (the scan writes the total to the pinned word itself: no copy command)
+        fp.bins = BinGrid{sl.d_bin_lists.ptr, sl.d_bin_counts.ptr + 4u * (size_t)n_bins, sl.d_bin_offsets.ptr, bins_x, bins_y, (uint32_t)sl.d_bin_lists.count, 1u};
+    }
+    timing.on = ctx->timing_every && (ctx->timing_calls++ % ctx->timing_every == 0) && ctx->timing_pairs < 256;
+    timing.dispatch = timing.on && kernel == FrameKernel::kTwoPixel;
+    if (timing.on) {
+        while (ctx->timing_events.size() < 2u * (ctx->timing_pairs + 1u)) {
+            ctx->timing_events.emplace_back();
+            RWR_HIP_CHECK(hipEventCreate(&ctx->timing_events.back().h));
+        }
+        if (!timing.dispatch) RWR_HIP_CHECK(hipEventRecord(ctx->timing_events[2 * ctx->timing_pairs], stream));
+    }
+    return RWR_OK;
+}
+
+// A/B (RWR_FRAME_GRAPH=1): the plain reference frame — records + frame kernel, nothing else on the stream — as one graph launch
+int launch_frame_graph(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc, const FrameSetupOut &so, const QuadTex &quad_tex, const Targets &tg)
+{
+    const FrameParams &fp = fc.fp;
+    const hipStream_t stream = sl.stream;
+    std::vector<unsigned char> key(sizeof(FrameParams) + sizeof(CullConsts));
+    std::memcpy(key.data(), &fp, sizeof fp);
+    std::memcpy(key.data() + sizeof fp, &fc.cc, sizeof fc.cc);
+    if (!sl.frame_graph || key != sl.frame_graph_key) {
+        hipGraph_t g = nullptr;
+        RWR_HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+        hipError_t e = launch_frame_setup(stream, fc.cc, fp.cam, fp.width, fp.height, ctx->d_cull.ptr, ctx->d_tris.ptr, ctx->n_tris, so);
+        if (e == hipSuccess) e = launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, quad_tex, tg);
+        const hipError_t e2 = hipStreamEndCapture(stream, &g);
+        RWR_HIP_CHECK(e);
+        RWR_HIP_CHECK(e2);
+        bool updated = false;
+        if (sl.frame_graph) {
+            hipGraphNode_t bad = nullptr;
+            hipGraphExecUpdateResult res;
+            updated = hipGraphExecUpdate(sl.frame_graph, g, &bad, &res) == hipSuccess;
+            if (!updated) { (void)hipGetLastError(); sl.frame_graph = OwnedGraphExec{}; }
+        }
+        if (!updated) {
+            const hipError_t e3 = hipGraphInstantiate(&sl.frame_graph.h, g, nullptr, nullptr, 0);
+            if (e3 != hipSuccess) { (void)hipGraphDestroy(g); RWR_HIP_CHECK(e3); }
+        }
+        (void)hipGraphDestroy(g);
+        sl.frame_graph_key.swap(key);
+    }
+    RWR_HIP_CHECK(hipGraphLaunch(sl.frame_graph, stream));
+    return RWR_OK;
+}
+
+// The plain reference frame — records + frame kernel, nothing else — as ONE launch: the frame kernel's first workgroups
+// make the records (kernels_primary_p2.hip, FUSED).
+// Where it pays (A/B in one box, tools/fused_ab.py, profiles/r03_fused_ab.txt): SMALL frames with frames in flight, which
+// are bound by the host's launches — one rank's share of a multi-GPU 1080p frame: 9.8 -> 6.9 us per frame (1/8), 10.4 -> 8.2
+// (1/4), the host's enqueue time 9.8 -> 5.2 us.  A whole 1080p frame is VALU-bound and LOSES (15.0 -> 17.4 us with two slots:
+// the next frame's waiting workgroups hold slots the running frame could use; 22.7 -> 23.8 us alone), so it keeps its two
+// launches.  RWR_FUSED_SETUP=1 forces the fused form wherever it is possible (tests), 0 switches it off.
+bool fused_pays(const rwr_context *ctx, const FrameParams &fp)
+{
+    const uint32_t render_groups = ((fp.width + 63u) / 64u) * ((fp.row_end - fp.row_begin + fp.row_pitch - 1u) / std::max(1u, fp.row_pitch));
+    return ctx->fused_setup_force || (ctx->n_slots > 1u && render_groups <= 1200u);
+}
+
+int launch_fused_frame(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc, const FrameSetupOut &so, const QuadTex &quad_tex, const Targets &tg)
+{
+    const hipStream_t stream = sl.stream;
+    FusedSetup fs{};
+    fs.cc = fc.cc;
+    fs.cull = ctx->d_cull.ptr;
+    fs.out = so;
+    fs.nb_tris = (ctx->n_tris + 255u) / 256u;
+    fs.n_blocks = fs.nb_tris + (so.ray_pairs + so.ray_rows + 255u) / 256u;
+    fs.extra_rows = primary_p2_fused_rows(fc.fp, fs.n_blocks);
+    if (!sl.d_fused.ptr || sl.fused_blocks != fs.n_blocks) {   // first use, or another scene / frame size: the count starts over
+        RWR_HIP_CHECK(hipStreamSynchronize(stream));
+        RWR_HIP_CHECK(sl.d_fused.ensure(2));
+        RWR_HIP_CHECK(hipMemsetAsync(sl.d_fused.ptr, 0, 2 * sizeof(uint32_t), stream));
+        sl.fused_count = 0;
+        sl.fused_blocks = fs.n_blocks;
+    }
+    fs.flag = sl.d_fused.ptr;
+    fs.flag_base = sl.fused_count;
+    sl.fused_count += fs.n_blocks;   // (modulo 2^32, like the device's count)
+    sl.fused_used = true;
+    RWR_HIP_CHECK(launch_primary_p2(stream, fc.fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, quad_tex, tg, nullptr, nullptr, &fs));
+    return RWR_OK;
+}
+
+// The reference frame (one sample per pixel, no bounce): records, bins, the chosen kernel — or, for the plain frame of a small
+// scene, the graph or the fused launch in their place.
+int enqueue_reference(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, FrameKernel kernel, FrameConsts &fc, const Targets &tg,
+                      FrameTiming &timing)
+{
+    FrameParams &fp = fc.fp;
+    const hipStream_t stream = sl.stream;
+    FrameSetupOut so{};
+    int rc = frame_tables(ctx, sl, fp, so);
+    if (rc != RWR_OK) return rc;
+    const bool small_culled = small_culled_frame(ctx, rq, kernel), band = fp.row_end > fp.row_begin;
+    // Unbinned scenes in the two-pixel frame kernel with culling: k_frame_setup's last blocks make every tile's face set
+    // (rwr_frame_setup.h frame_tile_lists_block), one wave per region of 4x4 of the kernel's workgroups (recomputing the faces'
+    // records per block is the blocks' fixed cost; one region per wave keeps the launch short: it delays this slot's frame kernel).
+    // (The fused form ignores them: its record makers run in the frame kernel's own launch.)
+    if (small_culled && ctx->tile_lists && ctx->n_tris <= kTileListMaxFaces && band) {
+        so.list_gx = (fp.width + 63u) / 64u;
+        so.list_gy = band_strips(fp);
+        so.list_row_begin = fp.row_begin;
+        so.list_row_pitch = fp.row_pitch;
+        const uint32_t regions = ((so.list_gx + kListRegionWgs - 1u) / kListRegionWgs) * ((so.list_gy + kListRegionWgs - 1u) / kListRegionWgs);
+        so.list_blocks = (regions + 4u * kListRegionsPerWave - 1u) / (4u * kListRegionsPerWave);
+        RWR_HIP_CHECK(sl.d_tile_lists.ensure((size_t)so.list_gx * so.list_gy * 4u * kTileListWords));
+        so.tile_lists = sl.d_tile_lists.ptr;
+        fp.tile_lists = so.tile_lists;
+    }
+    const QuadTex quad_tex{ctx->d_quads.empty() ? nullptr : ctx->d_quads[0].ptr, ctx->d_mat_quads.ptr, ctx->d_srgb_lut.ptr};
+    const bool plain = small_culled && !rq.aux && !ctx->timing_every;   // nothing but records + frame kernel on the stream
+    if (plain && ctx->frame_graph) return launch_frame_graph(ctx, sl, fc, so, quad_tex, tg);   // (an empty band too: captured as it is)
+    if (plain && ctx->fused_setup && fused_pays(ctx, fp) && !(fp.flags & RWR_FLAG_NORMAL_MAP) && band)
+        return launch_fused_frame(ctx, sl, fc, so, quad_tex, tg);
+    if ((rc = enqueue_records(ctx, sl, kernel, fc, so, timing)) != RWR_OK) return rc;
+    switch (kernel) {
+    case FrameKernel::kDormant: {
+        SingleTriangles st{};
+        st.n = ctx->n_triangles;
+        for (uint32_t i = 0; i < ctx->n_triangles; i++) st.t[i] = ctx->triangles[i];
+        RWR_HIP_CHECK(launch_primary_dormant(stream, fp, st, ctx->d_tris.ptr, ctx->d_shade.ptr, tex0_of(ctx), tg));
+        break;
+    }
+    case FrameKernel::kBvh: {
+        const BvhDevice bvh_p{ctx->d_bvh_nodes.ptr, ctx->d_bvh_leaf_faces.ptr, ctx->bvh_n_nodes, 3u * ctx->bvh_depth + 2u, 0.0f, 0u, 0u, 0u, 0u};
+        RWR_HIP_CHECK(launch_primary_bvh(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh_p, tex0_of(ctx), tg));
+        break;
+    }
+    case FrameKernel::kOnePixel:
+        RWR_HIP_CHECK(launch_primary(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0_of(ctx), tg));
+        break;
+    default:
+        RWR_HIP_CHECK(launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, quad_tex, tg,
+                                        timing.dispatch ? ctx->timing_events[2 * ctx->timing_pairs].h : nullptr,
+                                        timing.dispatch ? ctx->timing_events[2 * ctx->timing_pairs + 1].h : nullptr));
+    }
+    return RWR_OK;
+}
+
+// A frame of the wavefront integrator: the samples are traced in launch groups; per group the primary stage (all of the
+// group's samples of every pixel, rays into the fixed-slot queue) then the bounce stage (one workgroup per
+// 64x8-pixel tile and its ray pool)
+int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, AccumPlan &ap, FrameConsts &fc, const Targets &tg,
+                      FrameTiming &timing)
+{
+    FrameParams &fp = fc.fp;
+    const rwr_render_params &rp = rq.rp;
+    const hipStream_t stream = sl.stream;
+    const size_t n = (size_t)fp.width * fp.height;
+    const float4 *tex0 = tex0_of(ctx);
+    WfState &W = ctx->wf_state[ctx->n_slots > 1u ? ctx->cur : 0u];   // this slot's accumulators and queues
+    const uint32_t group = std::min(rp.spp, ctx->wf_group ? ctx->wf_group : (ctx->n_slots > 1u ? 64u : 32u));
+    const uint32_t tiles_x = (fp.width + kWfTileW - 1u) / kWfTileW, tiles_y = band_strips(fp);
+    const uint32_t n_tiles = tiles_x * tiles_y;
+    FrameSetupOut so{};
+    int rc = frame_tables(ctx, sl, fp, so);
+    if (rc != RWR_OK) return rc;
+    // the per-tile ray counts and the live-tile count start every frame from zero: k_frame_setup zeroes them
+    RWR_HIP_CHECK(W.d_wave_total.ensure((size_t)n_tiles * 4u));
+    RWR_HIP_CHECK(W.d_tiles.ensure(2u * (size_t)n_tiles + 1u));
+    so.zero_a = W.d_wave_total.ptr; so.n_zero_a = n_tiles * 4u;
+    so.zero_b = W.d_tiles.ptr + 2u * (size_t)n_tiles; so.n_zero_b = 1u;   // live_count (below)
+    if ((rc = enqueue_records(ctx, sl, FrameKernel::kWavefront, fc, so, timing)) != RWR_OK) return rc;
+    if (W.d_fix.count < 4u * n) W.fix_clean = false;
+    RWR_HIP_CHECK(W.d_fix.ensure(4u * n));
+    if (!W.fix_clean)   // first use, a new size, or a frame that did not reach its resolve
+        RWR_HIP_CHECK(hipMemsetAsync(W.d_fix.ptr, 0, 4u * n * sizeof(unsigned long long), stream));
+    W.fix_clean = false;
+    // two launch groups in flight (each on its own stream, with its own half of the queue) when the frame has several
+    const size_t n_queues = rp.max_bounces ? std::min<size_t>(ctx->wf_queues, (rp.spp + group - 1u) / group) : 1u;
+    const bool overlap = n_queues > 1u;
+    const size_t slots = (size_t)n_tiles * group * kWfTilePixels;
+    if (rp.max_bounces) {
+        // The ray queues are fixed-slot (space instead of atomics: 36 B per slot of every tile of the launch), the one large
+        // allocation of the library — 19 GB for a 4K frame at 64 samples per group.  A frame whose queues cannot be held is
+        // refused with its size, not left to a failed hipMalloc half-way through.
+        if (W.d_rays.count < n_queues * 2u * slots) {
+            const size_t need = n_queues * slots * (2u * sizeof(float4) + 2u * sizeof(uint16_t));
+            const size_t held = W.d_rays.count * sizeof(float4) + (W.d_sorted.count + W.d_bins.count) * sizeof(uint16_t);
+            size_t free_b = 0, total_b = 0;
+            RWR_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+            if (need > free_b + held)
+                return set_error(RWR_ERR_UNSUPPORTED, "the frame's ray queues need %.1f GB (%zu tiles x %u samples per launch group x 512 slots x 36 B x %zu queues), "
+                                 "%.1f GB are free: fewer frames in flight (each slot holds its own queues) or RWR_WF_GROUP < %u",
+                                 need * 1e-9, (size_t)n_tiles, group, n_queues, (free_b + held) * 1e-9, group);
+        }
+        RWR_HIP_CHECK(W.d_rays.ensure(n_queues * 2u * slots));
+        RWR_HIP_CHECK(W.d_sorted.ensure(n_queues * slots));
+        RWR_HIP_CHECK(W.d_bins.ensure(n_queues * slots));
+        RWR_HIP_CHECK(W.d_masks.ensure(n_queues * n_tiles * group * 8u));
+        if (rp.max_bounces > 1u) RWR_HIP_CHECK(W.d_masks_next.ensure(n_queues * n_tiles * group * 8u));
+        RWR_HIP_CHECK(W.d_pool_info.ensure(n_queues * n_tiles * wf_pool_info_bytes()));
+        RWR_HIP_CHECK(W.d_pool_list.ensure(n_queues * 2u * (size_t)n_tiles));
+        if (overlap && !W.fork) RWR_HIP_CHECK(hipEventCreateWithFlags(&W.fork.h, hipEventDisableTiming));
+        for (size_t q = 0; q < n_queues; q++) {
+            if (q && !W.streams[q]) RWR_HIP_CHECK(hipStreamCreateWithFlags(&W.streams[q].h, hipStreamNonBlocking));
+            if (q && !W.join[q]) RWR_HIP_CHECK(hipEventCreateWithFlags(&W.join[q].h, hipEventDisableTiming));
+        }
+        if (!W.d_live.ptr) {
+            RWR_HIP_CHECK(W.d_live.ensure(4u * kWfMaxQueues));
+            RWR_HIP_CHECK(hipMemsetAsync(W.d_live.ptr, 0, 4u * kWfMaxQueues * sizeof(uint32_t), stream));
+        }
+        if (!ctx->h_wf_live) {
+            RWR_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_wf_live.h), 2 * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));   // fine-grained: kernels store to it, the host reads it without a synchronisation
+            ctx->h_wf_live[0] = ctx->h_wf_live[1] = 0u;
+        }
+    }
+    // Did the frame before show LITTLE — fewer than 1 024 live tiles, and at most half of this frame's tiles (a small mesh
+    // on an empty screen; not a small frame full of geometry, such as a row band of a multi-GPU frame: measured, that one
+    // is best left alone)?  Its count arrives through pinned memory, a frame late, never waited for.  Then several
+    // workgroups share a tile's samples in the primary stage (enough of them to fill the chip twice, up to one per
+    // sample), and the tiles anything can be seen through are listed first (below).  Any choice gives the same frame: all
+    // sums are integers.
+    const uint32_t prev_packets = ctx->h_wf_live ? ctx->h_wf_live[0] : 0u, prev_lane = ctx->h_wf_live ? ctx->h_wf_live[1] : 0u;
+    const uint32_t live = prev_packets + prev_lane;
+    const bool shows_little = live != 0u && live < 1024u && 2u * live <= n_tiles;
+    uint32_t z_split = ctx->wf_z_split;
+    if (z_split == 0u) {
+        z_split = 1u;
+        if (shows_little)
+            while (z_split < kWfMaxGroup && z_split * live < 2048u) z_split *= 2u;
+    }
+    // queue q: its half of every per-group buffer and its set of four counters (the primary stage zeroes the set it
+    // is about to fill).  With one queue the frame's sums are read-modify-written by the tile's only workgroup; with
+    // two, a group's primary stage runs beside the other group's trace kernels and everybody adds atomically.
+    // A frame expected to show little (z_split > 1: the previous frame did) first lists the tiles anything can be seen
+    // through; the primary stage, the sort and the resolve then touch those alone.  Same frame either way.
+    uint32_t *live_list = nullptr, *live_count = nullptr, *tile_live = nullptr;
+    if (z_split > 1u && (shows_little || ctx->wf_z_split != 0u) && !(rp.flags & RWR_FLAG_NO_CULL)) {   // (a forced split: the tests' way in)
+        live_list = W.d_tiles.ptr; tile_live = live_list + n_tiles; live_count = tile_live + n_tiles;   // (zeroed by k_frame_setup)
+        RWR_HIP_CHECK(launch_wf_classify(stream, fp, sl.d_ftris.ptr, tg, tiles_x, live_list, live_count, tile_live));
+    }
+    WfBuffers wfq[kWfMaxQueues];
+    for (size_t q = 0; q < n_queues; q++) {
+        wfq[q] = WfBuffers{W.d_fix.ptr,
+                           W.d_rays.ptr ? W.d_rays.ptr + q * 2u * slots : nullptr,
+                           W.d_masks.ptr ? W.d_masks.ptr + q * n_tiles * group * 8u : nullptr,
+                           W.d_bins.ptr ? W.d_bins.ptr + q * slots : nullptr,
+                           W.d_sorted.ptr ? W.d_sorted.ptr + q * slots : nullptr,
+                           W.d_wave_total.ptr, group, tiles_x, ctx->d_wf_dbg.ptr,
+                           rp.max_bounces ? W.d_live.ptr + q * 4u : nullptr, overlap ? 1u : 0u, live_list, live_count, tile_live};
+    }
+    // The per-lane trace kernel as 1 024-thread workgroups that share ONE copy of the nodelets in LDS (kernels_wf_bounce.hip,
+    // WIDE; only for a BVH too large for a copy per 256-thread workgroup and small enough for one per CU), one work item per
+    // pool: when frames overlap and the frame before traced most of its pools per lane (a small mesh on an empty screen at few
+    // samples: configs[3] 0.604 -> 0.54 ms; one frame at a time it loses, 0.73 -> 0.81, and configs[4]'s frame, whose large
+    // pools are packets, loses 2 %: both keep the 256-thread kernel).  Same frame either way.
+    const bool wide_lane = ctx->wf_wide_lane >= 0 ? ctx->wf_wide_lane != 0
+                                                   : (ctx->n_slots > 1u && prev_lane >= 128u && prev_lane >= 4u * prev_packets);
+    const BvhDevice bvh{ctx->d_bvh_nodes.ptr, ctx->d_bvh_leaf_faces.ptr, ctx->bvh_n_nodes, 3u * ctx->bvh_depth + 2u,
+                        ctx->wf_packet_extent * ctx->bvh_leaf_extent, ctx->wf_min_packet_pools,
+                        // work items of the per-lane trace kernel when pools are few: one 256-ray chunk each for a context that
+                        // renders one frame at a time (the chip has nothing else to do: as many items as possible), about four
+                        // chunks each when frames overlap (a pool's rays grow with the group's samples; measured at configs[3],
+                        // 16 samples: 0.625 -> 0.607 ms with 4 096 items, but 0.74 -> 0.79 ms one frame at a time; configs[4]'s
+                        // frame, 64 samples: 16 384 is best either way)
+                        ctx->wf_lane_items ? ctx->wf_lane_items : (wide_lane ? 256u : ctx->n_slots > 1u ? std::min(16384u, 256u * group) : 16384u),
+                        ctx->wf_packet_dense_rays, wide_lane ? 1u : 0u};
+    if (overlap) {   // the other streams start behind this frame's setup (and so behind the previous frame's resolve)
+        RWR_HIP_CHECK(hipEventRecord(W.fork, stream));
+        for (size_t q = 1; q < n_queues; q++) RWR_HIP_CHECK(hipStreamWaitEvent(W.streams[q], W.fork, 0));
+    }
+    const uint32_t *last_counters = nullptr;
+    // (global sample indices: an accumulating frame traces [accum_before, accum_before + spp), keyed like one frame of them all)
+    for (uint32_t s0 = 0, g = 0; s0 < ap.trace_spp; s0 += group, g++) {
+        const uint32_t cnt = std::min(group, rp.spp - s0);
+        const size_t q = g % n_queues;
+        hipStream_t gs = q ? W.streams[q].h : stream;
+        RWR_HIP_CHECK(launch_wf_primary(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg, wfq[q],
+                                        (uint32_t)ap.before + s0, cnt, z_split));
+        // the bounce stage: one generation of rays per bounce (RWR_FLAG_MULTI_BOUNCE: up to RWR_MAX_BOUNCES).  Generation k traces
+        // ray k of every path that is still alive — the sort and trace kernels run again over the same fixed slots — and, unless
+        // it is the last, writes ray k + 1 back into the slot of every hit, with its bit in the other ballot array.
+        WfBuffers wg = wfq[q];
+        unsigned long long *masks_next = W.d_masks_next.ptr ? W.d_masks_next.ptr + q * n_tiles * group * 8u : nullptr;
+        for (uint32_t gen = 1; gen <= rp.max_bounces; gen++) {
+            if (gen > 1u)   // the sort counts this generation's live pools from zero (the primary stage zeroed the set of four for the first)
+                RWR_HIP_CHECK(hipMemsetAsync(wg.counters, 0, 4u * sizeof(uint32_t), gs));
+            const bool emit = gen < rp.max_bounces;
+            const WfEmit em{masks_next, 2u + 16u * gen, (uint32_t)ap.before + s0};
+            if (emit) RWR_HIP_CHECK(hipMemsetAsync(masks_next, 0, (size_t)n_tiles * group * 8u * sizeof(unsigned long long), gs));
+            RWR_HIP_CHECK(launch_wf_bounce(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh, tex0, wg, n_tiles, cnt,
+                                           (uint32_t)std::fmax(1.0f, std::ceil(ctx->wf_packet_fill * (float)(cnt * kWfTilePixels))),
+                                           W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles,
+                                           emit ? &em : nullptr));
+            if (emit) std::swap(wg.masks, masks_next);
+        }
+        if (rp.max_bounces && s0 + group >= rp.spp) last_counters = wfq[q].counters;   // the last group's live-pool counts, for the next frame's split
+    }
+    for (size_t q = 1; q < n_queues; q++) {
+        RWR_HIP_CHECK(hipEventRecord(W.join[q], W.streams[q]));
+        RWR_HIP_CHECK(hipStreamWaitEvent(stream, W.join[q], 0));
+    }
+    // (the resolve also hands the last group's live pool counts to the host: a store to pinned memory, no copy command.  The
+    // same store at the top of the per-lane trace kernel made THAT kernel twice as slow, 453 -> 840 us at configs[3], with the
+    // pointer null and the instruction mix unchanged; here it costs nothing measurable.)
+    if (!rq.accumulate) {
+        RWR_HIP_CHECK(launch_wf_resolve(stream, fp, tg, wfq[0], last_counters, last_counters ? ctx->h_wf_live.h : nullptr));
+    } else {
+        // The history is the context's, not the slot's: frames in flight trace side by side, their resolves run in frame order
+        Accum &A = ctx->accum;
+        if (ap.mode == AccumMode::kFirst) {
+            RWR_HIP_CHECK(A.d_hist.ensure(4u * n));
+            RWR_HIP_CHECK(A.d_depth.ensure(n));
+            if (rq.aux) { RWR_HIP_CHECK(A.d_obj_id.ensure(n)); RWR_HIP_CHECK(A.d_hit_t.ensure(n)); }
+        }
+        if (!A.done) RWR_HIP_CHECK(hipEventCreateWithFlags(&A.done.h, hipEventDisableTiming));
+        if (A.done_recorded) RWR_HIP_CHECK(hipStreamWaitEvent(stream, A.done, 0));
+        const AccumBuffers ab{A.d_hist.ptr, A.d_depth.ptr, rq.aux ? A.d_obj_id.ptr : nullptr, rq.aux ? A.d_hit_t.ptr : nullptr};
+        const uint64_t total = ap.mode == AccumMode::kShow ? ap.before : ap.before + rp.spp;
+        RWR_HIP_CHECK(launch_wf_resolve_accum(stream, fp, tg, wfq[0], ab, ap.mode, (uint32_t)total, last_counters,
+                                              last_counters ? ctx->h_wf_live.h : nullptr));
+        RWR_HIP_CHECK(hipEventRecord(A.done, stream));
+        A.done_recorded = true;
+        A.key.swap(ap.key);
+        A.samples = total;
+        ctx->last_accum_samples = total;
+    }
+    W.fix_clean = true;   // (the resolve zeroes what it reads; rows outside the band were never touched)
+    ctx->last_segments = n_tiles;
+    ctx->last_wf_state = ctx->n_slots > 1u ? ctx->cur : 0u;
+    return RWR_OK;
+}
+
+// One frame — rows [row_begin, row_end) in strips of 8 rows, strip k starting at row_begin + k * row_pitch (row_pitch 8: the
+// whole band; 8 N: every N-th strip).
+int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_render_params *params,
+                 uint32_t row_begin, uint32_t row_end, uint32_t row_pitch)
+{
+    FrameRequest rq;
+    int rc = validate(ctx, camera, params, row_begin, row_end, row_pitch, rq);
+    if (rc != RWR_OK) return rc;
+    AccumPlan ap;
+    if ((rc = plan_accumulation(ctx, *camera, rq, ap)) != RWR_OK) return rc;
+
+    DeviceGuard g(ctx->device);
+    if ((rc = rebuild_tris(ctx)) != RWR_OK) return rc;
+    // Frame slot: the next one in turn.  A slot owns everything a frame writes — targets, per-frame records, and for the
+    // wavefront integrator a whole set of accumulators and ray queues (WfState) — so frames in different slots share
+    // nothing and a slot is reused in stream order.
+    ctx->cur = (ctx->cur + 1u) % ctx->n_slots;
+    FrameSlot &sl = ctx->slots[ctx->cur];
+    if (rq.aux) {
+        // a band render leaves the rest of the planes untouched: they start zeroed, like the targets
+        const size_t n = (size_t)ctx->screen.width * ctx->screen.height;
+        const bool fresh = sl.d_color_f32.count < n * 4 || sl.d_obj_id.count < n || sl.d_hit_t.count < n;
+        RWR_HIP_CHECK(sl.d_color_f32.ensure(n * 4));
+        RWR_HIP_CHECK(sl.d_obj_id.ensure(n));
+        RWR_HIP_CHECK(sl.d_hit_t.ensure(n));
+        if (fresh) {
+            RWR_HIP_CHECK(hipMemsetAsync(sl.d_color_f32.ptr, 0, n * 4 * sizeof(float), sl.stream));
+            RWR_HIP_CHECK(hipMemsetAsync(sl.d_obj_id.ptr, 0, n * sizeof(int32_t), sl.stream));
+            RWR_HIP_CHECK(hipMemsetAsync(sl.d_hit_t.ptr, 0, n * sizeof(float), sl.stream));
+        }
+    }
+    RWR_HIP_CHECK(sl.d_ftris.ensure(ctx->n_tris));
+    RWR_HIP_CHECK(sl.d_tnum.ensure(ctx->n_tris));
+    const Targets tg{sl.d_color.ptr, sl.d_depth.ptr, rq.aux ? sl.d_color_f32.ptr : nullptr,
+                     rq.aux ? sl.d_obj_id.ptr : nullptr, rq.aux ? sl.d_hit_t.ptr : nullptr};
+
+    const FrameScene scene{ctx->screen.width, ctx->screen.height, ctx->spheres, ctx->n_spheres, ctx->n_tris, ctx->tex_w, ctx->tex_h,
+                           ctx->aabb_lo, ctx->aabb_hi, &ctx->material, ctx->d_materials.ptr, (uint32_t)ctx->st_materials.size(),
+                           ctx->d_tangent.ptr, ctx->wave_cull_min};
+    FrameConsts fc{};
+    fill_frame_consts(scene, *camera, rq.rp, rq.accumulate, row_begin, row_end, row_pitch, fc);
+    const FrameKernel kernel = choose_kernel(ctx, rq, fc);
+
+    FrameTiming timing;
+    rc = kernel == FrameKernel::kWavefront ? enqueue_wavefront(ctx, sl, rq, ap, fc, tg, timing)
+                                           : enqueue_reference(ctx, sl, rq, kernel, fc, tg, timing);
+    if (rc != RWR_OK) return rc;
+
+    // the frame is on its stream: what the context remembers of it
+    if (timing.on) {
+        if (!timing.dispatch) RWR_HIP_CHECK(hipEventRecord(ctx->timing_events[2 * ctx->timing_pairs + 1], sl.stream));
+        ctx->timing_pairs++;
+    }
+    sl.aux_valid = rq.aux;
+    ctx->last_spp = rq.wavefront ? rq.rp.spp : 0u;
+    ctx->last_had_bounce = rq.wavefront && rq.rp.max_bounces != 0;
+    ctx->last_primary = (uint64_t)ctx->screen.width * band_rows(fc.fp) * ap.trace_spp;
+    ctx->last_bounce = 0;  // filled in lazily by rwr_last_render_stats from the pass counters
+    return RWR_OK;
+}
+
+}  // namespace
+
+// A frame rendered by the fused frame kernel is complete unless one of its waves waited in vain for the records (the wait is
+// bounded; it has never been seen to run out): slot `i` is idle when this is called.
+int rwr::check_fused_frame(rwr_context *ctx, uint32_t i)
+{
+    FrameSlot &sl = ctx->slots[i];
+    if (!sl.fused_used || !sl.d_fused.ptr) return RWR_OK;
+    uint32_t timed_out = 0;
+    RWR_HIP_CHECK(hipMemcpy(&timed_out, sl.d_fused.ptr + 1, sizeof timed_out, hipMemcpyDeviceToHost));
+    if (timed_out) {
+        sl.fused_blocks = 0;   // the count is no longer what the host expects: start over with the next frame
+        return set_error(RWR_ERR_HIP, "a frame is incomplete: workgroups of the fused frame kernel waited in vain for the frame's records "
+                         "(RWR_FUSED_SETUP=0 renders with two launches per frame)");
+    }
+    return RWR_OK;
+}
+
+extern "C" {
+
+int rwr_render(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_render_params *params)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    return render_frame(ctx, camera, params, 0, ctx->screen.height, kStripRows);
+}
+
+int rwr_render_rows(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_render_params *params,
+                    uint32_t row_begin, uint32_t row_end)
+{
+    return render_frame(ctx, camera, params, row_begin, row_end, kStripRows);
+}
+
+int rwr_render_strips(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_render_params *params,
+                      uint32_t first_strip, uint32_t strip_stride)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (strip_stride == 0u || first_strip >= strip_stride || strip_stride > 0x0fffffffu)
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "strips %u, %u + %u, ...: the first strip must be below the stride", first_strip, first_strip, strip_stride);
+    const uint32_t h = ctx->screen.height, first_row = first_strip * kStripRows;
+    return render_frame(ctx, camera, params, std::min(first_row, h), h, strip_stride * kStripRows);
+}
+
+}  // extern "C"

@@ -38,9 +38,7 @@ RWR_DEV f3 fcross(f3 a, f3 b)
 }
 RWR_DEV float l1norm(f3 a) { return fabsf(a.x) + fabsf(a.y) + fabsf(a.z); }
 
-constexpr float kCullRel = 2e-5f;  // relative margin (context.cpp folds it into CullConsts::corner_margin)
-constexpr float kCullDegenerate = 1e-4f;
-constexpr float kCullWorld = 12.0f * 5.9604645e-8f;  // 12 f32 unit roundoffs of the world magnitude (context.cpp: same)
+constexpr float kCullDegenerate = 1e-4f;   // (kCullRel and kCullWorld: rwr_internal.h, the host needs them too)
 
 // rho for one face: the angle (relative to |dir|) by which a ray that the exact test lets hit the face may pass outside
 // it because that test rounds at world magnitude; +inf when the bound does not hold (the face is then never culled).

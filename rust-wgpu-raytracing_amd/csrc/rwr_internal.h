@@ -79,8 +79,10 @@ struct QuadTex {
     const uint4 *const *mats;   // per material (n_materials > 1)
     const float *lut;           // build_srgb_lut's table (device memory; the kernel copies it to LDS)
 };
-// host: the (w + 1) * (h + 1) records of a w x h RGBA8 image, 4 dwords each
+// host (frame_consts.cpp): the (w + 1) * (h + 1) records of a w x h RGBA8 image, 4 dwords each
 void build_tex_quads(const uint8_t *rgba8, uint32_t w, uint32_t h, uint32_t *out);
+// host (frame_consts.cpp): the 256 floats of the Rgba8UnormSrgb decode
+void build_srgb_lut(float *lut);
 
 // Per-face tangent frame for normal-mapped shading (extension; 32 B, made by k_prebake in double and rounded once):
 // t = normalize(dP/du - n (n . dP/du)), b = +-cross(n, t) towards -dP/dv' (v' = 1 - v: the sampling space of
@@ -107,8 +109,15 @@ struct Targets {
     float *hit_t;       // W*H, aux
 };
 
+// The culling margins (rwr_cull.h).  The host evaluates its side in double from these doubles (frame_consts.cpp); the kernels'
+// floats are the same numbers rounded once.
+constexpr double kCullRelHost = 2e-5;                      // relative margin, folded into CullConsts::corner_margin
+constexpr double kCullWorldHost = 12.0 * 5.9604645e-8;     // 12 f32 unit roundoffs of the world magnitude
+constexpr float kCullRel = (float)kCullRelHost;
+constexpr float kCullWorld = (float)kCullWorldHost;
+
 // Per-frame constants of the conservative culling code (host-computed in double
-// from the camera uniform, context.cpp).  The un-normalised world direction of the
+// from the camera uniform, frame_consts.cpp).  The un-normalised world direction of the
 // ray through pixel-space point (fx, fy) is affine:  dir = A + fx*Bx + fy*By
 // (compute.wgsl:151-159), so every plane through the origin that contains a
 // pixel column x = const or row y = const has the normal  Ux + x*Vx  resp.
@@ -173,7 +182,7 @@ struct FrameParams {
     uint32_t spp, jitter_spp, seed, bounces;
     rwr_sphere_buffer_data spheres[RWR_MAX_SPHERES];
     // conservative pixel-space bounds {x0, y0, x1, y1} of each sphere's silhouette
-    // (host-computed per frame, context.cpp); a tile outside them skips the sphere
+    // (host-computed per frame, frame_consts.cpp); a tile outside them skips the sphere
     float sphere_rect[RWR_MAX_SPHERES][4];
     // conservative pixel-space bounds of the whole mesh's bounding box (+-inf when the camera is in or near it):
     // a tile outside skips the mesh pass
@@ -203,6 +212,28 @@ struct FrameParams {
 // 8-row strips a launch renders (the y extent of every render kernel's grid)
 inline uint32_t band_strips(const FrameParams &fp) { return fp.row_end > fp.row_begin ? (fp.row_end - fp.row_begin + fp.row_pitch - 1u) / fp.row_pitch : 0u; }
 
+// Host arithmetic of a frame (frame_consts.cpp; no device needed): what fill_frame_consts reads of the scene and the screen ...
+struct FrameScene {
+    uint32_t width, height;
+    const rwr_sphere_buffer_data *spheres;
+    uint32_t n_spheres;
+    uint32_t n_tris, tex_w, tex_h;
+    const float *aabb_lo, *aabb_hi;   // of the world-space faces
+    const rwr_material_data *material;
+    const MaterialRec *materials;     // device
+    uint32_t n_materials;
+    const TangentRec *tangents;       // device
+    uint32_t wave_cull_min;
+};
+// ... and what it makes of them and the camera: the kernels' parameters but the per-frame tables, bins and tile lists (whoever
+// enqueues the frame owns those), the culling constants, and the mean projected area of a face in pixels (+inf: unknown)
+struct FrameConsts {
+    FrameParams fp;
+    CullConsts cc;
+    double mean_face_px;
+};
+void fill_frame_consts(const FrameScene &scene, const rwr_camera_inv_uniform &cam, const rwr_render_params &rp, bool accumulate,
+                       uint32_t row_begin, uint32_t row_end, uint32_t row_pitch, FrameConsts &out);
 
 // context.cpp: records the calling thread's error message, returns `code`.
 int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));

@@ -9,7 +9,7 @@
 // 32 * width bytes from the buffer's start: 16-byte aligned for any width).
 //
 // ONE definition for everything that has to agree: the sizes of the RCCL sends and receives and the receive offsets
-// (context.cpp), the pack and deal-out kernels (kernels_dist.hip), the host-memory forms and rwr_dist_strip_layout
+// (dist.cpp), the pack and deal-out kernels (kernels_dist.hip), the host-memory forms and rwr_dist_strip_layout
 // (what the tests and a host binding see).
 #pragma once
 #include <cstdint>

@@ -129,6 +129,26 @@ def test_frame_graph_knob_gives_the_same_frames(rwr, suzanne, monkeypatch):
 
 
 @pytest.mark.gpu
+def test_frame_graph_frame_invalidates_the_slots_aux_planes(rwr, suzanne, monkeypatch):
+    """A frame without FLAG_AUX_OUTPUTS leaves its slot without aux planes to read back, however it was launched: after an aux
+    frame, a plain frame in the same slot — a graph launch with RWR_FRAME_GRAPH=1 — must not hand out the older frame's."""
+    cam = rwr.camera_build_inv_uniform(rwr.make_camera(eye=(0, 0, 3), aspect=320 / 180))
+    for graph in ("0", "1"):
+        monkeypatch.setenv("RWR_FRAME_GRAPH", graph)
+        with rwr.Context(0) as ctx:
+            ctx.upload_model(suzanne)
+            ctx.set_spheres(rwr.make_spheres())
+            ctx.resize(320, 180)
+            ctx.render(cam, rwr.make_params(flags=rwr.FLAG_AUX_OUTPUTS))
+            assert (ctx.readback(aux=True)["obj_id"] >= 0).any()
+            ctx.render(cam, rwr.make_params())                  # one frame in flight: the same slot
+            with pytest.raises(rwr.RwrError) as ei:
+                ctx.readback(aux=True)
+            assert ei.value.code == rwr.ERR_NOT_READY, graph
+            assert ctx.readback()["color"].any()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("fused", ["0", "1"])
 def test_one_launch_per_frame_gives_the_same_frames(rwr, orc, suzanne, monkeypatch, fused):
     """The frame kernel's fused form (its first workgroups make the frame's records, the others wait for them: ONE launch per

@@ -2,7 +2,7 @@
 tests/test_gpu_world_offset.py).  For every pixel the oracle shows a face at, tests/world_offset_common.audit measures in
 float64 how far the pixel's centre ray passes outside that face, and the margin that each conservative test grants it:
 the edge functions and the face rectangle of csrc/rwr_cull.h make_frame_tri (with the half-pixel guard between tile
-bounds and pixel centres) and the whole-mesh rectangle of context.cpp.  Every stray must be covered (ratio <= 1), and the
+bounds and pixel centres) and the whole-mesh rectangle of frame_consts.cpp.  Every stray must be covered (ratio <= 1), and the
 margins without the world-magnitude term must NOT cover the far scenes: that is the hazard the term exists for."""
 import numpy as np
 import pytest

@@ -134,7 +134,7 @@ def audit(cam_inv, w, h, fovy, model, frame, world_term=True):
         with np.errstate(invalid="ignore"):
             rect = max(rect, float(np.where(front & (out_by > 0), out_by / (0.5 + pad), 0.0).max()))
     out["rect"] = rect
-    # the whole mesh's rectangle (context.cpp mesh_screen_rect + its margins), from the box of every face
+    # the whole mesh's rectangle (frame_consts.cpp mesh_screen_rect + its margins), from the box of every face
     lo3, hi3 = tri.reshape(-1, 3).min(0), tri.reshape(-1, 3).max(0)
     corners = np.array([[(hi3 if (c >> k) & 1 else lo3)[k] for k in range(3)] for c in range(8)]) - cc["O"]
     cvx, cvy = corners @ cc["Vx"], corners @ cc["Vy"]
