@@ -176,11 +176,37 @@ enum {
                                        more samples than the cap is RWR_ERR_INVALID_ARGUMENT.  With RWR_FLAG_ORTHO_RAYS,
                                        RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED.  Frames in flight and
                                        row bands / strips keep the contract (the sums are keyed by global pixel) */
-    RWR_FLAG_MULTI_BOUNCE = 1u << 6 /* extension: max_bounces may be 0 ... RWR_MAX_BOUNCES (diffuse paths of that many bounces,
+    RWR_FLAG_MULTI_BOUNCE = 1u << 6,/* extension: max_bounces may be 0 ... RWR_MAX_BOUNCES (diffuse paths of that many bounces,
                                        rwr_render_params); more is RWR_ERR_INVALID_ARGUMENT.  With max_bounces <= 1 every plane
                                        is the frame without the flag, byte for byte.  RWR_FLAG_USE_BVH, RWR_FLAG_ORTHO_RAYS and
                                        single-triangle passes stay reference-frame only.  rwr_last_render_stats' bounce_rays
                                        counts the rays of every bounce */
+    RWR_FLAG_SHADOWS = 1u << 7      /* extension: shadow rays towards the reference's two directional lights.  Without the flag
+                                       every frame is what it was, byte for byte.  With it:
+                                       1. The frame always takes the path integrator, also at spp 1 / max_bounces 0.  Samples are
+                                          placed as without the flag (pixel centre at spp 1, jittered from spp 2; an accumulating
+                                          frame: jittered).  Every term is clamped as in the integrator (E(h0) to [0, 16], later
+                                          terms to [0, 64], NaN as 0), also at spp 1 / no bounce.  The depth, object id and t
+                                          planes (sample 0) are unchanged by the flag, bit for bit.
+                                       2. Every hit h the integrator shades (h0 and every bounce hit) has one shadow ray:
+                                          origin P + 1e-4 n, P = origin + t * direction of the ray that found h, n the hit
+                                          record's normal (face normal flipped towards the ray, sphere's outward normal; normal
+                                          maps never change it) - operation for operation the origin of the bounce ray that
+                                          leaves h; direction -normalize(kLightDir) in f32, kLightDir = (1, -1, -5) for a mesh
+                                          hit and (1, -5, 1) for a sphere hit (the reference's two shaders have two lights).
+                                          occluded(h): any sphere or any face (all instances, all parts) is hit by that ray in
+                                          the reference's own sphereRayIntersect / triangleRayIntersect arithmetic.  No distance
+                                          limit, and the face h lies on is not excluded: a surface whose ray-facing side looks
+                                          away from the light shadows itself.
+                                       3. The local shading E(h) of an occluded hit is its ambient part alone: the part's
+                                          MaterialData.ambient for a mesh hit, (0.1, 0, 0) for a sphere hit.  Albedo, throughput,
+                                          random numbers and every primary and bounce ray are those of the frame without the
+                                          flag, bit for bit; term k is clamp(T(k-1) * E_V(h_k)) with the caps above.
+                                       4. RWR_FLAG_ACCUMULATE, RWR_FLAG_MULTI_BOUNCE, RWR_FLAG_NORMAL_MAP, RWR_FLAG_AUX_OUTPUTS,
+                                          RWR_FLAG_NO_CULL, instances, parts, frames in flight, row bands, strips and the multi-GPU
+                                          gather keep their contracts.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or
+                                          single-triangle passes: RWR_ERR_UNSUPPORTED.
+                                       5. rwr_last_shadow_stats counts the shadow rays and how many were occluded. */
 };
 
 #define RWR_MAX_BOUNCES 8u
@@ -399,6 +425,11 @@ RWR_API int rwr_kernel_timing_stats(rwr_context *ctx, double *mean_us, uint32_t 
  * W*rows*spp primary + bounce rays actually emitted, of every generation with RWR_FLAG_MULTI_BOUNCE (an accumulating frame:
  * its own spp; 0 past the cap). */
 RWR_API int rwr_last_render_stats(rwr_context *ctx, uint64_t *primary_rays, uint64_t *bounce_rays);
+
+/* RWR_FLAG_SHADOWS: shadow rays traced by the last render call (= hits shaded: primary hits and the bounce hits of every
+ * generation; an accumulating frame: its own samples; 0 without the flag) and how many of them were occluded.  Exact counts.
+ * Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_last_shadow_stats(rwr_context *ctx, uint64_t *shadow_rays, uint64_t *occluded);
 
 /* Progressive accumulation (RWR_FLAG_ACCUMULATE).  One context holds one accumulation.
  * rwr_accum_reset: the next accumulating frame starts over at N = 0 (host-side only, nothing waits).

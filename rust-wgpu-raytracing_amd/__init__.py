@@ -45,6 +45,7 @@ FLAG_ORTHO_RAYS = 1 << 3
 FLAG_NORMAL_MAP = 1 << 4
 FLAG_ACCUMULATE = 1 << 5
 FLAG_MULTI_BOUNCE = 1 << 6   # max_bounces up to MAX_BOUNCES (include/rwr_hip.h)
+FLAG_SHADOWS = 1 << 7        # shadow rays towards the reference's two lights (include/rwr_hip.h)
 MAX_BOUNCES = 8
 FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
 KEY_FORWARD, KEY_BACKWARD, KEY_LEFT, KEY_RIGHT, KEY_UP, KEY_DOWN = 1, 2, 4, 8, 16, 32
@@ -107,6 +108,7 @@ def lib() -> C.CDLL:
         "rwr_resize": [vp, vp], "rwr_render": [vp, vp, vp], "rwr_render_rows": [vp, vp, vp, u32, u32], "rwr_render_strips": [vp, vp, vp, u32, u32],
         "rwr_synchronize": [vp], "rwr_readback": [vp, vp, vp, vp, vp, vp], "rwr_get_device_targets": [vp, vp, vp],
         "rwr_timer_begin": [vp], "rwr_timer_end": [vp, vp], "rwr_timer_stop": [vp], "rwr_timer_elapsed": [vp, vp], "rwr_last_render_stats": [vp, vp, vp],
+        "rwr_last_shadow_stats": [vp, vp, vp],
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
         "rwr_load_model_compute": [C.c_char_p, C.c_char_p, vp], "rwr_model_free": [vp],
@@ -124,8 +126,13 @@ def lib() -> C.CDLL:
         "rwr_dist_loopback_deposit": [vp, u32, u32, i32], "rwr_dist_loopback_finish": [vp, u32, i32],
         "rwr_measure_valu_clock": [vp, u32, vp], "rwr_clock_probe_start": [vp, u32], "rwr_clock_probe_read": [vp, vp],
     }
+    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats",)   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
-        fn = getattr(L, name)
+        fn = getattr(L, name, None)
+        if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
+            continue   # an A/B build of an earlier commit (tools/ab.sh, tools/shadow_probe.py) lacks it; calling it raises
+        if fn is None:
+            raise AttributeError(f"{LIB_PATH} does not export {name}")
         fn.argtypes = argtypes
         if name not in ("rwr_ctx_destroy", "rwr_model_free", "rwr_free", "rwr_ctx_get_stream"):
             fn.restype = C.c_int
@@ -587,6 +594,12 @@ class Context:
     def last_render_stats(self) -> tuple[int, int]:
         a, b = C.c_uint64(), C.c_uint64()
         _check(lib().rwr_last_render_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def last_shadow_stats(self) -> tuple[int, int]:
+        """(shadow rays traced by the last render call, how many of them were occluded); (0, 0) without FLAG_SHADOWS."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(lib().rwr_last_shadow_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def accum_reset(self):

@@ -374,6 +374,20 @@ int rwr_last_render_stats(rwr_context *ctx, uint64_t *primary_rays, uint64_t *bo
     return RWR_OK;
 }
 
+int rwr_last_shadow_stats(rwr_context *ctx, uint64_t *shadow_rays, uint64_t *occluded)
+{
+    if (!ctx || !shadow_rays || !occluded) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    unsigned long long counts[2] = {0ull, 0ull};
+    if (ctx->last_shadows && ctx->wf_state[ctx->last_wf_state].d_shadow_counts.ptr) {
+        DeviceGuard g(ctx->device);
+        RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
+        RWR_HIP_CHECK(hipMemcpy(counts, ctx->wf_state[ctx->last_wf_state].d_shadow_counts.ptr, sizeof counts, hipMemcpyDeviceToHost));
+    }
+    *shadow_rays = counts[0];
+    *occluded = counts[1];
+    return RWR_OK;
+}
+
 int rwr_accum_reset(rwr_context *ctx)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");

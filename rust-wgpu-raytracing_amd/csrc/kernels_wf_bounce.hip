@@ -43,6 +43,7 @@
 #include "rwr_bvh.h"
 #include "rwr_primary.h"
 #include "rwr_shade_p2.h"
+#include "rwr_wf_pool.h"
 
 namespace rwr {
 
@@ -264,44 +265,6 @@ k_wf_sort(const WfBuffers wf, PoolInfo *__restrict__ info, uint32_t *__restrict_
     }
 }
 
-// What a trace workgroup keeps in LDS: fixed-point sums of albedo * E(h1) per pixel of the tile.
-struct TraceShared {
-    unsigned long long acc[kWfTilePixels * 3u];
-    uint32_t oct_begin[9], pk_begin[9];   // packet kernel: where each octant's rays / packets begin
-    uint32_t next_packet;
-    uint32_t item;                        // the work item the workgroup pulled
-};
-
-// Adds one ray's contribution albedo(h0) * E(h1) to its pixel's fixed-point sums.  e: the ray's pool slot.
-RWR_DEV void add_contribution(TraceShared &sh, uint32_t e, float cr, float cg, float cb)
-{
-    const uint32_t r = e & (kWfTilePixels - 1u), w = r >> 7, k = (r >> 6) & 1u, l = r & 63u;
-    const uint32_t lx = (w & 1u) * 32u + 2u * (l & 15u) + k, ly = (w >> 1) * 4u + (l >> 4);
-    unsigned long long *dst = &sh.acc[(ly * kWfTileW + lx) * 3u];
-    // float -> u32 conversion saturates and sends NaN / negatives to 0
-    atomicAdd(dst + 0, (unsigned long long)(uint32_t)(cr * kWfFixedScale));
-    atomicAdd(dst + 1, (unsigned long long)(uint32_t)(cg * kWfFixedScale));
-    atomicAdd(dst + 2, (unsigned long long)(uint32_t)(cb * kWfFixedScale));
-}
-
-// Step 4: the workgroup's sums -> the frame's fixed-point bounce planes (integer atomics: whichever workgroups
-// share the pool, in whatever order, the sums are the same bits).  Call after a barrier.
-RWR_DEV void flush_pool(TraceShared &sh, const FrameParams &p, const WfBuffers &wf, uint32_t tile)
-{
-    const uint32_t tile_x0 = (tile % wf.tiles_x) * kWfTileW, tile_y0 = p.row_begin + (tile / wf.tiles_x) * p.row_pitch;
-    const size_t plane = (size_t)p.width * p.height;   // (planes 0..2: red, green, blue; plane 3 is the primary stage's alpha)
-    for (uint32_t q = threadIdx.x; q < kWfTilePixels; q += blockDim.x) {
-        const uint32_t px = tile_x0 + (q & (kWfTileW - 1u)), py = tile_y0 + q / kWfTileW;
-        const unsigned long long sr = sh.acc[q * 3u], sg = sh.acc[q * 3u + 1u], sb = sh.acc[q * 3u + 2u];
-        if ((sr | sg | sb) != 0ull && px < p.width && py < p.row_end) {
-            const size_t pixel = (size_t)py * p.width + px;
-            if (sr) atomicAdd(&wf.fix[pixel], sr);
-            if (sg) atomicAdd(&wf.fix[plane + pixel], sg);
-            if (sb) atomicAdd(&wf.fix[2u * plane + pixel], sb);
-        }
-    }
-}
-
 // EMIT forms: the next ray of the path whose ray hit (obj, t) — from P + 1e-4 n (P = O + t D, n = the face's normal flipped
 // towards the ray or the sphere's outward normal, as the first stage builds the first bounce ray), in the cosine-distributed
 // direction of RNG dimensions em.next_dim ... keyed by the slot's global pixel and sample, throughput thr — goes back into slot
@@ -309,15 +272,8 @@ RWR_DEV void flush_pool(TraceShared &sh, const FrameParams &p, const WfBuffers &
 RWR_DEV void emit_next_ray(const FrameParams &p, const WfBuffers &wf, const WfEmit &em, const TriRecord *__restrict__ tris, uint32_t tile,
                            uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr)
 {
-    const f3 P = along(O, t, D);
     f3 n;
-    if (obj >= 0) {
-        n = ld3(tris[obj].nhat);
-        if (ndotd > 0.0f) n = neg3(n);   // compute.wgsl:140-142
-    } else {
-        n = normalize3(sub3(P, ld3(p.spheres[-2 - obj].center)));
-    }
-    const f3 O1 = mk3(P.x + n.x * 1e-4f, P.y + n.y * 1e-4f, P.z + n.z * 1e-4f);
+    const f3 O1 = hit_exit_point(p, tris, O, D, obj, t, ndotd, n);
     // the slot's pixel (as add_contribution maps it) and sample
     const uint32_t r = e & (kWfTilePixels - 1u), w = r >> 7, k = (r >> 6) & 1u, l = r & 63u;
     const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (w & 1u) * 32u + 2u * (l & 15u) + k;
@@ -328,6 +284,24 @@ RWR_DEV void emit_next_ray(const FrameParams &p, const WfBuffers &wf, const WfEm
     wf.rays[2u * slot + 1u] = make_float4(D1.x, D1.y, D1.z, wf_pack_unorm16x2(thr.z, 0.0f));
     wf.bins[slot] = (uint16_t)wf_direction_bin(D1);
     atomicOr(&em.masks_out[(size_t)tile * wf.group * 8u + (e >> 6)], 1ull << (e & 63u));
+}
+
+// SHADOW forms: the term T * E(h) of the hit (obj, t) of the ray in slot e is a select between clamp(T * ambient part) and
+// clamp(T * E(h)), decided by the hit's shadow ray.  The ambient value goes into the sums here, the record for k_wf_shadow
+// (origin = the next bounce ray's, the light of the shader that shades h, the difference of the two fixed-point values) into
+// the hit's slot, its bit into the shadow ballots (cleared before the generation).
+RWR_DEV void shadow_hit(TraceShared &sh, const FrameParams &p, const WfBuffers &wf, const WfShadow &sw, const TriRecord *__restrict__ tris,
+                        const ShadeRec *__restrict__ shade, uint32_t tile, uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr, f3 e1)
+{
+    const f3 amb = hit_ambient(p, shade, obj);
+    const float cf[3] = {thr.x * e1.x, thr.y * e1.y, thr.z * e1.z}, ca[3] = {thr.x * amb.x, thr.y * amb.y, thr.z * amb.z};
+    uint32_t ff[3], fa[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) { ff[c] = (uint32_t)(cf[c] * kWfFixedScale); fa[c] = (uint32_t)(ca[c] * kWfFixedScale); }   // (as add_contribution)
+    add_fixed(sh, e, fa[0], fa[1], fa[2]);
+    f3 n;
+    const f3 O1 = hit_exit_point(p, tris, O, D, obj, t, ndotd, n);
+    write_shadow_record(sw, (size_t)tile * wf.group * kWfTilePixels + e, (size_t)tile * wf.group * 8u + (e >> 6), e & 63u, O1, obj < 0, fa, ff);
 }
 
 // The trace kernels are PERSISTENT: kWfTraceGroups workgroups pull work items — (pool of the class, share of it)
@@ -373,11 +347,13 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // workgroups per CU to hold a copy each — 508 nodes = 65 KB at configs[3] — but small enough for one per CU): every node fetch
 // of the traversal then comes from LDS instead of through the vector memory pipe, 64 different 16-byte pieces per load.
 // EMIT: a generation of a deeper path that is not its last (emit_next_ray).
-template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false>
+// SHADOW: RWR_FLAG_SHADOWS — a hit adds its term's ambient part and leaves a shadow record (shadow_hit); separate instantiations,
+// so that frames without the flag keep their kernels.
+template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false>
 __global__ void __launch_bounds__(WIDE ? 1024 : 256)
 k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                 const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
-                uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em)
+                uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw)
 {
     __shared__ TraceShared sh;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
@@ -441,7 +417,8 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
             if (have) {
                 const Shaded s1 = shade_winner<NMAP>(p, obj, best_t, mh.u, mh.v, mh.ndotd, shade, tex, O, D);
                 const f3 e1 = s1.colour;
-                add_contribution(sh, e, thr.x * e1.x, thr.y * e1.y, thr.z * e1.z);
+                if (SHADOW) shadow_hit(sh, p, wf, sw, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, e1);
+                else add_contribution(sh, e, thr.x * e1.x, thr.y * e1.y, thr.z * e1.z);
                 if (EMIT)
                     emit_next_ray(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd,
                                   mk3(thr.x * s1.albedo.x, thr.y * s1.albedo.y, thr.z * s1.albedo.z));
@@ -535,11 +512,11 @@ RWR_DEV i2 sphere_pair_intersect_t(f3 center, float radius, v3 O, v3 D, f2 &t_ou
 #ifndef RWR_PACKET_OCC
 #define RWR_PACKET_OCC 4
 #endif
-template <bool NMAP, bool EMIT = false>   // EMIT: see k_wf_trace_lane
+template <bool NMAP, bool EMIT = false, bool SHADOW = false>   // EMIT, SHADOW: see k_wf_trace_lane
 __global__ void __launch_bounds__(256, RWR_PACKET_OCC)
 k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
-                  uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em)
+                  uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw)
 {
     __shared__ TraceShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -732,9 +709,18 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
                     }
                 }
             }
+            if (SHADOW) {   // one ray of the lane after the other
+#pragma unroll
+                for (int k = 0; k < 2; k++)
+                    if (k ? have.y : have.x)
+                        shadow_hit(sh, p, wf, sw, tris, shade, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), k ? obj.y : obj.x, k ? best_t.y : best_t.x,
+                                   k ? best.ndotd.y : best.ndotd.x, k ? mk3(thr.x.y, thr.y.y, thr.z.y) : mk3(thr.x.x, thr.y.x, thr.z.x),
+                                   k ? mk3(er.y, eg.y, eb.y) : mk3(er.x, eg.x, eb.x));
+            } else {
             const f2 cr = thr.x * er, cg = thr.y * eg, cb = thr.z * eb;
             if (have.x) add_contribution(sh, e0, cr.x, cg.x, cb.x);
             if (have.y) add_contribution(sh, e1, cr.y, cg.y, cb.y);
+            }
             if (EMIT) {   // every hit's next ray, one ray of the lane after the other
                 const f2 nr = thr.x * ar, ng = thr.y * ag, nb = thr.z * ab;
 #pragma unroll
@@ -754,9 +740,12 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
 
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf, uint32_t n_tiles,
-                            uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list, const WfEmit *emit)
+                            uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list, const WfEmit *emit,
+                            const WfShadow *shadow)
 {
     const WfEmit em = emit ? *emit : WfEmit{nullptr, 0u, 0u};
+    const WfShadow sw = shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr};
+    const bool shadows = sw.recs != nullptr;
     if (n_tiles == 0 || sample_count == 0) return hipSuccess;
     uint32_t *counters = wf.counters;   // this queue's set, zeroed by the primary stage that filled the queue
     PoolInfo *info = static_cast<PoolInfo *>(pool_info);
@@ -785,30 +774,36 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
                            sample_count, packets ? packet_min_rays : 0xffffffffu, bvh.packet_extent, bvh.packet_dense_rays);
     const dim3 grid(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit));
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
-    if (packets && emit) {
-        if (nmap) hipLaunchKernelGGL((k_wf_trace_packet<true, true>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em);
-        else hipLaunchKernelGGL((k_wf_trace_packet<false, true>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em);
+#define RWR_PACKET_LAUNCH(N, E, S) hipLaunchKernelGGL((k_wf_trace_packet<N, E, S>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw)
+    if (packets && shadows) {
+        if (emit) { if (nmap) RWR_PACKET_LAUNCH(true, true, true); else RWR_PACKET_LAUNCH(false, true, true); }
+        else { if (nmap) RWR_PACKET_LAUNCH(true, false, true); else RWR_PACKET_LAUNCH(false, false, true); }
+    } else if (packets && emit) {
+        if (nmap) RWR_PACKET_LAUNCH(true, true, false); else RWR_PACKET_LAUNCH(false, true, false);
     } else if (packets) {
-        if (nmap) hipLaunchKernelGGL((k_wf_trace_packet<true>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em);
-        else hipLaunchKernelGGL((k_wf_trace_packet<false>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em);
+        if (nmap) RWR_PACKET_LAUNCH(true, false, false); else RWR_PACKET_LAUNCH(false, false, false);
     }
+#undef RWR_PACKET_LAUNCH
     const bool stack16 = bvh.n_nodes <= 0x7fffu && fp.n_tris <= 4095u;   // node indices and leaf links (first << 3 | count - 1) in 15 bits
     const size_t fixed = (size_t)bvh.stack_depth * 256u * (stack16 ? 2u : 4u);
     const size_t node_bytes = (size_t)bvh.n_nodes * sizeof(BvhNode4);
     // nodelets go to LDS when the workgroup then still fits a CU at least four times (160 KiB LDS, 12 KiB static)
-#define RWR_LANE_LAUNCH(L, N, S16, E, BYTES) hipLaunchKernelGGL((k_wf_trace_lane<L, N, S16, false, E>), grid, dim3(256), BYTES, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em)
-#define RWR_LANE_LAUNCH1(L, E, BYTES) \
-    if (nmap) { if (stack16) RWR_LANE_LAUNCH(L, true, true, E, BYTES); else RWR_LANE_LAUNCH(L, true, false, E, BYTES); } \
-    else { if (stack16) RWR_LANE_LAUNCH(L, false, true, E, BYTES); else RWR_LANE_LAUNCH(L, false, false, E, BYTES); }
+#define RWR_LANE_LAUNCH(L, N, S16, E, S, BYTES) hipLaunchKernelGGL((k_wf_trace_lane<L, N, S16, false, E, S>), grid, dim3(256), BYTES, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw)
+#define RWR_LANE_LAUNCH0(L, E, S, BYTES) \
+    if (nmap) { if (stack16) RWR_LANE_LAUNCH(L, true, true, E, S, BYTES); else RWR_LANE_LAUNCH(L, true, false, E, S, BYTES); } \
+    else { if (stack16) RWR_LANE_LAUNCH(L, false, true, E, S, BYTES); else RWR_LANE_LAUNCH(L, false, false, E, S, BYTES); }
+#define RWR_LANE_LAUNCH1(L, E, BYTES) if (shadows) { RWR_LANE_LAUNCH0(L, E, true, BYTES) } else { RWR_LANE_LAUNCH0(L, E, false, BYTES) }
 #define RWR_LANE_LAUNCH2(L, BYTES) if (emit) { RWR_LANE_LAUNCH1(L, true, BYTES) } else { RWR_LANE_LAUNCH1(L, false, BYTES) }
     const size_t fixed_wide = 4u * fixed, wide_bytes = node_bytes + fixed_wide;
     if (node_bytes + fixed <= 28u * 1024u) { RWR_LANE_LAUNCH2(true, node_bytes + fixed) }
     else if (bvh.wide_lane && !nmap && stack16 && wide_bytes + 14u * 1024u <= 160u * 1024u) {
         // a BVH too large for a copy per 256-thread workgroup, small enough for one copy per CU: 1 024-thread workgroups
-        static std::atomic<uint64_t> wide_raised_on{0}, wide_emit_raised_on{0};
-        std::atomic<uint64_t> &raised = emit ? wide_emit_raised_on : wide_raised_on;
-        const void *kernel = emit ? reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, true>)
-                                  : reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true>);
+        static std::atomic<uint64_t> wide_raised_on[4];   // per form: [emit + 2 * shadows]
+        std::atomic<uint64_t> &raised = wide_raised_on[(emit ? 1 : 0) + (shadows ? 2 : 0)];
+        const void *kernel = shadows ? (emit ? reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, true, true>)
+                                             : reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, false, true>))
+                                     : (emit ? reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, true>)
+                                             : reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true>));
         int dev = 0;
         hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) return e;
@@ -818,16 +813,16 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
             if (e != hipSuccess) return e;
             raised.fetch_or(bit, std::memory_order_release);
         }
-        if (emit)
-            hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true, true>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, fp, tris,
-                               shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em);
-        else
-            hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, fp, tris, shade, bvh, tex,
-                               wf, info, counters, pool_list, n_tiles, em);
+#define RWR_WIDE_LAUNCH(E, S) hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true, E, S>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, fp, tris, \
+                                                 shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw)
+        if (shadows) { if (emit) RWR_WIDE_LAUNCH(true, true); else RWR_WIDE_LAUNCH(false, true); }
+        else { if (emit) RWR_WIDE_LAUNCH(true, false); else RWR_WIDE_LAUNCH(false, false); }
+#undef RWR_WIDE_LAUNCH
     }
     else { RWR_LANE_LAUNCH2(false, fixed) }
 #undef RWR_LANE_LAUNCH2
 #undef RWR_LANE_LAUNCH1
+#undef RWR_LANE_LAUNCH0
 #undef RWR_LANE_LAUNCH
     return hipGetLastError();
 }

@@ -146,6 +146,7 @@ struct WfPrimaryArgs {
     const float4 *tex;
     Targets tg;
     WfBuffers wf;
+    WfShadow sw;   // RWR_FLAG_SHADOWS (the SHADOW forms); last, so that the other forms read their arguments where they always did
 };
 template <typename T> using kernarg = const __attribute__((address_space(4))) T;
 RWR_DEV kernarg<WfPrimaryArgs> *wf_args_again(kernarg<WfPrimaryArgs> *q)
@@ -155,10 +156,13 @@ RWR_DEV kernarg<WfPrimaryArgs> *wf_args_again(kernarg<WfPrimaryArgs> *q)
 }
 RWR_DEV f3 ld3(kernarg<float> *q) { return mk3(q[0], q[1], q[2]); }
 
-template <bool AUX, bool CULL, bool NMAP, bool LIST = false>
+// SHADOW (RWR_FLAG_SHADOWS): a hit adds the AMBIENT part of E(h0) to the group's sums and leaves a shadow record — the bounce
+// ray's origin, the light of the shader that shaded it, fix(E) - fix(ambient) — at its queue slot, with its bit in the shadow
+// ballots, for k_wf_shadow (kernels_wf_shadow.hip).  Forms of their own: the others keep their registers.
+template <bool AUX, bool CULL, bool NMAP, bool LIST = false, bool SHADOW = false>
 // (LIST — frames that show little — keeps an item loop's state on top of everything else and needs 142 registers: three waves
 // per SIMD like the AUX / NMAP forms; such a frame does not fill the chip anyway)
-__global__ void __launch_bounds__(256, (AUX || NMAP || LIST) ? 3 : RWR_WF_OCC)
+__global__ void __launch_bounds__(256, (AUX || NMAP || LIST || SHADOW) ? 3 : RWR_WF_OCC)
 k_wf_primary(const WfPrimaryArgs a)
 {
     kernarg<WfPrimaryArgs> *const ka = (kernarg<WfPrimaryArgs> *)__builtin_amdgcn_kernarg_segment_ptr();
@@ -228,6 +232,11 @@ k_wf_primary(const WfPrimaryArgs a)
     if (empty_tile && qi->p.bounces != 0u && lane == 0u && z == 0u)    // nothing emitted: the bounce stage sees empty ballots
         for (uint32_t sidx = 0; sidx < sample_count; sidx++) {
             unsigned long long *mk = qi->wf.masks + (size_t)(tile * qi->wf.group + sidx) * 8u + wave * 2u;
+            mk[0] = 0ull; mk[1] = 0ull;
+        }
+    if (SHADOW && empty_tile && lane == 0u && z == 0u)   // ... and no shadow records
+        for (uint32_t sidx = 0; sidx < sample_count; sidx++) {
+            unsigned long long *mk = qi->sw.masks + (size_t)(tile * qi->wf.group + sidx) * 8u + wave * 2u;
             mk[0] = 0ull; mk[1] = 0ull;
         }
 
@@ -356,6 +365,34 @@ k_wf_primary(const WfPrimaryArgs a)
             }
         }
         const i2 hit = obj != -1;
+        int32_t dr0 = 0, dg0 = 0, db0 = 0, dr1 = 0, dg1 = 0, db1 = 0;   // SHADOW: fix(E) - fix(ambient part) in the planes' units
+        if (SHADOW) {
+            // the term is a select between its ambient part and E(h0), decided by the hit's shadow ray: the ambient part is summed
+            // here, the difference of the two fixed-point values travels in the record
+            constexpr float kScale22 = kWfFixedScale / 16.0f;
+            constexpr uint32_t kCap = (kWfE0Cap << 22) - 1u;
+            kernarg<WfPrimaryArgs> *const qa = wf_args_again(ka);
+            f2 ar = splat(qa->p.ambient[0]), ag = splat(qa->p.ambient[1]), ab = splat(qa->p.ambient[2]);
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int o = k ? obj.y : obj.x;
+                f3 am = mk3(k ? ar.y : ar.x, k ? ag.y : ag.x, k ? ab.y : ab.x);
+                if (o < -1) am = mk3(0.1f, 0.0f, 0.0f);   // sphere/compute.wgsl: 0.1 * mat_color
+                else if (o >= 0 && qa->p.n_materials > 1u) am = ld3(qa->p.materials[qa->shade[o].material].ambient);
+                if (o == -1) am = mk3(0.0f, 0.0f, 0.0f);
+                if (k) { ar.y = am.x; ag.y = am.y; ab.y = am.z; } else { ar.x = am.x; ag.x = am.y; ab.x = am.z; }
+            }
+            const f2 sr = cr * kScale22, sg = cg * kScale22, sb = cb * kScale22;
+            const f2 qr = ar * kScale22, qg = ag * kScale22, qb2 = ab * kScale22;
+            const uint32_t F[6] = {min((uint32_t)sr.x, kCap), min((uint32_t)sg.x, kCap), min((uint32_t)sb.x, kCap),
+                                   min((uint32_t)sr.y, kCap), min((uint32_t)sg.y, kCap), min((uint32_t)sb.y, kCap)};
+            const uint32_t A[6] = {min((uint32_t)qr.x, kCap), min((uint32_t)qg.x, kCap), min((uint32_t)qb2.x, kCap),
+                                   min((uint32_t)qr.y, kCap), min((uint32_t)qg.y, kCap), min((uint32_t)qb2.y, kCap)};
+            fr0 += A[0]; fg0 += A[1]; fb0 += A[2]; fr1 += A[3]; fg1 += A[4]; fb1 += A[5];
+            dr0 = ((int32_t)F[0] - (int32_t)A[0]) * 16; dg0 = ((int32_t)F[1] - (int32_t)A[1]) * 16; db0 = ((int32_t)F[2] - (int32_t)A[2]) * 16;
+            dr1 = ((int32_t)F[3] - (int32_t)A[3]) * 16; dg1 = ((int32_t)F[4] - (int32_t)A[4]) * 16; db1 = ((int32_t)F[5] - (int32_t)A[5]) * 16;
+            hits0 += hit.x ? 1u : 0u; hits1 += hit.y ? 1u : 0u;
+        } else
         {   // (cr, cg, cb are 0 where nothing was hit; float -> u32 conversion sends NaN / negatives to 0; alpha is 1 + 1 on a
             // written pixel, :231-234)
             constexpr float kScale22 = kWfFixedScale / 16.0f;
@@ -369,17 +406,22 @@ k_wf_primary(const WfPrimaryArgs a)
 
         // -- bounce ray of every pixel that hit something ----------------------------------------------------------
         kernarg<WfPrimaryArgs> *const qb = wf_args_again(ka);   // the ray queue
-        if (qb->p.bounces != 0u) {
+        if (SHADOW || qb->p.bounces != 0u) {
+            const bool bounces = !SHADOW || qb->p.bounces != 0u;   // (without SHADOW: what got us here)
             const uint32_t wf_group = qb->wf.group;
             const TriRecord *tris = qb->tris;
             const i2 emit = hit & i2{in0 ? -1 : 0, in1 ? -1 : 0};
             const unsigned long long m0 = __ballot(emit.x != 0), m1 = __ballot(emit.y != 0);
             const uint32_t slot_base = (tile * wf_group + sidx) * kWfTilePixels + wave * 128u;
-            if (lane == 0u) {
+            if (bounces && lane == 0u) {
                 unsigned long long *mk = qb->wf.masks + (size_t)(tile * wf_group + sidx) * 8u + wave * 2u;
                 mk[0] = m0; mk[1] = m1;
             }
-            emitted += (uint32_t)__popcll(m0) + (uint32_t)__popcll(m1);
+            if (SHADOW && lane == 0u) {
+                unsigned long long *mk = qb->sw.masks + (size_t)(tile * wf_group + sidx) * 8u + wave * 2u;
+                mk[0] = m0; mk[1] = m1;
+            }
+            if (bounces) emitted += (uint32_t)__popcll(m0) + (uint32_t)__popcll(m1);
             if (m0 | m1) {
                 // mesh winners: +-normalize(N), prebaked with the shader's own operations (TriRecord::nhat)
 #pragma unroll
@@ -393,6 +435,22 @@ k_wf_primary(const WfPrimaryArgs a)
                 }
                 const v3 P = along(splat3(O), win_t, D);
                 const v3 O1 = v3{P.x + n.x * 1e-4f, P.y + n.y * 1e-4f, P.z + n.z * 1e-4f};
+                if (SHADOW) {
+                    ShadowRec *const recs = wf_args_again(ka)->sw.recs;
+                    if (emit.x) {
+                        uint4 *dst = reinterpret_cast<uint4 *>(recs + slot_base + lane);
+                        const uint32_t fl = (obj.x < -1 ? 1u : 0u) | (dr0 < 0 ? 2u : 0u) | (dg0 < 0 ? 4u : 0u) | (db0 < 0 ? 8u : 0u);
+                        dst[0] = make_uint4(__float_as_uint(O1.x.x), __float_as_uint(O1.y.x), __float_as_uint(O1.z.x), fl);
+                        dst[1] = make_uint4((uint32_t)dr0, (uint32_t)dg0, (uint32_t)db0, 0u);
+                    }
+                    if (emit.y) {
+                        uint4 *dst = reinterpret_cast<uint4 *>(recs + slot_base + 64u + lane);
+                        const uint32_t fl = (obj.y < -1 ? 1u : 0u) | (dr1 < 0 ? 2u : 0u) | (dg1 < 0 ? 4u : 0u) | (db1 < 0 ? 8u : 0u);
+                        dst[0] = make_uint4(__float_as_uint(O1.x.y), __float_as_uint(O1.y.y), __float_as_uint(O1.z.y), fl);
+                        dst[1] = make_uint4((uint32_t)dr1, (uint32_t)dg1, (uint32_t)db1, 0u);
+                    }
+                }
+                if (bounces) {
                 const v3 D1 = bounce_direction_pair(n, base, emit);
                 kernarg<WfPrimaryArgs> *const qq = wf_args_again(ka);   // where the rays go
                 float4 *const rays = qq->wf.rays;
@@ -408,6 +466,7 @@ k_wf_primary(const WfPrimaryArgs a)
                     rays[2u * slot] = make_float4(O1.x.y, O1.y.y, O1.z.y, wf_pack_unorm16x2(tr.y, tgc.y));
                     rays[2u * slot + 1u] = make_float4(D1.x.y, D1.y.y, D1.z.y, wf_pack_unorm16x2(tb.y, 0.0f));
                     bins[slot] = (uint16_t)wf_direction_bin(lane3(D1, 1));
+                }
                 }
             }
         }
@@ -437,7 +496,7 @@ k_wf_primary(const WfPrimaryArgs a)
 
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg, const WfBuffers &wf,
-                             uint32_t sample_begin, uint32_t sample_count, uint32_t z_split)
+                             uint32_t sample_begin, uint32_t sample_count, uint32_t z_split, const WfShadow *shadow)
 {
     if (fp.row_end <= fp.row_begin || fp.width == 0 || sample_count == 0) return hipSuccess;
     z_split = std::max(1u, std::min(z_split, sample_count));
@@ -445,10 +504,23 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
     const dim3 block(256);
     const bool aux = (fp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, do_cull = (fp.flags & RWR_FLAG_NO_CULL) == 0;
     const WfPrimaryArgs args{ftris, fp.n_tris, fp.row_begin, fp.bins.enabled, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3],
-                             sample_begin, sample_count, z_split, fp, tris, shade, tex, tg, wf};
+                             sample_begin, sample_count, z_split, fp, tris, shade, tex, tg, wf,
+                             shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr}};
 #define RWR_WF_ARGS args
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
 #define RWR_WF_LAUNCH(A, C, N) hipLaunchKernelGGL((k_wf_primary<A, C, N>), grid, block, 0, s, RWR_WF_ARGS)
+#define RWR_WF_LAUNCH_SHADOW(A, C, N, L, G) hipLaunchKernelGGL((k_wf_primary<A, C, N, L, true>), G, block, 0, s, RWR_WF_ARGS)
+    if (shadow && shadow->recs) {   // the SHADOW forms
+        const bool list = wf.live_list && do_cull;
+        const dim3 sgrid = list ? dim3(std::min(grid.x * grid.y * z_split, 4096u)) : grid;
+#define RWR_WF_SHADOW_AN(C, L) \
+        if (nmap) { if (aux) RWR_WF_LAUNCH_SHADOW(true, C, true, L, sgrid); else RWR_WF_LAUNCH_SHADOW(false, C, true, L, sgrid); } \
+        else { if (aux) RWR_WF_LAUNCH_SHADOW(true, C, false, L, sgrid); else RWR_WF_LAUNCH_SHADOW(false, C, false, L, sgrid); }
+        if (list) { RWR_WF_SHADOW_AN(true, true) }
+        else if (do_cull) { RWR_WF_SHADOW_AN(true, false) }
+        else { RWR_WF_SHADOW_AN(false, false) }
+#undef RWR_WF_SHADOW_AN
+    } else
     if (wf.live_list && do_cull) {   // item after item of (live tile) x (share of its samples)
         const dim3 lgrid(std::min(grid.x * grid.y * z_split, 4096u));
 #define RWR_WF_LAUNCH_LIST(A, N) hipLaunchKernelGGL((k_wf_primary<A, true, N, true>), lgrid, block, 0, s, RWR_WF_ARGS)
@@ -466,6 +538,7 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
         else if (do_cull) RWR_WF_LAUNCH(false, true, false);
         else RWR_WF_LAUNCH(false, false, false);
     }
+#undef RWR_WF_LAUNCH_SHADOW
 #undef RWR_WF_LAUNCH
 #undef RWR_WF_ARGS
     return hipGetLastError();

@@ -16,7 +16,7 @@ namespace {
 struct FrameRequest {
     rwr_render_params rp;
     uint32_t row_begin, row_end, row_pitch;
-    bool aux, accumulate;
+    bool aux, accumulate, shadows;
     bool wavefront;   // the wavefront integrator renders it (several samples, a bounce, or an accumulation)
     bool dormant;     // the reference's dormant parts (single-triangle passes, orthographic rays) have their own plain kernel
 };
@@ -60,12 +60,16 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
     const bool accumulate = (rp.flags & RWR_FLAG_ACCUMULATE) != 0;
     if (accumulate && ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0))
         return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_ACCUMULATE: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
-    // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1)
-    const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate;
+    const bool shadows = (rp.flags & RWR_FLAG_SHADOWS) != 0;
+    if (shadows && ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0))
+        return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_SHADOWS: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
+    // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
+    // with shadow rays (the integrator's stages trace them)
+    const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate || shadows;
     const bool dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;
     if (dormant && (wavefront || (rp.flags & RWR_FLAG_USE_BVH)))
         return set_error(RWR_ERR_UNSUPPORTED, "single-triangle passes and RWR_FLAG_ORTHO_RAYS apply to the reference frame (spp 1, no bounce, no RWR_FLAG_USE_BVH)");
-    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, wavefront, dormant};
+    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, wavefront, dormant};
     return RWR_OK;
 }
 
@@ -355,20 +359,24 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
     const size_t n_queues = rp.max_bounces ? std::min<size_t>(ctx->wf_queues, (rp.spp + group - 1u) / group) : 1u;
     const bool overlap = n_queues > 1u;
     const size_t slots = (size_t)n_tiles * group * kWfTilePixels;
+    // The ray queues are fixed-slot (space instead of atomics: 36 B per slot of every tile of the launch), the one large
+    // allocation of the library — 19 GB for a 4K frame at 64 samples per group — and a frame with shadow rays holds a 32-byte
+    // record per slot on top (or alone, without a bounce).  A frame whose queues cannot be held is refused with its size, not
+    // left to a failed hipMalloc half-way through.
+    const size_t ray_slots = rp.max_bounces ? n_queues * slots : 0u, shadow_slots = rq.shadows ? n_queues * slots : 0u;
+    if (W.d_rays.count < 2u * ray_slots || W.d_shadow_recs.count < shadow_slots) {
+        const size_t slot_bytes = (rp.max_bounces ? 2u * sizeof(float4) + 2u * sizeof(uint16_t) : 0u) + (rq.shadows ? sizeof(ShadowRec) : 0u);
+        const size_t need = n_queues * slots * slot_bytes;
+        const size_t held = (rp.max_bounces ? W.d_rays.count * sizeof(float4) + (W.d_sorted.count + W.d_bins.count) * sizeof(uint16_t) : 0u) +
+                            (rq.shadows ? W.d_shadow_recs.count * sizeof(ShadowRec) : 0u);
+        size_t free_b = 0, total_b = 0;
+        RWR_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        if (need > free_b + held)
+            return set_error(RWR_ERR_UNSUPPORTED, "the frame's ray queues need %.1f GB (%zu tiles x %u samples per launch group x 512 slots x %zu B x %zu queues), "
+                             "%.1f GB are free: fewer frames in flight (each slot holds its own queues) or RWR_WF_GROUP < %u",
+                             need * 1e-9, (size_t)n_tiles, group, slot_bytes, n_queues, (free_b + held) * 1e-9, group);
+    }
     if (rp.max_bounces) {
-        // The ray queues are fixed-slot (space instead of atomics: 36 B per slot of every tile of the launch), the one large
-        // allocation of the library — 19 GB for a 4K frame at 64 samples per group.  A frame whose queues cannot be held is
-        // refused with its size, not left to a failed hipMalloc half-way through.
-        if (W.d_rays.count < n_queues * 2u * slots) {
-            const size_t need = n_queues * slots * (2u * sizeof(float4) + 2u * sizeof(uint16_t));
-            const size_t held = W.d_rays.count * sizeof(float4) + (W.d_sorted.count + W.d_bins.count) * sizeof(uint16_t);
-            size_t free_b = 0, total_b = 0;
-            RWR_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-            if (need > free_b + held)
-                return set_error(RWR_ERR_UNSUPPORTED, "the frame's ray queues need %.1f GB (%zu tiles x %u samples per launch group x 512 slots x 36 B x %zu queues), "
-                                 "%.1f GB are free: fewer frames in flight (each slot holds its own queues) or RWR_WF_GROUP < %u",
-                                 need * 1e-9, (size_t)n_tiles, group, n_queues, (free_b + held) * 1e-9, group);
-        }
         RWR_HIP_CHECK(W.d_rays.ensure(n_queues * 2u * slots));
         RWR_HIP_CHECK(W.d_sorted.ensure(n_queues * slots));
         RWR_HIP_CHECK(W.d_bins.ensure(n_queues * slots));
@@ -389,6 +397,22 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
             RWR_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_wf_live.h), 2 * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));   // fine-grained: kernels store to it, the host reads it without a synchronisation
             ctx->h_wf_live[0] = ctx->h_wf_live[1] = 0u;
         }
+    }
+    // Shadow rays (RWR_FLAG_SHADOWS): a record per queue slot and their ballots, per queue like the rays (and kept like them: until
+    // the slot is given up or the context destroyed); the slot's two counters start the frame from zero
+    if (rq.shadows) {
+        RWR_HIP_CHECK(W.d_shadow_recs.ensure(n_queues * slots));
+        RWR_HIP_CHECK(W.d_shadow_masks.ensure(n_queues * n_tiles * group * 8u));
+        RWR_HIP_CHECK(W.d_shadow_counts.ensure(2));
+        RWR_HIP_CHECK(hipMemsetAsync(W.d_shadow_counts.ptr, 0, 2 * sizeof(unsigned long long), stream));
+    }
+    // the unit vectors towards the reference's two lights, -normalize(kLightDir) in the oracle's f32 operations
+    // (triangle_list/compute.wgsl:55, sphere/compute.wgsl:41)
+    float light_mesh[3], light_sphere[3];
+    {
+        const float km[3] = {1.0f, -1.0f, -5.0f}, ks[3] = {1.0f, -5.0f, 1.0f};
+        const float lm = std::sqrt(km[0] * km[0] + km[1] * km[1] + km[2] * km[2]), ls = std::sqrt(ks[0] * ks[0] + ks[1] * ks[1] + ks[2] * ks[2]);
+        for (int k = 0; k < 3; k++) { light_mesh[k] = -(km[k] / lm); light_sphere[k] = -(ks[k] / ls); }
     }
     // Did the frame before show LITTLE — fewer than 1 024 live tiles, and at most half of this frame's tiles (a small mesh
     // on an empty screen; not a small frame full of geometry, such as a row band of a multi-GPU frame: measured, that one
@@ -415,6 +439,9 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
         live_list = W.d_tiles.ptr; tile_live = live_list + n_tiles; live_count = tile_live + n_tiles;   // (zeroed by k_frame_setup)
         RWR_HIP_CHECK(launch_wf_classify(stream, fp, sl.d_ftris.ptr, tg, tiles_x, live_list, live_count, tile_live));
     }
+    // tiles expected to hold shadow records (sizes k_wf_shadow's work items): the live pools of the frame before when this one
+    // walks a live list, else every tile
+    const uint32_t shadow_tiles = live_list ? std::max(1u, live) : n_tiles;
     WfBuffers wfq[kWfMaxQueues];
     for (size_t q = 0; q < n_queues; q++) {
         wfq[q] = WfBuffers{W.d_fix.ptr,
@@ -451,8 +478,13 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
         const uint32_t cnt = std::min(group, rp.spp - s0);
         const size_t q = g % n_queues;
         hipStream_t gs = q ? W.streams[q].h : stream;
+        const size_t mask_words = (size_t)n_tiles * group * 8u;
+        const WfShadow sw{rq.shadows ? W.d_shadow_recs.ptr + q * slots : nullptr, rq.shadows ? W.d_shadow_masks.ptr + q * mask_words : nullptr,
+                          W.d_shadow_counts.ptr};
         RWR_HIP_CHECK(launch_wf_primary(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg, wfq[q],
-                                        (uint32_t)ap.before + s0, cnt, z_split));
+                                        (uint32_t)ap.before + s0, cnt, z_split, rq.shadows ? &sw : nullptr));
+        if (rq.shadows)   // h0's shadow rays
+            RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], sw, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
         // the bounce stage: one generation of rays per bounce (RWR_FLAG_MULTI_BOUNCE: up to RWR_MAX_BOUNCES).  Generation k traces
         // ray k of every path that is still alive — the sort and trace kernels run again over the same fixed slots — and, unless
         // it is the last, writes ray k + 1 back into the slot of every hit, with its bit in the other ballot array.
@@ -464,10 +496,13 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
             const bool emit = gen < rp.max_bounces;
             const WfEmit em{masks_next, 2u + 16u * gen, (uint32_t)ap.before + s0};
             if (emit) RWR_HIP_CHECK(hipMemsetAsync(masks_next, 0, (size_t)n_tiles * group * 8u * sizeof(unsigned long long), gs));
+            if (rq.shadows) RWR_HIP_CHECK(hipMemsetAsync(sw.masks, 0, mask_words * sizeof(unsigned long long), gs));   // the trace kernels set bits
             RWR_HIP_CHECK(launch_wf_bounce(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh, tex0, wg, n_tiles, cnt,
                                            (uint32_t)std::fmax(1.0f, std::ceil(ctx->wf_packet_fill * (float)(cnt * kWfTilePixels))),
                                            W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles,
-                                           emit ? &em : nullptr));
+                                           emit ? &em : nullptr, rq.shadows ? &sw : nullptr));
+            if (rq.shadows)   // this generation's hits
+                RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, sw, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
             if (emit) std::swap(wg.masks, masks_next);
         }
         if (rp.max_bounces && s0 + group >= rp.spp) last_counters = wfq[q].counters;   // the last group's live-pool counts, for the next frame's split
@@ -564,6 +599,7 @@ int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const r
     ctx->last_spp = rq.wavefront ? rq.rp.spp : 0u;
     ctx->last_had_bounce = rq.wavefront && rq.rp.max_bounces != 0;
     ctx->last_primary = (uint64_t)ctx->screen.width * band_rows(fc.fp) * ap.trace_spp;
+    ctx->last_shadows = rq.shadows;
     ctx->last_bounce = 0;  // filled in lazily by rwr_last_render_stats from the pass counters
     return RWR_OK;
 }

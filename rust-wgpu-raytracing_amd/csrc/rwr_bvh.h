@@ -176,4 +176,74 @@ RWR_DEV void bvh_nearest(NodePtr nodes, const uint32_t *__restrict__ leaf_faces,
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Any-hit traversal (shadow rays, RWR_FLAG_SHADOWS): is ANY face hit?  The same nodelets, the same conservative slab
+// test (no distance limit: the light is at infinity) and the reference's literal hit test per face; no (t, u, v,
+// index) state, and a lane leaves at its first hit.  Visibility is an OR over faces: any visiting order gives the
+// brute-force answer.
+
+// triangleRayIntersect's verdict alone (compute.wgsl:82-148 up to the last early return), staged like
+// intersect_and_select_any_order: the wave leaves when none of its lanes is still in the running.
+RWR_DEV bool occludes_any_order(const TriRecord &T, f3 O, f3 D, bool active)
+{
+    const f3 N = ld3(T.N);
+    const float ndotd = dot3(N, D);
+    bool hit = active && !(fabsf(ndotd) < kEpsilon);    // :94
+    const float t = -(dot3(N, O) + T.d) / ndotd;        // :99-102
+    hit &= !(t < 0.0f);                                 // :105
+    if (!__any(hit)) return false;
+    const f3 P = along(O, t, D);                        // :110
+    f3 C = cross3(ld3(T.e0), sub3(P, ld3(T.p0)));       // :115-117
+    hit &= !(dot3(N, C) < 0.0f);                        // :118
+    if (!__any(hit)) return false;
+    C = cross3(ld3(T.e1), sub3(P, ld3(T.p1)));          // :123-125
+    hit &= !(dot3(N, C) < 0.0f);                        // :127
+    if (!__any(hit)) return false;
+    C = cross3(ld3(T.e2), sub3(P, ld3(T.p2)));          // :132-134
+    hit &= !(dot3(N, C) < 0.0f);                        // :136
+    return hit;
+}
+
+// The direction's share of a SlabRay (make_slab_ray), for rays that all run the same way: made once on the host with the same
+// IEEE divisions and passed as kernel arguments, so the reciprocals and the near-plane choice are wave-uniform scalars.
+struct SlabDir { float ix, iy, iz; uint32_t nx, ny, nz; };
+RWR_DEV SlabRay slab_ray_from(const SlabDir &d, f3 O)
+{
+    SlabRay r;
+    r.ix = d.ix; r.iy = d.iy; r.iz = d.iz;
+    r.ox = -O.x * r.ix; r.oy = -O.y * r.iy; r.oz = -O.z * r.iz;
+    r.nx = d.nx; r.ny = d.ny; r.nz = d.nz;
+    return r;
+}
+
+// One ray per lane, all in the SAME direction D (wave-uniform: rays towards a directional light; sd: its slab constants), lanes
+// with `active` unset only keep the wave company.  Per lane: the origin terms, the node, the stack.  A node's surviving children
+// are visited nearest first (bvh_inner_step's per-lane key minimum, as for any ray).  nodes, stack: as bvh_nearest.
+template <typename NodePtr, typename StackT>
+RWR_DEV bool bvh_occluded(NodePtr nodes, const uint32_t *__restrict__ leaf_faces, const TriRecord *__restrict__ tris,
+                          uint32_t n_faces, StackT *stack, f3 O, f3 D, const SlabDir &sd, bool active)
+{
+    const SlabRay sr = slab_ray_from(sd, O);
+    const uint32_t stride = blockDim.x;
+    StackT *sp = stack + threadIdx.x;
+    StackT *const sp0 = sp;
+    uint32_t cur = 0;  // the root is always an inner node
+    bool have_cur = active, occluded = false;
+    while (__any(have_cur)) {
+        while (have_cur && !(cur & kBvhLeafBit))
+            have_cur = bvh_inner_step(nodes, sr, __builtin_inff(), cur, sp, sp0, stride);
+        if (have_cur) {
+            const uint32_t first = (cur & ~kBvhLeafBit) >> 3, count = (cur & 7u) + 1u;
+            for (uint32_t k = 0; k < count; k++) {
+                if (first + k >= n_faces) break;  // (as bvh_leaf_step)
+                const uint32_t idx = leaf_faces[first + k];
+                if (idx < n_faces && occludes_any_order(tris[idx], O, D, true)) occluded = true;
+            }
+            if (occluded || sp == sp0) have_cur = false;
+            else { sp -= stride; cur = bvh_stack_dec(*sp); }
+        }
+    }
+    return occluded;
+}
+
 }  // namespace rwr

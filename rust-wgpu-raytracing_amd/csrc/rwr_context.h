@@ -122,6 +122,10 @@ struct WfState {
     DeviceBuffer<uint8_t> d_pool_info;
     DeviceBuffer<uint32_t> d_live;            // device counters of the bounce stage, a set of four per ray queue
     DeviceBuffer<uint32_t> d_pool_list;       // live pools by class, 2 x tiles
+    // RWR_FLAG_SHADOWS, allocated by the first frame that asks for them: a 32-byte record per queue slot (as d_rays), their
+    // ballots (as d_masks), the slot's two counters {shadow rays, occluded}
+    DeviceBuffer<ShadowRec> d_shadow_recs;
+    DeviceBuffer<unsigned long long> d_shadow_masks, d_shadow_counts;
     DeviceBuffer<uint32_t> d_tiles;           // frames that show little: live tile list, per-tile live pieces, the count (k_wf_classify)
 };
 
@@ -248,6 +252,7 @@ struct rwr_context {
     rwr_screen screen{0, 0};
 
     uint64_t last_primary = 0, last_bounce = 0;
+    bool last_shadows = false;      // the last render call traced shadow rays (RWR_FLAG_SHADOWS): their counters are in its WfState
     // optional per-kernel timing (rwr_ctx_set_kernel_timing)
     uint32_t timing_every = 0;
     uint64_t timing_calls = 0;

@@ -299,6 +299,23 @@ struct WfEmit {
     uint32_t next_dim;
     uint32_t sample_base;
 };
+// Shadow rays (RWR_FLAG_SHADOWS; kernels_wf_shadow.hip).  The kernel that shades a hit adds the term's ambient part to the sums and
+// leaves a 32-byte record at the hit's fixed queue slot: where the shadow ray starts, which of the reference's two lights it
+// runs towards (flags bit 0: the sphere shader's), and per channel what the light adds to the term — fix(lit) - fix(ambient)
+// modulo 2^32, flags bit 1 + c set when channel c's difference is negative — which k_wf_shadow adds when the ray gets through.
+// Wrapping 64-bit sums: ambient + (lit - ambient) is the lit term's bits whoever adds what when.
+struct alignas(16) ShadowRec {
+    float o[3]; uint32_t flags;
+    uint32_t d[3]; uint32_t pad;
+};
+static_assert(sizeof(ShadowRec) == 32, "ShadowRec is 32 B");
+// Per ray queue: the records (one per slot, as WfBuffers::rays), their ballots (layout of WfBuffers::masks) and the slot's two
+// counters {shadow rays traced, occluded}.  A kernel argument of its own behind the others (cf. WfEmit); recs == nullptr: no shadows.
+struct WfShadow {
+    ShadowRec *recs;
+    unsigned long long *masks;
+    unsigned long long *counts;
+};
 struct BvhNode4;
 struct BvhDevice {
     const BvhNode4 *nodes;
@@ -320,7 +337,8 @@ hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriReco
 uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks);
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg,
-                             const WfBuffers &wf, uint32_t sample_begin, uint32_t sample_count, uint32_t z_split);
+                             const WfBuffers &wf, uint32_t sample_begin, uint32_t sample_count, uint32_t z_split,
+                             const WfShadow *shadow = nullptr);
 // once per frame, ahead of the primary stage, when the frame is expected to show little: fills live_list / live_count / tile_live
 hipError_t launch_wf_classify(hipStream_t s, const FrameParams &fp, const FrameTri *ftris, const Targets &tg, uint32_t tiles_x,
                               uint32_t *live_list, uint32_t *live_count, uint32_t *tile_live);
@@ -329,7 +347,13 @@ hipError_t launch_wf_classify(hipStream_t s, const FrameParams &fp, const FrameT
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf,
                             uint32_t n_tiles, uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list,
-                            const WfEmit *emit = nullptr);
+                            const WfEmit *emit = nullptr, const WfShadow *shadow = nullptr);
+// RWR_FLAG_SHADOWS: traces the shadow records the kernels of one stage left in the queue (the primary stage's, or one generation's
+// trace kernels') and adds the light's part of every term whose ray got through.  light_mesh / light_sphere: the unit directions
+// towards the reference's two lights; expected_tiles: how many tiles are expected to hold records (sizes the work items only).
+hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
+                            const WfShadow &shadow, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count, const float light_mesh[3],
+                            const float light_sphere[3]);
 size_t wf_pool_info_bytes();
 hipError_t launch_primary_bvh(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                               const BvhDevice &bvh, const float4 *tex, const Targets &tg);
@@ -397,6 +421,7 @@ hipError_t preload_kernels_primary_p2();
 hipError_t preload_kernels_wavefront();
 hipError_t preload_kernels_wf_primary();
 hipError_t preload_kernels_wf_bounce();
+hipError_t preload_kernels_wf_shadow();
 hipError_t preload_kernels_dist();
 
 // kernels_dist.hip: the interleaved partition's gather (layout: rwr_strips.h) — every rank packs its strips into one message,

@@ -3,7 +3,7 @@
 // input* -> update -> render, with key events taken from a script instead of a window.
 //
 //   rwr_render --res DIR [--scene suzanne_lowpoly.obj] [--size 600x600] [--keys "S*15,D*4"]
-//              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--out frame.png] [--time]
+//              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
 // (KEY in W A S D Up Down Left Right Space LShift, or '-' for no key).  After the script,
@@ -43,7 +43,7 @@ int main(int argc, char **argv)
 {
     std::string res, scene = "suzanne_lowpoly.obj", out, keys;
     uint32_t w = 600, h = 600, frames = 1, spp = 1, bounces = 0;
-    bool timing = false, accumulate = false;
+    bool timing = false, accumulate = false, shadows = false;
     struct Resize { uint64_t frame; uint32_t w, h; };
     std::vector<Resize> resizes;
     for (int i = 1; i < argc; i++) {
@@ -61,6 +61,7 @@ int main(int argc, char **argv)
         else if (a == "--bounces") bounces = (uint32_t)std::atoi(next());
         else if (a == "--time") timing = true;
         else if (a == "--accumulate") accumulate = true;
+        else if (a == "--shadows") shadows = true;
         else if (a == "--resize") {
             Resize r{0, 0, 0};
             unsigned long long f = 0;
@@ -72,9 +73,11 @@ int main(int argc, char **argv)
             if (std::sscanf(next(), "%ux%u", &w, &h) != 2) { std::fprintf(stderr, "--size WxH\n"); return 2; }
         } else if (a == "--help" || a == "-h") {
             std::printf("usage: rwr_render --res DIR [--scene F.obj] [--size WxH] [--keys \"S*15,D*4\"] [--frames N] "
-                        "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--out frame.png] [--time]\n"
+                        "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
-                        "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n");
+                        "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n"
+                        "  --shadows     every hit casts a shadow ray towards its light (RWR_FLAG_SHADOWS); works with --spp, --bounces "
+                        "and --accumulate\n");
             return 0;
         } else {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
@@ -101,7 +104,8 @@ int main(int argc, char **argv)
     try {
         State state(w, h, res, scene);
         // more than one bounce: the deeper paths of RWR_FLAG_MULTI_BOUNCE
-        const rwr_render_params params{spp, bounces, 0u, (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u)};
+        const rwr_render_params params{spp, bounces, 0u, (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u) |
+                                       (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u)};
         uint64_t rendered = 0;
         const auto t0 = std::chrono::steady_clock::now();
         auto frame = [&]() {  // [Resized: resize()] then RedrawRequested: update() then render() (lib.rs:1323-1337)
