@@ -181,7 +181,7 @@ enum {
                                        is the frame without the flag, byte for byte.  RWR_FLAG_USE_BVH, RWR_FLAG_ORTHO_RAYS and
                                        single-triangle passes stay reference-frame only.  rwr_last_render_stats' bounce_rays
                                        counts the rays of every bounce */
-    RWR_FLAG_SHADOWS = 1u << 7      /* extension: shadow rays towards the reference's two directional lights.  Without the flag
+    RWR_FLAG_SHADOWS = 1u << 7,     /* extension: shadow rays towards the reference's two directional lights.  Without the flag
                                        every frame is what it was, byte for byte.  With it:
                                        1. The frame always takes the path integrator, also at spp 1 / max_bounces 0.  Samples are
                                           placed as without the flag (pixel centre at spp 1, jittered from spp 2; an accumulating
@@ -207,6 +207,32 @@ enum {
                                           gather keep their contracts.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or
                                           single-triangle passes: RWR_ERR_UNSUPPORTED.
                                        5. rwr_last_shadow_stats counts the shadow rays and how many were occluded. */
+    RWR_FLAG_DENOISE = 1u << 8      /* extension: an edge-avoiding a-trous filter (Dammertz et al. 2010) over the frame the integrator
+                                       resolved, for frames of few samples.  Without the flag every frame is what it was, byte for
+                                       byte, with no further launch or allocation.  With it:
+                                       1. The frame always takes the path integrator, also at spp 1 / max_bounces 0 (as with
+                                          RWR_FLAG_SHADOWS), and is rendered as if RWR_FLAG_AUX_OUTPUTS were set too: rwr_readback's three
+                                          aux planes are available.  Samples, rays, random numbers and sums are those of the frame
+                                          without the flag; depth, obj_id and hit_t (sample 0) are unchanged, bit for bit.
+                                       2. c0 = the resolved color_f32 plane.  For i = 0 ... N-1 (N = iterations), step s = 2^i, pixel p:
+                                          taps (dx, dy) in {-2 ... 2}^2, row-major, dy outer, q = p + s (dx, dy); a tap outside the
+                                          frame is skipped.  Kernel weight h = k[|dx|] k[|dy|], k = {3/8, 1/4, 1/16}.  Geometry weight
+                                          g in {0, 1}: a background pixel (id(p) = -1) keeps its colour, and a background tap has
+                                          g = 0; id(q) = id(p): g = 1; two mesh faces (both ids >= 0): g = 1 iff
+                                          dot3(nhat[id p], nhat[id q]) >= normal_cos_min (nhat = normalize(N) of the face as wound)
+                                          and fabsf(t(p) - t(q)) <= depth_rel * fminf(t(p), t(q)); anything else (two different
+                                          spheres, sphere against mesh): g = 0.  Colour weight w = 1 / (1 + d2 inv_i),
+                                          d2 = (dr dr + dg dg) + db db of c_i(p) - c_i(q), inv_0 = 1 / (sigma_color sigma_color),
+                                          inv_(i+1) = 4 inv_i.  Over the taps with g = 1, in tap order: sum += (h w) c_i(q) per
+                                          channel, norm += h w; c_(i+1)(p).rgb = sum / norm.  All in f32, + - * / only.
+                                       3. c_N replaces color_f32 (alpha is c0's); the rgba8 plane is its conversion, as the resolve's.
+                                       4. RWR_FLAG_ACCUMULATE: the filter is a post-process of the image shown; the history never
+                                          sees it.  Neither this bit nor rwr_denoise_set_params is part of the accumulation key; the
+                                          key holds the effective flags (RWR_FLAG_AUX_OUTPUTS implied).
+                                       5. rwr_render_rows / rwr_render_strips with the flag: RWR_ERR_UNSUPPORTED unless the call
+                                          covers the whole frame (the filter reaches 62 pixels; a rank does not hold its neighbours'
+                                          rows).  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
+                                          RWR_ERR_UNSUPPORTED. */
 };
 
 #define RWR_MAX_BOUNCES 8u
@@ -437,6 +463,18 @@ RWR_API int rwr_last_shadow_stats(rwr_context *ctx, uint64_t *shadow_rays, uint6
  * cap — and 0 when that frame did not accumulate.  Host-side, does not wait.  NULL ctx or samples: RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_accum_reset(rwr_context *ctx);
 RWR_API int rwr_accum_samples(rwr_context *ctx, uint64_t *samples);
+
+/* RWR_FLAG_DENOISE: the filter's parameters, per context.  iterations 1 ... 5 (default 5); sigma_color > 0, finite, with
+ * 256 / (sigma_color * sigma_color) finite in f32 (default 0.04: the
+ * filter sees textured radiance, and a wider tolerance blurs the texture by more than it removes noise — DESIGN.md §6); normal_cos_min, not NaN (default 0.95); depth_rel >= 0 (default
+ * 0.05).  Anything else, NaN included: RWR_ERR_INVALID_ARGUMENT, and the parameters stay as they were.  params = NULL restores the
+ * defaults.  Host-side, waits for nothing; frames rendered after the call use the new values.  An accumulation goes on. */
+typedef struct rwr_denoise_params {
+    uint32_t iterations;
+    float sigma_color, normal_cos_min, depth_rel;
+} rwr_denoise_params;
+RWR_API int rwr_denoise_set_params(rwr_context *ctx, const rwr_denoise_params *params);
+RWR_API int rwr_denoise_get_params(rwr_context *ctx, rwr_denoise_params *out);
 
 /* Self-test of the kernels' short exact forms ("Numerics"): the frame kernel replaces the
  * shader's  ((1/d) - (1/kNear)) / ((1/kFar) - (1/kNear))  (compute.wgsl:78-80) and the three divisions

@@ -46,6 +46,8 @@ FLAG_NORMAL_MAP = 1 << 4
 FLAG_ACCUMULATE = 1 << 5
 FLAG_MULTI_BOUNCE = 1 << 6   # max_bounces up to MAX_BOUNCES (include/rwr_hip.h)
 FLAG_SHADOWS = 1 << 7        # shadow rays towards the reference's two lights (include/rwr_hip.h)
+FLAG_DENOISE = 1 << 8        # the a-trous filter behind the integrator's resolve; implies FLAG_AUX_OUTPUTS (include/rwr_hip.h)
+DENOISE_PARAMS_DTYPE = np.dtype([("iterations", "<u4"), ("sigma_color", "<f4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
 MAX_BOUNCES = 8
 FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
 KEY_FORWARD, KEY_BACKWARD, KEY_LEFT, KEY_RIGHT, KEY_UP, KEY_DOWN = 1, 2, 4, 8, 16, 32
@@ -110,6 +112,7 @@ def lib() -> C.CDLL:
         "rwr_timer_begin": [vp], "rwr_timer_end": [vp, vp], "rwr_timer_stop": [vp], "rwr_timer_elapsed": [vp, vp], "rwr_last_render_stats": [vp, vp, vp],
         "rwr_last_shadow_stats": [vp, vp, vp],
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
+        "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
         "rwr_load_model_compute": [C.c_char_p, C.c_char_p, vp], "rwr_model_free": [vp],
         "rwr_model_info": [vp, vp, vp, vp, vp, vp, vp], "rwr_scene_upload_model": [vp, vp],
@@ -126,7 +129,7 @@ def lib() -> C.CDLL:
         "rwr_dist_loopback_deposit": [vp, u32, u32, i32], "rwr_dist_loopback_finish": [vp, u32, i32],
         "rwr_measure_valu_clock": [vp, u32, vp], "rwr_clock_probe_start": [vp, u32], "rwr_clock_probe_read": [vp, vp],
     }
-    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats",)   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -611,6 +614,24 @@ class Context:
         n = C.c_uint64()
         _check(lib().rwr_accum_samples(self._h, C.byref(n)))
         return n.value
+
+    def set_denoise_params(self, iterations=None, sigma_color=None, normal_cos_min=None, depth_rel=None):
+        """The FLAG_DENOISE filter's parameters (rwr_denoise_set_params); an argument left out keeps its value, no argument at all
+        restores the defaults.  Out of range: RwrError(ERR_INVALID_ARGUMENT), and the parameters stay."""
+        given = {"iterations": iterations, "sigma_color": sigma_color, "normal_cos_min": normal_cos_min, "depth_rel": depth_rel}
+        if all(v is None for v in given.values()):
+            _check(lib().rwr_denoise_set_params(self._h, None))
+            return
+        p = np.zeros(1, dtype=DENOISE_PARAMS_DTYPE)
+        for k, v in self.denoise_params().items():
+            p[k] = v if given[k] is None else given[k]
+        _check(lib().rwr_denoise_set_params(self._h, _p(p)))
+
+    def denoise_params(self) -> dict:
+        p = np.zeros(1, dtype=DENOISE_PARAMS_DTYPE)
+        _check(lib().rwr_denoise_get_params(self._h, _p(p)))
+        return {"iterations": int(p["iterations"][0]), "sigma_color": float(p["sigma_color"][0]),
+                "normal_cos_min": float(p["normal_cos_min"][0]), "depth_rel": float(p["depth_rel"][0])}
 
 
 def csrc_tree() -> str:

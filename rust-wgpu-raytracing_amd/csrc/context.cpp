@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -385,6 +386,32 @@ int rwr_last_shadow_stats(rwr_context *ctx, uint64_t *shadow_rays, uint64_t *occ
     }
     *shadow_rays = counts[0];
     *occluded = counts[1];
+    return RWR_OK;
+}
+
+int rwr_denoise_set_params(rwr_context *ctx, const rwr_denoise_params *params)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (!params) {
+        ctx->denoise = kDenoiseDefaults;
+        return RWR_OK;
+    }
+    const rwr_denoise_params p = *params;
+    if (p.iterations < 1u || p.iterations > 5u) return set_error(RWR_ERR_INVALID_ARGUMENT, "denoise iterations %u: 1 ... 5", p.iterations);
+    // inv_0 = 1 / (sigma * sigma) and its multiples up to 4^4 must be finite f32 numbers, sigma * sigma non-zero
+    const float s2 = p.sigma_color * p.sigma_color, inv4 = 1.0f / s2 * 256.0f;
+    if (!(p.sigma_color > 0.0f) || !std::isfinite(p.sigma_color) || !(s2 > 0.0f) || !std::isfinite(inv4))
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "denoise sigma_color %g: positive, finite, 256 / sigma^2 finite", (double)p.sigma_color);
+    if (std::isnan(p.normal_cos_min)) return set_error(RWR_ERR_INVALID_ARGUMENT, "denoise normal_cos_min is NaN");
+    if (!(p.depth_rel >= 0.0f)) return set_error(RWR_ERR_INVALID_ARGUMENT, "denoise depth_rel %g: >= 0", (double)p.depth_rel);
+    ctx->denoise = p;
+    return RWR_OK;
+}
+
+int rwr_denoise_get_params(rwr_context *ctx, rwr_denoise_params *out)
+{
+    if (!ctx || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = ctx->denoise;
     return RWR_OK;
 }
 

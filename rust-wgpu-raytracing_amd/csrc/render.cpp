@@ -17,6 +17,7 @@ struct FrameRequest {
     rwr_render_params rp;
     uint32_t row_begin, row_end, row_pitch;
     bool aux, accumulate, shadows;
+    bool denoise;     // RWR_FLAG_DENOISE: the filter runs behind the resolve (rp.flags holds the effective flags: AUX implied, this bit cleared)
     bool wavefront;   // the wavefront integrator renders it (several samples, a bounce, or an accumulation)
     bool dormant;     // the reference's dormant parts (single-triangle passes, orthographic rays) have their own plain kernel
 };
@@ -63,13 +64,25 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
     const bool shadows = (rp.flags & RWR_FLAG_SHADOWS) != 0;
     if (shadows && ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0))
         return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_SHADOWS: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
+    // the filter works on the whole frame's planes: the colour and the id / t planes it is guided by (so RWR_FLAG_AUX_OUTPUTS is
+    // implied).  From here on rp.flags is what the frame is rendered with; the filter's own bit is not part of it (nor of the
+    // accumulation's key).
+    const bool denoise = (rp.flags & RWR_FLAG_DENOISE) != 0;
+    if (denoise) {
+        if ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0)
+            return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_DENOISE: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
+        if (row_begin != 0u || row_end != ctx->screen.height || row_pitch != kStripRows)
+            return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_DENOISE: the filter needs the whole frame (its taps reach 62 pixels); rows [%u,%u) "
+                             "every %u-th strip is a part of it", row_begin, row_end, row_pitch / kStripRows);
+        rp.flags = (rp.flags & ~(uint32_t)RWR_FLAG_DENOISE) | RWR_FLAG_AUX_OUTPUTS;
+    }
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
-    // with shadow rays (the integrator's stages trace them)
-    const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate || shadows;
+    // with shadow rays (the integrator's stages trace them) or one the filter follows (it runs behind the integrator's resolve)
+    const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate || shadows || denoise;
     const bool dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;
     if (dormant && (wavefront || (rp.flags & RWR_FLAG_USE_BVH)))
         return set_error(RWR_ERR_UNSUPPORTED, "single-triangle passes and RWR_FLAG_ORTHO_RAYS apply to the reference frame (spp 1, no bounce, no RWR_FLAG_USE_BVH)");
-    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, wavefront, dormant};
+    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, denoise, wavefront, dormant};
     return RWR_OK;
 }
 
@@ -537,6 +550,14 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
         ctx->last_accum_samples = total;
     }
     W.fix_clean = true;   // (the resolve zeroes what it reads; rows outside the band were never touched)
+    // RWR_FLAG_DENOISE: the filter, behind either resolve on the slot's stream.  (An accumulating frame: behind the event the next
+    // accumulating resolve waits for — the history never sees the filter, and no other slot waits for it.)
+    if (rq.denoise) {
+        RWR_HIP_CHECK(sl.d_dn_guide.ensure(n));
+        RWR_HIP_CHECK(sl.d_dn_a.ensure(n));
+        RWR_HIP_CHECK(sl.d_dn_b.ensure(n));
+        RWR_HIP_CHECK(launch_wf_denoise(stream, fp.width, fp.height, ctx->d_tris.ptr, tg, ctx->denoise, sl.d_dn_guide.ptr, sl.d_dn_a.ptr, sl.d_dn_b.ptr));
+    }
     ctx->last_segments = n_tiles;
     ctx->last_wf_state = ctx->n_slots > 1u ? ctx->cur : 0u;
     return RWR_OK;

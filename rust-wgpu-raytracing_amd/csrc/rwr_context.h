@@ -83,6 +83,9 @@ struct FrameSlot {
     DeviceBuffer<uint32_t> d_bin_lists, d_bin_counts, d_bin_offsets, d_bin_total;   // per-frame screen bins (large scenes)
     PinnedWords h_bin_total;   // entries the last binned frame of this slot needed (read a frame late, never waited for)
     bool aux_valid = false;
+    // RWR_FLAG_DENOISE, allocated by the slot's first denoised frame: the guide records and the two colour planes the iterations
+    // alternate between (kernels_wf_denoise.hip)
+    DeviceBuffer<float4> d_dn_guide, d_dn_a, d_dn_b;
     // RWR_FRAME_GRAPH (A/B knob): the reference frame's two launches (k_frame_setup -> k_primary_p2) as a
     // hipGraph of this slot — replayed as it is while camera and parameters stay the same, updated in place when they change
     OwnedGraphExec frame_graph;
@@ -103,6 +106,7 @@ struct FrameSlot {
     }
 };
 constexpr uint32_t kMaxFramesInFlight = 3;
+constexpr rwr_denoise_params kDenoiseDefaults{5u, 0.04f, 0.95f, 0.05f};   // RWR_FLAG_DENOISE: DESIGN.md §6 says why these
 constexpr uint32_t kWfMaxQueues = 4;
 
 // The wavefront integrator's device state, one set per frame slot: a frame of the integrator then shares nothing with the
@@ -225,6 +229,7 @@ struct rwr_context {
     rwr::Accum accum;
     uint64_t accum_max = 1u << 24;         // samples per pixel at most (f32 holds the divisor exactly); RWR_ACCUM_MAX_SAMPLES lowers it
     uint64_t last_accum_samples = 0;       // rwr_accum_samples: of the frame rendered last, 0 when it did not accumulate
+    rwr_denoise_params denoise = rwr::kDenoiseDefaults;   // RWR_FLAG_DENOISE (rwr_denoise_set_params)
     uint64_t scene_generation = 0;         // bumped by every change of the scene (an accumulation does not survive one)
     // one decoded texture per scene part (texels decoded to linear f32 at upload, Rgba8UnormSrgb semantics)
     std::vector<rwr::DeviceBuffer<float4>> d_texs;

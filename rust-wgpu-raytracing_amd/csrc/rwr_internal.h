@@ -376,6 +376,11 @@ hipError_t launch_wf_resolve_accum(hipStream_t s, const FrameParams &fp, const T
                                    AccumMode mode, uint32_t total_samples, const uint32_t *live_counters = nullptr,
                                    uint32_t *host_live = nullptr);
 
+// RWR_FLAG_DENOISE (kernels_wf_denoise.hip): the guide pre-pass and dp.iterations filter launches behind the frame's resolve.  tg holds
+// the resolved frame with its aux planes; guide, plane_a and plane_b are width * height records each (the slot's scratch).
+hipError_t launch_wf_denoise(hipStream_t s, uint32_t width, uint32_t height, const TriRecord *tris, const Targets &tg,
+                             const rwr_denoise_params &dp, float4 *guide, float4 *plane_a, float4 *plane_b);
+
 // per-frame records and tables (kernels_primary.hip): FrameTri + tnum per face, ray tables per column pair / row
 struct FrameSetupOut {
     FrameTri *ftris;   // n_tris

@@ -3,7 +3,8 @@
 // input* -> update -> render, with key events taken from a script instead of a window.
 //
 //   rwr_render --res DIR [--scene suzanne_lowpoly.obj] [--size 600x600] [--keys "S*15,D*4"]
-//              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] [--out frame.png] [--time]
+//              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows]
+//              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
 // (KEY in W A S D Up Down Left Right Space LShift, or '-' for no key).  After the script,
@@ -43,7 +44,9 @@ int main(int argc, char **argv)
 {
     std::string res, scene = "suzanne_lowpoly.obj", out, keys;
     uint32_t w = 600, h = 600, frames = 1, spp = 1, bounces = 0;
-    bool timing = false, accumulate = false, shadows = false;
+    bool timing = false, accumulate = false, shadows = false, denoise = false;
+    int denoise_iterations = 0;      // 0: the library's default
+    float denoise_sigma = 0.0f;      // 0: the library's default
     struct Resize { uint64_t frame; uint32_t w, h; };
     std::vector<Resize> resizes;
     for (int i = 1; i < argc; i++) {
@@ -62,6 +65,9 @@ int main(int argc, char **argv)
         else if (a == "--time") timing = true;
         else if (a == "--accumulate") accumulate = true;
         else if (a == "--shadows") shadows = true;
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-iterations") { denoise = true; denoise_iterations = std::atoi(next()); }
+        else if (a == "--denoise-sigma") { denoise = true; denoise_sigma = (float)std::atof(next()); }
         else if (a == "--resize") {
             Resize r{0, 0, 0};
             unsigned long long f = 0;
@@ -73,11 +79,14 @@ int main(int argc, char **argv)
             if (std::sscanf(next(), "%ux%u", &w, &h) != 2) { std::fprintf(stderr, "--size WxH\n"); return 2; }
         } else if (a == "--help" || a == "-h") {
             std::printf("usage: rwr_render --res DIR [--scene F.obj] [--size WxH] [--keys \"S*15,D*4\"] [--frames N] "
-                        "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] [--out frame.png] [--time]\n"
+                        "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] "
+                        "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
                         "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n"
                         "  --shadows     every hit casts a shadow ray towards its light (RWR_FLAG_SHADOWS); works with --spp, --bounces "
-                        "and --accumulate\n");
+                        "and --accumulate\n"
+                        "  --denoise     the edge-avoiding a-trous filter over every frame (RWR_FLAG_DENOISE): N iterations (1-5), colour "
+                        "sigma S (rwr_denoise_set_params)\n");
             return 0;
         } else {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
@@ -105,7 +114,15 @@ int main(int argc, char **argv)
         State state(w, h, res, scene);
         // more than one bounce: the deeper paths of RWR_FLAG_MULTI_BOUNCE
         const rwr_render_params params{spp, bounces, 0u, (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u) |
-                                       (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u)};
+                                       (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u) | (denoise ? (uint32_t)RWR_FLAG_DENOISE : 0u)};
+        if (denoise_iterations != 0 || denoise_sigma != 0.0f) {
+            rwr_denoise_params dp;
+            int rc = rwr_denoise_get_params(state.context(), &dp);
+            if (denoise_iterations != 0) dp.iterations = (uint32_t)denoise_iterations;
+            if (denoise_sigma != 0.0f) dp.sigma_color = denoise_sigma;
+            if (rc == RWR_OK) rc = rwr_denoise_set_params(state.context(), &dp);
+            if (rc != RWR_OK) { std::fprintf(stderr, "--denoise: %s\n", rwr_last_error_string()); return 2; }
+        }
         uint64_t rendered = 0;
         const auto t0 = std::chrono::steady_clock::now();
         auto frame = [&]() {  // [Resized: resize()] then RedrawRequested: update() then render() (lib.rs:1323-1337)
