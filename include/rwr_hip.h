@@ -452,6 +452,13 @@ RWR_API int rwr_kernel_timing_stats(rwr_context *ctx, double *mean_us, uint32_t 
  * its own spp; 0 past the cap). */
 RWR_API int rwr_last_render_stats(rwr_context *ctx, uint64_t *primary_rays, uint64_t *bounce_rays);
 
+/* k_frame_setup launches this context has put on its streams since it was created.  A frame slot keeps its per-frame records
+ * (culling records, ray tables, per-tile face sets) while everything they are made from stands still — camera uniform,
+ * screen, the call's rows, scene — and a frame that finds them made launches no setup: the count then stays where it was.
+ * RWR_SETUP_CACHE=0 (read when the context is created) makes them every frame.  Frames are the same bytes either way.
+ * Host-side, does not wait.  NULL ctx or launches: RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_frame_setup_launches(rwr_context *ctx, uint64_t *launches);
+
 /* RWR_FLAG_SHADOWS: shadow rays traced by the last render call (= hits shaded: primary hits and the bounce hits of every
  * generation; an accumulating frame: its own samples; 0 without the flag) and how many of them were occluded.  Exact counts.
  * Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */

@@ -110,7 +110,7 @@ def lib() -> C.CDLL:
         "rwr_resize": [vp, vp], "rwr_render": [vp, vp, vp], "rwr_render_rows": [vp, vp, vp, u32, u32], "rwr_render_strips": [vp, vp, vp, u32, u32],
         "rwr_synchronize": [vp], "rwr_readback": [vp, vp, vp, vp, vp, vp], "rwr_get_device_targets": [vp, vp, vp],
         "rwr_timer_begin": [vp], "rwr_timer_end": [vp, vp], "rwr_timer_stop": [vp], "rwr_timer_elapsed": [vp, vp], "rwr_last_render_stats": [vp, vp, vp],
-        "rwr_last_shadow_stats": [vp, vp, vp],
+        "rwr_last_shadow_stats": [vp, vp, vp], "rwr_frame_setup_launches": [vp, vp],
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
@@ -129,7 +129,7 @@ def lib() -> C.CDLL:
         "rwr_dist_loopback_deposit": [vp, u32, u32, i32], "rwr_dist_loopback_finish": [vp, u32, i32],
         "rwr_measure_valu_clock": [vp, u32, vp], "rwr_clock_probe_start": [vp, u32], "rwr_clock_probe_read": [vp, vp],
     }
-    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -598,6 +598,13 @@ class Context:
         a, b = C.c_uint64(), C.c_uint64()
         _check(lib().rwr_last_render_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def frame_setup_launches(self) -> int:
+        """k_frame_setup launches of this context so far (rwr_frame_setup_launches): a frame whose slot still holds the records of
+        its camera, screen, rows and scene adds none (RWR_SETUP_CACHE=0: every frame adds one)."""
+        n = C.c_uint64()
+        _check(lib().rwr_frame_setup_launches(self._h, C.byref(n)))
+        return n.value
 
     def last_shadow_stats(self) -> tuple[int, int]:
         """(shadow rays traced by the last render call, how many of them were occluded); (0, 0) without FLAG_SHADOWS."""

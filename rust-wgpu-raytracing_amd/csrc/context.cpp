@@ -37,12 +37,18 @@ hipError_t ensure_frame_buffers(rwr_context *ctx)
     const uint32_t total = (uint32_t)instanced_faces(ctx->n_faces, ctx->n_instances);
     for (uint32_t i = 0; i < ctx->n_slots; i++) {
         FrameSlot &sl = ctx->slots[i];
-        hipError_t e;
-        if (total && ((e = sl.d_ftris.ensure(total)) != hipSuccess || (e = sl.d_tnum.ensure(total)) != hipSuccess)) return e;
-        if (ctx->screen.width) {
-            if ((e = sl.d_ray_colp.ensure(2u * (size_t)(((ctx->screen.width + 63u) / 64u) * 32u))) != hipSuccess) return e;
-            if ((e = sl.d_ray_row.ensure(ctx->screen.height + 8u)) != hipSuccess) return e;
+        const void *const before[4] = {sl.d_ftris.ptr, sl.d_tnum.ptr, sl.d_ray_colp.ptr, sl.d_ray_row.ptr};
+        hipError_t e = hipSuccess;
+        if (total && (e = sl.d_ftris.ensure(total)) == hipSuccess) e = sl.d_tnum.ensure(total);
+        if (e == hipSuccess && ctx->screen.width) {
+            e = sl.d_ray_colp.ensure(2u * (size_t)(((ctx->screen.width + 63u) / 64u) * 32u));
+            if (e == hipSuccess) e = sl.d_ray_row.ensure(ctx->screen.height + 8u);
         }
+        // a buffer that moves here moves outside any frame: a later frame's key could name the old address again (the
+        // allocator may hand it back) over memory nobody has written, so the slot's records no longer stand
+        if (before[0] != sl.d_ftris.ptr || before[1] != sl.d_tnum.ptr || before[2] != sl.d_ray_colp.ptr || before[3] != sl.d_ray_row.ptr)
+            sl.records_key.clear();
+        if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -79,6 +85,7 @@ void read_tunables(rwr_context *ctx)
     env_flag("RWR_FRAME_GRAPH", &ctx->frame_graph);
     if (env_flag("RWR_FUSED_SETUP", &ctx->fused_setup)) ctx->fused_setup_force = ctx->fused_setup;
     env_flag("RWR_TILE_LISTS", &ctx->tile_lists);
+    env_flag("RWR_SETUP_CACHE", &ctx->setup_cache);
     env_f32("RWR_AUTO_BVH_FACE_PX", &ctx->auto_bvh_face_px);
     if (env_u32("RWR_WF_GROUP", &ctx->wf_group)) ctx->wf_group = std::min(kWfMaxGroup, std::max(1u, ctx->wf_group));
     bool stats = false, wide = false;
@@ -372,6 +379,13 @@ int rwr_last_render_stats(rwr_context *ctx, uint64_t *primary_rays, uint64_t *bo
     }
     if (primary_rays) *primary_rays = ctx->last_primary;
     if (bounce_rays) *bounce_rays = ctx->last_bounce;
+    return RWR_OK;
+}
+
+int rwr_frame_setup_launches(rwr_context *ctx, uint64_t *launches)
+{
+    if (!ctx || !launches) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *launches = ctx->setup_launches;
     return RWR_OK;
 }
 

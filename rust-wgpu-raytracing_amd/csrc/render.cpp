@@ -151,8 +151,9 @@ uint64_t band_rows(const FrameParams &fp)
 
 const float4 *tex0_of(const rwr_context *ctx) { return ctx->d_texs.empty() ? nullptr : ctx->d_texs[0].ptr; }
 
-// Per-frame records and tables (k_frame_setup): they depend on the camera, so they are rebuilt
-// every frame, on the render stream just ahead of the render kernel.  (Running this small
+// Per-frame records and tables (k_frame_setup): they depend on the camera, the screen, the launch's rows and the scene, and
+// on nothing else — not on the frame's number — so a slot keeps them while those stand still (launch_records below) and
+// makes them again, on the render stream just ahead of the render kernel, when one of them changes.  (Running this small
 // kernel on a side stream, double-buffered so that it overlaps the previous frame, was
 // measured 4-10 us SLOWER per frame than the 3 us it hides: cross-stream event waits cost
 // more than the kernel.)  Here: where they go.
@@ -168,12 +169,53 @@ int frame_tables(rwr_context *ctx, FrameSlot &sl, FrameParams &fp, FrameSetupOut
     return RWR_OK;
 }
 
+// Everything k_frame_setup reads, and everything that decides where and what it writes: two launches with equal keys write the
+// same bytes to the same addresses.  Field by field (no padding bytes); the buffers' addresses are part of it, so a buffer that
+// moved between two frames is a different key.
+struct RecordsKey {
+    rwr_camera_inv_uniform cam;
+    CullConsts cc;
+    uint64_t scene_generation;
+    const void *cull, *tris, *ftris, *tnum, *ray_colp, *ray_row, *zero_a, *zero_b, *tile_lists;
+    uint32_t width, height, n_tris, ray_pairs, ray_rows, n_zero_a, n_zero_b, list_gx, list_gy, list_row_begin, list_row_pitch, list_blocks;
+    uint32_t row_begin, row_end, row_pitch, pad;   // the launch's rows, with or without face sets: a change of rows is a change of key
+};
+static_assert(sizeof(RecordsKey) == sizeof(rwr_camera_inv_uniform) + sizeof(CullConsts) + 8 + 9 * sizeof(void *) + 16 * 4, "RecordsKey has no padding");
+static_assert(sizeof(FrameSetupOut) == 96, "a new member of FrameSetupOut belongs in RecordsKey");
+
+// Every k_frame_setup goes through here.  The slot's records are a pure function of the launch's key, so a launch whose key is
+// the one the slot's records were made from is not made: camera, screen, rows and scene stand still on most frames of a redraw
+// loop (and on all of a progressive accumulation).  Not pure are the words the wavefront integrator wants zeroed (zero_a /
+// zero_b: its kernels count in them, every frame from zero), so a launch that carries such words is always made; the records
+// it leaves are those of its key all the same.  `captured`: the launch is being recorded into a graph whose replays rewrite the
+// records whenever they run — made, not counted (launch_frame_graph counts replays), and it leaves no key.
+// This is the only place that leaves a key behind; whatever else writes the slot's records clears it (launch_frame_graph,
+// launch_fused_frame, and ensure_frame_buffers when a buffer moves outside a frame).
+hipError_t launch_records(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc, const FrameSetupOut &so, bool captured = false)
+{
+    const FrameParams &fp = fc.fp;
+    const RecordsKey key{fp.cam, fc.cc, ctx->scene_generation, ctx->d_cull.ptr, ctx->d_tris.ptr, so.ftris, so.tnum, so.ray_colp, so.ray_row,
+                         so.zero_a, so.zero_b, so.tile_lists, fp.width, fp.height, ctx->n_tris, so.ray_pairs, so.ray_rows, so.n_zero_a,
+                         so.n_zero_b, so.list_gx, so.list_gy, so.list_row_begin, so.list_row_pitch, so.list_blocks,
+                         fp.row_begin, fp.row_end, fp.row_pitch, 0u};
+    const unsigned char *bytes = reinterpret_cast<const unsigned char *>(&key);
+    const bool pure = so.n_zero_a == 0u && so.n_zero_b == 0u;
+    if (!captured && pure && sl.records_key.size() == sizeof key && std::memcmp(sl.records_key.data(), bytes, sizeof key) == 0)
+        return hipSuccess;
+    sl.records_key.clear();
+    const hipError_t e = launch_frame_setup(sl.stream, fc.cc, fp.cam, fp.width, fp.height, ctx->d_cull.ptr, ctx->d_tris.ptr, ctx->n_tris, so);
+    if (e != hipSuccess || captured) return e;
+    ctx->setup_launches++;
+    if (ctx->setup_cache) sl.records_key.assign(bytes, bytes + sizeof key);   // (RWR_SETUP_CACHE=0: never a key, never a hit)
+    return hipSuccess;
+}
+
 // k_frame_setup, the screen bins of a large scene, and the start of the frame's timing pair.
 int enqueue_records(rwr_context *ctx, FrameSlot &sl, FrameKernel kernel, FrameConsts &fc, const FrameSetupOut &so, FrameTiming &timing)
 {
     FrameParams &fp = fc.fp;
     const hipStream_t stream = sl.stream;
-    RWR_HIP_CHECK(launch_frame_setup(stream, fc.cc, fp.cam, fp.width, fp.height, ctx->d_cull.ptr, ctx->d_tris.ptr, ctx->n_tris, so));
+    RWR_HIP_CHECK(launch_records(ctx, sl, fc, so));
     if (ctx->n_tris > ctx->bin_min_faces && !(fp.flags & RWR_FLAG_NO_CULL)) {
         // more faces than one 256-wide batch: bin them per 64x32-pixel screen region, once per frame.  The lists
         // are sized by a count pass on the device; the buffer keeps what the previous frames needed (read back a
@@ -216,13 +258,14 @@ int launch_frame_graph(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc, c
 {
     const FrameParams &fp = fc.fp;
     const hipStream_t stream = sl.stream;
+    sl.records_key.clear();   // the graph's k_frame_setup writes the slot's records
     std::vector<unsigned char> key(sizeof(FrameParams) + sizeof(CullConsts));
     std::memcpy(key.data(), &fp, sizeof fp);
     std::memcpy(key.data() + sizeof fp, &fc.cc, sizeof fc.cc);
     if (!sl.frame_graph || key != sl.frame_graph_key) {
         hipGraph_t g = nullptr;
         RWR_HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        hipError_t e = launch_frame_setup(stream, fc.cc, fp.cam, fp.width, fp.height, ctx->d_cull.ptr, ctx->d_tris.ptr, ctx->n_tris, so);
+        hipError_t e = launch_records(ctx, sl, fc, so, true);
         if (e == hipSuccess) e = launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, quad_tex, tg);
         const hipError_t e2 = hipStreamEndCapture(stream, &g);
         RWR_HIP_CHECK(e);
@@ -242,6 +285,7 @@ int launch_frame_graph(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc, c
         sl.frame_graph_key.swap(key);
     }
     RWR_HIP_CHECK(hipGraphLaunch(sl.frame_graph, stream));
+    ctx->setup_launches++;
     return RWR_OK;
 }
 
@@ -261,6 +305,7 @@ bool fused_pays(const rwr_context *ctx, const FrameParams &fp)
 int launch_fused_frame(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc, const FrameSetupOut &so, const QuadTex &quad_tex, const Targets &tg)
 {
     const hipStream_t stream = sl.stream;
+    sl.records_key.clear();   // the launch's record makers write the slot's records (and no tile lists)
     FusedSetup fs{};
     fs.cc = fc.cc;
     fs.cull = ctx->d_cull.ptr;

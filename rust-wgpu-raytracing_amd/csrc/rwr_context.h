@@ -90,6 +90,9 @@ struct FrameSlot {
     // hipGraph of this slot — replayed as it is while camera and parameters stay the same, updated in place when they change
     OwnedGraphExec frame_graph;
     std::vector<unsigned char> frame_graph_key;
+    // what the records, tables and face sets above were made from, byte for byte (render.cpp launch_records), while they stand:
+    // a frame with the same key on this slot finds them made and launches no k_frame_setup.  Empty: nothing to rely on
+    std::vector<unsigned char> records_key;
     // the frame kernel's fused form (one launch per frame): {finished record blocks, "a wait ran out"} on the device, the count
     // the host expects before the next frame, and the block count it is valid for
     DeviceBuffer<uint32_t> d_fused;
@@ -192,6 +195,8 @@ struct rwr_context {
     bool fused_setup = true;                            // one launch per small reference frame (k_primary_p2<FUSED>); RWR_FUSED_SETUP=0: two
     bool fused_setup_force = false;                     // RWR_FUSED_SETUP=1: wherever the fused form is possible
     bool tile_lists = true;                             // per-tile face sets from k_frame_setup for the two-pixel kernel; RWR_TILE_LISTS=0: it culls itself
+    bool setup_cache = true;                            // a slot keeps its records while their inputs stand still (FrameSlot::records_key); RWR_SETUP_CACHE=0: made every frame
+    uint64_t setup_launches = 0;                        // k_frame_setup launches put on a stream so far (rwr_frame_setup_launches)
     // BVH over the (flattened) world-space faces, for bounce rays
     rwr::DeviceBuffer<rwr::BvhNode4> d_bvh_nodes;
     rwr::DeviceBuffer<uint32_t> d_bvh_leaf_faces;
