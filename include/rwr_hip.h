@@ -459,6 +459,18 @@ RWR_API int rwr_last_render_stats(rwr_context *ctx, uint64_t *primary_rays, uint
  * Host-side, does not wait.  NULL ctx or launches: RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_frame_setup_launches(rwr_context *ctx, uint64_t *launches);
 
+/* The kept plane of ray directions.  While the camera rests, the two-pixel frame kernel (the reference frame: spp 1, no bounce,
+ * culled, no normal maps, two launches per frame) loads the normalised ray directions of its pixels from a plane the frame slot
+ * keeps — 24 bytes per pixel pair of the launch's workgroups, allocated by the first build — instead of computing them from the
+ * ray tables.  Per slot: a frame whose camera uniform, screen and rows are those of the slot's frame before fills the plane once
+ * (one launch of k_ray_plane, which calls the frame kernel's own ray function); frames after it load; a frame with another
+ * camera, screen or rows computes its rays as ever and leaves no plane.  Scene changes do not touch the plane.  Frames wider
+ * than 3840 or higher than 2160 pixels, and frames whose plane cannot be allocated, compute their rays.
+ * builds: k_ray_plane launches this context has put on its streams since it was created; frames: frames that loaded their rays
+ * from a plane.  RWR_RAY_PLANE=0 (read when the context is created) switches the plane off: both stay 0.  Frames are the same
+ * bytes either way.  Host-side, does not wait.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_ray_plane_stats(rwr_context *ctx, uint64_t *builds, uint64_t *frames);
+
 /* RWR_FLAG_SHADOWS: shadow rays traced by the last render call (= hits shaded: primary hits and the bounce hits of every
  * generation; an accumulating frame: its own samples; 0 without the flag) and how many of them were occluded.  Exact counts.
  * Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */

@@ -110,7 +110,7 @@ def lib() -> C.CDLL:
         "rwr_resize": [vp, vp], "rwr_render": [vp, vp, vp], "rwr_render_rows": [vp, vp, vp, u32, u32], "rwr_render_strips": [vp, vp, vp, u32, u32],
         "rwr_synchronize": [vp], "rwr_readback": [vp, vp, vp, vp, vp, vp], "rwr_get_device_targets": [vp, vp, vp],
         "rwr_timer_begin": [vp], "rwr_timer_end": [vp, vp], "rwr_timer_stop": [vp], "rwr_timer_elapsed": [vp, vp], "rwr_last_render_stats": [vp, vp, vp],
-        "rwr_last_shadow_stats": [vp, vp, vp], "rwr_frame_setup_launches": [vp, vp],
+        "rwr_last_shadow_stats": [vp, vp, vp], "rwr_frame_setup_launches": [vp, vp], "rwr_ray_plane_stats": [vp, vp, vp],
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
@@ -129,7 +129,7 @@ def lib() -> C.CDLL:
         "rwr_dist_loopback_deposit": [vp, u32, u32, i32], "rwr_dist_loopback_finish": [vp, u32, i32],
         "rwr_measure_valu_clock": [vp, u32, vp], "rwr_clock_probe_start": [vp, u32], "rwr_clock_probe_read": [vp, vp],
     }
-    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -605,6 +605,13 @@ class Context:
         n = C.c_uint64()
         _check(lib().rwr_frame_setup_launches(self._h, C.byref(n)))
         return n.value
+
+    def ray_plane_stats(self) -> tuple[int, int]:
+        """(k_ray_plane launches, frames that loaded their ray directions from a slot's kept plane) of this context so far
+        (rwr_ray_plane_stats); (0, 0) for ever with RWR_RAY_PLANE=0."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(lib().rwr_ray_plane_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def last_shadow_stats(self) -> tuple[int, int]:
         """(shadow rays traced by the last render call, how many of them were occluded); (0, 0) without FLAG_SHADOWS."""

@@ -48,6 +48,7 @@ hipError_t ensure_frame_buffers(rwr_context *ctx)
         // allocator may hand it back) over memory nobody has written, so the slot's records no longer stand
         if (before[0] != sl.d_ftris.ptr || before[1] != sl.d_tnum.ptr || before[2] != sl.d_ray_colp.ptr || before[3] != sl.d_ray_row.ptr)
             sl.records_key.clear();
+        if (before[2] != sl.d_ray_colp.ptr || before[3] != sl.d_ray_row.ptr) sl.forget_ray_plane();   // (its key names the tables' addresses)
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -86,6 +87,7 @@ void read_tunables(rwr_context *ctx)
     if (env_flag("RWR_FUSED_SETUP", &ctx->fused_setup)) ctx->fused_setup_force = ctx->fused_setup;
     env_flag("RWR_TILE_LISTS", &ctx->tile_lists);
     env_flag("RWR_SETUP_CACHE", &ctx->setup_cache);
+    env_flag("RWR_RAY_PLANE", &ctx->ray_plane);
     env_f32("RWR_AUTO_BVH_FACE_PX", &ctx->auto_bvh_face_px);
     if (env_u32("RWR_WF_GROUP", &ctx->wf_group)) ctx->wf_group = std::min(kWfMaxGroup, std::max(1u, ctx->wf_group));
     bool stats = false, wide = false;
@@ -217,6 +219,7 @@ int rwr_resize(rwr_context *ctx, const rwr_screen *screen)
     for (uint32_t i = 0; i < ctx->n_slots; i++) {
         RWR_HIP_CHECK(ensure_slot_targets(ctx, i));
         ctx->slots[i].aux_valid = false;
+        ctx->slots[i].forget_ray_plane();   // (the key holds the screen size too; the buffer stays for the next build)
     }
     for (GatherSet &gs : ctx->gather) gs.valid = false;   // a frame gathered at the old size is gone
     RWR_HIP_CHECK(ensure_frame_buffers(ctx));
@@ -386,6 +389,14 @@ int rwr_frame_setup_launches(rwr_context *ctx, uint64_t *launches)
 {
     if (!ctx || !launches) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
     *launches = ctx->setup_launches;
+    return RWR_OK;
+}
+
+int rwr_ray_plane_stats(rwr_context *ctx, uint64_t *builds, uint64_t *frames)
+{
+    if (!ctx || !builds || !frames) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *builds = ctx->ray_plane_builds;
+    *frames = ctx->ray_plane_frames;
     return RWR_OK;
 }
 

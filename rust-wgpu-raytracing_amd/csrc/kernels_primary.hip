@@ -350,6 +350,7 @@ hipError_t preload_kernels()
 {
     hipError_t e = preload_kernels_primary();
     if (e == hipSuccess) e = preload_kernels_primary_p2();
+    if (e == hipSuccess) e = preload_kernels_ray_plane();
     if (e == hipSuccess) e = preload_kernels_wavefront();
     if (e == hipSuccess) e = preload_kernels_wf_primary();
     if (e == hipSuccess) e = preload_kernels_wf_bounce();

@@ -12,17 +12,12 @@
 #include <hip/hip_ext.h>
 
 #include "rwr_frame_setup.h"
+#include "rwr_p2_tile.h"   // RWR_P2_TILE_32x4: a wave's tile, 32x4 pixels (default) or 16x8
 #include "rwr_primary.h"
 #include "rwr_shade_p2.h"
 
 namespace rwr {
 
-// Tile of a wave: 32x4 pixels (default) or 16x8.  With 32x4 every row of a tile is one whole 128-byte line
-// of the RGBA8 and the R32F target, which the streaming stores then write without a partial-line pass
-// through the L2 (WRITE_SIZE = 8 B/pixel exactly; 16x8 tiles measured 10 % more); the frame time is the same.
-#ifndef RWR_P2_TILE_32x4
-#define RWR_P2_TILE_32x4 1
-#endif
 #ifndef RWR_P2_OCC
 #define RWR_P2_OCC 7  // 72 VGPRs: the shading step needs 66; at 8 waves (64) it spills and is slower (measured)
 #endif
@@ -34,7 +29,11 @@ namespace rwr {
 // order of their flattened index, so the record makers are running before a waiting one exists; the wait is BOUNDED all the
 // same: a wave whose wait runs out flags the frame as incomplete and leaves, it never hangs).  Saves the host one of its two
 // launches per frame and the device the boundary between them.
-template <bool AUX, bool CULL, bool NMAP, bool FUSED = false>
+// PLANE: the camera rests (render.cpp ray_plane_step) — the pairs' ray directions are loaded from the slot's kept plane
+// (rwr_internal.h RayPlane, filled by k_ray_plane from the same function) instead of computed from the ray tables.  The form has
+// no use for the tables, and the plane's two arrays arrive in the tables' arguments (ray_colp: RayPlane::xy, ray_row:
+// RayPlane::z), so that the kernel's arguments, and with them the code of every other form, stay what they were.
+template <bool AUX, bool CULL, bool NMAP, bool FUSED = false, bool PLANE = false>
 __global__ void __launch_bounds__(256, (AUX || NMAP) ? 4 : RWR_P2_OCC)
 // (the first eleven arguments repeat FrameParams fields: they are what a wave needs first, and the Makefile
 // has their 14 dwords preloaded into SGPRs)
@@ -44,6 +43,7 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
              const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
              const QuadTex tex, const Targets tg, const FusedSetup fs)
 {
+    static_assert(!PLANE || (CULL && !NMAP && !FUSED), "the loading form exists for the culled two-launch frame without normal maps");
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     uint32_t by = blockIdx.y;
     const_ptr<TriRecord> tris_c = nullptr;
@@ -169,7 +169,15 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
                                      (__attribute__((address_space(3))) void *)&s_lut[64u * wu], 4, 0, 0);
 
     const f3 O = ld3(p.cam.origin);
-    const v3 D = pixel_pair_ray_dir_tab(p.cam, ray_colp, ray_row, px0, py);
+    v3 D;
+    if constexpr (PLANE) {   // requested where the table loads are: ahead of the LDS table's wait, behind the same work
+        const uint32_t i = (by * gridDim.x + blockIdx.x) * 256u + threadIdx.x;   // this lane's entry (k_ray_plane's index)
+        const float4 dxy = ray_colp[i];
+        const float2 dz = reinterpret_cast<const float2 *>(ray_row)[i];
+        D = v3{f2{dxy.x, dxy.y}, f2{dxy.z, dxy.w}, f2{dz.x, dz.y}};
+    } else {
+        D = pixel_pair_ray_dir_tab(p.cam, ray_colp, ray_row, px0, py);
+    }
 
     // framebuffer state of the two pixels, as the reference's cleared textures hold it
     f2 depth_tex = splat(0.0f), win_t = splat(0.0f);
@@ -378,7 +386,7 @@ uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks)
 
 hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const QuadTex &tex, const Targets &tg, hipEvent_t ev_start,
-                             hipEvent_t ev_stop, const FusedSetup *fused)
+                             hipEvent_t ev_stop, const FusedSetup *fused, const RayPlane *plane)
 {
     if (fp.row_end <= fp.row_begin || fp.width == 0) return hipSuccess;
     if (fp.row_pitch % kStripRows != 0u) return hipErrorInvalidValue;   // a workgroup's four tiles must share a screen bin
@@ -393,7 +401,15 @@ hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriReco
     const FusedSetup fs = fused ? *fused : FusedSetup{};
 #define RWR_P2_LAUNCH(A, C, N, F) hipExtLaunchKernelGGL((k_primary_p2<A, C, N, F>), grid, block, 0, s, ev_start, ev_stop, 0, ftris, fp.ray_colp, fp.ray_row, \
     fp.n_tris, fp.row_begin, fp.bins.enabled, fp.row_pitch, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3], fp, tris, shade, tex, tg, fs)
-    if (fused) {   // (the plain reference frame only: context.cpp)
+    if (plane) {   // (a resting camera's frame: render.cpp ray_plane_step)
+        if (fused || nmap || !do_cull || !plane->xy || !plane->z) return hipErrorInvalidValue;
+        const float4 *const pxy = plane->xy, *const pz = reinterpret_cast<const float4 *>(plane->z);   // in the ray tables' arguments
+#define RWR_P2_LAUNCH_PLANE(A) hipExtLaunchKernelGGL((k_primary_p2<A, true, false, false, true>), grid, block, 0, s, ev_start, ev_stop, 0, ftris, pxy, pz, \
+    fp.n_tris, fp.row_begin, fp.bins.enabled, fp.row_pitch, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3], fp, tris, shade, tex, tg, fs)
+        if (aux) RWR_P2_LAUNCH_PLANE(true);
+        else RWR_P2_LAUNCH_PLANE(false);
+#undef RWR_P2_LAUNCH_PLANE
+    } else if (fused) {   // (the plain reference frame only: context.cpp)
         RWR_P2_LAUNCH(false, true, false, true);
     } else if (nmap) {
         if (aux && do_cull) RWR_P2_LAUNCH(true, true, true, false);

@@ -210,6 +210,67 @@ hipError_t launch_records(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc
     return hipSuccess;
 }
 
+// What a slot's plane of ray directions (rwr_internal.h RayPlane) is a function of, and where it lies: the camera uniform, the
+// screen, the launch's rows (they place the grid's workgroups) and the addresses of the two ray tables it is made from and of
+// the plane itself.  No scene generation and no culling constants: the directions survive other spheres, instances or meshes.
+// Field by field (no padding bytes).
+struct RayPlaneKey {
+    rwr_camera_inv_uniform cam;
+    const void *ray_colp, *ray_row, *plane;
+    uint32_t width, height, row_begin, row_end, row_pitch, pad;
+};
+static_assert(sizeof(RayPlaneKey) == sizeof(rwr_camera_inv_uniform) + 3 * sizeof(void *) + 6 * 4, "RayPlaneKey has no padding");
+
+// The two-pixel frame kernel's rays for a camera at rest.  A fifth of the kernel's instructions turn the ray tables into the
+// normalised directions of its pixel pairs, the same ones every frame while camera, screen and rows stand still — in a redraw
+// loop that is most frames, the camera moves only while a key is held.  Per slot, for a frame with key K behind launch_records
+// on the slot's stream:
+//   the slot's plane was built for K:        the frame kernel loads its directions from it            (returns true)
+//   else the slot's frame before had key K:  k_ray_plane fills the plane once, then the same          (returns true)
+//   else:                                    K is remembered and the frame computes its rays, as ever (returns false)
+// so a moving camera never pays for a plane it would not use, and a camera that comes to rest computes one more frame per
+// slot, builds on the next and loads from then on.  Frames that cannot use a plane (another kernel or form, RWR_RAY_PLANE=0, a
+// frame beyond kRayPlaneMaxW x kRayPlaneMaxH) pass the slot's key and plane by.  A plane that cannot be allocated is no
+// error: the frame computes its rays.  The key is cleared by whatever moves the tables outside a frame (ensure_frame_buffers)
+// and by rwr_resize.
+bool ray_plane_step(rwr_context *ctx, FrameSlot &sl, const FrameParams &fp, RayPlane &plane)
+{
+    if (!ctx->ray_plane || fp.width > kRayPlaneMaxW || fp.height > kRayPlaneMaxH || fp.row_end <= fp.row_begin) return false;
+    const size_t n = ray_plane_entries(fp);
+    auto key_of = [&]() {
+        const RayPlaneKey k{fp.cam, fp.ray_colp, fp.ray_row, sl.d_ray_plane.ptr, fp.width, fp.height, fp.row_begin, fp.row_end, fp.row_pitch, 0u};
+        const unsigned char *b = reinterpret_cast<const unsigned char *>(&k);
+        return std::vector<unsigned char>(b, b + sizeof k);
+    };
+    std::vector<unsigned char> key = key_of();
+    if (key != sl.ray_plane_key) {
+        sl.ray_plane_key.swap(key);
+        sl.ray_plane_built = false;
+        return false;
+    }
+    if (!sl.ray_plane_built) {
+        if (sl.d_ray_plane.count < 3u * n) {   // (a larger plane than the slot has held: the old one goes, and with it the key's address)
+            if (sl.d_ray_plane.ensure(3u * n) != hipSuccess) {
+                (void)hipGetLastError();
+                sl.forget_ray_plane();
+                return false;
+            }
+            sl.ray_plane_key = key_of();
+        }
+        plane = RayPlane{reinterpret_cast<float4 *>(sl.d_ray_plane.ptr), sl.d_ray_plane.ptr + 2u * n};
+        if (launch_ray_plane(sl.stream, fp, plane) != hipSuccess) {
+            (void)hipGetLastError();
+            sl.forget_ray_plane();
+            return false;
+        }
+        sl.ray_plane_built = true;
+        ctx->ray_plane_builds++;
+    }
+    plane = RayPlane{reinterpret_cast<float4 *>(sl.d_ray_plane.ptr), sl.d_ray_plane.ptr + 2u * n};
+    ctx->ray_plane_frames++;
+    return true;
+}
+
 // k_frame_setup, the screen bins of a large scene, and the start of the frame's timing pair.
 int enqueue_records(rwr_context *ctx, FrameSlot &sl, FrameKernel kernel, FrameConsts &fc, const FrameSetupOut &so, FrameTiming &timing)
 {
@@ -376,10 +437,16 @@ int enqueue_reference(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, F
     case FrameKernel::kOnePixel:
         RWR_HIP_CHECK(launch_primary(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0_of(ctx), tg));
         break;
-    default:
+    default: {
+        // (the forms with a loading twin: culled, no normal maps — launch_primary_p2's own rule for RWR_FLAG_NORMAL_MAP)
+        RayPlane plane{};
+        const bool can_load = !(fp.flags & RWR_FLAG_NO_CULL) && !((fp.flags & RWR_FLAG_NORMAL_MAP) && fp.tangents);
+        const bool load = can_load && ray_plane_step(ctx, sl, fp, plane);
         RWR_HIP_CHECK(launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, quad_tex, tg,
                                         timing.dispatch ? ctx->timing_events[2 * ctx->timing_pairs].h : nullptr,
-                                        timing.dispatch ? ctx->timing_events[2 * ctx->timing_pairs + 1].h : nullptr));
+                                        timing.dispatch ? ctx->timing_events[2 * ctx->timing_pairs + 1].h : nullptr, nullptr,
+                                        load ? &plane : nullptr));
+    }
     }
     return RWR_OK;
 }

@@ -93,6 +93,13 @@ struct FrameSlot {
     // what the records, tables and face sets above were made from, byte for byte (render.cpp launch_records), while they stand:
     // a frame with the same key on this slot finds them made and launches no k_frame_setup.  Empty: nothing to rely on
     std::vector<unsigned char> records_key;
+    // The kept plane of ray directions (rwr_internal.h RayPlane; render.cpp ray_plane_step), allocated by the slot's first build:
+    // the xy array, then the z array.  ray_plane_key: the plane key (camera, screen, rows, addresses) of the slot's last frame
+    // that could use a plane, empty when there is nothing to rely on; ray_plane_built: d_ray_plane holds that key's directions
+    DeviceBuffer<float2> d_ray_plane;
+    std::vector<unsigned char> ray_plane_key;
+    bool ray_plane_built = false;
+    void forget_ray_plane() { ray_plane_key.clear(); ray_plane_built = false; }
     // the frame kernel's fused form (one launch per frame): {finished record blocks, "a wait ran out"} on the device, the count
     // the host expects before the next frame, and the block count it is valid for
     DeviceBuffer<uint32_t> d_fused;
@@ -197,6 +204,8 @@ struct rwr_context {
     bool tile_lists = true;                             // per-tile face sets from k_frame_setup for the two-pixel kernel; RWR_TILE_LISTS=0: it culls itself
     bool setup_cache = true;                            // a slot keeps its records while their inputs stand still (FrameSlot::records_key); RWR_SETUP_CACHE=0: made every frame
     uint64_t setup_launches = 0;                        // k_frame_setup launches put on a stream so far (rwr_frame_setup_launches)
+    bool ray_plane = true;                              // a slot keeps its pixels' ray directions while the camera rests (FrameSlot::d_ray_plane); RWR_RAY_PLANE=0: computed every frame
+    uint64_t ray_plane_builds = 0, ray_plane_frames = 0;   // k_ray_plane launches / frames that loaded their rays from a plane, so far (rwr_ray_plane_stats)
     // BVH over the (flattened) world-space faces, for bounce rays
     rwr::DeviceBuffer<rwr::BvhNode4> d_bvh_nodes;
     rwr::DeviceBuffer<uint32_t> d_bvh_leaf_faces;

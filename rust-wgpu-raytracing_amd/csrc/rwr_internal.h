@@ -329,10 +329,27 @@ struct BvhDevice {
     uint32_t wide_lane;         // the per-lane trace kernel may run as 1 024-thread workgroups sharing one LDS copy of the nodelets
 };
 
+// A frame slot's kept plane of ray directions (render.cpp ray_plane_step): the normalised directions of the two-pixel frame
+// kernel's pixel pairs, 24 bytes per lane of its grid — xy[i] = {x.x, x.y, y.x, y.y}, z[i] = {z.x, z.y} of the pair whose lane
+// is thread i % 256 of workgroup i / 256 (workgroups in the order of their flattened index).  Every lane of the grid has an
+// entry, on or off the frame, so neither the kernel that fills it nor the one that loads from it tests a bound.
+struct RayPlane {
+    float4 *xy;
+    float2 *z;
+};
+constexpr uint32_t kRayPlaneMaxW = 3840, kRayPlaneMaxH = 2160;   // larger frames compute their rays every frame
+// entries (lanes of the frame kernel's grid) of the plane of fp's launch
+inline size_t ray_plane_entries(const FrameParams &fp) { return (size_t)((fp.width + 63u) / 64u) * band_strips(fp) * 256u; }
+// kernels_ray_plane.hip: fills the plane for the launch of fp from the slot's ray tables (fp.ray_colp / ray_row, made for fp.cam)
+hipError_t launch_ray_plane(hipStream_t s, const FrameParams &fp, const RayPlane &plane);
+hipError_t preload_kernels_ray_plane();
+
 struct FusedSetup;
+// plane (may be null): the frame's ray directions are loaded from it instead of computed (the culled frame without normal
+// maps, two launches per frame: anything else with a plane is hipErrorInvalidValue)
 hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const QuadTex &tex, const Targets &tg, hipEvent_t ev_start = nullptr,
-                             hipEvent_t ev_stop = nullptr, const FusedSetup *fused = nullptr);
+                             hipEvent_t ev_stop = nullptr, const FusedSetup *fused = nullptr, const RayPlane *plane = nullptr);
 // grid rows the fused form puts in front of the frame's strips for `n_blocks` record-making workgroups
 uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks);
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
