@@ -207,7 +207,7 @@ enum {
                                           gather keep their contracts.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or
                                           single-triangle passes: RWR_ERR_UNSUPPORTED.
                                        5. rwr_last_shadow_stats counts the shadow rays and how many were occluded. */
-    RWR_FLAG_DENOISE = 1u << 8      /* extension: an edge-avoiding a-trous filter (Dammertz et al. 2010) over the frame the integrator
+    RWR_FLAG_DENOISE = 1u << 8,     /* extension: an edge-avoiding a-trous filter (Dammertz et al. 2010) over the frame the integrator
                                        resolved, for frames of few samples.  Without the flag every frame is what it was, byte for
                                        byte, with no further launch or allocation.  With it:
                                        1. The frame always takes the path integrator, also at spp 1 / max_bounces 0 (as with
@@ -233,6 +233,31 @@ enum {
                                           covers the whole frame (the filter reaches 62 pixels; a rank does not hold its neighbours'
                                           rows).  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED. */
+    RWR_FLAG_SKY = 1u << 9          /* extension: sky light — a bounce ray that leaves the scene returns the radiance of a sky gradient
+                                       (rwr_sky_set_params) instead of nothing.  Without the flag every frame is what it was, byte for
+                                       byte, with no further launch or allocation.  With it:
+                                       1. S(D), per channel c in f32 with no contraction: u = fminf(fmaxf(0.5f * D.y + 0.5f, 0.0f), 1.0f),
+                                          S_c = horizon_c + (zenith_c - horizon_c) * u.  World +y is up (the reference's Camera.up).
+                                       2. When bounce ray k (k = 1 ... max_bounces) with direction D_k finds no hit - no sphere and no
+                                          face of any instance or part - the sample adds term k = clamp(T(k-1) * S(D_k), 0, 64) per
+                                          channel, NaN counting as 0, and the path ends as it does without the flag.  A generation
+                                          still adds at most one term <= 64 per sample.
+                                       3. Primary rays that miss are unchanged: background pixels keep their colour, alpha and
+                                          obj_id = -1 (the sky is a light, not a backdrop).  Depth, obj_id and hit_t (sample 0) do not
+                                          depend on the flag, bit for bit.
+                                       4. max_bounces = 0: the flag is ignored, the frame is the frame without it, byte for byte.
+                                          zenith = horizon = 0: every plane equals the frame without the flag, byte for byte.
+                                       5. No random numbers are used; every primary, bounce and shadow ray is the one of the frame
+                                          without the flag, bit for bit.  A sky term casts no shadow ray: rwr_last_shadow_stats and
+                                          rwr_last_render_stats do not depend on the flag.  RWR_FLAG_MULTI_BOUNCE, RWR_FLAG_SHADOWS,
+                                          RWR_FLAG_NORMAL_MAP, RWR_FLAG_AUX_OUTPUTS, RWR_FLAG_NO_CULL, RWR_FLAG_DENOISE, instances, parts,
+                                          frames in flight, row bands, strips and the multi-GPU gather keep their contracts.
+                                       6. RWR_FLAG_ACCUMULATE: this bit is part of the key, and while it is set so are the 24 bytes of
+                                          rwr_sky_params: changing a parameter starts over at N = 0.  Without the bit,
+                                          rwr_sky_set_params does not disturb an accumulation.
+                                       7. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED.  The
+                                          refusal comes first: it holds at max_bounces = 0 too, where item 4 would otherwise ignore the
+                                          flag — a combination that is refused does not start to work when the bounces go to 0. */
 };
 
 #define RWR_MAX_BOUNCES 8u
@@ -494,6 +519,20 @@ typedef struct rwr_denoise_params {
 } rwr_denoise_params;
 RWR_API int rwr_denoise_set_params(rwr_context *ctx, const rwr_denoise_params *params);
 RWR_API int rwr_denoise_get_params(rwr_context *ctx, rwr_denoise_params *out);
+
+/* RWR_FLAG_SKY: the sky's two colours, per context.  In S(D) at the flag u is 1 straight up, 1/2 along the geometric horizon and 0
+ * straight down: `zenith` is the radiance at u = 1, `horizon` the radiance at u = 0, the mean of the two along the horizon.
+ * Defaults: zenith (0.5, 0.7, 1.0), horizon (1, 1, 1); params = NULL restores them.  Every component must be finite and in
+ * [0, 16]; anything else, NaN included: RWR_ERR_INVALID_ARGUMENT, and the parameters stay as they were.  Host-side, waits for
+ * nothing; frames rendered after the call use the new values. */
+typedef struct rwr_sky_params {
+    float zenith[3];
+    float horizon[3];
+} rwr_sky_params;
+#define RWR_SKY_DEFAULTS {{0.5f, 0.7f, 1.0f}, {1.0f, 1.0f, 1.0f}}   /* an initialiser of rwr_sky_params: what NULL restores */
+#define RWR_SKY_COMPONENT_MAX 16.0f                                 /* the largest component rwr_sky_set_params takes */
+RWR_API int rwr_sky_set_params(rwr_context *ctx, const rwr_sky_params *params);
+RWR_API int rwr_sky_get_params(rwr_context *ctx, rwr_sky_params *out);
 
 /* Self-test of the kernels' short exact forms ("Numerics"): the frame kernel replaces the
  * shader's  ((1/d) - (1/kNear)) / ((1/kFar) - (1/kNear))  (compute.wgsl:78-80) and the three divisions

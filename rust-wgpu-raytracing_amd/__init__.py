@@ -48,6 +48,8 @@ FLAG_MULTI_BOUNCE = 1 << 6   # max_bounces up to MAX_BOUNCES (include/rwr_hip.h)
 FLAG_SHADOWS = 1 << 7        # shadow rays towards the reference's two lights (include/rwr_hip.h)
 FLAG_DENOISE = 1 << 8        # the a-trous filter behind the integrator's resolve; implies FLAG_AUX_OUTPUTS (include/rwr_hip.h)
 DENOISE_PARAMS_DTYPE = np.dtype([("iterations", "<u4"), ("sigma_color", "<f4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
+FLAG_SKY = 1 << 9            # bounce rays that leave the scene return the sky's radiance (include/rwr_hip.h)
+SKY_PARAMS_DTYPE = np.dtype([("zenith", "<f4", 3), ("horizon", "<f4", 3)])
 MAX_BOUNCES = 8
 FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
 KEY_FORWARD, KEY_BACKWARD, KEY_LEFT, KEY_RIGHT, KEY_UP, KEY_DOWN = 1, 2, 4, 8, 16, 32
@@ -113,6 +115,7 @@ def lib() -> C.CDLL:
         "rwr_last_shadow_stats": [vp, vp, vp], "rwr_frame_setup_launches": [vp, vp], "rwr_ray_plane_stats": [vp, vp, vp],
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
+        "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
         "rwr_load_model_compute": [C.c_char_p, C.c_char_p, vp], "rwr_model_free": [vp],
         "rwr_model_info": [vp, vp, vp, vp, vp, vp, vp], "rwr_scene_upload_model": [vp, vp],
@@ -129,7 +132,8 @@ def lib() -> C.CDLL:
         "rwr_dist_loopback_deposit": [vp, u32, u32, i32], "rwr_dist_loopback_finish": [vp, u32, i32],
         "rwr_measure_valu_clock": [vp, u32, vp], "rwr_clock_probe_start": [vp, u32], "rwr_clock_probe_read": [vp, vp],
     }
-    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats",
+                           "rwr_sky_set_params", "rwr_sky_get_params")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -646,6 +650,24 @@ class Context:
         _check(lib().rwr_denoise_get_params(self._h, _p(p)))
         return {"iterations": int(p["iterations"][0]), "sigma_color": float(p["sigma_color"][0]),
                 "normal_cos_min": float(p["normal_cos_min"][0]), "depth_rel": float(p["depth_rel"][0])}
+
+    def sky_set_params(self, zenith=None, horizon=None):
+        """The FLAG_SKY sky's two colours (rwr_sky_set_params), each three floats in [0, 16]; an argument left out keeps its value,
+        no argument at all restores the defaults.  Out of range or NaN: RwrError(ERR_INVALID_ARGUMENT), and the parameters stay."""
+        if zenith is None and horizon is None:
+            _check(lib().rwr_sky_set_params(self._h, None))
+            return
+        p = np.zeros(1, dtype=SKY_PARAMS_DTYPE)
+        now = self.sky_get_params()
+        p["zenith"] = now["zenith"] if zenith is None else np.asarray(zenith, np.float32)
+        p["horizon"] = now["horizon"] if horizon is None else np.asarray(horizon, np.float32)
+        _check(lib().rwr_sky_set_params(self._h, _p(p)))
+
+    def sky_get_params(self) -> dict:
+        """{"zenith": float32[3], "horizon": float32[3]} (rwr_sky_get_params)."""
+        p = np.zeros(1, dtype=SKY_PARAMS_DTYPE)
+        _check(lib().rwr_sky_get_params(self._h, _p(p)))
+        return {"zenith": p["zenith"][0].copy(), "horizon": p["horizon"][0].copy()}
 
 
 def csrc_tree() -> str:

@@ -91,7 +91,10 @@ void read_tunables(rwr_context *ctx)
     env_f32("RWR_AUTO_BVH_FACE_PX", &ctx->auto_bvh_face_px);
     if (env_u32("RWR_WF_GROUP", &ctx->wf_group)) ctx->wf_group = std::min(kWfMaxGroup, std::max(1u, ctx->wf_group));
     bool stats = false, wide = false;
-    if (env_flag("RWR_WF_STATS", &stats) && stats && ctx->d_wf_dbg.ensure(4) == hipSuccess) (void)hipMemset(ctx->d_wf_dbg.ptr, 0, 32);
+    if (env_flag("RWR_WF_STATS", &stats) && stats && ctx->d_wf_dbg.ensure(4) == hipSuccess) {
+        (void)hipMemset(ctx->d_wf_dbg.ptr, 0, 32);
+        wf_trace_launch_counts(ctx->wf_launches_before);
+    }
     if (env_u32("RWR_WF_OVERLAP", &ctx->wf_queues)) ctx->wf_queues = std::min(kWfMaxQueues, std::max(1u, ctx->wf_queues));
     env_u32("RWR_WF_ZSPLIT", &ctx->wf_z_split);
     env_u32("RWR_WF_PACKET_RAYS", &ctx->wf_packet_dense_rays);
@@ -176,6 +179,11 @@ void rwr_ctx_destroy(rwr_context *ctx)
         (void)hipMemcpy(h, ctx->d_wf_dbg.ptr, sizeof h, hipMemcpyDeviceToHost);
         std::fprintf(stderr, "rwr wavefront pools: packets %llu pools / %llu rays, per-lane %llu pools / %llu rays (leaf extent %g)\n",
                      h[0], h[1], h[2], h[3], (double)ctx->bvh_leaf_extent);
+        uint64_t n[3];
+        wf_trace_launch_counts(n);   // (of the process: exact while one context renders at a time)
+        std::fprintf(stderr, "rwr wavefront launches: packet %llu, per-lane %llu, per-lane wide %llu\n",
+                     (unsigned long long)(n[0] - ctx->wf_launches_before[0]), (unsigned long long)(n[1] - ctx->wf_launches_before[1]),
+                     (unsigned long long)(n[2] - ctx->wf_launches_before[2]));
     }
     (void)rwr_dist_destroy(ctx);
     delete ctx;   // (inside the scope of the guard: the members free themselves with the right device current)
@@ -437,6 +445,31 @@ int rwr_denoise_get_params(rwr_context *ctx, rwr_denoise_params *out)
 {
     if (!ctx || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
     *out = ctx->denoise;
+    return RWR_OK;
+}
+
+int rwr_sky_set_params(rwr_context *ctx, const rwr_sky_params *params)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (!params) {
+        ctx->sky = kSkyDefaults;
+        return RWR_OK;
+    }
+    const rwr_sky_params p = *params;
+    for (int c = 0; c < 3; c++) {
+        if (!(p.zenith[c] >= 0.0f && p.zenith[c] <= RWR_SKY_COMPONENT_MAX))   // (false for NaN)
+            return set_error(RWR_ERR_INVALID_ARGUMENT, "sky zenith[%d] %g: finite, 0 ... 16", c, (double)p.zenith[c]);
+        if (!(p.horizon[c] >= 0.0f && p.horizon[c] <= RWR_SKY_COMPONENT_MAX))
+            return set_error(RWR_ERR_INVALID_ARGUMENT, "sky horizon[%d] %g: finite, 0 ... 16", c, (double)p.horizon[c]);
+    }
+    ctx->sky = p;
+    return RWR_OK;
+}
+
+int rwr_sky_get_params(rwr_context *ctx, rwr_sky_params *out)
+{
+    if (!ctx || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = ctx->sky;
     return RWR_OK;
 }
 

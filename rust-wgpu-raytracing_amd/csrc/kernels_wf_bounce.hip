@@ -304,6 +304,20 @@ RWR_DEV void shadow_hit(TraceShared &sh, const FrameParams &p, const WfBuffers &
     write_shadow_record(sw, (size_t)tile * wf.group * kWfTilePixels + e, (size_t)tile * wf.group * 8u + (e >> 6), e & 63u, O1, obj < 0, fa, ff);
 }
 
+// SKY forms (RWR_FLAG_SKY): the ray in slot e, direction D with D.y = dy, throughput thr, found no hit.  Its path ends as ever, and
+// its term is clamp(thr * S(D)): S = horizon + (zenith - horizon) * u per channel, u = clamp(0.5 dy + 0.5, 0, 1) (+y is up) — f32
+// operations in this order, no contraction (the build's -ffp-contract=off), converted like a hit's term (add_contribution) and added
+// to the same sums.  sky is a kernel argument: its six floats sit in scalar registers.
+RWR_DEV void add_sky(TraceShared &sh, const WfSky &sky, uint32_t e, float dy, f3 thr)
+{
+    const float u = fminf(fmaxf(0.5f * dy + 0.5f, 0.0f), 1.0f);
+    const float s0 = sky.hr + (sky.zr - sky.hr) * u;
+    const float s1 = sky.hg + (sky.zg - sky.hg) * u;
+    const float s2 = sky.hb + (sky.zb - sky.hb) * u;
+    // (a black sky adds nothing at all: add_fixed skips zeros)
+    add_fixed(sh, e, (uint32_t)(thr.x * s0 * kWfFixedScale), (uint32_t)(thr.y * s1 * kWfFixedScale), (uint32_t)(thr.z * s2 * kWfFixedScale));
+}
+
 // The trace kernels are PERSISTENT: kWfTraceGroups workgroups pull work items — (pool of the class, share of it)
 // — from a device counter until the class's live x split items are handed out.  Returns false when none are left.
 // Contains barriers; uniform over the workgroup.
@@ -349,11 +363,13 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // EMIT: a generation of a deeper path that is not its last (emit_next_ray).
 // SHADOW: RWR_FLAG_SHADOWS — a hit adds its term's ambient part and leaves a shadow record (shadow_hit); separate instantiations,
 // so that frames without the flag keep their kernels.
-template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false>
+// SKY: RWR_FLAG_SKY — a ray that hits nothing adds the sky's term (add_sky); separate instantiations for the same reason.
+template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false, bool SKY = false>
 __global__ void __launch_bounds__(WIDE ? 1024 : 256)
 k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                 const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
-                uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw)
+                uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
+                const WfSky sky)
 {
     __shared__ TraceShared sh;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
@@ -422,6 +438,8 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                 if (EMIT)
                     emit_next_ray(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd,
                                   mk3(thr.x * s1.albedo.x, thr.y * s1.albedo.y, thr.z * s1.albedo.z));
+            } else if (SKY) {
+                add_sky(sh, sky, e, D.y, thr);
             }
             if (EMIT) {   // rays written for the next generation (lanes past the pool's end have left the iteration)
                 const unsigned long long em = __ballot(have);
@@ -512,11 +530,12 @@ RWR_DEV i2 sphere_pair_intersect_t(f3 center, float radius, v3 O, v3 D, f2 &t_ou
 #ifndef RWR_PACKET_OCC
 #define RWR_PACKET_OCC 4
 #endif
-template <bool NMAP, bool EMIT = false, bool SHADOW = false>   // EMIT, SHADOW: see k_wf_trace_lane
+template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false>   // EMIT, SHADOW, SKY: see k_wf_trace_lane
 __global__ void __launch_bounds__(256, RWR_PACKET_OCC)
 k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
-                  uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw)
+                  uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
+                  const WfSky sky)
 {
     __shared__ TraceShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -732,20 +751,29 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
                 if (lane == 0u) atomicAdd(&wf.wave_total[tile * 4u], n_emit);
             }
         }
+        if (SKY) {   // per ray, not per wave: every ray of the packet (not the padding of its last lanes: i0, i1 < last) that found nothing
+            if (i0 < last && !have.x) add_sky(sh, sky, e0, R.D.y.x, mk3(thr.x.x, thr.y.x, thr.z.x));
+            if (i1 < last && !have.y) add_sky(sh, sky, e1, R.D.y.y, mk3(thr.x.y, thr.y.y, thr.z.y));
+        }
     }
     __syncthreads();
     flush_pool(sh, p, wf, tile);
     }   // next work item
 }
 
+// RWR_WF_STATS=1 (wf.dbg set): launches of the packet kernel, the per-lane kernel and its WIDE form, by this process
+static std::atomic<uint64_t> g_trace_launches[3];
+
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf, uint32_t n_tiles,
                             uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list, const WfEmit *emit,
-                            const WfShadow *shadow)
+                            const WfShadow *shadow, const WfSky *sky)
 {
     const WfEmit em = emit ? *emit : WfEmit{nullptr, 0u, 0u};
     const WfShadow sw = shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr};
     const bool shadows = sw.recs != nullptr;
+    const WfSky sk = sky ? *sky : WfSky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    const bool sky_on = sky != nullptr;
     if (n_tiles == 0 || sample_count == 0) return hipSuccess;
     uint32_t *counters = wf.counters;   // this queue's set, zeroed by the primary stage that filled the queue
     PoolInfo *info = static_cast<PoolInfo *>(pool_info);
@@ -774,7 +802,9 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
                            sample_count, packets ? packet_min_rays : 0xffffffffu, bvh.packet_extent, bvh.packet_dense_rays);
     const dim3 grid(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit));
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
-#define RWR_PACKET_LAUNCH(N, E, S) hipLaunchKernelGGL((k_wf_trace_packet<N, E, S>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw)
+    if (wf.dbg && packets) g_trace_launches[0].fetch_add(1u, std::memory_order_relaxed);
+#define RWR_PACKET_LAUNCH_K(N, E, S, K) hipLaunchKernelGGL((k_wf_trace_packet<N, E, S, K>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk)
+#define RWR_PACKET_LAUNCH(N, E, S) do { if (sky_on) RWR_PACKET_LAUNCH_K(N, E, S, true); else RWR_PACKET_LAUNCH_K(N, E, S, false); } while (0)
     if (packets && shadows) {
         if (emit) { if (nmap) RWR_PACKET_LAUNCH(true, true, true); else RWR_PACKET_LAUNCH(false, true, true); }
         else { if (nmap) RWR_PACKET_LAUNCH(true, false, true); else RWR_PACKET_LAUNCH(false, false, true); }
@@ -784,26 +814,36 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
         if (nmap) RWR_PACKET_LAUNCH(true, false, false); else RWR_PACKET_LAUNCH(false, false, false);
     }
 #undef RWR_PACKET_LAUNCH
+#undef RWR_PACKET_LAUNCH_K
     const bool stack16 = bvh.n_nodes <= 0x7fffu && fp.n_tris <= 4095u;   // node indices and leaf links (first << 3 | count - 1) in 15 bits
     const size_t fixed = (size_t)bvh.stack_depth * 256u * (stack16 ? 2u : 4u);
     const size_t node_bytes = (size_t)bvh.n_nodes * sizeof(BvhNode4);
     // nodelets go to LDS when the workgroup then still fits a CU at least four times (160 KiB LDS, 12 KiB static)
-#define RWR_LANE_LAUNCH(L, N, S16, E, S, BYTES) hipLaunchKernelGGL((k_wf_trace_lane<L, N, S16, false, E, S>), grid, dim3(256), BYTES, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw)
+#define RWR_LANE_LAUNCH_K(L, N, S16, E, S, K, BYTES) hipLaunchKernelGGL((k_wf_trace_lane<L, N, S16, false, E, S, K>), grid, dim3(256), BYTES, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk)
+#define RWR_LANE_LAUNCH(L, N, S16, E, S, BYTES) do { if (sky_on) RWR_LANE_LAUNCH_K(L, N, S16, E, S, true, BYTES); else RWR_LANE_LAUNCH_K(L, N, S16, E, S, false, BYTES); } while (0)
 #define RWR_LANE_LAUNCH0(L, E, S, BYTES) \
     if (nmap) { if (stack16) RWR_LANE_LAUNCH(L, true, true, E, S, BYTES); else RWR_LANE_LAUNCH(L, true, false, E, S, BYTES); } \
     else { if (stack16) RWR_LANE_LAUNCH(L, false, true, E, S, BYTES); else RWR_LANE_LAUNCH(L, false, false, E, S, BYTES); }
 #define RWR_LANE_LAUNCH1(L, E, BYTES) if (shadows) { RWR_LANE_LAUNCH0(L, E, true, BYTES) } else { RWR_LANE_LAUNCH0(L, E, false, BYTES) }
 #define RWR_LANE_LAUNCH2(L, BYTES) if (emit) { RWR_LANE_LAUNCH1(L, true, BYTES) } else { RWR_LANE_LAUNCH1(L, false, BYTES) }
     const size_t fixed_wide = 4u * fixed, wide_bytes = node_bytes + fixed_wide;
+    const bool wide = node_bytes + fixed > 28u * 1024u && bvh.wide_lane && !nmap && stack16 && wide_bytes + 14u * 1024u <= 160u * 1024u;
+    if (wf.dbg) g_trace_launches[wide ? 2 : 1].fetch_add(1u, std::memory_order_relaxed);
     if (node_bytes + fixed <= 28u * 1024u) { RWR_LANE_LAUNCH2(true, node_bytes + fixed) }
-    else if (bvh.wide_lane && !nmap && stack16 && wide_bytes + 14u * 1024u <= 160u * 1024u) {
+    else if (wide) {
         // a BVH too large for a copy per 256-thread workgroup, small enough for one copy per CU: 1 024-thread workgroups
-        static std::atomic<uint64_t> wide_raised_on[4];   // per form: [emit + 2 * shadows]
-        std::atomic<uint64_t> &raised = wide_raised_on[(emit ? 1 : 0) + (shadows ? 2 : 0)];
-        const void *kernel = shadows ? (emit ? reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, true, true>)
-                                             : reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, false, true>))
-                                     : (emit ? reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, true>)
-                                             : reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true>));
+        // per form: [emit + 2 * shadows + 4 * sky]
+#define RWR_WIDE_FORMS(X) X(0, false, false, false) X(1, true, false, false) X(2, false, true, false) X(3, true, true, false) \
+                          X(4, false, false, true) X(5, true, false, true) X(6, false, true, true) X(7, true, true, true)
+        static std::atomic<uint64_t> wide_raised_on[8];
+        const uint32_t form = (emit ? 1u : 0u) + (shadows ? 2u : 0u) + (sky_on ? 4u : 0u);
+        std::atomic<uint64_t> &raised = wide_raised_on[form];
+        const void *kernel = nullptr;
+        switch (form) {
+#define RWR_WIDE_KERNEL(F, E, S, K) case F: kernel = reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, E, S, K>); break;
+        RWR_WIDE_FORMS(RWR_WIDE_KERNEL)
+#undef RWR_WIDE_KERNEL
+        }
         int dev = 0;
         hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) return e;
@@ -813,21 +853,29 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
             if (e != hipSuccess) return e;
             raised.fetch_or(bit, std::memory_order_release);
         }
-#define RWR_WIDE_LAUNCH(E, S) hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true, E, S>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, fp, tris, \
-                                                 shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw)
-        if (shadows) { if (emit) RWR_WIDE_LAUNCH(true, true); else RWR_WIDE_LAUNCH(false, true); }
-        else { if (emit) RWR_WIDE_LAUNCH(true, false); else RWR_WIDE_LAUNCH(false, false); }
+        switch (form) {
+#define RWR_WIDE_LAUNCH(F, E, S, K) case F: hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true, E, S, K>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, \
+                                                               fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk); break;
+        RWR_WIDE_FORMS(RWR_WIDE_LAUNCH)
 #undef RWR_WIDE_LAUNCH
+        }
+#undef RWR_WIDE_FORMS
     }
     else { RWR_LANE_LAUNCH2(false, fixed) }
 #undef RWR_LANE_LAUNCH2
 #undef RWR_LANE_LAUNCH1
 #undef RWR_LANE_LAUNCH0
 #undef RWR_LANE_LAUNCH
+#undef RWR_LANE_LAUNCH_K
     return hipGetLastError();
 }
 
 size_t wf_pool_info_bytes() { return sizeof(PoolInfo); }
+
+void wf_trace_launch_counts(uint64_t out[3])
+{
+    for (int i = 0; i < 3; i++) out[i] = g_trace_launches[i].load(std::memory_order_relaxed);
+}
 
 hipError_t preload_kernels_wf_bounce()
 {

@@ -18,6 +18,7 @@ struct FrameRequest {
     uint32_t row_begin, row_end, row_pitch;
     bool aux, accumulate, shadows;
     bool denoise;     // RWR_FLAG_DENOISE: the filter runs behind the resolve (rp.flags holds the effective flags: AUX implied, this bit cleared)
+    bool sky;         // RWR_FLAG_SKY with at least one bounce: the trace kernels' SKY forms (without a bounce the bit is cleared from rp.flags)
     bool wavefront;   // the wavefront integrator renders it (several samples, a bounce, or an accumulation)
     bool dormant;     // the reference's dormant parts (single-triangle passes, orthographic rays) have their own plain kernel
 };
@@ -76,26 +77,34 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
                              "every %u-th strip is a part of it", row_begin, row_end, row_pitch / kStripRows);
         rp.flags = (rp.flags & ~(uint32_t)RWR_FLAG_DENOISE) | RWR_FLAG_AUX_OUTPUTS;
     }
+    // the refusal first: it holds whatever max_bounces is (rwr_hip.h, RWR_FLAG_SKY item 7)
+    if ((rp.flags & RWR_FLAG_SKY) && ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0))
+        return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_SKY: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
+    // the sky lights bounce rays alone: a frame without a bounce is the frame without the flag
+    if (rp.max_bounces == 0u) rp.flags &= ~(uint32_t)RWR_FLAG_SKY;
+    const bool sky = (rp.flags & RWR_FLAG_SKY) != 0;
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
     // with shadow rays (the integrator's stages trace them) or one the filter follows (it runs behind the integrator's resolve)
     const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate || shadows || denoise;
     const bool dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;
     if (dormant && (wavefront || (rp.flags & RWR_FLAG_USE_BVH)))
         return set_error(RWR_ERR_UNSUPPORTED, "single-triangle passes and RWR_FLAG_ORTHO_RAYS apply to the reference frame (spp 1, no bounce, no RWR_FLAG_USE_BVH)");
-    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, denoise, wavefront, dormant};
+    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, denoise, sky, wavefront, dormant};
     return RWR_OK;
 }
 
 // What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
-// camera uniform's bytes, the screen, the rows, bounces, seed, flags but the ACCUMULATE bit, frames in flight and the scene.
+// camera uniform's bytes, the screen, the rows, bounces, seed, flags but the ACCUMULATE bit, frames in flight and the scene — and, while
+// the frame is lit by the sky (RWR_FLAG_SKY), the sky's parameters.
 std::vector<unsigned char> accum_key_of(const rwr_context *ctx, const rwr_camera_inv_uniform &cam, const FrameRequest &rq)
 {
     const uint32_t words[9] = {ctx->screen.width, ctx->screen.height, rq.row_begin, rq.row_end, rq.row_pitch, rq.rp.max_bounces, rq.rp.seed,
                                rq.rp.flags & ~(uint32_t)RWR_FLAG_ACCUMULATE, ctx->n_slots};
-    std::vector<unsigned char> key(sizeof cam + sizeof words + sizeof ctx->scene_generation);
+    std::vector<unsigned char> key(sizeof cam + sizeof words + sizeof ctx->scene_generation + (rq.sky ? sizeof ctx->sky : 0u));
     std::memcpy(key.data(), &cam, sizeof cam);
     std::memcpy(key.data() + sizeof cam, words, sizeof words);
     std::memcpy(key.data() + sizeof cam + sizeof words, &ctx->scene_generation, sizeof ctx->scene_generation);
+    if (rq.sky) std::memcpy(key.data() + sizeof cam + sizeof words + sizeof ctx->scene_generation, &ctx->sky, sizeof ctx->sky);
     return key;
 }
 
@@ -597,6 +606,8 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
         RWR_HIP_CHECK(hipEventRecord(W.fork, stream));
         for (size_t q = 1; q < n_queues; q++) RWR_HIP_CHECK(hipStreamWaitEvent(W.streams[q], W.fork, 0));
     }
+    WfSky sky{};
+    if (rq.sky) std::memcpy(&sky, &ctx->sky, sizeof sky);
     const uint32_t *last_counters = nullptr;
     // (global sample indices: an accumulating frame traces [accum_before, accum_before + spp), keyed like one frame of them all)
     for (uint32_t s0 = 0, g = 0; s0 < ap.trace_spp; s0 += group, g++) {
@@ -625,7 +636,7 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
             RWR_HIP_CHECK(launch_wf_bounce(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh, tex0, wg, n_tiles, cnt,
                                            (uint32_t)std::fmax(1.0f, std::ceil(ctx->wf_packet_fill * (float)(cnt * kWfTilePixels))),
                                            W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles,
-                                           emit ? &em : nullptr, rq.shadows ? &sw : nullptr));
+                                           emit ? &em : nullptr, rq.shadows ? &sw : nullptr, rq.sky ? &sky : nullptr));
             if (rq.shadows)   // this generation's hits
                 RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, sw, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
             if (emit) std::swap(wg.masks, masks_next);

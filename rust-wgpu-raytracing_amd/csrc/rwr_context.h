@@ -117,6 +117,7 @@ struct FrameSlot {
 };
 constexpr uint32_t kMaxFramesInFlight = 3;
 constexpr rwr_denoise_params kDenoiseDefaults{5u, 0.04f, 0.95f, 0.05f};   // RWR_FLAG_DENOISE: DESIGN.md §6 says why these
+constexpr rwr_sky_params kSkyDefaults = RWR_SKY_DEFAULTS;   // RWR_FLAG_SKY
 constexpr uint32_t kWfMaxQueues = 4;
 
 // The wavefront integrator's device state, one set per frame slot: a frame of the integrator then shares nothing with the
@@ -228,6 +229,7 @@ struct rwr_context {
     rwr::PinnedWords h_wf_live;     // live pools of the last launch group {packets, per-lane}, read a frame late
     uint32_t wf_z_split = 0;        // tunable: RWR_WF_ZSPLIT (0 = from the previous frame's live pools)
     rwr::DeviceBuffer<unsigned long long> d_wf_dbg;   // RWR_WF_STATS=1: pool classification counters, printed at destroy
+    uint64_t wf_launches_before[3] = {0, 0, 0};       // RWR_WF_STATS=1: wf_trace_launch_counts when the context was made
     uint32_t wf_group = 0;          // samples per launch group; tunable: RWR_WF_GROUP (1..64); 0: 32 for a context that renders one
                                     // frame at a time (a 64-spp frame's two groups overlap each other on two queues), 64 with frames in
                                     // flight (larger pools sort into tighter packets; the overlap comes from the other frame): measured
@@ -244,6 +246,7 @@ struct rwr_context {
     uint64_t accum_max = 1u << 24;         // samples per pixel at most (f32 holds the divisor exactly); RWR_ACCUM_MAX_SAMPLES lowers it
     uint64_t last_accum_samples = 0;       // rwr_accum_samples: of the frame rendered last, 0 when it did not accumulate
     rwr_denoise_params denoise = rwr::kDenoiseDefaults;   // RWR_FLAG_DENOISE (rwr_denoise_set_params)
+    rwr_sky_params sky = rwr::kSkyDefaults;               // RWR_FLAG_SKY (rwr_sky_set_params)
     uint64_t scene_generation = 0;         // bumped by every change of the scene (an accumulation does not survive one)
     // one decoded texture per scene part (texels decoded to linear f32 at upload, Rgba8UnormSrgb semantics)
     std::vector<rwr::DeviceBuffer<float4>> d_texs;

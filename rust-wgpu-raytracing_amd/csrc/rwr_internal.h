@@ -316,6 +316,13 @@ struct WfShadow {
     unsigned long long *masks;
     unsigned long long *counts;
 };
+// Sky light (RWR_FLAG_SKY; the SKY forms of the trace kernels, kernels_wf_bounce.hip): the context's rwr_sky_params.  A kernel
+// argument of its own behind the others (cf. WfEmit), so that the six floats are scalar registers and the kernels without the
+// flag keep their code.
+struct WfSky {
+    float zr, zg, zb, hr, hg, hb;   // zenith, horizon: rwr_sky_params' six floats in its order (plain members, no arrays: they stay registers)
+};
+static_assert(sizeof(WfSky) == sizeof(rwr_sky_params), "WfSky is rwr_sky_params");
 struct BvhNode4;
 struct BvhDevice {
     const BvhNode4 *nodes;
@@ -360,11 +367,11 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
 hipError_t launch_wf_classify(hipStream_t s, const FrameParams &fp, const FrameTri *ftris, const Targets &tg, uint32_t tiles_x,
                               uint32_t *live_list, uint32_t *live_count, uint32_t *tile_live);
 // emit: one generation of a deeper path that is not its last — the trace kernels' EMIT forms write every hit's next ray back
-// into its slot; null: the kernels that end the path
+// into its slot; null: the kernels that end the path.  sky: RWR_FLAG_SKY — the SKY forms, a ray that hits nothing adds the sky's term
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf,
                             uint32_t n_tiles, uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list,
-                            const WfEmit *emit = nullptr, const WfShadow *shadow = nullptr);
+                            const WfEmit *emit = nullptr, const WfShadow *shadow = nullptr, const WfSky *sky = nullptr);
 // RWR_FLAG_SHADOWS: traces the shadow records the kernels of one stage left in the queue (the primary stage's, or one generation's
 // trace kernels') and adds the light's part of every term whose ray got through.  light_mesh / light_sphere: the unit directions
 // towards the reference's two lights; expected_tiles: how many tiles are expected to hold records (sizes the work items only).
@@ -372,6 +379,8 @@ hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecor
                             const WfShadow &shadow, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count, const float light_mesh[3],
                             const float light_sphere[3]);
 size_t wf_pool_info_bytes();
+// RWR_WF_STATS=1: trace launches of this process so far {packet kernel, per-lane kernel, its 1 024-thread form}
+void wf_trace_launch_counts(uint64_t out[3]);
 hipError_t launch_primary_bvh(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                               const BvhDevice &bvh, const float4 *tex, const Targets &tg);
 // live_counters / host_live: the last launch group's counters (kernels_wf_bounce.hip) and the pinned words the host reads them from

@@ -4,7 +4,8 @@
 //
 //   rwr_render --res DIR [--scene suzanne_lowpoly.obj] [--size 600x600] [--keys "S*15,D*4"]
 //              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows]
-//              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--out frame.png] [--time]
+//              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]]
+//              [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
 // (KEY in W A S D Up Down Left Right Space LShift, or '-' for no key).  After the script,
@@ -47,6 +48,18 @@ int main(int argc, char **argv)
     bool timing = false, accumulate = false, shadows = false, denoise = false;
     int denoise_iterations = 0;      // 0: the library's default
     float denoise_sigma = 0.0f;      // 0: the library's default
+    bool sky = false, sky_zenith_set = false, sky_horizon_set = false, show_params = false;
+    rwr_sky_params sky_params = RWR_SKY_DEFAULTS;   // the library's defaults
+    // "r,g,b": three numbers and nothing else, each finite and in [0, 16] (rwr_sky_set_params' range)
+    auto parse_colour = [](const char *text, float out[3]) {
+        float v[3];
+        char tail = 0;
+        if (std::sscanf(text, "%f,%f,%f%c", &v[0], &v[1], &v[2], &tail) != 3) return false;
+        for (int c = 0; c < 3; c++)
+            if (!(v[c] >= 0.0f && v[c] <= RWR_SKY_COMPONENT_MAX)) return false;
+        for (int c = 0; c < 3; c++) out[c] = v[c];
+        return true;
+    };
     struct Resize { uint64_t frame; uint32_t w, h; };
     std::vector<Resize> resizes;
     for (int i = 1; i < argc; i++) {
@@ -68,6 +81,17 @@ int main(int argc, char **argv)
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-iterations") { denoise = true; denoise_iterations = std::atoi(next()); }
         else if (a == "--denoise-sigma") { denoise = true; denoise_sigma = (float)std::atof(next()); }
+        else if (a == "--sky") sky = true;
+        else if (a == "--sky-zenith" || a == "--sky-horizon") {
+            const bool zenith = a == "--sky-zenith";
+            if (!parse_colour(next(), zenith ? sky_params.zenith : sky_params.horizon)) {
+                std::fprintf(stderr, "%s r,g,b: three numbers in [0, 16]\n", a.c_str());
+                return 2;
+            }
+            sky = true;
+            (zenith ? sky_zenith_set : sky_horizon_set) = true;
+        }
+        else if (a == "--show-params") show_params = true;
         else if (a == "--resize") {
             Resize r{0, 0, 0};
             unsigned long long f = 0;
@@ -80,18 +104,31 @@ int main(int argc, char **argv)
         } else if (a == "--help" || a == "-h") {
             std::printf("usage: rwr_render --res DIR [--scene F.obj] [--size WxH] [--keys \"S*15,D*4\"] [--frames N] "
                         "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] "
-                        "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--out frame.png] [--time]\n"
+                        "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
+                        "[--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
                         "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n"
                         "  --shadows     every hit casts a shadow ray towards its light (RWR_FLAG_SHADOWS); works with --spp, --bounces "
                         "and --accumulate\n"
                         "  --denoise     the edge-avoiding a-trous filter over every frame (RWR_FLAG_DENOISE): N iterations (1-5), colour "
-                        "sigma S (rwr_denoise_set_params)\n");
+                        "sigma S (rwr_denoise_set_params)\n"
+                        "  --sky         bounce rays that leave the scene return the sky's radiance (RWR_FLAG_SKY; needs --bounces >= 1): a "
+                        "gradient from --sky-horizon (straight down) to --sky-zenith (straight up), components in [0, 16] "
+                        "(rwr_sky_set_params); either colour implies --sky\n"
+                        "  --show-params prints the render parameters the arguments give and exits, without a device\n");
             return 0;
         } else {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
             return 2;
         }
+    }
+    const uint32_t flags = (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u) |   // more than one bounce: the deeper paths
+                           (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u) | (denoise ? (uint32_t)RWR_FLAG_DENOISE : 0u) | (sky ? (uint32_t)RWR_FLAG_SKY : 0u);
+    if (show_params) {
+        std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g\n", spp, bounces, flags, sky ? 1 : 0,
+                    (double)sky_params.zenith[0], (double)sky_params.zenith[1], (double)sky_params.zenith[2],
+                    (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2]);
+        return 0;
     }
     if (res.empty()) { std::fprintf(stderr, "--res DIR is required (the reference bakes OUT_DIR/res in at compile time)\n"); return 2; }
 
@@ -112,9 +149,10 @@ int main(int argc, char **argv)
 
     try {
         State state(w, h, res, scene);
-        // more than one bounce: the deeper paths of RWR_FLAG_MULTI_BOUNCE
-        const rwr_render_params params{spp, bounces, 0u, (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u) |
-                                       (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u) | (denoise ? (uint32_t)RWR_FLAG_DENOISE : 0u)};
+        const rwr_render_params params{spp, bounces, 0u, flags};
+        if (sky_zenith_set || sky_horizon_set) {
+            if (rwr_sky_set_params(state.context(), &sky_params) != RWR_OK) { std::fprintf(stderr, "--sky: %s\n", rwr_last_error_string()); return 2; }
+        }
         if (denoise_iterations != 0 || denoise_sigma != 0.0f) {
             rwr_denoise_params dp;
             int rc = rwr_denoise_get_params(state.context(), &dp);
