@@ -233,7 +233,7 @@ enum {
                                           covers the whole frame (the filter reaches 62 pixels; a rank does not hold its neighbours'
                                           rows).  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED. */
-    RWR_FLAG_SKY = 1u << 9          /* extension: sky light — a bounce ray that leaves the scene returns the radiance of a sky gradient
+    RWR_FLAG_SKY = 1u << 9,         /* extension: sky light — a bounce ray that leaves the scene returns the radiance of a sky gradient
                                        (rwr_sky_set_params) instead of nothing.  Without the flag every frame is what it was, byte for
                                        byte, with no further launch or allocation.  With it:
                                        1. S(D), per channel c in f32 with no contraction: u = fminf(fmaxf(0.5f * D.y + 0.5f, 0.0f), 1.0f),
@@ -258,6 +258,41 @@ enum {
                                        7. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED.  The
                                           refusal comes first: it holds at max_bounces = 0 too, where item 4 would otherwise ignore the
                                           flag — a combination that is refused does not start to work when the bounces go to 0. */
+    RWR_FLAG_MIRRORS = 1u << 10     /* extension: mirror surfaces — a scene part or a sphere marked as a mirror (rwr_scene_set_part_mirror,
+                                       rwr_scene_set_sphere_mirror) sends the reflection of the ray that found it onwards instead of a
+                                       cosine-distributed ray.  Without the flag every frame is what it was, byte for byte, with no further
+                                       launch or allocation.  With it:
+                                       1. Let h be a hit a path goes on from (h0, or bounce hit h_k with k < max_bounces) on a mirror
+                                          surface of reflectance R, D the direction of the ray that found it, n the reference's HitRecord
+                                          normal (the face normal flipped towards the ray, or the sphere's outward normal; normal maps
+                                          never change it).  The next ray starts where it always does, P + 1e-4 n, operation for
+                                          operation the diffuse ray's and the shadow ray's origin.  Its direction, in f32 with no
+                                          contraction: d = n.x D.x + n.y D.y + n.z D.z, D' = D - (2 d) n per component — not
+                                          re-normalised (the hit tests take a direction of any length).
+                                       2. Throughput: T(k) = T(k-1) * R in place of T(k-1) * albedo(h); T(0) = R at a mirror h0.
+                                       3. The local term of h is unchanged: E(h) (with RWR_FLAG_SHADOWS the shadowed E(h)) is added as
+                                          ever, only what the surface sends onwards becomes specular — a coated surface.  For a pure
+                                          mirror give the part Ka = Ks = 0 and a black texture.  Primary-stage sums, sample-0 planes
+                                          (depth, obj_id, hit_t), h0's shadow records and their part of rwr_last_shadow_stats therefore
+                                          do not depend on the flag.
+                                       4. No random number is read at a mirror hit; that generation's 16 RNG dimensions are skipped, not
+                                          reused: a later diffuse hit h_j of the path still reads dimensions 2 + 16 (j - 1) ... 17 + 16 (j - 1).
+                                       5. The nearest-hit rule, the clamps (term k to [0, 64], NaN as 0) and RWR_FLAG_SKY's term at a
+                                          miss, T * S(D') — a mirror shows the sky — are untouched.  The first generation has as many
+                                          rays as the frame without the flag; later ones differ, because paths go elsewhere.  R <= 1:
+                                          the integrator's range analysis stands.
+                                       6. max_bounces = 0, or no part of the scene and none of its spheres (indices below the count
+                                          rwr_scene_set_spheres gave) is a mirror: the flag is ignored — cleared before the frame's kernels
+                                          are chosen — and the frame is the frame without it, byte for byte, in the same kernels.
+                                       7. RWR_FLAG_ACCUMULATE: this bit (after item 6) is part of the key, and every call of the two
+                                          setters that is accepted changes the scene (as rwr_scene_set_spheres does): setting or
+                                          clearing a mirror or changing R by one ulp starts over at N = 0 — with or without the flag,
+                                          whether or not the value is new.  A refused call changes nothing: the accumulation goes on.
+                                       8. RWR_FLAG_MULTI_BOUNCE, RWR_FLAG_SHADOWS, RWR_FLAG_SKY, RWR_FLAG_NORMAL_MAP, RWR_FLAG_AUX_OUTPUTS,
+                                          RWR_FLAG_NO_CULL, RWR_FLAG_DENOISE, instances, parts, frames in flight, row bands, strips and the
+                                          multi-GPU gather keep their contracts.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or
+                                          single-triangle passes: RWR_ERR_UNSUPPORTED, whatever max_bounces is and whether or not a
+                                          mirror is set (the refusal comes first, as RWR_FLAG_SKY's). */
 };
 
 #define RWR_MAX_BOUNCES 8u
@@ -333,6 +368,17 @@ RWR_API int rwr_scene_commit(rwr_context *ctx);
 RWR_API int rwr_scene_set_normal_map(rwr_context *ctx, uint32_t part, const uint8_t *rgba8_linear, uint32_t tex_w, uint32_t tex_h);
 /* Parts (meshes with faces) added to the scene so far. */
 RWR_API int rwr_scene_part_count(rwr_context *ctx, uint32_t *n_parts);
+
+/* RWR_FLAG_MIRRORS: the mirror attribute of a scene part (part < rwr_scene_part_count) or of a sphere index (sphere <
+ * RWR_MAX_SPHERES; kept per index, whatever rwr_scene_set_spheres holds or sets later).  reflectance: 3 floats, each finite and
+ * in [0, 1]; NULL = not a mirror (the default).  Anything else, NaN included: RWR_ERR_INVALID_ARGUMENT and the old state stays.
+ * Host-side, waits for nothing; frames rendered after the call see the new state.  rwr_scene_clear and with it every
+ * rwr_scene_upload_* reset the part attributes (a new upload is a new scene); the sphere attributes persist.  The getters
+ * return *is_mirror = 0 / 1 and, for a mirror, its reflectance (zeros otherwise); either output may be NULL. */
+RWR_API int rwr_scene_set_part_mirror(rwr_context *ctx, uint32_t part, const float *reflectance);
+RWR_API int rwr_scene_set_sphere_mirror(rwr_context *ctx, uint32_t sphere, const float *reflectance);
+RWR_API int rwr_scene_get_part_mirror(rwr_context *ctx, uint32_t part, int *is_mirror, float reflectance[3]);
+RWR_API int rwr_scene_get_sphere_mirror(rwr_context *ctx, uint32_t sphere, int *is_mirror, float reflectance[3]);
 
 /* Replaces Sphere::new's uniform, one per analytic sphere pass, composited in
  * array order before the mesh (src/lib.rs:532-534, 1106-1173).  n <= RWR_MAX_SPHERES. */

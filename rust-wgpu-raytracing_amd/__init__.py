@@ -50,6 +50,7 @@ FLAG_DENOISE = 1 << 8        # the a-trous filter behind the integrator's resolv
 DENOISE_PARAMS_DTYPE = np.dtype([("iterations", "<u4"), ("sigma_color", "<f4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
 FLAG_SKY = 1 << 9            # bounce rays that leave the scene return the sky's radiance (include/rwr_hip.h)
 SKY_PARAMS_DTYPE = np.dtype([("zenith", "<f4", 3), ("horizon", "<f4", 3)])
+FLAG_MIRRORS = 1 << 10       # parts and spheres marked as mirrors reflect the ray that found them (include/rwr_hip.h)
 MAX_BOUNCES = 8
 FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
 KEY_FORWARD, KEY_BACKWARD, KEY_LEFT, KEY_RIGHT, KEY_UP, KEY_DOWN = 1, 2, 4, 8, 16, 32
@@ -116,6 +117,8 @@ def lib() -> C.CDLL:
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
         "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
+        "rwr_scene_set_part_mirror": [vp, u32, vp], "rwr_scene_set_sphere_mirror": [vp, u32, vp],
+        "rwr_scene_get_part_mirror": [vp, u32, vp, vp], "rwr_scene_get_sphere_mirror": [vp, u32, vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
         "rwr_load_model_compute": [C.c_char_p, C.c_char_p, vp], "rwr_model_free": [vp],
         "rwr_model_info": [vp, vp, vp, vp, vp, vp, vp], "rwr_scene_upload_model": [vp, vp],
@@ -133,7 +136,8 @@ def lib() -> C.CDLL:
         "rwr_measure_valu_clock": [vp, u32, vp], "rwr_clock_probe_start": [vp, u32], "rwr_clock_probe_read": [vp, vp],
     }
     _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats",
-                           "rwr_sky_set_params", "rwr_sky_get_params")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_sky_set_params", "rwr_sky_get_params", "rwr_scene_set_part_mirror", "rwr_scene_set_sphere_mirror",
+                           "rwr_scene_get_part_mirror", "rwr_scene_get_sphere_mirror")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -427,6 +431,40 @@ class Context:
     def set_spheres(self, spheres):
         spheres = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
         _check(lib().rwr_scene_set_spheres(self._h, _p(spheres) if len(spheres) else None, len(spheres)))
+
+    @staticmethod
+    def _reflectance(reflectance):
+        if reflectance is None:
+            return None
+        r = np.ascontiguousarray(reflectance, dtype=np.float32)
+        if r.shape != (3,):
+            raise ValueError("reflectance: three floats, or None")
+        return r
+
+    def set_part_mirror(self, part: int, reflectance=(1.0, 1.0, 1.0)):
+        """FLAG_MIRRORS: scene part `part` is a mirror of this reflectance (three floats in [0, 1]); None: not a mirror.  Out of
+        range or NaN: RwrError(ERR_INVALID_ARGUMENT), and the old state stays (rwr_scene_set_part_mirror)."""
+        r = self._reflectance(reflectance)
+        _check(lib().rwr_scene_set_part_mirror(self._h, part, _p(r)))
+
+    def set_sphere_mirror(self, sphere: int, reflectance=(1.0, 1.0, 1.0)):
+        """FLAG_MIRRORS: the sphere of index `sphere` (< 8, kept whatever set_spheres holds) is a mirror; None: not a mirror."""
+        r = self._reflectance(reflectance)
+        _check(lib().rwr_scene_set_sphere_mirror(self._h, sphere, _p(r)))
+
+    def _get_mirror(self, fn, index: int):
+        on = C.c_int(0)
+        r = np.zeros(3, np.float32)
+        _check(fn(self._h, index, C.byref(on), _p(r)))
+        return r if on.value else None
+
+    def get_part_mirror(self, part: int):
+        """The part's reflectance (float32[3]) when it is a mirror, else None (rwr_scene_get_part_mirror)."""
+        return self._get_mirror(lib().rwr_scene_get_part_mirror, part)
+
+    def get_sphere_mirror(self, sphere: int):
+        """The sphere index's reflectance (float32[3]) when it is a mirror, else None (rwr_scene_get_sphere_mirror)."""
+        return self._get_mirror(lib().rwr_scene_get_sphere_mirror, sphere)
 
     def set_triangles(self, triangles):
         """Single-triangle passes (the reference's dormant models/triangle), after the spheres."""

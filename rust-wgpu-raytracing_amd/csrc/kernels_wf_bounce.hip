@@ -269,21 +269,48 @@ k_wf_sort(const WfBuffers wf, PoolInfo *__restrict__ info, uint32_t *__restrict_
 // towards the ray or the sphere's outward normal, as the first stage builds the first bounce ray), in the cosine-distributed
 // direction of RNG dimensions em.next_dim ... keyed by the slot's global pixel and sample, throughput thr — goes back into slot
 // e of the tile's pool; the slot's bit is set in the next generation's ballots.
+// MIRROR forms (RWR_FLAG_MIRRORS), a hit on a mirror surface (`mirror`): the direction is the reflection of D about n instead
+// (reflect_direction: no random number is read, the generation's RNG dimensions are left unused), thr is T * R.
+template <bool MIRROR = false>
 RWR_DEV void emit_next_ray(const FrameParams &p, const WfBuffers &wf, const WfEmit &em, const TriRecord *__restrict__ tris, uint32_t tile,
-                           uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr)
+                           uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr, bool mirror = false)
 {
     f3 n;
     const f3 O1 = hit_exit_point(p, tris, O, D, obj, t, ndotd, n);
-    // the slot's pixel (as add_contribution maps it) and sample
-    const uint32_t r = e & (kWfTilePixels - 1u), w = r >> 7, k = (r >> 6) & 1u, l = r & 63u;
-    const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (w & 1u) * 32u + 2u * (l & 15u) + k;
-    const uint32_t py = p.row_begin + (tile / wf.tiles_x) * p.row_pitch + (w >> 1) * 4u + (l >> 4);
-    const f3 D1 = bounce_direction(n, py * p.width + px, em.sample_base + e / kWfTilePixels, p.seed, em.next_dim);
+    f3 D1;
+    if (MIRROR && mirror) {
+        D1 = reflect_direction(n, D);
+    } else {
+        // the slot's pixel (as add_contribution maps it) and sample
+        const uint32_t r = e & (kWfTilePixels - 1u), w = r >> 7, k = (r >> 6) & 1u, l = r & 63u;
+        const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (w & 1u) * 32u + 2u * (l & 15u) + k;
+        const uint32_t py = p.row_begin + (tile / wf.tiles_x) * p.row_pitch + (w >> 1) * 4u + (l >> 4);
+        D1 = bounce_direction(n, py * p.width + px, em.sample_base + e / kWfTilePixels, p.seed, em.next_dim);
+    }
     const size_t slot = (size_t)tile * wf.group * kWfTilePixels + e;
     wf.rays[2u * slot] = make_float4(O1.x, O1.y, O1.z, wf_pack_unorm16x2(thr.x, thr.y));
     wf.rays[2u * slot + 1u] = make_float4(D1.x, D1.y, D1.z, wf_pack_unorm16x2(thr.z, 0.0f));
     wf.bins[slot] = (uint16_t)wf_direction_bin(D1);
     atomicOr(&em.masks_out[(size_t)tile * wf.group * 8u + (e >> 6)], 1ull << (e & 63u));
+}
+
+// MIRROR forms: the surface record {r, g, b, on} of the hit `obj` (rwr_internal.h WfMirror).  Part 0's record is read at a constant
+// index through the constant address space: a wave-uniform address, one scalar load into scalar registers, and all a face of a
+// one-part scene needs (it never looks at ShadeRec::material).  Only a sphere hit (by its index) and a face of a scene with
+// several parts (by ShadeRec::material) read their record per lane, under a branch of their own, so that the two reads stay two.
+RWR_DEV float4 mirror_record(const FrameParams &p, const WfMirror &mir, const ShadeRec *__restrict__ shade, int32_t obj)
+{
+    const const_ptr<float> tab = to_const_space(reinterpret_cast<const float *>(mir.table));
+    // part 0; the empty asm pins the four values to scalar registers where they are read, or the compiler folds this read into the
+    // per-lane one below (one vector load at a selected index)
+    float r0 = tab[0], r1 = tab[1], r2 = tab[2], r3 = tab[3];
+    asm volatile("" : "+s"(r0), "+s"(r1), "+s"(r2), "+s"(r3));
+    float4 m = make_float4(r0, r1, r2, r3);
+    if (obj < 0 || p.n_materials > 1u) {
+        const uint32_t i = obj < 0 ? mir.n_parts + (uint32_t)(-2 - obj) : shade[obj].material;
+        m = make_float4(tab[4u * i], tab[4u * i + 1u], tab[4u * i + 2u], tab[4u * i + 3u]);
+    }
+    return m;
 }
 
 // SHADOW forms: the term T * E(h) of the hit (obj, t) of the ray in slot e is a select between clamp(T * ambient part) and
@@ -364,13 +391,17 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // SHADOW: RWR_FLAG_SHADOWS — a hit adds its term's ambient part and leaves a shadow record (shadow_hit); separate instantiations,
 // so that frames without the flag keep their kernels.
 // SKY: RWR_FLAG_SKY — a ray that hits nothing adds the sky's term (add_sky); separate instantiations for the same reason.
-template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false, bool SKY = false>
+// MIRROR: RWR_FLAG_MIRRORS — of the EMIT forms alone: a hit on a mirror surface sends the reflected ray on, with T * R
+// (emit_next_ray); separate instantiations for the same reason.
+template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false, bool SKY = false,
+          bool MIRROR = false>
 __global__ void __launch_bounds__(WIDE ? 1024 : 256)
 k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                 const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                 uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
-                const WfSky sky)
+                const WfSky sky, const WfMirror mir)
 {
+    static_assert(EMIT || !MIRROR, "only a kernel that emits rays has a MIRROR form");
     __shared__ TraceShared sh;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
     const uint32_t tid = threadIdx.x;
@@ -435,9 +466,15 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                 const f3 e1 = s1.colour;
                 if (SHADOW) shadow_hit(sh, p, wf, sw, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, e1);
                 else add_contribution(sh, e, thr.x * e1.x, thr.y * e1.y, thr.z * e1.z);
-                if (EMIT)
+                if (EMIT && !MIRROR)
                     emit_next_ray(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd,
                                   mk3(thr.x * s1.albedo.x, thr.y * s1.albedo.y, thr.z * s1.albedo.z));
+                if (EMIT && MIRROR) {
+                    const float4 m = mirror_record(p, mir, shade, obj);
+                    const bool mirror = m.w != 0.0f;
+                    const f3 next = mirror ? mk3(m.x, m.y, m.z) : s1.albedo;
+                    emit_next_ray<true>(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd, mk3(thr.x * next.x, thr.y * next.y, thr.z * next.z), mirror);
+                }
             } else if (SKY) {
                 add_sky(sh, sky, e, D.y, thr);
             }
@@ -530,13 +567,14 @@ RWR_DEV i2 sphere_pair_intersect_t(f3 center, float radius, v3 O, v3 D, f2 &t_ou
 #ifndef RWR_PACKET_OCC
 #define RWR_PACKET_OCC 4
 #endif
-template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false>   // EMIT, SHADOW, SKY: see k_wf_trace_lane
+template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false, bool MIRROR = false>   // EMIT, SHADOW, SKY, MIRROR: see k_wf_trace_lane
 __global__ void __launch_bounds__(256, RWR_PACKET_OCC)
 k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                   uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
-                  const WfSky sky)
+                  const WfSky sky, const WfMirror mir)
 {
+    static_assert(EMIT || !MIRROR, "only a kernel that emits rays has a MIRROR form");
     __shared__ TraceShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const const_ptr<BvhNode4> nodes = to_const_space(bvh.nodes);
@@ -740,13 +778,28 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
             if (have.x) add_contribution(sh, e0, cr.x, cg.x, cb.x);
             if (have.y) add_contribution(sh, e1, cr.y, cg.y, cb.y);
             }
-            if (EMIT) {   // every hit's next ray, one ray of the lane after the other
+            if (EMIT && !MIRROR) {   // every hit's next ray, one ray of the lane after the other
                 const f2 nr = thr.x * ar, ng = thr.y * ag, nb = thr.z * ab;
 #pragma unroll
                 for (int k = 0; k < 2; k++)
                     if (k ? have.y : have.x)
                         emit_next_ray(p, wf, em, tris, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), k ? obj.y : obj.x, k ? best_t.y : best_t.x,
                                       k ? best.ndotd.y : best.ndotd.x, k ? mk3(nr.y, ng.y, nb.y) : mk3(nr.x, ng.x, nb.x));
+            }
+            if (EMIT && MIRROR) {   // the same, but a hit on a mirror sends T * R on, not T * albedo, in the reflected direction
+#pragma unroll
+                for (int k = 0; k < 2; k++)
+                    if (k ? have.y : have.x) {
+                        const int32_t o = k ? obj.y : obj.x;
+                        const float4 m = mirror_record(p, mir, shade, o);
+                        const bool mirror = m.w != 0.0f;
+                        const f3 next = mirror ? mk3(m.x, m.y, m.z) : (k ? mk3(ar.y, ag.y, ab.y) : mk3(ar.x, ag.x, ab.x));
+                        const f3 t = k ? mk3(thr.x.y, thr.y.y, thr.z.y) : mk3(thr.x.x, thr.y.x, thr.z.x);
+                        emit_next_ray<true>(p, wf, em, tris, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), o, k ? best_t.y : best_t.x,
+                                            k ? best.ndotd.y : best.ndotd.x, mk3(t.x * next.x, t.y * next.y, t.z * next.z), mirror);
+                    }
+            }
+            if (EMIT) {
                 const uint32_t n_emit = (uint32_t)__popcll(__ballot(have.x != 0)) + (uint32_t)__popcll(__ballot(have.y != 0));
                 if (lane == 0u) atomicAdd(&wf.wave_total[tile * 4u], n_emit);
             }
@@ -767,13 +820,15 @@ static std::atomic<uint64_t> g_trace_launches[3];
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf, uint32_t n_tiles,
                             uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list, const WfEmit *emit,
-                            const WfShadow *shadow, const WfSky *sky)
+                            const WfShadow *shadow, const WfSky *sky, const WfMirror *mirror)
 {
     const WfEmit em = emit ? *emit : WfEmit{nullptr, 0u, 0u};
     const WfShadow sw = shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr};
     const bool shadows = sw.recs != nullptr;
     const WfSky sk = sky ? *sky : WfSky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     const bool sky_on = sky != nullptr;
+    const WfMirror mr = mirror ? *mirror : WfMirror{nullptr, 0u, 0u};
+    const bool mirror_on = mirror != nullptr && emit != nullptr;   // (the kernels that end a path emit nothing: no MIRROR form)
     if (n_tiles == 0 || sample_count == 0) return hipSuccess;
     uint32_t *counters = wf.counters;   // this queue's set, zeroed by the primary stage that filled the queue
     PoolInfo *info = static_cast<PoolInfo *>(pool_info);
@@ -803,7 +858,8 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     const dim3 grid(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit));
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
     if (wf.dbg && packets) g_trace_launches[0].fetch_add(1u, std::memory_order_relaxed);
-#define RWR_PACKET_LAUNCH_K(N, E, S, K) hipLaunchKernelGGL((k_wf_trace_packet<N, E, S, K>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk)
+#define RWR_PACKET_LAUNCH_M(N, E, S, K, M) hipLaunchKernelGGL((k_wf_trace_packet<N, E, S, K, M>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk, mr)
+#define RWR_PACKET_LAUNCH_K(N, E, S, K) do { if (E && mirror_on) RWR_PACKET_LAUNCH_M(N, E, S, K, E); else RWR_PACKET_LAUNCH_M(N, E, S, K, false); } while (0)
 #define RWR_PACKET_LAUNCH(N, E, S) do { if (sky_on) RWR_PACKET_LAUNCH_K(N, E, S, true); else RWR_PACKET_LAUNCH_K(N, E, S, false); } while (0)
     if (packets && shadows) {
         if (emit) { if (nmap) RWR_PACKET_LAUNCH(true, true, true); else RWR_PACKET_LAUNCH(false, true, true); }
@@ -815,11 +871,13 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     }
 #undef RWR_PACKET_LAUNCH
 #undef RWR_PACKET_LAUNCH_K
+#undef RWR_PACKET_LAUNCH_M
     const bool stack16 = bvh.n_nodes <= 0x7fffu && fp.n_tris <= 4095u;   // node indices and leaf links (first << 3 | count - 1) in 15 bits
     const size_t fixed = (size_t)bvh.stack_depth * 256u * (stack16 ? 2u : 4u);
     const size_t node_bytes = (size_t)bvh.n_nodes * sizeof(BvhNode4);
     // nodelets go to LDS when the workgroup then still fits a CU at least four times (160 KiB LDS, 12 KiB static)
-#define RWR_LANE_LAUNCH_K(L, N, S16, E, S, K, BYTES) hipLaunchKernelGGL((k_wf_trace_lane<L, N, S16, false, E, S, K>), grid, dim3(256), BYTES, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk)
+#define RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, M, BYTES) hipLaunchKernelGGL((k_wf_trace_lane<L, N, S16, false, E, S, K, M>), grid, dim3(256), BYTES, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk, mr)
+#define RWR_LANE_LAUNCH_K(L, N, S16, E, S, K, BYTES) do { if (E && mirror_on) RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, E, BYTES); else RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, false, BYTES); } while (0)
 #define RWR_LANE_LAUNCH(L, N, S16, E, S, BYTES) do { if (sky_on) RWR_LANE_LAUNCH_K(L, N, S16, E, S, true, BYTES); else RWR_LANE_LAUNCH_K(L, N, S16, E, S, false, BYTES); } while (0)
 #define RWR_LANE_LAUNCH0(L, E, S, BYTES) \
     if (nmap) { if (stack16) RWR_LANE_LAUNCH(L, true, true, E, S, BYTES); else RWR_LANE_LAUNCH(L, true, false, E, S, BYTES); } \
@@ -832,15 +890,16 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     if (node_bytes + fixed <= 28u * 1024u) { RWR_LANE_LAUNCH2(true, node_bytes + fixed) }
     else if (wide) {
         // a BVH too large for a copy per 256-thread workgroup, small enough for one copy per CU: 1 024-thread workgroups
-        // per form: [emit + 2 * shadows + 4 * sky]
-#define RWR_WIDE_FORMS(X) X(0, false, false, false) X(1, true, false, false) X(2, false, true, false) X(3, true, true, false) \
-                          X(4, false, false, true) X(5, true, false, true) X(6, false, true, true) X(7, true, true, true)
-        static std::atomic<uint64_t> wide_raised_on[8];
-        const uint32_t form = (emit ? 1u : 0u) + (shadows ? 2u : 0u) + (sky_on ? 4u : 0u);
+        // per form: [emit + 2 * shadows + 4 * sky], and the EMIT forms again with MIRROR: [8 + (shadows + 2 * sky)]
+#define RWR_WIDE_FORMS(X) X(0, false, false, false, false) X(1, true, false, false, false) X(2, false, true, false, false) X(3, true, true, false, false) \
+                          X(4, false, false, true, false) X(5, true, false, true, false) X(6, false, true, true, false) X(7, true, true, true, false) \
+                          X(8, true, false, false, true) X(9, true, true, false, true) X(10, true, false, true, true) X(11, true, true, true, true)
+        static std::atomic<uint64_t> wide_raised_on[12];
+        const uint32_t form = mirror_on ? 8u + (shadows ? 1u : 0u) + (sky_on ? 2u : 0u) : (emit ? 1u : 0u) + (shadows ? 2u : 0u) + (sky_on ? 4u : 0u);
         std::atomic<uint64_t> &raised = wide_raised_on[form];
         const void *kernel = nullptr;
         switch (form) {
-#define RWR_WIDE_KERNEL(F, E, S, K) case F: kernel = reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, E, S, K>); break;
+#define RWR_WIDE_KERNEL(F, E, S, K, M) case F: kernel = reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, E, S, K, M>); break;
         RWR_WIDE_FORMS(RWR_WIDE_KERNEL)
 #undef RWR_WIDE_KERNEL
         }
@@ -854,8 +913,8 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
             raised.fetch_or(bit, std::memory_order_release);
         }
         switch (form) {
-#define RWR_WIDE_LAUNCH(F, E, S, K) case F: hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true, E, S, K>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, \
-                                                               fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk); break;
+#define RWR_WIDE_LAUNCH(F, E, S, K, M) case F: hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true, E, S, K, M>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, \
+                                                                  fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk, mr); break;
         RWR_WIDE_FORMS(RWR_WIDE_LAUNCH)
 #undef RWR_WIDE_LAUNCH
         }
@@ -867,6 +926,7 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
 #undef RWR_LANE_LAUNCH0
 #undef RWR_LANE_LAUNCH
 #undef RWR_LANE_LAUNCH_K
+#undef RWR_LANE_LAUNCH_M
     return hipGetLastError();
 }
 

@@ -146,7 +146,8 @@ struct WfPrimaryArgs {
     const float4 *tex;
     Targets tg;
     WfBuffers wf;
-    WfShadow sw;   // RWR_FLAG_SHADOWS (the SHADOW forms); last, so that the other forms read their arguments where they always did
+    WfShadow sw;   // RWR_FLAG_SHADOWS (the SHADOW forms); behind the rest, so that the other forms read their arguments where they always did
+    WfMirror mr;   // RWR_FLAG_MIRRORS (the MIRROR forms); last, for the same reason
 };
 template <typename T> using kernarg = const __attribute__((address_space(4))) T;
 RWR_DEV kernarg<WfPrimaryArgs> *wf_args_again(kernarg<WfPrimaryArgs> *q)
@@ -159,9 +160,14 @@ RWR_DEV f3 ld3(kernarg<float> *q) { return mk3(q[0], q[1], q[2]); }
 // SHADOW (RWR_FLAG_SHADOWS): a hit adds the AMBIENT part of E(h0) to the group's sums and leaves a shadow record — the bounce
 // ray's origin, the light of the shader that shaded it, fix(E) - fix(ambient) — at its queue slot, with its bit in the shadow
 // ballots, for k_wf_shadow (kernels_wf_shadow.hip).  Forms of their own: the others keep their registers.
-template <bool AUX, bool CULL, bool NMAP, bool LIST = false, bool SHADOW = false>
+// MIRROR (RWR_FLAG_MIRRORS): a hit on a mirror surface (WfMirror's table: per part, per sphere) emits the reflection of its ray
+// with throughput R instead of the cosine-distributed ray with the albedo, decided per pixel of the lane's pair.  A tile without
+// a mirror hit skips the reflection, a tile whose emitting pixels are all mirror hits skips the RNG and the disk-to-hemisphere
+// arithmetic (wave-uniform branches on ballots), a mixed tile computes both and selects.  Forms of their own again.
+template <bool AUX, bool CULL, bool NMAP, bool LIST = false, bool SHADOW = false, bool MIRROR = false>
 // (LIST — frames that show little — keeps an item loop's state on top of everything else and needs 142 registers: three waves
-// per SIMD like the AUX / NMAP forms; such a frame does not fill the chip anyway)
+// per SIMD like the AUX / NMAP forms; such a frame does not fill the chip anyway.  MIRROR does not loosen the bound: the plain
+// mirror forms hold RWR_WF_OCC waves like their twins, profiles/mirror_kernel_resources.txt)
 __global__ void __launch_bounds__(256, (AUX || NMAP || LIST || SHADOW) ? 3 : RWR_WF_OCC)
 k_wf_primary(const WfPrimaryArgs a)
 {
@@ -451,7 +457,45 @@ k_wf_primary(const WfPrimaryArgs a)
                     }
                 }
                 if (bounces) {
-                const v3 D1 = bounce_direction_pair(n, base, emit);
+                v3 D1;
+                if (MIRROR) {
+                    // each pixel's surface record.  Part 0's is read at a constant index — a wave-uniform address, one scalar load
+                    // into scalar registers — and is all a face of a one-part scene needs (no look at ShadeRec::material); a sphere
+                    // (by its index) and a face of a scene with several parts read theirs per lane, under a branch of their own
+                    kernarg<WfPrimaryArgs> *const qv = wf_args_again(ka);
+                    const const_ptr<float> tab = to_const_space(reinterpret_cast<const float *>(qv->mr.table));
+                    const uint32_t n_parts = qv->mr.n_parts;
+                    const bool parts = qv->p.n_materials > 1u;
+                    const ShadeRec *const shade = qv->shade;
+                    float r0 = tab[0], r1 = tab[1], r2 = tab[2], r3 = tab[3];
+                    asm volatile("" : "+s"(r0), "+s"(r1), "+s"(r2), "+s"(r3));   // (pinned to scalar registers: not folded into the per-lane read)
+                    const float4 m0 = make_float4(r0, r1, r2, r3);
+                    i2 mir = i2{0, 0};
+#pragma unroll
+                    for (int k = 0; k < 2; k++) {
+                        const int o = k ? obj.y : obj.x;
+                        if (k ? emit.y : emit.x) {
+                            float4 m = m0;
+                            if (o < 0 || parts) {
+                                const uint32_t i = o < 0 ? n_parts + (uint32_t)(-2 - o) : shade[o].material;
+                                m = make_float4(tab[4u * i], tab[4u * i + 1u], tab[4u * i + 2u], tab[4u * i + 3u]);
+                            }
+                            if (m.w != 0.0f) {
+                                if (k) { tr.y = m.x; tgc.y = m.y; tb.y = m.z; mir.y = -1; } else { tr.x = m.x; tgc.x = m.y; tb.x = m.z; mir.x = -1; }
+                            }
+                        }
+                    }
+                    const i2 diffuse = emit & ~mir;
+                    v3 Dd = D, Dm = D;
+                    if (__any(any2(diffuse))) Dd = bounce_direction_pair(n, base, diffuse);
+                    if (__any(any2(mir))) {   // D' = D - (2 d) n, d = dot3(n, D) (rwr_device.h reflect_direction, for the pair)
+                        const f2 two_d = 2.0f * dot3(n, D);
+                        Dm = v3{D.x - two_d * n.x, D.y - two_d * n.y, D.z - two_d * n.z};
+                    }
+                    D1 = v3{mir ? Dm.x : Dd.x, mir ? Dm.y : Dd.y, mir ? Dm.z : Dd.z};
+                } else {
+                    D1 = bounce_direction_pair(n, base, emit);
+                }
                 kernarg<WfPrimaryArgs> *const qq = wf_args_again(ka);   // where the rays go
                 float4 *const rays = qq->wf.rays;
                 uint16_t *const bins = qq->wf.bins;
@@ -496,7 +540,7 @@ k_wf_primary(const WfPrimaryArgs a)
 
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg, const WfBuffers &wf,
-                             uint32_t sample_begin, uint32_t sample_count, uint32_t z_split, const WfShadow *shadow)
+                             uint32_t sample_begin, uint32_t sample_count, uint32_t z_split, const WfShadow *shadow, const WfMirror *mirror)
 {
     if (fp.row_end <= fp.row_begin || fp.width == 0 || sample_count == 0) return hipSuccess;
     z_split = std::max(1u, std::min(z_split, sample_count));
@@ -505,11 +549,14 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
     const bool aux = (fp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, do_cull = (fp.flags & RWR_FLAG_NO_CULL) == 0;
     const WfPrimaryArgs args{ftris, fp.n_tris, fp.row_begin, fp.bins.enabled, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3],
                              sample_begin, sample_count, z_split, fp, tris, shade, tex, tg, wf,
-                             shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr}};
+                             shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr}, mirror ? *mirror : WfMirror{nullptr, 0u, 0u}};
+    const bool mirror_on = mirror != nullptr && fp.bounces != 0u;   // (the MIRROR forms differ where rays are emitted, nowhere else)
 #define RWR_WF_ARGS args
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
-#define RWR_WF_LAUNCH(A, C, N) hipLaunchKernelGGL((k_wf_primary<A, C, N>), grid, block, 0, s, RWR_WF_ARGS)
-#define RWR_WF_LAUNCH_SHADOW(A, C, N, L, G) hipLaunchKernelGGL((k_wf_primary<A, C, N, L, true>), G, block, 0, s, RWR_WF_ARGS)
+#define RWR_WF_LAUNCH_M(A, C, N, L, S, G) do { if (mirror_on) hipLaunchKernelGGL((k_wf_primary<A, C, N, L, S, true>), G, block, 0, s, RWR_WF_ARGS); \
+                                               else hipLaunchKernelGGL((k_wf_primary<A, C, N, L, S, false>), G, block, 0, s, RWR_WF_ARGS); } while (0)
+#define RWR_WF_LAUNCH(A, C, N) RWR_WF_LAUNCH_M(A, C, N, false, false, grid)
+#define RWR_WF_LAUNCH_SHADOW(A, C, N, L, G) RWR_WF_LAUNCH_M(A, C, N, L, true, G)
     if (shadow && shadow->recs) {   // the SHADOW forms
         const bool list = wf.live_list && do_cull;
         const dim3 sgrid = list ? dim3(std::min(grid.x * grid.y * z_split, 4096u)) : grid;
@@ -523,7 +570,7 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
     } else
     if (wf.live_list && do_cull) {   // item after item of (live tile) x (share of its samples)
         const dim3 lgrid(std::min(grid.x * grid.y * z_split, 4096u));
-#define RWR_WF_LAUNCH_LIST(A, N) hipLaunchKernelGGL((k_wf_primary<A, true, N, true>), lgrid, block, 0, s, RWR_WF_ARGS)
+#define RWR_WF_LAUNCH_LIST(A, N) RWR_WF_LAUNCH_M(A, true, N, true, false, lgrid)
         if (nmap) { if (aux) RWR_WF_LAUNCH_LIST(true, true); else RWR_WF_LAUNCH_LIST(false, true); }
         else { if (aux) RWR_WF_LAUNCH_LIST(true, false); else RWR_WF_LAUNCH_LIST(false, false); }
 #undef RWR_WF_LAUNCH_LIST
@@ -540,6 +587,7 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
     }
 #undef RWR_WF_LAUNCH_SHADOW
 #undef RWR_WF_LAUNCH
+#undef RWR_WF_LAUNCH_M
 #undef RWR_WF_ARGS
     return hipGetLastError();
 }

@@ -63,6 +63,10 @@ using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
 using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
 using OwnedGraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
 using PinnedWords = Owned<uint32_t *, free_pinned_words>;
+struct MirrorRec { float r, g, b, on; };   // RWR_FLAG_MIRRORS: a surface's reflectance and whether it is a mirror (on: 0 or 1): a float4 of WfMirror::table
+static_assert(sizeof(MirrorRec) == sizeof(float4), "MirrorRec is a float4");
+inline hipError_t free_pinned_mirror(MirrorRec *p) { return hipHostFree(p); }
+using PinnedMirror = Owned<MirrorRec *, free_pinned_mirror>;
 
 // Everything one frame in flight owns: its stream, its targets and the per-frame records / tables.
 // Frames alternate between slots (rwr_ctx_set_frames_in_flight), so the ramp-up of one frame's kernel
@@ -142,6 +146,14 @@ struct WfState {
     DeviceBuffer<ShadowRec> d_shadow_recs;
     DeviceBuffer<unsigned long long> d_shadow_masks, d_shadow_counts;
     DeviceBuffer<uint32_t> d_tiles;           // frames that show little: live tile list, per-tile live pieces, the count (k_wf_classify)
+    // RWR_FLAG_MIRRORS, allocated by the first frame with mirrors: this slot's copy of the surface table (WfMirror::table), the
+    // pinned image it is copied from on the slot's stream, the event behind that copy (the image is not rewritten before it), and
+    // the context's mirror_version the copy holds (0: none)
+    DeviceBuffer<float4> d_mirror;
+    PinnedMirror h_mirror;
+    size_t h_mirror_count = 0;
+    OwnedEvent mirror_copied;
+    uint64_t mirror_version = 0;
 };
 
 // Progressive accumulation (RWR_FLAG_ACCUMULATE): ONE accumulation per context.  Its sums and the first frame's sample-0 planes
@@ -267,6 +279,11 @@ struct rwr_context {
     bool tris_dirty = false;
     rwr_sphere_buffer_data spheres[RWR_MAX_SPHERES]{};
     uint32_t n_spheres = 0;
+    // RWR_FLAG_MIRRORS (rwr_scene_set_part_mirror / _sphere_mirror): {r, g, b, on} per scene part (one entry per st_materials
+    // entry) and per sphere index; mirror_version counts their changes, a WfState's table is refreshed when it lags behind
+    std::vector<rwr::MirrorRec> part_mirrors;
+    rwr::MirrorRec sphere_mirrors[RWR_MAX_SPHERES]{};
+    uint64_t mirror_version = 1;
     rwr_triangle_buffer_data triangles[RWR_MAX_TRIANGLES]{};
     uint32_t n_triangles = 0;
 

@@ -479,6 +479,14 @@ RWR_DEV f3 bounce_direction(f3 n, uint32_t pixel, uint32_t sample, uint32_t seed
     return normalize3(d);
 }
 
+// RWR_FLAG_MIRRORS: the ray that leaves a mirror hit — D' = D - (2 d) n, d = dot3(n, D), n the HitRecord normal hit_exit_point
+// builds — f32 operations in this order, no contraction, not re-normalised (the hit tests take any direction length).
+RWR_DEV f3 reflect_direction(f3 n, f3 D)
+{
+    const float two_d = 2.0f * dot3(n, D);
+    return mk3(D.x - two_d * n.x, D.y - two_d * n.y, D.z - two_d * n.z);
+}
+
 // Wavefront integrator: the key a tile's ray pool is sorted by (kernels_wf_primary.hip stores it, kernels_wf_bounce.hip sorts).
 // Direction bin: 3 bits of octant (Gray-coded so that neighbours share two signs) and 2 x kWfDirCellBits bits of position
 // inside the octant's triangle of the octahedral map (Morton order of a 2^bits x 2^bits grid).

@@ -323,6 +323,17 @@ struct WfSky {
     float zr, zg, zb, hr, hg, hb;   // zenith, horizon: rwr_sky_params' six floats in its order (plain members, no arrays: they stay registers)
 };
 static_assert(sizeof(WfSky) == sizeof(rwr_sky_params), "WfSky is rwr_sky_params");
+// Mirror surfaces (RWR_FLAG_MIRRORS; the MIRROR forms of k_wf_primary and of the trace kernels' EMIT forms): the surface table —
+// one record {reflectance r, g, b, on} per scene part, then one per sphere index (RWR_MAX_SPHERES of them); on != 0: the surface
+// is a mirror.  A kernel argument of its own behind the others (cf. WfSky), so that MaterialRec and ShadeRec stay as they are and
+// the kernels without the flag keep their code.  Part 0's record sits at the table's start: the kernels read it at a constant
+// index — a wave-uniform address, scalar registers — and a one-part scene needs no other for its faces and never looks at
+// ShadeRec::material; spheres and the faces of a scene with several parts read their records per lane.
+struct WfMirror {
+    const float4 *table;
+    uint32_t n_parts;
+    uint32_t pad;
+};
 struct BvhNode4;
 struct BvhDevice {
     const BvhNode4 *nodes;
@@ -362,16 +373,18 @@ uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks);
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg,
                              const WfBuffers &wf, uint32_t sample_begin, uint32_t sample_count, uint32_t z_split,
-                             const WfShadow *shadow = nullptr);
+                             const WfShadow *shadow = nullptr, const WfMirror *mirror = nullptr);
 // once per frame, ahead of the primary stage, when the frame is expected to show little: fills live_list / live_count / tile_live
 hipError_t launch_wf_classify(hipStream_t s, const FrameParams &fp, const FrameTri *ftris, const Targets &tg, uint32_t tiles_x,
                               uint32_t *live_list, uint32_t *live_count, uint32_t *tile_live);
 // emit: one generation of a deeper path that is not its last — the trace kernels' EMIT forms write every hit's next ray back
-// into its slot; null: the kernels that end the path.  sky: RWR_FLAG_SKY — the SKY forms, a ray that hits nothing adds the sky's term
+// into its slot; null: the kernels that end the path.  sky: RWR_FLAG_SKY — the SKY forms, a ray that hits nothing adds the sky's term.
+// mirror: RWR_FLAG_MIRRORS — the MIRROR forms of the EMIT kernels (a path's last generation emits nothing: its kernels are the same)
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf,
                             uint32_t n_tiles, uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list,
-                            const WfEmit *emit = nullptr, const WfShadow *shadow = nullptr, const WfSky *sky = nullptr);
+                            const WfEmit *emit = nullptr, const WfShadow *shadow = nullptr, const WfSky *sky = nullptr,
+                            const WfMirror *mirror = nullptr);
 // RWR_FLAG_SHADOWS: traces the shadow records the kernels of one stage left in the queue (the primary stage's, or one generation's
 // trace kernels') and adds the light's part of every term whose ray got through.  light_mesh / light_sphere: the unit directions
 // towards the reference's two lights; expected_tiles: how many tiles are expected to hold records (sizes the work items only).

@@ -72,6 +72,8 @@ int rwr_scene_clear(rwr_context *ctx)
     RWR_HIP_CHECK(sync_all(ctx));
     ctx->st_verts.clear(); ctx->st_faces.clear(); ctx->st_face_mat.clear(); ctx->st_materials.clear();
     ctx->d_texs.clear(); ctx->d_quads.clear(); ctx->d_nmaps.clear();
+    ctx->part_mirrors.clear();   // (a new scene: its parts are no mirrors; the sphere attributes are kept per index)
+    ctx->mirror_version++;
     ctx->have_mesh = false;
     ctx->n_faces = ctx->n_verts = ctx->n_tris = 0;
     return RWR_OK;
@@ -142,6 +144,8 @@ int rwr_scene_add_mesh(rwr_context *ctx, const rwr_model_vertex_small *verts, ui
     M.nmap = nullptr; M.nmap_w = M.nmap_h = 0u;
     ctx->st_materials.push_back(M);
     ctx->d_nmaps.emplace_back();
+    ctx->part_mirrors.push_back(MirrorRec{0.0f, 0.0f, 0.0f, 0.0f});
+    ctx->mirror_version++;
     if (mid == 0) ctx->material = *material;
     return RWR_OK;
 }
@@ -216,6 +220,68 @@ int rwr_scene_set_normal_map(rwr_context *ctx, uint32_t part, const uint8_t *rgb
     }
     if (ctx->have_mesh && ctx->d_materials.ptr && ctx->d_materials.count >= ctx->st_materials.size())   // already committed: refresh the device copy
         RWR_HIP_CHECK(hipMemcpy(ctx->d_materials.ptr, ctx->st_materials.data(), ctx->st_materials.size() * sizeof(MaterialRec), hipMemcpyHostToDevice));
+    return RWR_OK;
+}
+
+// RWR_FLAG_MIRRORS: a surface's attribute from the caller's three floats (NULL: not a mirror)
+static int mirror_from(const float *reflectance, const char *what, uint32_t index, MirrorRec &out)
+{
+    if (!reflectance) {
+        out = MirrorRec{0.0f, 0.0f, 0.0f, 0.0f};
+        return RWR_OK;
+    }
+    for (int c = 0; c < 3; c++)
+        if (!(reflectance[c] >= 0.0f && reflectance[c] <= 1.0f))   // (false for NaN)
+            return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: reflectance[%d] %g: finite, 0 ... 1", what, index, c, (double)reflectance[c]);
+    out = MirrorRec{reflectance[0], reflectance[1], reflectance[2], 1.0f};
+    return RWR_OK;
+}
+
+int rwr_scene_set_part_mirror(rwr_context *ctx, uint32_t part, const float *reflectance)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
+    MirrorRec m;
+    const int rc = mirror_from(reflectance, "part", part, m);
+    if (rc != RWR_OK) return rc;   // (a refused call changes nothing, the scene's generation included)
+    ctx->scene_generation++;
+    ctx->part_mirrors[part] = m;
+    ctx->mirror_version++;
+    return RWR_OK;
+}
+
+int rwr_scene_set_sphere_mirror(rwr_context *ctx, uint32_t sphere, const float *reflectance)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
+    MirrorRec m;
+    const int rc = mirror_from(reflectance, "sphere", sphere, m);
+    if (rc != RWR_OK) return rc;
+    ctx->scene_generation++;
+    ctx->sphere_mirrors[sphere] = m;
+    ctx->mirror_version++;
+    return RWR_OK;
+}
+
+static void mirror_out(const MirrorRec &m, int *is_mirror, float reflectance[3])
+{
+    if (is_mirror) *is_mirror = m.on != 0.0f ? 1 : 0;
+    if (reflectance) { reflectance[0] = m.r; reflectance[1] = m.g; reflectance[2] = m.b; }
+}
+
+int rwr_scene_get_part_mirror(rwr_context *ctx, uint32_t part, int *is_mirror, float reflectance[3])
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
+    mirror_out(ctx->part_mirrors[part], is_mirror, reflectance);
+    return RWR_OK;
+}
+
+int rwr_scene_get_sphere_mirror(rwr_context *ctx, uint32_t sphere, int *is_mirror, float reflectance[3])
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
+    mirror_out(ctx->sphere_mirrors[sphere], is_mirror, reflectance);
     return RWR_OK;
 }
 

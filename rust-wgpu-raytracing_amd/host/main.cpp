@@ -5,7 +5,7 @@
 //   rwr_render --res DIR [--scene suzanne_lowpoly.obj] [--size 600x600] [--keys "S*15,D*4"]
 //              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows]
 //              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]]
-//              [--show-params] [--out frame.png] [--time]
+//              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
 // (KEY in W A S D Up Down Left Right Space LShift, or '-' for no key).  After the script,
@@ -60,6 +60,26 @@ int main(int argc, char **argv)
         for (int c = 0; c < 3; c++) out[c] = v[c];
         return true;
     };
+    // --mirror-part / --mirror-sphere "N" or "N:r,g,b": an index and a reflectance in [0, 1]^3 (1,1,1 when left out)
+    struct Mirror { bool sphere; uint32_t index; float r[3]; };
+    std::vector<Mirror> mirrors;
+    auto parse_mirror = [](const char *text, Mirror &m) {
+        char *end = nullptr;
+        if (*text < '0' || *text > '9') return false;
+        const unsigned long idx = std::strtoul(text, &end, 10);
+        if (end == text || idx > 0xfffffffful) return false;
+        m.index = (uint32_t)idx;
+        m.r[0] = m.r[1] = m.r[2] = 1.0f;
+        if (*end == '\0') return true;
+        if (*end != ':') return false;
+        float v[3];
+        char tail = 0;
+        if (std::sscanf(end + 1, "%f,%f,%f%c", &v[0], &v[1], &v[2], &tail) != 3) return false;
+        for (int c = 0; c < 3; c++)
+            if (!(v[c] >= 0.0f && v[c] <= 1.0f)) return false;
+        for (int c = 0; c < 3; c++) m.r[c] = v[c];
+        return true;
+    };
     struct Resize { uint64_t frame; uint32_t w, h; };
     std::vector<Resize> resizes;
     for (int i = 1; i < argc; i++) {
@@ -91,6 +111,14 @@ int main(int argc, char **argv)
             sky = true;
             (zenith ? sky_zenith_set : sky_horizon_set) = true;
         }
+        else if (a == "--mirror-part" || a == "--mirror-sphere") {
+            Mirror m{a == "--mirror-sphere", 0u, {1.0f, 1.0f, 1.0f}};
+            if (!parse_mirror(next(), m) || (m.sphere && m.index >= RWR_MAX_SPHERES)) {
+                std::fprintf(stderr, "%s N[:r,g,b]: an index%s and three numbers in [0, 1]\n", a.c_str(), m.sphere ? " below 8" : "");
+                return 2;
+            }
+            mirrors.push_back(m);
+        }
         else if (a == "--show-params") show_params = true;
         else if (a == "--resize") {
             Resize r{0, 0, 0};
@@ -105,7 +133,7 @@ int main(int argc, char **argv)
             std::printf("usage: rwr_render --res DIR [--scene F.obj] [--size WxH] [--keys \"S*15,D*4\"] [--frames N] "
                         "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] "
                         "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
-                        "[--show-params] [--out frame.png] [--time]\n"
+                        "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
                         "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n"
                         "  --shadows     every hit casts a shadow ray towards its light (RWR_FLAG_SHADOWS); works with --spp, --bounces "
@@ -115,6 +143,9 @@ int main(int argc, char **argv)
                         "  --sky         bounce rays that leave the scene return the sky's radiance (RWR_FLAG_SKY; needs --bounces >= 1): a "
                         "gradient from --sky-horizon (straight down) to --sky-zenith (straight up), components in [0, 16] "
                         "(rwr_sky_set_params); either colour implies --sky\n"
+                        "  --mirror-part N[:r,g,b], --mirror-sphere N[:r,g,b]  part N of the scene / sphere N is a mirror of reflectance r,g,b "
+                        "in [0, 1] (1,1,1 when left out) and reflects the ray that found it (RWR_FLAG_MIRRORS, implied; needs --bounces >= 1; "
+                        "rwr_scene_set_part_mirror / rwr_scene_set_sphere_mirror); repeatable\n"
                         "  --show-params prints the render parameters the arguments give and exits, without a device\n");
             return 0;
         } else {
@@ -123,11 +154,15 @@ int main(int argc, char **argv)
         }
     }
     const uint32_t flags = (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u) |   // more than one bounce: the deeper paths
-                           (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u) | (denoise ? (uint32_t)RWR_FLAG_DENOISE : 0u) | (sky ? (uint32_t)RWR_FLAG_SKY : 0u);
+                           (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u) | (denoise ? (uint32_t)RWR_FLAG_DENOISE : 0u) | (sky ? (uint32_t)RWR_FLAG_SKY : 0u) |
+                           (mirrors.empty() ? 0u : (uint32_t)RWR_FLAG_MIRRORS);
     if (show_params) {
-        std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g\n", spp, bounces, flags, sky ? 1 : 0,
+        std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g mirrors %zu", spp, bounces, flags, sky ? 1 : 0,
                     (double)sky_params.zenith[0], (double)sky_params.zenith[1], (double)sky_params.zenith[2],
-                    (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2]);
+                    (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2], mirrors.size());
+        for (const Mirror &m : mirrors)
+            std::printf(" %s %u:%g,%g,%g", m.sphere ? "sphere" : "part", m.index, (double)m.r[0], (double)m.r[1], (double)m.r[2]);
+        std::printf("\n");
         return 0;
     }
     if (res.empty()) { std::fprintf(stderr, "--res DIR is required (the reference bakes OUT_DIR/res in at compile time)\n"); return 2; }
@@ -152,6 +187,10 @@ int main(int argc, char **argv)
         const rwr_render_params params{spp, bounces, 0u, flags};
         if (sky_zenith_set || sky_horizon_set) {
             if (rwr_sky_set_params(state.context(), &sky_params) != RWR_OK) { std::fprintf(stderr, "--sky: %s\n", rwr_last_error_string()); return 2; }
+        }
+        for (const Mirror &m : mirrors) {   // (the scene is loaded: a part the scene does not have is the library's refusal)
+            const int rc = m.sphere ? rwr_scene_set_sphere_mirror(state.context(), m.index, m.r) : rwr_scene_set_part_mirror(state.context(), m.index, m.r);
+            if (rc != RWR_OK) { std::fprintf(stderr, "%s: %s\n", m.sphere ? "--mirror-sphere" : "--mirror-part", rwr_last_error_string()); return 2; }
         }
         if (denoise_iterations != 0 || denoise_sigma != 0.0f) {
             rwr_denoise_params dp;
