@@ -4,6 +4,10 @@
     python tools/fuzz_parity.py --rest [seed] [seconds]     see tests/rest_common.py
 --rest: lists of cases (seed, seed + 1, ...) each held at rest for 2 n + 2 frames on a context whose slots are modelled, so that
 the frames compared with the oracle are served from the slot's kept records and ray plane.
+    python tools/fuzz_parity.py --path [first] [count] [seconds]      see tests/path_cases.py
+--path: path_cases.case(i) for i in [first, first + count) (default: the 64 cases after the committed list; a new context every
+256 cases) against the tests' CPU reference of the extensions taken together (mirror_ref.c), with the tests' own comparison; with
+seconds, the walk ends early once that time is up and says how far it came.
 """
 import os
 import sys
@@ -18,7 +22,52 @@ import fuzz_common
 r = g.load_package()
 far = "--far" in sys.argv[1:]
 rest = "--rest" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a not in ("--far", "--rest")]
+path = "--path" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--far", "--rest", "--path")]
+if path:
+    import tempfile
+
+    import mirror_ref
+    import path_cases
+
+    class _Tmp:   # mirror_ref.lib builds into a directory from pytest's factory; here one of our own
+        @staticmethod
+        def mktemp(name):
+            return tempfile.mkdtemp(prefix=name)
+
+    L = mirror_ref.lib(_Tmp)
+    meshes = {n: ref_loader.load_model_compute(r.RES_DIR, n + ".obj") for n in ("suzanne_lowpoly", "cube")}
+    first = int(args[0]) if len(args) > 0 else path_cases.N_CASES
+    count = int(args[1]) if len(args) > 1 else 64
+    t_end = time.time() + float(args[2]) if len(args) > 2 else None
+    worst = worst_ratio = 0.0
+    at = None
+    t0 = time.time()
+    done, failed, ctx = 0, [], None
+    for i in range(first, first + count):
+        if t_end is not None and time.time() >= t_end:
+            break
+        if done % 256 == 0:
+            if ctx is not None:
+                ctx.close()
+            ctx = r.Context(0)
+        c = path_cases.case(i, ref_loader, orc, meshes["cube"], meshes["suzanne_lowpoly"])
+        try:
+            err = path_cases.compare(path_cases.gpu_frame(r, c, ctx), path_cases.reference(L, orc, c), c)
+        except AssertionError as e:      # a mismatch is a finding: say which case, go on (an error of the device is not caught)
+            failed.append(i)
+            print(f"MISMATCH {e}", flush=True)
+            err = 0.0
+        path_cases.forget(c)
+        if err / path_cases.color_bar(c) >= worst_ratio:
+            worst, worst_ratio, at = err, err / path_cases.color_bar(c), i
+        done += 1
+        if done % 500 == 0:
+            print(f"... {done} cases so far, {time.time() - t0:.0f} s, worst colour error {worst:.2e} (case {at}, {worst_ratio:.2f} of its bar)", flush=True)
+    if ctx is not None:
+        ctx.close()
+    print(f"{'ok' if not failed else 'FAILED ' + str(failed)}: {done} path cases ({first} ... {first + done - 1}) in {time.time() - t0:.0f} s, worst colour error {worst:.2e} (case {at}, {worst_ratio:.2f} of its bar)")
+    sys.exit(1 if failed else 0)
 seed = int(args[0]) if len(args) > 0 else 1
 seconds = float(args[1]) if len(args) > 1 else 30.0
 if rest:
