@@ -258,7 +258,7 @@ enum {
                                        7. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED.  The
                                           refusal comes first: it holds at max_bounces = 0 too, where item 4 would otherwise ignore the
                                           flag — a combination that is refused does not start to work when the bounces go to 0. */
-    RWR_FLAG_MIRRORS = 1u << 10     /* extension: mirror surfaces — a scene part or a sphere marked as a mirror (rwr_scene_set_part_mirror,
+    RWR_FLAG_MIRRORS = 1u << 10,    /* extension: mirror surfaces — a scene part or a sphere marked as a mirror (rwr_scene_set_part_mirror,
                                        rwr_scene_set_sphere_mirror) sends the reflection of the ray that found it onwards instead of a
                                        cosine-distributed ray.  Without the flag every frame is what it was, byte for byte, with no further
                                        launch or allocation.  With it:
@@ -293,6 +293,44 @@ enum {
                                           multi-GPU gather keep their contracts.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or
                                           single-triangle passes: RWR_ERR_UNSUPPORTED, whatever max_bounces is and whether or not a
                                           mirror is set (the refusal comes first, as RWR_FLAG_SKY's). */
+    RWR_FLAG_GLASS = 1u << 11       /* extension: glass surfaces — a scene part or a sphere marked as glass (rwr_scene_set_part_glass,
+                                       rwr_scene_set_sphere_glass) of index eta and tint C reflects by Fresnel's law (Schlick's form),
+                                       refracts by Snell's, and reflects totally on the way out beyond the critical angle.  Independent
+                                       of RWR_FLAG_MIRRORS: each flag switches its own surfaces on; a glass surface in a frame without
+                                       this flag is the diffuse surface it was.  Without the flag every frame is what it was, byte for
+                                       byte, with no further launch or allocation.  With it, at a hit h a path goes on from (h0, or h_k
+                                       with k < max_bounces) on a glass surface, all in f32 with no contraction:
+                                       1. Dh = normalize3(D), the oracle's routine (three divisions by the length); D is the direction
+                                          of the ray that found h (un-normalised after a mirror or a refraction).
+                                       2. n is the reference's HitRecord normal.  A face: entering = !(N.D > 0) with the winner's stored
+                                          N.D — outside is the side the winding's normal points to — and n_f = n, already flipped
+                                          towards the ray.  A sphere: s = dot3(n, Dh), entering = !(s > 0), n_f = entering ? n : -n.
+                                       3. c = fminf(1, fmaxf(0, -dot3(n_f, Dh))), e = entering ? 1.0f / eta : eta,
+                                          k = 1 - (e e) (1 - c c).
+                                       4. k < 0, total internal reflection: (a, b) = (1, 2 c), no random number is read, m = n_f.
+                                       5. Otherwise ct = sqrtf(k), r0 = ((1 - eta) / (1 + eta))^2, x = 1 - (entering ? c : ct),
+                                          F = r0 + (1 - r0) ((x x) (x x) x), u = rng_uniform(pixel, sample, d0, seed) with d0 the first
+                                          dimension of the generation's block (2 for the ray that leaves h0, 2 + 16 k for the one that
+                                          leaves h_k); the block's other 15 dimensions are skipped, as at a mirror.  u < F: a Fresnel
+                                          reflection, (a, b) = (1, 2 c), m = n_f.  Else a transmission: (a, b) = (e, e c - ct), m = -n_f.
+                                       6. The next ray: direction a Dh + b n_f per component (a*Dh.x + b*n_f.x), not re-normalised;
+                                          origin P + 1e-4 m (P.x + m.x*1e-4f, P = O + t D on the ray's own D); throughput T * C in all
+                                          three events (the choice has probability F and weight 1).
+                                       7. The local term of h is unchanged, E(h) or the shadowed E(h): a coated surface, as a mirror.
+                                          For clear glass give the part Ka = Ks = 0 and a black texture.  h's shadow ray keeps the
+                                          origin P + 1e-4 n whatever side the path goes on from; glass occludes shadow rays like any
+                                          surface.  Primary-stage sums, sample-0 planes, h0's shadow records and generation 1's ray
+                                          count do not depend on the flag; the nearest-hit rule, the clamps, the sky's term at a miss
+                                          and (C <= 1) the integrator's range analysis are untouched.
+                                       8. max_bounces = 0, or no part of the scene and none of its spheres (indices below the count
+                                          rwr_scene_set_spheres gave) is glass: the flag is ignored — cleared before the frame's kernels
+                                          are chosen — and the frame is the frame without it, byte for byte, in the same kernels.
+                                       9. RWR_FLAG_ACCUMULATE: this bit (after item 8) is part of the key; every accepted call of the
+                                          glass setters changes the scene's generation, a refused one changes nothing.
+                                       10. rwr_last_glass_stats counts the three events.  Every other flag, instances, parts, frames in
+                                          flight, row bands, strips and the multi-GPU gather keep their contracts.  With
+                                          RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED, whatever
+                                          max_bounces is and whether or not a surface is glass. */
 };
 
 #define RWR_MAX_BOUNCES 8u
@@ -379,6 +417,17 @@ RWR_API int rwr_scene_set_part_mirror(rwr_context *ctx, uint32_t part, const flo
 RWR_API int rwr_scene_set_sphere_mirror(rwr_context *ctx, uint32_t sphere, const float *reflectance);
 RWR_API int rwr_scene_get_part_mirror(rwr_context *ctx, uint32_t part, int *is_mirror, float reflectance[3]);
 RWR_API int rwr_scene_get_sphere_mirror(rwr_context *ctx, uint32_t sphere, int *is_mirror, float reflectance[3]);
+
+/* RWR_FLAG_GLASS: the glass attribute of a scene part or of a sphere index, with the mirror attribute's index and reset rules.
+ * tint: 3 floats, each finite and in [0, 1]; NULL = not glass (ior is then ignored).  ior: finite, in [1, 4].  Anything else, NaN
+ * included: RWR_ERR_INVALID_ARGUMENT and the old state stays.  A surface has one model: an accepted call of a glass setter
+ * clears the surface's mirror attribute, an accepted call of a mirror setter its glass attribute (with NULL either makes the
+ * surface diffuse).  Every accepted call changes the scene's generation.  The getters return *is_glass = 0 / 1 and, for glass,
+ * its ior and tint (zeros otherwise); every output may be NULL. */
+RWR_API int rwr_scene_set_part_glass(rwr_context *ctx, uint32_t part, float ior, const float *tint);
+RWR_API int rwr_scene_set_sphere_glass(rwr_context *ctx, uint32_t sphere, float ior, const float *tint);
+RWR_API int rwr_scene_get_part_glass(rwr_context *ctx, uint32_t part, int *is_glass, float *ior, float tint[3]);
+RWR_API int rwr_scene_get_sphere_glass(rwr_context *ctx, uint32_t sphere, int *is_glass, float *ior, float tint[3]);
 
 /* Replaces Sphere::new's uniform, one per analytic sphere pass, composited in
  * array order before the mesh (src/lib.rs:532-534, 1106-1173).  n <= RWR_MAX_SPHERES. */
@@ -546,6 +595,11 @@ RWR_API int rwr_ray_plane_stats(rwr_context *ctx, uint64_t *builds, uint64_t *fr
  * generation; an accumulating frame: its own samples; 0 without the flag) and how many of them were occluded.  Exact counts.
  * Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_last_shadow_stats(rwr_context *ctx, uint64_t *shadow_rays, uint64_t *occluded);
+
+/* RWR_FLAG_GLASS: what the glass hits of the last render call did — Fresnel reflections, transmissions, total internal
+ * reflections (an accumulating frame: its own samples; zeros for a frame the flag did nothing to).  Exact counts.  Waits for the
+ * frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_last_glass_stats(rwr_context *ctx, uint64_t *reflected, uint64_t *transmitted, uint64_t *tir);
 
 /* Progressive accumulation (RWR_FLAG_ACCUMULATE).  One context holds one accumulation.
  * rwr_accum_reset: the next accumulating frame starts over at N = 0 (host-side only, nothing waits).

@@ -51,6 +51,7 @@ DENOISE_PARAMS_DTYPE = np.dtype([("iterations", "<u4"), ("sigma_color", "<f4"), 
 FLAG_SKY = 1 << 9            # bounce rays that leave the scene return the sky's radiance (include/rwr_hip.h)
 SKY_PARAMS_DTYPE = np.dtype([("zenith", "<f4", 3), ("horizon", "<f4", 3)])
 FLAG_MIRRORS = 1 << 10       # parts and spheres marked as mirrors reflect the ray that found them (include/rwr_hip.h)
+FLAG_GLASS = 1 << 11         # parts and spheres marked as glass reflect by Fresnel's law and refract by Snell's (include/rwr_hip.h)
 MAX_BOUNCES = 8
 FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
 KEY_FORWARD, KEY_BACKWARD, KEY_LEFT, KEY_RIGHT, KEY_UP, KEY_DOWN = 1, 2, 4, 8, 16, 32
@@ -119,6 +120,9 @@ def lib() -> C.CDLL:
         "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
         "rwr_scene_set_part_mirror": [vp, u32, vp], "rwr_scene_set_sphere_mirror": [vp, u32, vp],
         "rwr_scene_get_part_mirror": [vp, u32, vp, vp], "rwr_scene_get_sphere_mirror": [vp, u32, vp, vp],
+        "rwr_scene_set_part_glass": [vp, u32, f32, vp], "rwr_scene_set_sphere_glass": [vp, u32, f32, vp],
+        "rwr_scene_get_part_glass": [vp, u32, vp, vp, vp], "rwr_scene_get_sphere_glass": [vp, u32, vp, vp, vp],
+        "rwr_last_glass_stats": [vp, vp, vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
         "rwr_load_model_compute": [C.c_char_p, C.c_char_p, vp], "rwr_model_free": [vp],
         "rwr_model_info": [vp, vp, vp, vp, vp, vp, vp], "rwr_scene_upload_model": [vp, vp],
@@ -137,7 +141,8 @@ def lib() -> C.CDLL:
     }
     _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats",
                            "rwr_sky_set_params", "rwr_sky_get_params", "rwr_scene_set_part_mirror", "rwr_scene_set_sphere_mirror",
-                           "rwr_scene_get_part_mirror", "rwr_scene_get_sphere_mirror")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_scene_get_part_mirror", "rwr_scene_get_sphere_mirror", "rwr_scene_set_part_glass", "rwr_scene_set_sphere_glass",
+                           "rwr_scene_get_part_glass", "rwr_scene_get_sphere_glass", "rwr_last_glass_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -465,6 +470,39 @@ class Context:
     def get_sphere_mirror(self, sphere: int):
         """The sphere index's reflectance (float32[3]) when it is a mirror, else None (rwr_scene_get_sphere_mirror)."""
         return self._get_mirror(lib().rwr_scene_get_sphere_mirror, sphere)
+
+    def set_part_glass(self, part: int, ior: float = 1.5, tint=(1.0, 1.0, 1.0)):
+        """FLAG_GLASS: scene part `part` is glass of index of refraction `ior` (in [1, 4]) and this tint (three floats in [0, 1]);
+        tint None: not glass.  Out of range or NaN: RwrError(ERR_INVALID_ARGUMENT), and the old state stays.  An accepted call
+        clears the part's mirror attribute (rwr_scene_set_part_glass)."""
+        t = self._reflectance(tint)
+        _check(lib().rwr_scene_set_part_glass(self._h, part, ior, _p(t)))
+
+    def set_sphere_glass(self, sphere: int, ior: float = 1.5, tint=(1.0, 1.0, 1.0)):
+        """FLAG_GLASS: the sphere of index `sphere` (< 8, kept whatever set_spheres holds) is glass; tint None: not glass."""
+        t = self._reflectance(tint)
+        _check(lib().rwr_scene_set_sphere_glass(self._h, sphere, ior, _p(t)))
+
+    def _get_glass(self, fn, index: int):
+        on = C.c_int(0)
+        ior = C.c_float(0.0)
+        t = np.zeros(3, np.float32)
+        _check(fn(self._h, index, C.byref(on), C.byref(ior), _p(t)))
+        return (float(ior.value), t) if on.value else None
+
+    def get_part_glass(self, part: int):
+        """(ior, tint float32[3]) when the part is glass, else None (rwr_scene_get_part_glass)."""
+        return self._get_glass(lib().rwr_scene_get_part_glass, part)
+
+    def get_sphere_glass(self, sphere: int):
+        """(ior, tint float32[3]) when the sphere index is glass, else None (rwr_scene_get_sphere_glass)."""
+        return self._get_glass(lib().rwr_scene_get_sphere_glass, sphere)
+
+    def last_glass_stats(self):
+        """(reflected, transmitted, totally reflected): what the glass hits of the last render call did (rwr_last_glass_stats)."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rwr_last_glass_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
 
     def set_triangles(self, triangles):
         """Single-triangle passes (the reference's dormant models/triangle), after the spheres."""

@@ -422,6 +422,21 @@ int rwr_last_shadow_stats(rwr_context *ctx, uint64_t *shadow_rays, uint64_t *occ
     return RWR_OK;
 }
 
+int rwr_last_glass_stats(rwr_context *ctx, uint64_t *reflected, uint64_t *transmitted, uint64_t *tir)
+{
+    if (!ctx || !reflected || !transmitted || !tir) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    unsigned long long counts[3] = {0ull, 0ull, 0ull};
+    if (ctx->last_glass && ctx->wf_state[ctx->last_wf_state].d_glass_counts.ptr) {
+        DeviceGuard g(ctx->device);
+        RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
+        RWR_HIP_CHECK(hipMemcpy(counts, ctx->wf_state[ctx->last_wf_state].d_glass_counts.ptr, sizeof counts, hipMemcpyDeviceToHost));
+    }
+    *reflected = counts[0];
+    *transmitted = counts[1];
+    *tir = counts[2];
+    return RWR_OK;
+}
+
 int rwr_denoise_set_params(rwr_context *ctx, const rwr_denoise_params *params)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");

@@ -269,29 +269,55 @@ k_wf_sort(const WfBuffers wf, PoolInfo *__restrict__ info, uint32_t *__restrict_
 // towards the ray or the sphere's outward normal, as the first stage builds the first bounce ray), in the cosine-distributed
 // direction of RNG dimensions em.next_dim ... keyed by the slot's global pixel and sample, throughput thr — goes back into slot
 // e of the tile's pool; the slot's bit is set in the next generation's ballots.
-// MIRROR forms (RWR_FLAG_MIRRORS), a hit on a mirror surface (`mirror`): the direction is the reflection of D about n instead
-// (reflect_direction: no random number is read, the generation's RNG dimensions are left unused), thr is T * R.
-template <bool MIRROR = false>
-RWR_DEV void emit_next_ray(const FrameParams &p, const WfBuffers &wf, const WfEmit &em, const TriRecord *__restrict__ tris, uint32_t tile,
-                           uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr, bool mirror = false)
+// MIRROR forms (RWR_FLAG_MIRRORS; SURF != kSurfNone), a hit on a mirror surface (`mirror`): the direction is the reflection of D
+// about n instead (reflect_direction: no random number is read, the generation's RNG dimensions are left unused), thr is T * R.
+// Glass forms (RWR_FLAG_GLASS; SURF == kSurfGlass), a hit on glass (`eta` != 0, its index): direction and side by
+// refract_or_reflect with the generation's first random number, origin P + 1e-4 m, thr is T * C — computed here, where the
+// traversal's registers are dead.  Returns the glass event (0 reflected, 1 transmitted, 2 totally reflected), 3 for no glass hit.
+template <int SURF = kSurfNone>
+RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const WfEmit &em, const TriRecord *__restrict__ tris, uint32_t tile,
+                               uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr, bool mirror = false, float eta = 0.0f)
 {
     f3 n;
-    const f3 O1 = hit_exit_point(p, tris, O, D, obj, t, ndotd, n);
+    f3 O1 = hit_exit_point(p, tris, O, D, obj, t, ndotd, n);
     f3 D1;
-    if (MIRROR && mirror) {
+    uint32_t event = 3u;
+    if (SURF != kSurfNone && mirror) {
         D1 = reflect_direction(n, D);
     } else {
         // the slot's pixel (as add_contribution maps it) and sample
         const uint32_t r = e & (kWfTilePixels - 1u), w = r >> 7, k = (r >> 6) & 1u, l = r & 63u;
         const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (w & 1u) * 32u + 2u * (l & 15u) + k;
         const uint32_t py = p.row_begin + (tile / wf.tiles_x) * p.row_pitch + (w >> 1) * 4u + (l >> 4);
-        D1 = bounce_direction(n, py * p.width + px, em.sample_base + e / kWfTilePixels, p.seed, em.next_dim);
+        if (SURF == kSurfGlass && eta != 0.0f) {
+            const float u = rng_uniform(py * p.width + px, em.sample_base + e / kWfTilePixels, em.next_dim, p.seed);
+            f3 m;
+            event = refract_or_reflect(n, D, obj >= 0, ndotd, eta, u, D1, m);
+            const f3 P = along(O, t, D);
+            O1 = mk3(P.x + m.x * 1e-4f, P.y + m.y * 1e-4f, P.z + m.z * 1e-4f);
+        } else {
+            D1 = bounce_direction(n, py * p.width + px, em.sample_base + e / kWfTilePixels, p.seed, em.next_dim);
+        }
     }
     const size_t slot = (size_t)tile * wf.group * kWfTilePixels + e;
     wf.rays[2u * slot] = make_float4(O1.x, O1.y, O1.z, wf_pack_unorm16x2(thr.x, thr.y));
     wf.rays[2u * slot + 1u] = make_float4(D1.x, D1.y, D1.z, wf_pack_unorm16x2(thr.z, 0.0f));
     wf.bins[slot] = (uint16_t)wf_direction_bin(D1);
     atomicOr(&em.masks_out[(size_t)tile * wf.group * 8u + (e >> 6)], 1ull << (e & 63u));
+    return event;
+}
+
+// Glass forms: a wave's glass events into the frame's three counters (WfMirror::glass_counts) — ballots and popcounts, added by
+// the wave's first active lane, one atomic per event kind the wave saw.  Call where the wave's lanes have come together again.
+RWR_DEV void count_glass_events(unsigned long long *__restrict__ counts, uint32_t ev0, uint32_t ev1 = 3u)
+{
+    const unsigned long long active = __ballot(true);
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; k++) {
+        const uint32_t n = (uint32_t)__popcll(__ballot(ev0 == k)) + (uint32_t)__popcll(__ballot(ev1 == k));
+        if (n && lane == (uint32_t)__builtin_ctzll(active)) atomicAdd(&counts[k], (unsigned long long)n);
+    }
 }
 
 // MIRROR forms: the surface record {r, g, b, on} of the hit `obj` (rwr_internal.h WfMirror).  Part 0's record is read at a constant
@@ -393,15 +419,18 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // SKY: RWR_FLAG_SKY — a ray that hits nothing adds the sky's term (add_sky); separate instantiations for the same reason.
 // MIRROR: RWR_FLAG_MIRRORS — of the EMIT forms alone: a hit on a mirror surface sends the reflected ray on, with T * R
 // (emit_next_ray); separate instantiations for the same reason.
+// SURF: which surface models the EMIT form knows — kSurfNone, kSurfMirrors (RWR_FLAG_MIRRORS alone: the MIRROR forms) or kSurfGlass
+// (RWR_FLAG_GLASS, with or without mirrors: a hit on glass sends on a reflected or a refracted ray with T * C and is counted).
 template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false, bool SKY = false,
-          bool MIRROR = false>
+          int SURF = kSurfNone>
 __global__ void __launch_bounds__(WIDE ? 1024 : 256)
 k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                 const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                 uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
                 const WfSky sky, const WfMirror mir)
 {
-    static_assert(EMIT || !MIRROR, "only a kernel that emits rays has a MIRROR form");
+    static_assert(EMIT || SURF == kSurfNone, "only a kernel that emits rays has a MIRROR or a glass form");
+    constexpr bool MIRROR = SURF != kSurfNone;
     __shared__ TraceShared sh;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
     const uint32_t tid = threadIdx.x;
@@ -461,6 +490,7 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                 else bvh_nearest(bvh.nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, D, mh);
                 if (mh.have && (!have || mh.t < best_t)) { have = true; best_t = mh.t; obj = (int32_t)mh.idx; }
             }
+            uint32_t event = 3u;   // glass forms: what a glass hit did
             if (have) {
                 const Shaded s1 = shade_winner<NMAP>(p, obj, best_t, mh.u, mh.v, mh.ndotd, shade, tex, O, D);
                 const f3 e1 = s1.colour;
@@ -471,13 +501,15 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                                   mk3(thr.x * s1.albedo.x, thr.y * s1.albedo.y, thr.z * s1.albedo.z));
                 if (EMIT && MIRROR) {
                     const float4 m = mirror_record(p, mir, shade, obj);
-                    const bool mirror = m.w != 0.0f;
-                    const f3 next = mirror ? mk3(m.x, m.y, m.z) : s1.albedo;
-                    emit_next_ray<true>(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd, mk3(thr.x * next.x, thr.y * next.y, thr.z * next.z), mirror);
+                    const bool mirror = SURF == kSurfGlass ? m.w > 0.0f : m.w != 0.0f, glass = SURF == kSurfGlass && m.w < 0.0f;
+                    const f3 next = (mirror || glass) ? mk3(m.x, m.y, m.z) : s1.albedo;
+                    event = emit_next_ray<SURF>(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd, mk3(thr.x * next.x, thr.y * next.y, thr.z * next.z),
+                                                mirror, glass ? -m.w : 0.0f);
                 }
             } else if (SKY) {
                 add_sky(sh, sky, e, D.y, thr);
             }
+            if (SURF == kSurfGlass) count_glass_events(mir.glass_counts, event);
             if (EMIT) {   // rays written for the next generation (lanes past the pool's end have left the iteration)
                 const unsigned long long em = __ballot(have);
                 if (em && (tid & 63u) == (uint32_t)__builtin_ctzll(em)) atomicAdd(&wf.wave_total[tile * 4u], (uint32_t)__popcll(em));
@@ -567,14 +599,15 @@ RWR_DEV i2 sphere_pair_intersect_t(f3 center, float radius, v3 O, v3 D, f2 &t_ou
 #ifndef RWR_PACKET_OCC
 #define RWR_PACKET_OCC 4
 #endif
-template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false, bool MIRROR = false>   // EMIT, SHADOW, SKY, MIRROR: see k_wf_trace_lane
+template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false, int SURF = kSurfNone>   // EMIT, SHADOW, SKY, SURF: see k_wf_trace_lane
 __global__ void __launch_bounds__(256, RWR_PACKET_OCC)
 k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                   uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
                   const WfSky sky, const WfMirror mir)
 {
-    static_assert(EMIT || !MIRROR, "only a kernel that emits rays has a MIRROR form");
+    static_assert(EMIT || SURF == kSurfNone, "only a kernel that emits rays has a MIRROR or a glass form");
+    constexpr bool MIRROR = SURF != kSurfNone;
     __shared__ TraceShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const const_ptr<BvhNode4> nodes = to_const_space(bvh.nodes);
@@ -787,17 +820,20 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
                                       k ? best.ndotd.y : best.ndotd.x, k ? mk3(nr.y, ng.y, nb.y) : mk3(nr.x, ng.x, nb.x));
             }
             if (EMIT && MIRROR) {   // the same, but a hit on a mirror sends T * R on, not T * albedo, in the reflected direction
+                uint32_t event[2] = {3u, 3u};   // glass forms: what each ray's glass hit did
 #pragma unroll
                 for (int k = 0; k < 2; k++)
                     if (k ? have.y : have.x) {
                         const int32_t o = k ? obj.y : obj.x;
                         const float4 m = mirror_record(p, mir, shade, o);
-                        const bool mirror = m.w != 0.0f;
-                        const f3 next = mirror ? mk3(m.x, m.y, m.z) : (k ? mk3(ar.y, ag.y, ab.y) : mk3(ar.x, ag.x, ab.x));
+                        const bool mirror = SURF == kSurfGlass ? m.w > 0.0f : m.w != 0.0f, glass = SURF == kSurfGlass && m.w < 0.0f;
+                        const f3 next = (mirror || glass) ? mk3(m.x, m.y, m.z) : (k ? mk3(ar.y, ag.y, ab.y) : mk3(ar.x, ag.x, ab.x));
                         const f3 t = k ? mk3(thr.x.y, thr.y.y, thr.z.y) : mk3(thr.x.x, thr.y.x, thr.z.x);
-                        emit_next_ray<true>(p, wf, em, tris, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), o, k ? best_t.y : best_t.x,
-                                            k ? best.ndotd.y : best.ndotd.x, mk3(t.x * next.x, t.y * next.y, t.z * next.z), mirror);
+                        event[k] = emit_next_ray<SURF>(p, wf, em, tris, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), o, k ? best_t.y : best_t.x,
+                                                       k ? best.ndotd.y : best.ndotd.x, mk3(t.x * next.x, t.y * next.y, t.z * next.z), mirror,
+                                                       glass ? -m.w : 0.0f);
                     }
+                if (SURF == kSurfGlass) count_glass_events(mir.glass_counts, event[0], event[1]);
             }
             if (EMIT) {
                 const uint32_t n_emit = (uint32_t)__popcll(__ballot(have.x != 0)) + (uint32_t)__popcll(__ballot(have.y != 0));
@@ -820,15 +856,16 @@ static std::atomic<uint64_t> g_trace_launches[3];
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf, uint32_t n_tiles,
                             uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list, const WfEmit *emit,
-                            const WfShadow *shadow, const WfSky *sky, const WfMirror *mirror)
+                            const WfShadow *shadow, const WfSky *sky, const WfMirror *mirror, bool glass)
 {
     const WfEmit em = emit ? *emit : WfEmit{nullptr, 0u, 0u};
     const WfShadow sw = shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr};
     const bool shadows = sw.recs != nullptr;
     const WfSky sk = sky ? *sky : WfSky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     const bool sky_on = sky != nullptr;
-    const WfMirror mr = mirror ? *mirror : WfMirror{nullptr, 0u, 0u};
+    const WfMirror mr = mirror ? *mirror : WfMirror{nullptr, 0u, 0u, nullptr};
     const bool mirror_on = mirror != nullptr && emit != nullptr;   // (the kernels that end a path emit nothing: no MIRROR form)
+    const bool glass_on = mirror_on && glass;                      // the table may hold glass records: the SURF = 2 forms
     if (n_tiles == 0 || sample_count == 0) return hipSuccess;
     uint32_t *counters = wf.counters;   // this queue's set, zeroed by the primary stage that filled the queue
     PoolInfo *info = static_cast<PoolInfo *>(pool_info);
@@ -859,7 +896,9 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
     if (wf.dbg && packets) g_trace_launches[0].fetch_add(1u, std::memory_order_relaxed);
 #define RWR_PACKET_LAUNCH_M(N, E, S, K, M) hipLaunchKernelGGL((k_wf_trace_packet<N, E, S, K, M>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk, mr)
-#define RWR_PACKET_LAUNCH_K(N, E, S, K) do { if (E && mirror_on) RWR_PACKET_LAUNCH_M(N, E, S, K, E); else RWR_PACKET_LAUNCH_M(N, E, S, K, false); } while (0)
+#define RWR_PACKET_LAUNCH_K(N, E, S, K) do { if (E && glass_on) RWR_PACKET_LAUNCH_M(N, E, S, K, (E ? kSurfGlass : kSurfNone)); \
+                                             else if (E && mirror_on) RWR_PACKET_LAUNCH_M(N, E, S, K, (E ? kSurfMirrors : kSurfNone)); \
+                                             else RWR_PACKET_LAUNCH_M(N, E, S, K, kSurfNone); } while (0)
 #define RWR_PACKET_LAUNCH(N, E, S) do { if (sky_on) RWR_PACKET_LAUNCH_K(N, E, S, true); else RWR_PACKET_LAUNCH_K(N, E, S, false); } while (0)
     if (packets && shadows) {
         if (emit) { if (nmap) RWR_PACKET_LAUNCH(true, true, true); else RWR_PACKET_LAUNCH(false, true, true); }
@@ -877,7 +916,9 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     const size_t node_bytes = (size_t)bvh.n_nodes * sizeof(BvhNode4);
     // nodelets go to LDS when the workgroup then still fits a CU at least four times (160 KiB LDS, 12 KiB static)
 #define RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, M, BYTES) hipLaunchKernelGGL((k_wf_trace_lane<L, N, S16, false, E, S, K, M>), grid, dim3(256), BYTES, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk, mr)
-#define RWR_LANE_LAUNCH_K(L, N, S16, E, S, K, BYTES) do { if (E && mirror_on) RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, E, BYTES); else RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, false, BYTES); } while (0)
+#define RWR_LANE_LAUNCH_K(L, N, S16, E, S, K, BYTES) do { if (E && glass_on) RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, (E ? kSurfGlass : kSurfNone), BYTES); \
+                                                          else if (E && mirror_on) RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, (E ? kSurfMirrors : kSurfNone), BYTES); \
+                                                          else RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, kSurfNone, BYTES); } while (0)
 #define RWR_LANE_LAUNCH(L, N, S16, E, S, BYTES) do { if (sky_on) RWR_LANE_LAUNCH_K(L, N, S16, E, S, true, BYTES); else RWR_LANE_LAUNCH_K(L, N, S16, E, S, false, BYTES); } while (0)
 #define RWR_LANE_LAUNCH0(L, E, S, BYTES) \
     if (nmap) { if (stack16) RWR_LANE_LAUNCH(L, true, true, E, S, BYTES); else RWR_LANE_LAUNCH(L, true, false, E, S, BYTES); } \
@@ -890,12 +931,13 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     if (node_bytes + fixed <= 28u * 1024u) { RWR_LANE_LAUNCH2(true, node_bytes + fixed) }
     else if (wide) {
         // a BVH too large for a copy per 256-thread workgroup, small enough for one copy per CU: 1 024-thread workgroups
-        // per form: [emit + 2 * shadows + 4 * sky], and the EMIT forms again with MIRROR: [8 + (shadows + 2 * sky)]
-#define RWR_WIDE_FORMS(X) X(0, false, false, false, false) X(1, true, false, false, false) X(2, false, true, false, false) X(3, true, true, false, false) \
-                          X(4, false, false, true, false) X(5, true, false, true, false) X(6, false, true, true, false) X(7, true, true, true, false) \
-                          X(8, true, false, false, true) X(9, true, true, false, true) X(10, true, false, true, true) X(11, true, true, true, true)
-        static std::atomic<uint64_t> wide_raised_on[12];
-        const uint32_t form = mirror_on ? 8u + (shadows ? 1u : 0u) + (sky_on ? 2u : 0u) : (emit ? 1u : 0u) + (shadows ? 2u : 0u) + (sky_on ? 4u : 0u);
+        // per form: [emit + 2 * shadows + 4 * sky], the EMIT forms again with mirrors: [8 + (shadows + 2 * sky)], and with glass: [12 + ...]
+#define RWR_WIDE_FORMS(X) X(0, false, false, false, kSurfNone) X(1, true, false, false, kSurfNone) X(2, false, true, false, kSurfNone) X(3, true, true, false, kSurfNone) \
+                          X(4, false, false, true, kSurfNone) X(5, true, false, true, kSurfNone) X(6, false, true, true, kSurfNone) X(7, true, true, true, kSurfNone) \
+                          X(8, true, false, false, kSurfMirrors) X(9, true, true, false, kSurfMirrors) X(10, true, false, true, kSurfMirrors) X(11, true, true, true, kSurfMirrors) \
+                          X(12, true, false, false, kSurfGlass) X(13, true, true, false, kSurfGlass) X(14, true, false, true, kSurfGlass) X(15, true, true, true, kSurfGlass)
+        static std::atomic<uint64_t> wide_raised_on[16];
+        const uint32_t form = mirror_on ? (glass_on ? 12u : 8u) + (shadows ? 1u : 0u) + (sky_on ? 2u : 0u) : (emit ? 1u : 0u) + (shadows ? 2u : 0u) + (sky_on ? 4u : 0u);
         std::atomic<uint64_t> &raised = wide_raised_on[form];
         const void *kernel = nullptr;
         switch (form) {

@@ -164,13 +164,17 @@ RWR_DEV f3 ld3(kernarg<float> *q) { return mk3(q[0], q[1], q[2]); }
 // with throughput R instead of the cosine-distributed ray with the albedo, decided per pixel of the lane's pair.  A tile without
 // a mirror hit skips the reflection, a tile whose emitting pixels are all mirror hits skips the RNG and the disk-to-hemisphere
 // arithmetic (wave-uniform branches on ballots), a mixed tile computes both and selects.  Forms of their own again.
-template <bool AUX, bool CULL, bool NMAP, bool LIST = false, bool SHADOW = false, bool MIRROR = false>
+// SURF (rwr_internal.h): kSurfNone, kSurfMirrors — the MIRROR forms — or kSurfGlass (RWR_FLAG_GLASS, with or without mirrors): a hit
+// on glass emits the reflected or the refracted ray of refract_or_reflect from P + 1e-4 m with throughput C, decided per pixel too.
+// A tile without a glass hit skips that arithmetic, a tile whose emitting pixels are all specular skips the RNG disk loop.
+template <bool AUX, bool CULL, bool NMAP, bool LIST = false, bool SHADOW = false, int SURF = kSurfNone>
 // (LIST — frames that show little — keeps an item loop's state on top of everything else and needs 142 registers: three waves
 // per SIMD like the AUX / NMAP forms; such a frame does not fill the chip anyway.  MIRROR does not loosen the bound: the plain
 // mirror forms hold RWR_WF_OCC waves like their twins, profiles/mirror_kernel_resources.txt)
 __global__ void __launch_bounds__(256, (AUX || NMAP || LIST || SHADOW) ? 3 : RWR_WF_OCC)
 k_wf_primary(const WfPrimaryArgs a)
 {
+    constexpr bool MIRROR = SURF != kSurfNone, GLASS = SURF == kSurfGlass;
     kernarg<WfPrimaryArgs> *const ka = (kernarg<WfPrimaryArgs> *)__builtin_amdgcn_kernarg_segment_ptr();
     const uint32_t sample_begin = a.sample_begin, sample_count = a.sample_count, z_split = a.z_split;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -440,7 +444,7 @@ k_wf_primary(const WfPrimaryArgs a)
                     }
                 }
                 const v3 P = along(splat3(O), win_t, D);
-                const v3 O1 = v3{P.x + n.x * 1e-4f, P.y + n.y * 1e-4f, P.z + n.z * 1e-4f};
+                v3 O1 = v3{P.x + n.x * 1e-4f, P.y + n.y * 1e-4f, P.z + n.z * 1e-4f};
                 if (SHADOW) {
                     ShadowRec *const recs = wf_args_again(ka)->sw.recs;
                     if (emit.x) {
@@ -470,7 +474,8 @@ k_wf_primary(const WfPrimaryArgs a)
                     float r0 = tab[0], r1 = tab[1], r2 = tab[2], r3 = tab[3];
                     asm volatile("" : "+s"(r0), "+s"(r1), "+s"(r2), "+s"(r3));   // (pinned to scalar registers: not folded into the per-lane read)
                     const float4 m0 = make_float4(r0, r1, r2, r3);
-                    i2 mir = i2{0, 0};
+                    i2 mir = i2{0, 0}, gl = i2{0, 0};
+                    f2 eta = splat(0.0f);   // GLASS: the index of a pixel's glass hit
 #pragma unroll
                     for (int k = 0; k < 2; k++) {
                         const int o = k ? obj.y : obj.x;
@@ -481,11 +486,16 @@ k_wf_primary(const WfPrimaryArgs a)
                                 m = make_float4(tab[4u * i], tab[4u * i + 1u], tab[4u * i + 2u], tab[4u * i + 3u]);
                             }
                             if (m.w != 0.0f) {
-                                if (k) { tr.y = m.x; tgc.y = m.y; tb.y = m.z; mir.y = -1; } else { tr.x = m.x; tgc.x = m.y; tb.x = m.z; mir.x = -1; }
+                                if (k) { tr.y = m.x; tgc.y = m.y; tb.y = m.z; } else { tr.x = m.x; tgc.x = m.y; tb.x = m.z; }
+                                if (GLASS && m.w < 0.0f) {
+                                    if (k) { gl.y = -1; eta.y = -m.w; } else { gl.x = -1; eta.x = -m.w; }
+                                } else {
+                                    if (k) mir.y = -1; else mir.x = -1;
+                                }
                             }
                         }
                     }
-                    const i2 diffuse = emit & ~mir;
+                    const i2 diffuse = emit & ~mir & ~gl;
                     v3 Dd = D, Dm = D;
                     if (__any(any2(diffuse))) Dd = bounce_direction_pair(n, base, diffuse);
                     if (__any(any2(mir))) {   // D' = D - (2 d) n, d = dot3(n, D) (rwr_device.h reflect_direction, for the pair)
@@ -493,6 +503,27 @@ k_wf_primary(const WfPrimaryArgs a)
                         Dm = v3{D.x - two_d * n.x, D.y - two_d * n.y, D.z - two_d * n.z};
                     }
                     D1 = v3{mir ? Dm.x : Dd.x, mir ? Dm.y : Dd.y, mir ? Dm.z : Dd.z};
+                    if (GLASS) {
+                        uint32_t ev[2] = {3u, 3u};
+                        if (__any(any2(gl))) {   // (rwr_device.h refract_or_reflect, one pixel of the pair after the other; dimension 2 of the sample)
+#pragma unroll
+                            for (int k = 0; k < 2; k++)
+                                if (k ? gl.y : gl.x) {
+                                    f3 Dg, mg;
+                                    ev[k] = refract_or_reflect(lane3(n, k), lane3(D, k), (k ? obj.y : obj.x) >= 0, k ? best.ndotd.y : best.ndotd.x,
+                                                               k ? eta.y : eta.x, rng_dim(k ? base.y : base.x, 2u), Dg, mg);
+                                    if (k) { D1.x.y = Dg.x; D1.y.y = Dg.y; D1.z.y = Dg.z; O1.x.y = P.x.y + mg.x * 1e-4f; O1.y.y = P.y.y + mg.y * 1e-4f; O1.z.y = P.z.y + mg.z * 1e-4f; }
+                                    else { D1.x.x = Dg.x; D1.y.x = Dg.y; D1.z.x = Dg.z; O1.x.x = P.x.x + mg.x * 1e-4f; O1.y.x = P.y.x + mg.y * 1e-4f; O1.z.x = P.z.x + mg.z * 1e-4f; }
+                                }
+                            // the wave's events into the frame's three counters: ballots and popcounts, one atomic per kind it saw
+                            unsigned long long *const counts = wf_args_again(ka)->mr.glass_counts;
+#pragma unroll
+                            for (uint32_t c = 0; c < 3u; c++) {
+                                const uint32_t cnt = (uint32_t)__popcll(__ballot(ev[0] == c)) + (uint32_t)__popcll(__ballot(ev[1] == c));
+                                if (cnt && lane == 0u) atomicAdd(&counts[c], (unsigned long long)cnt);
+                            }
+                        }
+                    }
                 } else {
                     D1 = bounce_direction_pair(n, base, emit);
                 }
@@ -540,7 +571,7 @@ k_wf_primary(const WfPrimaryArgs a)
 
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg, const WfBuffers &wf,
-                             uint32_t sample_begin, uint32_t sample_count, uint32_t z_split, const WfShadow *shadow, const WfMirror *mirror)
+                             uint32_t sample_begin, uint32_t sample_count, uint32_t z_split, const WfShadow *shadow, const WfMirror *mirror, bool glass)
 {
     if (fp.row_end <= fp.row_begin || fp.width == 0 || sample_count == 0) return hipSuccess;
     z_split = std::max(1u, std::min(z_split, sample_count));
@@ -549,12 +580,14 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
     const bool aux = (fp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, do_cull = (fp.flags & RWR_FLAG_NO_CULL) == 0;
     const WfPrimaryArgs args{ftris, fp.n_tris, fp.row_begin, fp.bins.enabled, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3],
                              sample_begin, sample_count, z_split, fp, tris, shade, tex, tg, wf,
-                             shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr}, mirror ? *mirror : WfMirror{nullptr, 0u, 0u}};
+                             shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr}, mirror ? *mirror : WfMirror{nullptr, 0u, 0u, nullptr}};
     const bool mirror_on = mirror != nullptr && fp.bounces != 0u;   // (the MIRROR forms differ where rays are emitted, nowhere else)
+    const bool glass_on = mirror_on && glass;                       // the table may hold glass records: the SURF = 2 forms
 #define RWR_WF_ARGS args
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
-#define RWR_WF_LAUNCH_M(A, C, N, L, S, G) do { if (mirror_on) hipLaunchKernelGGL((k_wf_primary<A, C, N, L, S, true>), G, block, 0, s, RWR_WF_ARGS); \
-                                               else hipLaunchKernelGGL((k_wf_primary<A, C, N, L, S, false>), G, block, 0, s, RWR_WF_ARGS); } while (0)
+#define RWR_WF_LAUNCH_M(A, C, N, L, S, G) do { if (glass_on) hipLaunchKernelGGL((k_wf_primary<A, C, N, L, S, kSurfGlass>), G, block, 0, s, RWR_WF_ARGS); \
+                                               else if (mirror_on) hipLaunchKernelGGL((k_wf_primary<A, C, N, L, S, kSurfMirrors>), G, block, 0, s, RWR_WF_ARGS); \
+                                               else hipLaunchKernelGGL((k_wf_primary<A, C, N, L, S, kSurfNone>), G, block, 0, s, RWR_WF_ARGS); } while (0)
 #define RWR_WF_LAUNCH(A, C, N) RWR_WF_LAUNCH_M(A, C, N, false, false, grid)
 #define RWR_WF_LAUNCH_SHADOW(A, C, N, L, G) RWR_WF_LAUNCH_M(A, C, N, L, true, G)
     if (shadow && shadow->recs) {   // the SHADOW forms

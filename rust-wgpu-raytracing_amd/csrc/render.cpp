@@ -19,6 +19,7 @@ struct FrameRequest {
     bool aux, accumulate, shadows;
     bool denoise;     // RWR_FLAG_DENOISE: the filter runs behind the resolve (rp.flags holds the effective flags: AUX implied, this bit cleared)
     bool mirrors;     // RWR_FLAG_MIRRORS with at least one bounce and one mirror surface: the MIRROR forms (else the bit is cleared from rp.flags)
+    bool glass;       // RWR_FLAG_GLASS with at least one bounce and one glass surface: the glass forms (else the bit is cleared from rp.flags)
     bool sky;         // RWR_FLAG_SKY with at least one bounce: the trace kernels' SKY forms (without a bounce the bit is cleared from rp.flags)
     bool wavefront;   // the wavefront integrator renders it (several samples, a bounce, or an accumulation)
     bool dormant;     // the reference's dormant parts (single-triangle passes, orthographic rays) have their own plain kernel
@@ -90,25 +91,35 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
         return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_MIRRORS: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
     if (rp.flags & RWR_FLAG_MIRRORS) {
         bool any = false;
-        for (const MirrorRec &m : ctx->part_mirrors) any = any || m.on != 0.0f;
-        for (uint32_t i = 0; i < ctx->n_spheres; i++) any = any || ctx->sphere_mirrors[i].on != 0.0f;
+        for (const MirrorRec &m : ctx->part_mirrors) any = any || m.on > 0.0f;
+        for (uint32_t i = 0; i < ctx->n_spheres; i++) any = any || ctx->sphere_mirrors[i].on > 0.0f;
         if (rp.max_bounces == 0u || !any) rp.flags &= ~(uint32_t)RWR_FLAG_MIRRORS;
     }
     const bool mirrors = (rp.flags & RWR_FLAG_MIRRORS) != 0;
+    // glass surfaces: the same two rules (rwr_hip.h, RWR_FLAG_GLASS items 10 and 8); a glass record is one with on < 0
+    if ((rp.flags & RWR_FLAG_GLASS) && ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0))
+        return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_GLASS: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
+    if (rp.flags & RWR_FLAG_GLASS) {
+        bool any = false;
+        for (const MirrorRec &m : ctx->part_mirrors) any = any || m.on < 0.0f;
+        for (uint32_t i = 0; i < ctx->n_spheres; i++) any = any || ctx->sphere_mirrors[i].on < 0.0f;
+        if (rp.max_bounces == 0u || !any) rp.flags &= ~(uint32_t)RWR_FLAG_GLASS;
+    }
+    const bool glass = (rp.flags & RWR_FLAG_GLASS) != 0;
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
     // with shadow rays (the integrator's stages trace them) or one the filter follows (it runs behind the integrator's resolve)
     const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate || shadows || denoise;
     const bool dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;
     if (dormant && (wavefront || (rp.flags & RWR_FLAG_USE_BVH)))
         return set_error(RWR_ERR_UNSUPPORTED, "single-triangle passes and RWR_FLAG_ORTHO_RAYS apply to the reference frame (spp 1, no bounce, no RWR_FLAG_USE_BVH)");
-    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, denoise, mirrors, sky, wavefront, dormant};
+    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, denoise, mirrors, glass, sky, wavefront, dormant};
     return RWR_OK;
 }
 
 // What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
 // camera uniform's bytes, the screen, the rows, bounces, seed, flags but the ACCUMULATE bit, frames in flight and the scene — and, while
 // the frame is lit by the sky (RWR_FLAG_SKY), the sky's parameters.  (Mirror surfaces, RWR_FLAG_MIRRORS: the flag is one of the
-// flags, and every call of their setters changes the scene's generation.)
+// flags, and every call of their setters changes the scene's generation; glass surfaces, RWR_FLAG_GLASS, likewise.)
 std::vector<unsigned char> accum_key_of(const rwr_context *ctx, const rwr_camera_inv_uniform &cam, const FrameRequest &rq)
 {
     const uint32_t words[9] = {ctx->screen.width, ctx->screen.height, rq.row_begin, rq.row_end, rq.row_pitch, rq.rp.max_bounces, rq.rp.seed,
@@ -617,10 +628,11 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
                         ctx->wf_packet_dense_rays, wide_lane ? 1u : 0u};
     // RWR_FLAG_MIRRORS: this slot's copy of the surface table — a record per part, then one per sphere index — refreshed on the
     // frame's stream (ahead of the fork below: every queue's kernels read it) when the context's attributes have changed since the slot's last copy
-    WfMirror mirror{nullptr, 0u, 0u};
-    if (rq.mirrors) {
+    WfMirror mirror{nullptr, 0u, 0u, nullptr};
+    const uint32_t modes = (rq.mirrors ? 1u : 0u) | (rq.glass ? 2u : 0u);   // whose records the frame's copy holds: a flag switches its own surfaces on
+    if (modes) {
         const size_t n_parts = ctx->part_mirrors.size(), n_recs = n_parts + RWR_MAX_SPHERES;
-        if (W.mirror_version != ctx->mirror_version || W.d_mirror.count < n_recs) {
+        if (W.mirror_version != ctx->mirror_version || W.mirror_modes != modes || W.d_mirror.count < n_recs) {
             if (W.mirror_version != 0u) RWR_HIP_CHECK(hipEventSynchronize(W.mirror_copied));   // the image's last copy has been read
             if (W.h_mirror_count < n_recs) {
                 W.h_mirror = PinnedMirror();
@@ -629,13 +641,23 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
             }
             RWR_HIP_CHECK(W.d_mirror.ensure(n_recs));
             if (!W.mirror_copied) RWR_HIP_CHECK(hipEventCreateWithFlags(&W.mirror_copied.h, hipEventDisableTiming));
-            for (size_t i = 0; i < n_parts; i++) W.h_mirror.h[i] = ctx->part_mirrors[i];
-            for (size_t i = 0; i < RWR_MAX_SPHERES; i++) W.h_mirror.h[n_parts + i] = ctx->sphere_mirrors[i];
+            auto visible = [&](const MirrorRec &m) {   // a surface whose flag the frame lacks is the diffuse surface it was
+                const bool on = m.on > 0.0f ? rq.mirrors : m.on < 0.0f ? rq.glass : false;
+                return on ? m : MirrorRec{0.0f, 0.0f, 0.0f, 0.0f};
+            };
+            for (size_t i = 0; i < n_parts; i++) W.h_mirror.h[i] = visible(ctx->part_mirrors[i]);
+            for (size_t i = 0; i < RWR_MAX_SPHERES; i++) W.h_mirror.h[n_parts + i] = visible(ctx->sphere_mirrors[i]);
             RWR_HIP_CHECK(hipMemcpyAsync(W.d_mirror.ptr, W.h_mirror.h, n_recs * sizeof(MirrorRec), hipMemcpyHostToDevice, stream));
             RWR_HIP_CHECK(hipEventRecord(W.mirror_copied, stream));
             W.mirror_version = ctx->mirror_version;
+            W.mirror_modes = modes;
         }
-        mirror = WfMirror{W.d_mirror.ptr, (uint32_t)n_parts, 0u};
+        mirror = WfMirror{W.d_mirror.ptr, (uint32_t)n_parts, 0u, nullptr};
+        if (rq.glass) {   // the frame's three event counters start from zero
+            RWR_HIP_CHECK(W.d_glass_counts.ensure(3));
+            RWR_HIP_CHECK(hipMemsetAsync(W.d_glass_counts.ptr, 0, 3 * sizeof(unsigned long long), stream));
+            mirror.glass_counts = W.d_glass_counts.ptr;
+        }
     }
     if (overlap) {   // the other streams start behind this frame's setup (and so behind the previous frame's resolve)
         RWR_HIP_CHECK(hipEventRecord(W.fork, stream));
@@ -653,7 +675,7 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
         const WfShadow sw{rq.shadows ? W.d_shadow_recs.ptr + q * slots : nullptr, rq.shadows ? W.d_shadow_masks.ptr + q * mask_words : nullptr,
                           W.d_shadow_counts.ptr};
         RWR_HIP_CHECK(launch_wf_primary(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg, wfq[q],
-                                        (uint32_t)ap.before + s0, cnt, z_split, rq.shadows ? &sw : nullptr, rq.mirrors ? &mirror : nullptr));
+                                        (uint32_t)ap.before + s0, cnt, z_split, rq.shadows ? &sw : nullptr, modes ? &mirror : nullptr, rq.glass));
         if (rq.shadows)   // h0's shadow rays
             RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], sw, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
         // the bounce stage: one generation of rays per bounce (RWR_FLAG_MULTI_BOUNCE: up to RWR_MAX_BOUNCES).  Generation k traces
@@ -671,7 +693,7 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
             RWR_HIP_CHECK(launch_wf_bounce(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh, tex0, wg, n_tiles, cnt,
                                            (uint32_t)std::fmax(1.0f, std::ceil(ctx->wf_packet_fill * (float)(cnt * kWfTilePixels))),
                                            W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles,
-                                           emit ? &em : nullptr, rq.shadows ? &sw : nullptr, rq.sky ? &sky : nullptr, rq.mirrors ? &mirror : nullptr));
+                                           emit ? &em : nullptr, rq.shadows ? &sw : nullptr, rq.sky ? &sky : nullptr, modes ? &mirror : nullptr, rq.glass));
             if (rq.shadows)   // this generation's hits
                 RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, sw, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
             if (emit) std::swap(wg.masks, masks_next);
@@ -779,6 +801,7 @@ int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const r
     ctx->last_had_bounce = rq.wavefront && rq.rp.max_bounces != 0;
     ctx->last_primary = (uint64_t)ctx->screen.width * band_rows(fc.fp) * ap.trace_spp;
     ctx->last_shadows = rq.shadows;
+    ctx->last_glass = rq.wavefront && rq.glass && ap.trace_spp != 0u;
     ctx->last_bounce = 0;  // filled in lazily by rwr_last_render_stats from the pass counters
     return RWR_OK;
 }

@@ -487,6 +487,35 @@ RWR_DEV f3 reflect_direction(f3 n, f3 D)
     return mk3(D.x - two_d * n.x, D.y - two_d * n.y, D.z - two_d * n.z);
 }
 
+// RWR_FLAG_GLASS: the ray that leaves a hit on glass of index eta (rwr_hip.h, RWR_FLAG_GLASS items 1-6) — a Fresnel reflection, a
+// transmission or a total internal reflection, one formula for all three: D' = a Dh + b n_f.  n: the HitRecord normal
+// hit_exit_point builds; D: the direction of the ray that found the hit, of any length; face / ndotd: a face hit decides its side
+// by the winner's stored N.D (n is flipped towards the ray already), a sphere hit by dot3(n, Dh); u: the generation's first
+// random number (unused under total internal reflection).  m: the side the next ray starts on, its origin is P + 1e-4 m.
+// Returns the event: 0 reflected, 1 transmitted, 2 totally reflected.  f32 operations in this order, no contraction; selects, no
+// branches.
+RWR_DEV uint32_t refract_or_reflect(f3 n, f3 D, bool face, float ndotd, float eta, float u, f3 &D1, f3 &m)
+{
+    const f3 Dh = normalize3(D);
+    const float s = dot3(n, Dh);
+    const bool entering = face ? !(ndotd > 0.0f) : !(s > 0.0f);
+    const f3 nf = (face || entering) ? n : neg3(n);
+    const float c = fminf(1.0f, fmaxf(0.0f, -dot3(nf, Dh)));
+    const float e = entering ? 1.0f / eta : eta;
+    const float k = 1.0f - (e * e) * (1.0f - c * c);
+    const bool tir = k < 0.0f;
+    const float ct = sqrtf(k);   // (NaN under total internal reflection, where nothing reads it)
+    const float q = (1.0f - eta) / (1.0f + eta);
+    const float r0 = q * q;
+    const float x = 1.0f - (entering ? c : ct);
+    const float F = r0 + (1.0f - r0) * (((x * x) * (x * x)) * x);
+    const bool reflect = tir || u < F;
+    const float a = reflect ? 1.0f : e, b = reflect ? 2.0f * c : e * c - ct;
+    D1 = mk3(a * Dh.x + b * nf.x, a * Dh.y + b * nf.y, a * Dh.z + b * nf.z);
+    m = reflect ? nf : neg3(nf);
+    return tir ? 2u : reflect ? 0u : 1u;
+}
+
 // Wavefront integrator: the key a tile's ray pool is sorted by (kernels_wf_primary.hip stores it, kernels_wf_bounce.hip sorts).
 // Direction bin: 3 bits of octant (Gray-coded so that neighbours share two signs) and 2 x kWfDirCellBits bits of position
 // inside the octant's triangle of the octahedral map (Morton order of a 2^bits x 2^bits grid).

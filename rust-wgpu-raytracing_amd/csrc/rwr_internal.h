@@ -329,11 +329,17 @@ static_assert(sizeof(WfSky) == sizeof(rwr_sky_params), "WfSky is rwr_sky_params"
 // the kernels without the flag keep their code.  Part 0's record sits at the table's start: the kernels read it at a constant
 // index — a wave-uniform address, scalar registers — and a one-part scene needs no other for its faces and never looks at
 // ShadeRec::material; spheres and the faces of a scene with several parts read their records per lane.
+// Glass surfaces (RWR_FLAG_GLASS; the glass forms of the same kernels, SURF = 2) share the table: on > 0 marks a mirror, on < 0
+// glass of index -on and tint r, g, b.  A slot's copy holds the surfaces of the flags its frame has, the others' records are
+// zero there, so no kernel looks at a flag.  glass_counts: the frame's three event counters (reflected, transmitted, totally
+// reflected), one atomic per wave; null in the mirror forms.
 struct WfMirror {
     const float4 *table;
     uint32_t n_parts;
     uint32_t pad;
+    unsigned long long *glass_counts;
 };
+constexpr int kSurfNone = 0, kSurfMirrors = 1, kSurfGlass = 2;   // the kernels' SURF argument: no table, mirrors alone, mirrors and glass
 struct BvhNode4;
 struct BvhDevice {
     const BvhNode4 *nodes;
@@ -373,18 +379,19 @@ uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks);
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg,
                              const WfBuffers &wf, uint32_t sample_begin, uint32_t sample_count, uint32_t z_split,
-                             const WfShadow *shadow = nullptr, const WfMirror *mirror = nullptr);
+                             const WfShadow *shadow = nullptr, const WfMirror *mirror = nullptr, bool glass = false);
 // once per frame, ahead of the primary stage, when the frame is expected to show little: fills live_list / live_count / tile_live
 hipError_t launch_wf_classify(hipStream_t s, const FrameParams &fp, const FrameTri *ftris, const Targets &tg, uint32_t tiles_x,
                               uint32_t *live_list, uint32_t *live_count, uint32_t *tile_live);
 // emit: one generation of a deeper path that is not its last — the trace kernels' EMIT forms write every hit's next ray back
 // into its slot; null: the kernels that end the path.  sky: RWR_FLAG_SKY — the SKY forms, a ray that hits nothing adds the sky's term.
-// mirror: RWR_FLAG_MIRRORS — the MIRROR forms of the EMIT kernels (a path's last generation emits nothing: its kernels are the same)
+// mirror: RWR_FLAG_MIRRORS / RWR_FLAG_GLASS — the surface forms of the EMIT kernels (a path's last generation emits nothing: its
+// kernels are the same); glass: the table may hold glass records (the SURF = 2 forms)
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf,
                             uint32_t n_tiles, uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list,
                             const WfEmit *emit = nullptr, const WfShadow *shadow = nullptr, const WfSky *sky = nullptr,
-                            const WfMirror *mirror = nullptr);
+                            const WfMirror *mirror = nullptr, bool glass = false);
 // RWR_FLAG_SHADOWS: traces the shadow records the kernels of one stage left in the queue (the primary stage's, or one generation's
 // trace kernels') and adds the light's part of every term whose ray got through.  light_mesh / light_sphere: the unit directions
 // towards the reference's two lights; expected_tiles: how many tiles are expected to hold records (sizes the work items only).

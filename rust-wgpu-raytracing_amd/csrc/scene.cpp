@@ -245,7 +245,7 @@ int rwr_scene_set_part_mirror(rwr_context *ctx, uint32_t part, const float *refl
     const int rc = mirror_from(reflectance, "part", part, m);
     if (rc != RWR_OK) return rc;   // (a refused call changes nothing, the scene's generation included)
     ctx->scene_generation++;
-    ctx->part_mirrors[part] = m;
+    ctx->part_mirrors[part] = m;   // (a surface has one model: this replaces a glass attribute too)
     ctx->mirror_version++;
     return RWR_OK;
 }
@@ -258,15 +258,16 @@ int rwr_scene_set_sphere_mirror(rwr_context *ctx, uint32_t sphere, const float *
     const int rc = mirror_from(reflectance, "sphere", sphere, m);
     if (rc != RWR_OK) return rc;
     ctx->scene_generation++;
-    ctx->sphere_mirrors[sphere] = m;
+    ctx->sphere_mirrors[sphere] = m;   // (a surface has one model: this replaces a glass attribute too)
     ctx->mirror_version++;
     return RWR_OK;
 }
 
 static void mirror_out(const MirrorRec &m, int *is_mirror, float reflectance[3])
 {
-    if (is_mirror) *is_mirror = m.on != 0.0f ? 1 : 0;
-    if (reflectance) { reflectance[0] = m.r; reflectance[1] = m.g; reflectance[2] = m.b; }
+    const bool on = m.on > 0.0f;   // (on < 0: glass, rwr_scene_set_part_glass)
+    if (is_mirror) *is_mirror = on ? 1 : 0;
+    if (reflectance) { reflectance[0] = on ? m.r : 0.0f; reflectance[1] = on ? m.g : 0.0f; reflectance[2] = on ? m.b : 0.0f; }
 }
 
 int rwr_scene_get_part_mirror(rwr_context *ctx, uint32_t part, int *is_mirror, float reflectance[3])
@@ -282,6 +283,73 @@ int rwr_scene_get_sphere_mirror(rwr_context *ctx, uint32_t sphere, int *is_mirro
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
     if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
     mirror_out(ctx->sphere_mirrors[sphere], is_mirror, reflectance);
+    return RWR_OK;
+}
+
+// RWR_FLAG_GLASS: a surface's attribute from the caller's index of refraction and three floats of tint (tint NULL: not glass).
+// The record is the mirror attribute's: {tint r, g, b, -ior} — on < 0 marks glass, on > 0 a mirror, 0 neither.
+static int glass_from(float ior, const float *tint, const char *what, uint32_t index, MirrorRec &out)
+{
+    if (!tint) {
+        out = MirrorRec{0.0f, 0.0f, 0.0f, 0.0f};
+        return RWR_OK;
+    }
+    if (!(ior >= 1.0f && ior <= 4.0f))   // (false for NaN)
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: ior %g: finite, 1 ... 4", what, index, (double)ior);
+    for (int c = 0; c < 3; c++)
+        if (!(tint[c] >= 0.0f && tint[c] <= 1.0f))
+            return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: tint[%d] %g: finite, 0 ... 1", what, index, c, (double)tint[c]);
+    out = MirrorRec{tint[0], tint[1], tint[2], -ior};
+    return RWR_OK;
+}
+
+int rwr_scene_set_part_glass(rwr_context *ctx, uint32_t part, float ior, const float *tint)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
+    MirrorRec m;
+    const int rc = glass_from(ior, tint, "part", part, m);
+    if (rc != RWR_OK) return rc;   // (a refused call changes nothing, the scene's generation included)
+    ctx->scene_generation++;
+    ctx->part_mirrors[part] = m;   // (a surface has one model: this replaces a mirror attribute too)
+    ctx->mirror_version++;
+    return RWR_OK;
+}
+
+int rwr_scene_set_sphere_glass(rwr_context *ctx, uint32_t sphere, float ior, const float *tint)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
+    MirrorRec m;
+    const int rc = glass_from(ior, tint, "sphere", sphere, m);
+    if (rc != RWR_OK) return rc;
+    ctx->scene_generation++;
+    ctx->sphere_mirrors[sphere] = m;   // (a surface has one model: this replaces a mirror attribute too)
+    ctx->mirror_version++;
+    return RWR_OK;
+}
+
+static void glass_out(const MirrorRec &m, int *is_glass, float *ior, float tint[3])
+{
+    const bool on = m.on < 0.0f;
+    if (is_glass) *is_glass = on ? 1 : 0;
+    if (ior) *ior = on ? -m.on : 0.0f;
+    if (tint) { tint[0] = on ? m.r : 0.0f; tint[1] = on ? m.g : 0.0f; tint[2] = on ? m.b : 0.0f; }
+}
+
+int rwr_scene_get_part_glass(rwr_context *ctx, uint32_t part, int *is_glass, float *ior, float tint[3])
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
+    glass_out(ctx->part_mirrors[part], is_glass, ior, tint);
+    return RWR_OK;
+}
+
+int rwr_scene_get_sphere_glass(rwr_context *ctx, uint32_t sphere, int *is_glass, float *ior, float tint[3])
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
+    glass_out(ctx->sphere_mirrors[sphere], is_glass, ior, tint);
     return RWR_OK;
 }
 

@@ -5,7 +5,8 @@
 //   rwr_render --res DIR [--scene suzanne_lowpoly.obj] [--size 600x600] [--keys "S*15,D*4"]
 //              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows]
 //              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]]
-//              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--show-params] [--out frame.png] [--time]
+//              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]...
+//              [--glass-sphere N[:ior[:r,g,b]]]... [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
 // (KEY in W A S D Up Down Left Right Space LShift, or '-' for no key).  After the script,
@@ -80,6 +81,35 @@ int main(int argc, char **argv)
         for (int c = 0; c < 3; c++) m.r[c] = v[c];
         return true;
     };
+    // --glass-part / --glass-sphere "N", "N:ior" or "N:ior:r,g,b": an index, an index of refraction in [1, 4] (1.5 when left out)
+    // and a tint in [0, 1]^3 (1,1,1 when left out)
+    struct Glass { bool sphere; uint32_t index; float ior; float tint[3]; };
+    std::vector<Glass> glasses;
+    auto parse_glass = [](const char *text, Glass &g) {
+        char *end = nullptr;
+        if (*text < '0' || *text > '9') return false;
+        const unsigned long idx = std::strtoul(text, &end, 10);
+        if (end == text || idx > 0xfffffffful) return false;
+        g.index = (uint32_t)idx;
+        g.ior = 1.5f;
+        g.tint[0] = g.tint[1] = g.tint[2] = 1.0f;
+        if (*end == '\0') return true;
+        if (*end != ':') return false;
+        const char *ior_text = end + 1;
+        if (!((*ior_text >= '0' && *ior_text <= '9') || *ior_text == '.')) return false;   // (no sign, no "nan", no "inf")
+        const float ior = std::strtof(ior_text, &end);
+        if (end == ior_text || !(ior >= 1.0f && ior <= 4.0f)) return false;
+        g.ior = ior;
+        if (*end == '\0') return true;
+        if (*end != ':') return false;
+        float v[3];
+        char tail = 0;
+        if (std::sscanf(end + 1, "%f,%f,%f%c", &v[0], &v[1], &v[2], &tail) != 3) return false;
+        for (int c = 0; c < 3; c++)
+            if (!(v[c] >= 0.0f && v[c] <= 1.0f)) return false;
+        for (int c = 0; c < 3; c++) g.tint[c] = v[c];
+        return true;
+    };
     struct Resize { uint64_t frame; uint32_t w, h; };
     std::vector<Resize> resizes;
     for (int i = 1; i < argc; i++) {
@@ -119,6 +149,15 @@ int main(int argc, char **argv)
             }
             mirrors.push_back(m);
         }
+        else if (a == "--glass-part" || a == "--glass-sphere") {
+            Glass g{a == "--glass-sphere", 0u, 1.5f, {1.0f, 1.0f, 1.0f}};
+            if (!parse_glass(next(), g) || (g.sphere && g.index >= RWR_MAX_SPHERES)) {
+                std::fprintf(stderr, "%s N[:ior[:r,g,b]]: an index%s, an index of refraction in [1, 4] and three numbers in [0, 1]\n", a.c_str(),
+                             g.sphere ? " below 8" : "");
+                return 2;
+            }
+            glasses.push_back(g);
+        }
         else if (a == "--show-params") show_params = true;
         else if (a == "--resize") {
             Resize r{0, 0, 0};
@@ -133,7 +172,8 @@ int main(int argc, char **argv)
             std::printf("usage: rwr_render --res DIR [--scene F.obj] [--size WxH] [--keys \"S*15,D*4\"] [--frames N] "
                         "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] "
                         "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
-                        "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--show-params] [--out frame.png] [--time]\n"
+                        "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]... "
+                        "[--glass-sphere N[:ior[:r,g,b]]]... [--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
                         "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n"
                         "  --shadows     every hit casts a shadow ray towards its light (RWR_FLAG_SHADOWS); works with --spp, --bounces "
@@ -146,6 +186,10 @@ int main(int argc, char **argv)
                         "  --mirror-part N[:r,g,b], --mirror-sphere N[:r,g,b]  part N of the scene / sphere N is a mirror of reflectance r,g,b "
                         "in [0, 1] (1,1,1 when left out) and reflects the ray that found it (RWR_FLAG_MIRRORS, implied; needs --bounces >= 1; "
                         "rwr_scene_set_part_mirror / rwr_scene_set_sphere_mirror); repeatable\n"
+                        "  --glass-part N[:ior[:r,g,b]], --glass-sphere N[:ior[:r,g,b]]  part N of the scene / sphere N is glass of index of "
+                        "refraction ior in [1, 4] (1.5 when left out) and tint r,g,b in [0, 1] (1,1,1 when left out): it reflects by Fresnel's law and "
+                        "refracts by Snell's (RWR_FLAG_GLASS, implied; needs --bounces >= 1, and several for a ray to get through; "
+                        "rwr_scene_set_part_glass / rwr_scene_set_sphere_glass); repeatable\n"
                         "  --show-params prints the render parameters the arguments give and exits, without a device\n");
             return 0;
         } else {
@@ -155,11 +199,14 @@ int main(int argc, char **argv)
     }
     const uint32_t flags = (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u) |   // more than one bounce: the deeper paths
                            (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u) | (denoise ? (uint32_t)RWR_FLAG_DENOISE : 0u) | (sky ? (uint32_t)RWR_FLAG_SKY : 0u) |
-                           (mirrors.empty() ? 0u : (uint32_t)RWR_FLAG_MIRRORS);
+                           (mirrors.empty() ? 0u : (uint32_t)RWR_FLAG_MIRRORS) | (glasses.empty() ? 0u : (uint32_t)RWR_FLAG_GLASS);
     if (show_params) {
-        std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g mirrors %zu", spp, bounces, flags, sky ? 1 : 0,
+        std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g glass %zu", spp, bounces, flags, sky ? 1 : 0,
                     (double)sky_params.zenith[0], (double)sky_params.zenith[1], (double)sky_params.zenith[2],
-                    (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2], mirrors.size());
+                    (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2], glasses.size());
+        for (const Glass &g : glasses)
+            std::printf(" %s %u:%g:%g,%g,%g", g.sphere ? "sphere" : "part", g.index, (double)g.ior, (double)g.tint[0], (double)g.tint[1], (double)g.tint[2]);
+        std::printf(" mirrors %zu", mirrors.size());
         for (const Mirror &m : mirrors)
             std::printf(" %s %u:%g,%g,%g", m.sphere ? "sphere" : "part", m.index, (double)m.r[0], (double)m.r[1], (double)m.r[2]);
         std::printf("\n");
@@ -191,6 +238,10 @@ int main(int argc, char **argv)
         for (const Mirror &m : mirrors) {   // (the scene is loaded: a part the scene does not have is the library's refusal)
             const int rc = m.sphere ? rwr_scene_set_sphere_mirror(state.context(), m.index, m.r) : rwr_scene_set_part_mirror(state.context(), m.index, m.r);
             if (rc != RWR_OK) { std::fprintf(stderr, "%s: %s\n", m.sphere ? "--mirror-sphere" : "--mirror-part", rwr_last_error_string()); return 2; }
+        }
+        for (const Glass &g : glasses) {   // (after the mirrors: a surface has one model, the later option wins)
+            const int rc = g.sphere ? rwr_scene_set_sphere_glass(state.context(), g.index, g.ior, g.tint) : rwr_scene_set_part_glass(state.context(), g.index, g.ior, g.tint);
+            if (rc != RWR_OK) { std::fprintf(stderr, "%s: %s\n", g.sphere ? "--glass-sphere" : "--glass-part", rwr_last_error_string()); return 2; }
         }
         if (denoise_iterations != 0 || denoise_sigma != 0.0f) {
             rwr_denoise_params dp;
