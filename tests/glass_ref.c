@@ -16,7 +16,11 @@
  * The local term of h and its shadow ray (origin P + 1e-4 n) are as ever.  With no glass record it is mirror_render_path,
  * operation for operation.
  * For the tests: gen_rays_out[k] counts every bounce ray of generation k, gen_mirror_out[k] the mirror reflections, events_out[3]
- * the Fresnel reflections, transmissions and total internal reflections, *multi_out the paths with two or more transmissions. */
+ * the Fresnel reflections, transmissions and total internal reflections, *multi_out the paths with two or more transmissions,
+ * *deep_out those with four or more, gen_glass_out[k] the glass events of generation k (the last two may be NULL).
+ * thr_unorm16 (off by default; on for the cases of glass_cases.ROUNDED_THROUGHPUT, in the host tests and on the GPU): the
+ * throughput every bounce ray carries is rounded to unorm16 per channel, as the product's ray record stores it -
+ * for telling that rounding from a fault where a colour misses the bar. */
 #include "mirror_ref.c"
 
 typedef struct { v3 dir, side; int event; } GlassOut;   /* event: 0 reflected, 1 transmitted, 2 totally reflected */
@@ -58,6 +62,16 @@ OR_API void glass_ref_scatter(const float n[3], const float d_in[3], int face, i
     *event_out = o.event;
 }
 
+/* x clamped to [0, 1], rounded to the nearest of 65536 levels and back, as v_cvt_pknorm_u16_f32 and a multiplication by 1 / 65535.
+ * The instruction rounds the exact product x * 65535, which a double holds (24 + 16 bits) and which is a tie only at x = 0.5, where
+ * either convention gives 32768; rounding the f32 product instead lands on k + 0.5 for other x and then goes the wrong way (a tint of
+ * 0.99980926 is one: 65523, not 65522). */
+static inline float unorm16_round(float x)
+{
+    float c = fminf(1.0f, fmaxf(0.0f, x));
+    return (float)(uint32_t)nearbyint((double)c * 65535.0) * (1.0f / 65535.0f);
+}
+
 /* the record of the surface `id` (a face index, or -2 - sphere) */
 static inline const float *surface_of(const float *table, uint32_t n_materials, const Mesh *m, int32_t id)
 {
@@ -87,7 +101,7 @@ OR_API int glass_render_path(const OrCameraInvUniform *cam, const OrScreen *scre
                              int shadows, uint64_t *shadow_rays_out, uint64_t *occluded_out, uint8_t *occl0_out,
                              const float *sky_zenith_horizon, uint64_t *sky_terms_out, float *miss_out,
                              const float *mirrors, uint64_t *gen_mirror_out, uint64_t *gen_rays_out, float *first_out,
-                             uint64_t *events_out, uint64_t *multi_out)
+                             uint64_t *events_out, uint64_t *multi_out, uint64_t *deep_out, uint64_t *gen_glass_out, int thr_unorm16)
 {
     /* scene set-up: render_path_core's */
     const OrMaterial *material = materials;
@@ -144,13 +158,14 @@ OR_API int glass_render_path(const OrCameraInvUniform *cam, const OrScreen *scre
     const int bounce = max_bounces >= 1;
     uint64_t rays = 0, shadow_rays = 0, occluded = 0, sky_terms = 0;
     uint64_t gen_mirror[OR_MAX_GEN] = {0}, gen_rays[OR_MAX_GEN] = {0};
-    uint64_t ev_refl = 0, ev_trans = 0, ev_tir = 0, multi = 0;
+    uint64_t ev_refl = 0, ev_trans = 0, ev_tir = 0, multi = 0, deep = 0;
+    uint64_t gen_glass[OR_MAX_GEN] = {0};
     if (max_bounces >= OR_MAX_GEN) { free(wverts); free(wfaces); free(texs); free(nmaps); return -2; }
     SkyParams skyp;
     const SkyParams *sky = NULL;
     if (sky_zenith_horizon) { memcpy(&skyp, sky_zenith_horizon, sizeof skyp); sky = &skyp; }
 
-#pragma omp parallel for schedule(dynamic, 2) reduction(+ : rays, shadow_rays, occluded, sky_terms, ev_refl, ev_trans, ev_tir, multi, gen_mirror[:OR_MAX_GEN], gen_rays[:OR_MAX_GEN])
+#pragma omp parallel for schedule(dynamic, 2) reduction(+ : rays, shadow_rays, occluded, sky_terms, ev_refl, ev_trans, ev_tir, multi, deep, gen_mirror[:OR_MAX_GEN], gen_rays[:OR_MAX_GEN], gen_glass[:OR_MAX_GEN])
     for (int y = (int)row_begin; y < (int)row_end; y++) {
         for (uint32_t x = 0; x < W; x++) {
             const uint32_t pixel = (uint32_t)y * W + x;
@@ -219,7 +234,8 @@ OR_API int glass_render_path(const OrCameraInvUniform *cam, const OrScreen *scre
                         br.direction = g.dir;
                         br.origin = V3(P.x + g.side.x * 1e-4f, P.y + g.side.y * 1e-4f, P.z + g.side.z * 1e-4f);
                         thr = (k == 1u) ? V3(grec[0], grec[1], grec[2]) : V3(thr_prev.x * grec[0], thr_prev.y * grec[1], thr_prev.z * grec[2]);
-                        if (g.event == 0) ev_refl++; else if (g.event == 1) { ev_trans++; if (++n_trans == 2u) multi++; } else ev_tir++;
+                        if (g.event == 0) ev_refl++; else if (g.event == 1) { ev_trans++; if (++n_trans == 2u) multi++; if (n_trans == 4u) deep++; } else ev_tir++;
+                        gen_glass[k]++;
                     } else if (mrec) {
                         float d = dot3(win.normal, ray.direction);
                         float two_d = 2.0f * d;
@@ -232,6 +248,7 @@ OR_API int glass_render_path(const OrCameraInvUniform *cam, const OrScreen *scre
                     } else {
                         br.direction = pr_bounce_direction_dim(win.normal, pixel, s, params->seed, 2u + 16u * (k - 1u));
                     }
+                    if (thr_unorm16) thr = V3(unorm16_round(thr.x), unorm16_round(thr.y), unorm16_round(thr.z));
                     rays++;
                     gen_rays[k]++;
                     HitRecord h;
@@ -294,9 +311,11 @@ OR_API int glass_render_path(const OrCameraInvUniform *cam, const OrScreen *scre
     if (sky_terms_out) *sky_terms_out = sky_terms;
     if (events_out) { events_out[0] = ev_refl; events_out[1] = ev_trans; events_out[2] = ev_tir; }
     if (multi_out) *multi_out = multi;
+    if (deep_out) *deep_out = deep;
     for (uint32_t k = 0; k <= max_bounces; k++) {
         if (gen_mirror_out) gen_mirror_out[k] = gen_mirror[k];
         if (gen_rays_out) gen_rays_out[k] = gen_rays[k];
+        if (gen_glass_out) gen_glass_out[k] = gen_glass[k];
     }
     return 0;
 }

@@ -106,10 +106,11 @@ def surface_table(n_parts: int, mirror_parts=None, mirror_spheres=None, glass_pa
 
 
 def render_path(L, orc, cam_inv, screen, params, spheres, model, instances=None, rows=None, shadows=False, sky=None, misses=False,
-                mirror_parts=None, mirror_spheres=None, first=False, glass_parts=None, glass_spheres=None, use_mirror_ref=False) -> dict:
+                mirror_parts=None, mirror_spheres=None, first=False, glass_parts=None, glass_spheres=None, use_mirror_ref=False, thr_unorm16=False) -> dict:
     """glass_render_path with mirror_ref.render_path's arguments and the glass surfaces, {part: (ior, tint)} and
     {sphere index: (ior, tint)} (None: none).  The result has mirror_ref's entries and "events": (reflected, transmitted, totally
-    reflected), "multi": the paths with two or more transmissions.
+    reflected), "multi": the paths with two or more transmissions, "deep": those with four or more, "gen_glass": the glass events
+    per generation.  thr_unorm16=True rounds the throughput every bounce ray carries to unorm16, as the product's ray record does.
     use_mirror_ref=True calls mirror_render_path of the same library instead (no glass): what the reference must equal without it."""
     scene = orc.concat_parts(list(model) if isinstance(model, (list, tuple)) else [model])
     w, h = int(screen["width"][0]), int(screen["height"][0])
@@ -146,6 +147,8 @@ def render_path(L, orc, cam_inv, screen, params, spheres, model, instances=None,
         table = np.ascontiguousarray(surface_table(n_mat, mirror_parts, mirror_spheres, glass_parts, glass_spheres))
     events = np.zeros(3, np.uint64)
     multi = np.zeros(1, np.uint64)
+    deep = np.zeros(1, np.uint64)
+    gen_glass = np.zeros(bounces + 1, np.uint64)
     gen_mirror = np.zeros(bounces + 1, np.uint64)
     gen_rays = np.zeros(bounces + 1, np.uint64)
     first_a = np.zeros((h, w, spp, 8), np.float32) if first else None
@@ -158,10 +161,10 @@ def render_path(L, orc, cam_inv, screen, params, spheres, model, instances=None,
         assert not glass_parts and not glass_spheres
         rc = L.mirror_render_path(*args, _p(table), _p(gen_mirror), _p(gen_rays), _p(first_a))
     else:
-        rc = L.glass_render_path(*args, _p(table), _p(gen_mirror), _p(gen_rays), _p(first_a), _p(events), _p(multi))
+        rc = L.glass_render_path(*args, _p(table), _p(gen_mirror), _p(gen_rays), _p(first_a), _p(events), _p(multi), _p(deep), _p(gen_glass), C.c_int(int(thr_unorm16)))
     if rc != 0:
         raise MemoryError("glass_render_path")
     return {"color": color, "depth": depth, "color_f32": color_f, "obj_id": obj_id, "hit_t": hit_t, "rays": int(rays[0]),
             "shadow_rays": int(shadow_rays[0]), "occluded": int(occluded[0]), "occluded0": occl0, "sky_terms": int(sky_terms[0]), "misses": miss,
             "gen_mirror": gen_mirror.astype(np.int64), "gen_rays": gen_rays.astype(np.int64), "first": first_a,
-            "events": tuple(int(v) for v in events), "multi": int(multi[0])}
+            "events": tuple(int(v) for v in events), "multi": int(multi[0]), "deep": int(deep[0]), "gen_glass": gen_glass.astype(np.int64)}

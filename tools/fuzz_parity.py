@@ -8,6 +8,10 @@ the frames compared with the oracle are served from the slot's kept records and 
 --path: path_cases.case(i) for i in [first, first + count) (default: the 64 cases after the committed list; a new context every
 256 cases) against the tests' CPU reference of the extensions taken together (mirror_ref.c), with the tests' own comparison; with
 seconds, the walk ends early once that time is up and says how far it came.
+    python tools/fuzz_parity.py --path --glass [first] [count] [seconds]      see tests/glass_cases.py
+--path --glass: glass_cases.glass_case(g) for g in [first, first + count) (default: the 64 cases after the committed list) against
+glass_ref.c with glass_cases.compare, the three glass event counts included; the cases of glass_cases.ROUNDED_THROUGHPUT against
+the reference that rounds the throughput to unorm16 (glass_cases.compare_rounded); the walk stops at the first mismatch.
 """
 import os
 import sys
@@ -23,27 +27,38 @@ r = g.load_package()
 far = "--far" in sys.argv[1:]
 rest = "--rest" in sys.argv[1:]
 path = "--path" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a not in ("--far", "--rest", "--path")]
+glass = "--glass" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--far", "--rest", "--path", "--glass")]
+if glass and not path:
+    sys.exit("--glass goes with --path")
 if path:
     import tempfile
 
-    import mirror_ref
     import path_cases
 
-    class _Tmp:   # mirror_ref.lib builds into a directory from pytest's factory; here one of our own
+    class _Tmp:   # the references' lib() builds into a directory from pytest's factory; here one of our own
         @staticmethod
         def mktemp(name):
             return tempfile.mkdtemp(prefix=name)
 
-    L = mirror_ref.lib(_Tmp)
+    if glass:     # the list, its reference, its comparison; the glass walk stops at the first mismatch
+        import glass_cases as cases
+        import glass_ref
+
+        L, make, n_listed, what = glass_ref.lib(_Tmp), cases.glass_case, cases.N_GLASS_CASES, "glass"
+    else:
+        import mirror_ref
+
+        cases = path_cases
+        L, make, n_listed, what = mirror_ref.lib(_Tmp), cases.case, cases.N_CASES, "path"
     meshes = {n: ref_loader.load_model_compute(r.RES_DIR, n + ".obj") for n in ("suzanne_lowpoly", "cube")}
-    first = int(args[0]) if len(args) > 0 else path_cases.N_CASES
+    first = int(args[0]) if len(args) > 0 else n_listed
     count = int(args[1]) if len(args) > 1 else 64
     t_end = time.time() + float(args[2]) if len(args) > 2 else None
     worst = worst_ratio = 0.0
     at = None
     t0 = time.time()
-    done, failed, ctx = 0, [], None
+    done, failed, ctx, with_events, events = 0, [], None, 0, [0, 0, 0]
     for i in range(first, first + count):
         if t_end is not None and time.time() >= t_end:
             break
@@ -51,14 +66,34 @@ if path:
             if ctx is not None:
                 ctx.close()
             ctx = r.Context(0)
-        c = path_cases.case(i, ref_loader, orc, meshes["cube"], meshes["suzanne_lowpoly"])
+        c = make(i, ref_loader, orc, meshes["cube"], meshes["suzanne_lowpoly"])
+        got = None
         try:
-            err = path_cases.compare(path_cases.gpu_frame(r, c, ctx), path_cases.reference(L, orc, c), c)
-        except AssertionError as e:      # a mismatch is a finding: say which case, go on (an error of the device is not caught)
+            got = cases.gpu_frame(r, c, ctx)
+            if glass and i in cases.ROUNDED_THROUGHPUT:      # held to the reference that rounds the throughput, as the GPU test holds it
+                err, against_plain = cases.compare_rounded(got, L, orc, c)
+                print(f"glass case {i}: colour error {against_plain:.3g} against the plain reference, {err:.3g} against the one that rounds the "
+                      f"throughput to unorm16 ({err / path_cases.color_bar(c):.2f} of its bar)", flush=True)
+            else:
+                err = cases.compare(got, cases.reference(L, orc, c), c)
+        except AssertionError as e:      # a mismatch is a finding: say which case (an error of the device is not caught)
             failed.append(i)
-            print(f"MISMATCH {e}", flush=True)
+            print(f"MISMATCH at {what} case {i}: {e}", flush=True)
+            if glass and got is None:
+                break
+            if glass:     # where it stops it also says what the reference that rounds the throughput would have said
+                try:
+                    err, _ = cases.compare_rounded(got, L, orc, c)
+                    print(f"glass case {i}: every integer equal; against the reference that rounds the throughput to unorm16 {err:.3g} "
+                          f"({err / path_cases.color_bar(c):.2f} of its bar)", flush=True)
+                except AssertionError as e2:
+                    print(f"glass case {i}: no match with the reference that rounds the throughput either: {e2}", flush=True)
+                break
             err = 0.0
-        path_cases.forget(c)
+        cases.forget(c)
+        if glass:
+            with_events += sum(got["glass"]) > 0
+            events = [a + b for a, b in zip(events, got["glass"])]
         if err / path_cases.color_bar(c) >= worst_ratio:
             worst, worst_ratio, at = err, err / path_cases.color_bar(c), i
         done += 1
@@ -66,7 +101,9 @@ if path:
             print(f"... {done} cases so far, {time.time() - t0:.0f} s, worst colour error {worst:.2e} (case {at}, {worst_ratio:.2f} of its bar)", flush=True)
     if ctx is not None:
         ctx.close()
-    print(f"{'ok' if not failed else 'FAILED ' + str(failed)}: {done} path cases ({first} ... {first + done - 1}) in {time.time() - t0:.0f} s, worst colour error {worst:.2e} (case {at}, {worst_ratio:.2f} of its bar)")
+    seen = f" {with_events} with glass events (reflected, transmitted, totally reflected: {tuple(events)})," if glass else ""
+    print(f"{'ok' if not failed else 'FAILED ' + str(failed)}: {done} {what} cases ({first} ... {first + done - 1}) in {time.time() - t0:.0f} s,{seen} "
+          f"worst colour error {worst:.2e} (case {at}, {worst_ratio:.2f} of its bar)")
     sys.exit(1 if failed else 0)
 seed = int(args[0]) if len(args) > 0 else 1
 seconds = float(args[1]) if len(args) > 1 else 30.0
