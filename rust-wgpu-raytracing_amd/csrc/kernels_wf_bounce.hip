@@ -43,6 +43,7 @@
 #include "rwr_bvh.h"
 #include "rwr_primary.h"
 #include "rwr_shade_p2.h"
+#include "rwr_wf_forms.h"
 #include "rwr_wf_pool.h"
 
 namespace rwr {
@@ -421,6 +422,7 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // (emit_next_ray); separate instantiations for the same reason.
 // SURF: which surface models the EMIT form knows — kSurfNone, kSurfMirrors (RWR_FLAG_MIRRORS alone: the MIRROR forms) or kSurfGlass
 // (RWR_FLAG_GLASS, with or without mirrors: a hit on glass sends on a reflected or a refracted ray with T * C and is counted).
+// Which combinations exist, and how launch_wf_bounce picks one: LaneForms and PacketForms below, behind the kernels.
 template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false, bool SKY = false,
           int SURF = kSurfNone>
 __global__ void __launch_bounds__(WIDE ? 1024 : 256)
@@ -850,22 +852,63 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
     }   // next work item
 }
 
+// The three templates' forms (rwr_wf_forms.h).  Only a kernel that emits rays has a surface form: SURF != kSurfNone only with EMIT.
+struct SortForms {
+    struct Form { bool list; };
+    static constexpr uint32_t kRange = 2u;
+    static constexpr uint32_t encode(Form f) { return f.list; }
+    static constexpr Form decode(uint32_t i) { return Form{i != 0u}; }
+    static constexpr bool valid(Form) { return true; }
+    using Kernel = decltype(&k_wf_sort<false>);
+    template <uint32_t I> static constexpr Kernel kernel() { return &k_wf_sort<decode(I).list>; }
+};
+struct PacketForms {
+    struct Form { bool nmap, emit, shadow, sky; int surf; };
+    static constexpr uint32_t kRange = 16u * 3u;
+    static constexpr uint32_t encode(Form f) { return f.nmap + 2u * f.emit + 4u * f.shadow + 8u * f.sky + 16u * (uint32_t)f.surf; }
+    static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (int)(i >> 4)}; }
+    static constexpr bool valid(Form f) { return f.emit || f.surf == kSurfNone; }
+    using Kernel = decltype(&k_wf_trace_packet<false>);
+    template <uint32_t I> static constexpr Kernel kernel()
+    {
+        constexpr Form f = decode(I);
+        return &k_wf_trace_packet<f.nmap, f.emit, f.shadow, f.sky, f.surf>;
+    }
+};
+// WIDE — 1 024 threads around one copy of the nodelets — only with the nodelets in LDS, 16-bit stacks and no normal map (LaneLdsPlan)
+struct LaneForms {
+    struct Form { bool nodes_in_lds, nmap, stack16, wide, emit, shadow, sky; int surf; };
+    static constexpr uint32_t kRange = 128u * 3u;
+    static constexpr uint32_t encode(Form f)
+    {
+        return f.nodes_in_lds + 2u * f.nmap + 4u * f.stack16 + 8u * f.wide + 16u * f.emit + 32u * f.shadow + 64u * f.sky + 128u * (uint32_t)f.surf;
+    }
+    static constexpr Form decode(uint32_t i)
+    {
+        return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (i & 16u) != 0, (i & 32u) != 0, (i & 64u) != 0, (int)(i >> 7)};
+    }
+    static constexpr bool valid(Form f) { return (f.emit || f.surf == kSurfNone) && (!f.wide || (f.nodes_in_lds && !f.nmap && f.stack16)); }
+    static constexpr bool is_wide(Form f) { return f.wide; }
+    using Kernel = decltype(&k_wf_trace_lane<false, false, false>);
+    template <uint32_t I> static constexpr Kernel kernel()
+    {
+        constexpr Form f = decode(I);
+        return &k_wf_trace_lane<f.nodes_in_lds, f.nmap, f.stack16, f.wide, f.emit, f.shadow, f.sky, f.surf>;
+    }
+};
+static constexpr auto kSortForms = form_table<SortForms>();
+static constexpr auto kPacketForms = form_table<PacketForms>();
+static constexpr auto kLaneForms = form_table<LaneForms>();
+static_assert(check_forms<SortForms>(2) && check_forms<PacketForms>(32), "packets: NMAP x (4 path-ending + 12 EMIT forms)");
+static_assert(check_forms<LaneForms>(144) && count_forms<LaneForms>(LaneForms::is_wide) == 16, "per lane: 8 x 16 with 256 threads, 16 wide");
+
 // RWR_WF_STATS=1 (wf.dbg set): launches of the packet kernel, the per-lane kernel and its WIDE form, by this process
 static std::atomic<uint64_t> g_trace_launches[3];
 
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf, uint32_t n_tiles,
-                            uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list, const WfEmit *emit,
-                            const WfShadow *shadow, const WfSky *sky, const WfMirror *mirror, bool glass)
+                            uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list, const WfFeatures &ft)
 {
-    const WfEmit em = emit ? *emit : WfEmit{nullptr, 0u, 0u};
-    const WfShadow sw = shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr};
-    const bool shadows = sw.recs != nullptr;
-    const WfSky sk = sky ? *sky : WfSky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    const bool sky_on = sky != nullptr;
-    const WfMirror mr = mirror ? *mirror : WfMirror{nullptr, 0u, 0u, nullptr};
-    const bool mirror_on = mirror != nullptr && emit != nullptr;   // (the kernels that end a path emit nothing: no MIRROR form)
-    const bool glass_on = mirror_on && glass;                      // the table may hold glass records: the SURF = 2 forms
     if (n_tiles == 0 || sample_count == 0) return hipSuccess;
     uint32_t *counters = wf.counters;   // this queue's set, zeroed by the primary stage that filled the queue
     PoolInfo *info = static_cast<PoolInfo *>(pool_info);
@@ -873,102 +916,31 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     const bool packets = bvh.stack_depth <= 64u && packet_min_rays <= sample_count * kWfTilePixels && bvh.packet_extent > 0.0f;
     const size_t sort_lds = 2u * (size_t)sample_count * kWfTilePixels * sizeof(uint16_t);
     if (sort_lds > 64u * 1024u) {   // beyond the default limit of dynamic LDS (groups of more than 32 samples)
-        // a function attribute belongs to the function ON ONE DEVICE: raised once per device a context renders on
         static std::atomic<uint64_t> raised_on{0};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
+        const hipError_t e = raise_dynamic_lds_once(raised_on, 144 * 1024, {kSortForms[0], kSortForms[1]});
         if (e != hipSuccess) return e;
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(raised_on.load(std::memory_order_acquire) & bit)) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wf_sort<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wf_sort<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-            if (e != hipSuccess) return e;
-            raised_on.fetch_or(bit, std::memory_order_release);
-        }
     }
-    if (wf.live_list)
-        hipLaunchKernelGGL(k_wf_sort<true>, dim3(std::min(n_tiles, 2048u)), dim3(kWfSortThreads), sort_lds, s, wf, info, counters, pool_list, n_tiles,
-                           sample_count, packets ? packet_min_rays : 0xffffffffu, bvh.packet_extent, bvh.packet_dense_rays);
-    else
-        hipLaunchKernelGGL(k_wf_sort<false>, dim3(n_tiles), dim3(kWfSortThreads), sort_lds, s, wf, info, counters, pool_list, n_tiles,
-                           sample_count, packets ? packet_min_rays : 0xffffffffu, bvh.packet_extent, bvh.packet_dense_rays);
-    const dim3 grid(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit));
+    const bool list = wf.live_list != nullptr;   // striding over the live tiles instead of one workgroup per pool
+    hipLaunchKernelGGL(kSortForms[SortForms::encode({list})], dim3(list ? std::min(n_tiles, 2048u) : n_tiles), dim3(kWfSortThreads), sort_lds, s,
+                       wf, info, counters, pool_list, n_tiles, sample_count, packets ? packet_min_rays : 0xffffffffu, bvh.packet_extent, bvh.packet_dense_rays);
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
-    if (wf.dbg && packets) g_trace_launches[0].fetch_add(1u, std::memory_order_relaxed);
-#define RWR_PACKET_LAUNCH_M(N, E, S, K, M) hipLaunchKernelGGL((k_wf_trace_packet<N, E, S, K, M>), grid, dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk, mr)
-#define RWR_PACKET_LAUNCH_K(N, E, S, K) do { if (E && glass_on) RWR_PACKET_LAUNCH_M(N, E, S, K, (E ? kSurfGlass : kSurfNone)); \
-                                             else if (E && mirror_on) RWR_PACKET_LAUNCH_M(N, E, S, K, (E ? kSurfMirrors : kSurfNone)); \
-                                             else RWR_PACKET_LAUNCH_M(N, E, S, K, kSurfNone); } while (0)
-#define RWR_PACKET_LAUNCH(N, E, S) do { if (sky_on) RWR_PACKET_LAUNCH_K(N, E, S, true); else RWR_PACKET_LAUNCH_K(N, E, S, false); } while (0)
-    if (packets && shadows) {
-        if (emit) { if (nmap) RWR_PACKET_LAUNCH(true, true, true); else RWR_PACKET_LAUNCH(false, true, true); }
-        else { if (nmap) RWR_PACKET_LAUNCH(true, false, true); else RWR_PACKET_LAUNCH(false, false, true); }
-    } else if (packets && emit) {
-        if (nmap) RWR_PACKET_LAUNCH(true, true, false); else RWR_PACKET_LAUNCH(false, true, false);
-    } else if (packets) {
-        if (nmap) RWR_PACKET_LAUNCH(true, false, false); else RWR_PACKET_LAUNCH(false, false, false);
+    const int surf = ft.trace_surf();
+    if (packets) {
+        if (wf.dbg) g_trace_launches[0].fetch_add(1u, std::memory_order_relaxed);
+        hipLaunchKernelGGL(kPacketForms[PacketForms::encode({nmap, ft.emits, ft.shadows, ft.sky_on, surf})], dim3(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit)),
+                           dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, ft.emit, ft.shadow, ft.sky, ft.mirror);
     }
-#undef RWR_PACKET_LAUNCH
-#undef RWR_PACKET_LAUNCH_K
-#undef RWR_PACKET_LAUNCH_M
-    const bool stack16 = bvh.n_nodes <= 0x7fffu && fp.n_tris <= 4095u;   // node indices and leaf links (first << 3 | count - 1) in 15 bits
-    const size_t fixed = (size_t)bvh.stack_depth * 256u * (stack16 ? 2u : 4u);
-    const size_t node_bytes = (size_t)bvh.n_nodes * sizeof(BvhNode4);
-    // nodelets go to LDS when the workgroup then still fits a CU at least four times (160 KiB LDS, 12 KiB static)
-#define RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, M, BYTES) hipLaunchKernelGGL((k_wf_trace_lane<L, N, S16, false, E, S, K, M>), grid, dim3(256), BYTES, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk, mr)
-#define RWR_LANE_LAUNCH_K(L, N, S16, E, S, K, BYTES) do { if (E && glass_on) RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, (E ? kSurfGlass : kSurfNone), BYTES); \
-                                                          else if (E && mirror_on) RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, (E ? kSurfMirrors : kSurfNone), BYTES); \
-                                                          else RWR_LANE_LAUNCH_M(L, N, S16, E, S, K, kSurfNone, BYTES); } while (0)
-#define RWR_LANE_LAUNCH(L, N, S16, E, S, BYTES) do { if (sky_on) RWR_LANE_LAUNCH_K(L, N, S16, E, S, true, BYTES); else RWR_LANE_LAUNCH_K(L, N, S16, E, S, false, BYTES); } while (0)
-#define RWR_LANE_LAUNCH0(L, E, S, BYTES) \
-    if (nmap) { if (stack16) RWR_LANE_LAUNCH(L, true, true, E, S, BYTES); else RWR_LANE_LAUNCH(L, true, false, E, S, BYTES); } \
-    else { if (stack16) RWR_LANE_LAUNCH(L, false, true, E, S, BYTES); else RWR_LANE_LAUNCH(L, false, false, E, S, BYTES); }
-#define RWR_LANE_LAUNCH1(L, E, BYTES) if (shadows) { RWR_LANE_LAUNCH0(L, E, true, BYTES) } else { RWR_LANE_LAUNCH0(L, E, false, BYTES) }
-#define RWR_LANE_LAUNCH2(L, BYTES) if (emit) { RWR_LANE_LAUNCH1(L, true, BYTES) } else { RWR_LANE_LAUNCH1(L, false, BYTES) }
-    const size_t fixed_wide = 4u * fixed, wide_bytes = node_bytes + fixed_wide;
-    const bool wide = node_bytes + fixed > 28u * 1024u && bvh.wide_lane && !nmap && stack16 && wide_bytes + 14u * 1024u <= 160u * 1024u;
-    if (wf.dbg) g_trace_launches[wide ? 2 : 1].fetch_add(1u, std::memory_order_relaxed);
-    if (node_bytes + fixed <= 28u * 1024u) { RWR_LANE_LAUNCH2(true, node_bytes + fixed) }
-    else if (wide) {
-        // a BVH too large for a copy per 256-thread workgroup, small enough for one copy per CU: 1 024-thread workgroups
-        // per form: [emit + 2 * shadows + 4 * sky], the EMIT forms again with mirrors: [8 + (shadows + 2 * sky)], and with glass: [12 + ...]
-#define RWR_WIDE_FORMS(X) X(0, false, false, false, kSurfNone) X(1, true, false, false, kSurfNone) X(2, false, true, false, kSurfNone) X(3, true, true, false, kSurfNone) \
-                          X(4, false, false, true, kSurfNone) X(5, true, false, true, kSurfNone) X(6, false, true, true, kSurfNone) X(7, true, true, true, kSurfNone) \
-                          X(8, true, false, false, kSurfMirrors) X(9, true, true, false, kSurfMirrors) X(10, true, false, true, kSurfMirrors) X(11, true, true, true, kSurfMirrors) \
-                          X(12, true, false, false, kSurfGlass) X(13, true, true, false, kSurfGlass) X(14, true, false, true, kSurfGlass) X(15, true, true, true, kSurfGlass)
-        static std::atomic<uint64_t> wide_raised_on[16];
-        const uint32_t form = mirror_on ? (glass_on ? 12u : 8u) + (shadows ? 1u : 0u) + (sky_on ? 2u : 0u) : (emit ? 1u : 0u) + (shadows ? 2u : 0u) + (sky_on ? 4u : 0u);
-        std::atomic<uint64_t> &raised = wide_raised_on[form];
-        const void *kernel = nullptr;
-        switch (form) {
-#define RWR_WIDE_KERNEL(F, E, S, K, M) case F: kernel = reinterpret_cast<const void *>(&k_wf_trace_lane<true, false, true, true, E, S, K, M>); break;
-        RWR_WIDE_FORMS(RWR_WIDE_KERNEL)
-#undef RWR_WIDE_KERNEL
-        }
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
+    const LaneLdsPlan l = lane_lds_plan(bvh, fp, bvh.wide_lane && !nmap);
+    const uint32_t form = LaneForms::encode({l.nodes_in_lds, nmap, l.stack16, l.wide, ft.emits, ft.shadows, ft.sky_on, surf});
+    if (wf.dbg) g_trace_launches[l.wide ? 2 : 1].fetch_add(1u, std::memory_order_relaxed);
+    if (l.wide) {   // (at most 146 KiB: beyond the default limit, raised per form)
+        static std::atomic<uint64_t> wide_raised_on[LaneForms::kRange];
+        const hipError_t e = raise_dynamic_lds_once(wide_raised_on[form], 146 * 1024, {kLaneForms[form]});
         if (e != hipSuccess) return e;
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(raised.load(std::memory_order_acquire) & bit)) {
-            e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 146 * 1024);
-            if (e != hipSuccess) return e;
-            raised.fetch_or(bit, std::memory_order_release);
-        }
-        switch (form) {
-#define RWR_WIDE_LAUNCH(F, E, S, K, M) case F: hipLaunchKernelGGL((k_wf_trace_lane<true, false, true, true, E, S, K, M>), dim3(std::min(512u, n_tiles * kWfMaxSplit)), dim3(1024), wide_bytes, s, \
-                                                                  fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, em, sw, sk, mr); break;
-        RWR_WIDE_FORMS(RWR_WIDE_LAUNCH)
-#undef RWR_WIDE_LAUNCH
-        }
-#undef RWR_WIDE_FORMS
     }
-    else { RWR_LANE_LAUNCH2(false, fixed) }
-#undef RWR_LANE_LAUNCH2
-#undef RWR_LANE_LAUNCH1
-#undef RWR_LANE_LAUNCH0
-#undef RWR_LANE_LAUNCH
-#undef RWR_LANE_LAUNCH_K
-#undef RWR_LANE_LAUNCH_M
+    const dim3 grid(std::min(l.wide ? 512u : kWfTraceGroups, n_tiles * kWfMaxSplit));
+    hipLaunchKernelGGL(kLaneForms[form], grid, dim3(l.wide ? 1024 : 256), l.bytes, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles,
+                       ft.emit, ft.shadow, ft.sky, ft.mirror);
     return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@
 #include "rwr_primary.h"
 #include "rwr_shade_p2.h"
 #include "rwr_wf_cull.h"
+#include "rwr_wf_forms.h"
 
 namespace rwr {
 
@@ -569,59 +570,42 @@ k_wf_primary(const WfPrimaryArgs a)
     } while (LIST);
 }
 
+// k_wf_primary's forms (rwr_wf_forms.h).  LIST walks the list of the tiles the culling found live: only with CULL.  SHADOW goes
+// with every such (CULL, LIST) — (1, 1), (1, 0), (0, 0) — so it adds no condition of its own.
+struct PrimaryForms {
+    struct Form { bool aux, cull, nmap, list, shadow; int surf; };
+    static constexpr uint32_t kRange = 32u * 3u;
+    static constexpr uint32_t encode(Form f) { return f.aux + 2u * f.cull + 4u * f.nmap + 8u * f.list + 16u * f.shadow + 32u * (uint32_t)f.surf; }
+    static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (i & 16u) != 0, (int)(i >> 5)}; }
+    static constexpr bool valid(Form f) { return !f.list || f.cull; }
+    using Kernel = decltype(&k_wf_primary<false, false, false>);
+    template <uint32_t I> static constexpr Kernel kernel()
+    {
+        constexpr Form f = decode(I);
+        return &k_wf_primary<f.aux, f.cull, f.nmap, f.list, f.shadow, f.surf>;
+    }
+};
+static constexpr auto kPrimaryForms = form_table<PrimaryForms>();
+static_assert(check_forms<PrimaryForms>(72), "8 plain + 4 LIST + 12 SHADOW forms, times three surface models");
+
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg, const WfBuffers &wf,
-                             uint32_t sample_begin, uint32_t sample_count, uint32_t z_split, const WfShadow *shadow, const WfMirror *mirror, bool glass)
+                             uint32_t sample_begin, uint32_t sample_count, uint32_t z_split, const WfFeatures &ft)
 {
     if (fp.row_end <= fp.row_begin || fp.width == 0 || sample_count == 0) return hipSuccess;
     z_split = std::max(1u, std::min(z_split, sample_count));
-    const dim3 grid((fp.width + kWfTileW - 1u) / kWfTileW, band_strips(fp), z_split);
-    const dim3 block(256);
-    const bool aux = (fp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, do_cull = (fp.flags & RWR_FLAG_NO_CULL) == 0;
     const WfPrimaryArgs args{ftris, fp.n_tris, fp.row_begin, fp.bins.enabled, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3],
-                             sample_begin, sample_count, z_split, fp, tris, shade, tex, tg, wf,
-                             shadow ? *shadow : WfShadow{nullptr, nullptr, nullptr}, mirror ? *mirror : WfMirror{nullptr, 0u, 0u, nullptr}};
-    const bool mirror_on = mirror != nullptr && fp.bounces != 0u;   // (the MIRROR forms differ where rays are emitted, nowhere else)
-    const bool glass_on = mirror_on && glass;                       // the table may hold glass records: the SURF = 2 forms
-#define RWR_WF_ARGS args
-    const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
-#define RWR_WF_LAUNCH_M(A, C, N, L, S, G) do { if (glass_on) hipLaunchKernelGGL((k_wf_primary<A, C, N, L, S, kSurfGlass>), G, block, 0, s, RWR_WF_ARGS); \
-                                               else if (mirror_on) hipLaunchKernelGGL((k_wf_primary<A, C, N, L, S, kSurfMirrors>), G, block, 0, s, RWR_WF_ARGS); \
-                                               else hipLaunchKernelGGL((k_wf_primary<A, C, N, L, S, kSurfNone>), G, block, 0, s, RWR_WF_ARGS); } while (0)
-#define RWR_WF_LAUNCH(A, C, N) RWR_WF_LAUNCH_M(A, C, N, false, false, grid)
-#define RWR_WF_LAUNCH_SHADOW(A, C, N, L, G) RWR_WF_LAUNCH_M(A, C, N, L, true, G)
-    if (shadow && shadow->recs) {   // the SHADOW forms
-        const bool list = wf.live_list && do_cull;
-        const dim3 sgrid = list ? dim3(std::min(grid.x * grid.y * z_split, 4096u)) : grid;
-#define RWR_WF_SHADOW_AN(C, L) \
-        if (nmap) { if (aux) RWR_WF_LAUNCH_SHADOW(true, C, true, L, sgrid); else RWR_WF_LAUNCH_SHADOW(false, C, true, L, sgrid); } \
-        else { if (aux) RWR_WF_LAUNCH_SHADOW(true, C, false, L, sgrid); else RWR_WF_LAUNCH_SHADOW(false, C, false, L, sgrid); }
-        if (list) { RWR_WF_SHADOW_AN(true, true) }
-        else if (do_cull) { RWR_WF_SHADOW_AN(true, false) }
-        else { RWR_WF_SHADOW_AN(false, false) }
-#undef RWR_WF_SHADOW_AN
-    } else
-    if (wf.live_list && do_cull) {   // item after item of (live tile) x (share of its samples)
-        const dim3 lgrid(std::min(grid.x * grid.y * z_split, 4096u));
-#define RWR_WF_LAUNCH_LIST(A, N) RWR_WF_LAUNCH_M(A, true, N, true, false, lgrid)
-        if (nmap) { if (aux) RWR_WF_LAUNCH_LIST(true, true); else RWR_WF_LAUNCH_LIST(false, true); }
-        else { if (aux) RWR_WF_LAUNCH_LIST(true, false); else RWR_WF_LAUNCH_LIST(false, false); }
-#undef RWR_WF_LAUNCH_LIST
-    } else if (nmap) {
-        if (aux && do_cull) RWR_WF_LAUNCH(true, true, true);
-        else if (aux) RWR_WF_LAUNCH(true, false, true);
-        else if (do_cull) RWR_WF_LAUNCH(false, true, true);
-        else RWR_WF_LAUNCH(false, false, true);
-    } else {
-        if (aux && do_cull) RWR_WF_LAUNCH(true, true, false);
-        else if (aux) RWR_WF_LAUNCH(true, false, false);
-        else if (do_cull) RWR_WF_LAUNCH(false, true, false);
-        else RWR_WF_LAUNCH(false, false, false);
-    }
-#undef RWR_WF_LAUNCH_SHADOW
-#undef RWR_WF_LAUNCH
-#undef RWR_WF_LAUNCH_M
-#undef RWR_WF_ARGS
+                             sample_begin, sample_count, z_split, fp, tris, shade, tex, tg, wf, ft.shadow, ft.mirror};
+    PrimaryForms::Form f;
+    f.aux = (fp.flags & RWR_FLAG_AUX_OUTPUTS) != 0;
+    f.cull = (fp.flags & RWR_FLAG_NO_CULL) == 0;
+    f.nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
+    f.list = wf.live_list && f.cull;   // item after item of (live tile) x (share of its samples)
+    f.shadow = ft.shadows;
+    f.surf = ft.primary_surf(fp);
+    const dim3 tiles((fp.width + kWfTileW - 1u) / kWfTileW, band_strips(fp), z_split);
+    const dim3 grid = f.list ? dim3(std::min(tiles.x * tiles.y * z_split, 4096u)) : tiles;
+    hipLaunchKernelGGL(kPrimaryForms[PrimaryForms::encode(f)], grid, dim3(256), 0, s, args);
     return hipGetLastError();
 }
 
@@ -670,10 +654,9 @@ hipError_t launch_wf_classify(hipStream_t s, const FrameParams &fp, const FrameT
 {
     if (fp.row_end <= fp.row_begin || fp.width == 0) return hipSuccess;
     const dim3 grid(tiles_x, band_strips(fp));
-#define RWR_WF_CLASSIFY(A) hipLaunchKernelGGL((k_wf_classify<A>), grid, dim3(256), 0, s, ftris, fp.n_tris, fp.row_begin, fp.bins.enabled, \
-        fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3], fp, tg, tiles_x, live_list, live_count, tile_live)
-    if (fp.flags & RWR_FLAG_AUX_OUTPUTS) RWR_WF_CLASSIFY(true); else RWR_WF_CLASSIFY(false);
-#undef RWR_WF_CLASSIFY
+    constexpr decltype(&k_wf_classify<false>) forms[2] = {&k_wf_classify<false>, &k_wf_classify<true>};   // [AUX]
+    hipLaunchKernelGGL(forms[(fp.flags & RWR_FLAG_AUX_OUTPUTS) != 0], grid, dim3(256), 0, s, ftris, fp.n_tris, fp.row_begin, fp.bins.enabled,
+                       fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3], fp, tg, tiles_x, live_list, live_count, tile_live);
     return hipGetLastError();
 }
 

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "rwr_bvh.h"
+#include "rwr_wf_forms.h"
 #include "rwr_wf_pool.h"
 
 namespace rwr {
@@ -110,6 +111,18 @@ k_wf_shadow(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDe
     }
 }
 
+struct ShadowForms {   // rwr_wf_forms.h
+    struct Form { bool nodes_in_lds, stack16; };
+    static constexpr uint32_t kRange = 4u;
+    static constexpr uint32_t encode(Form f) { return f.nodes_in_lds + 2u * f.stack16; }
+    static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0}; }
+    static constexpr bool valid(Form) { return true; }
+    using Kernel = decltype(&k_wf_shadow<false, false>);
+    template <uint32_t I> static constexpr Kernel kernel() { return &k_wf_shadow<decode(I).nodes_in_lds, decode(I).stack16>; }
+};
+static constexpr auto kShadowForms = form_table<ShadowForms>();
+static_assert(check_forms<ShadowForms>(4), "nodelets in LDS or not, 16-bit stacks or not");
+
 hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
                             const WfShadow &shadow, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count, const float light_mesh[3],
                             const float light_sphere[3])
@@ -130,13 +143,9 @@ hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecor
     const uint32_t work_tiles = std::max(1u, std::min(expected_tiles, n_tiles));
     const uint32_t n_shares = std::max(1u, std::min(std::min(32u, sample_count * 8u), 4096u / work_tiles));
     const dim3 grid((uint32_t)std::min<uint64_t>(2048u, (uint64_t)n_tiles * n_shares));
-    const bool stack16 = bvh.n_nodes <= 0x7fffu && fp.n_tris <= 4095u;   // (as launch_wf_bounce)
-    const size_t fixed = (size_t)bvh.stack_depth * 256u * (stack16 ? 2u : 4u);
-    const size_t node_bytes = (size_t)bvh.n_nodes * sizeof(BvhNode4);
-#define RWR_SHADOW_LAUNCH(L, S16, BYTES) hipLaunchKernelGGL((k_wf_shadow<L, S16>), grid, dim3(256), BYTES, s, fp, tris, bvh, wf, shadow, n_tiles, sample_count, n_shares, lights)
-    if (node_bytes + fixed <= 28u * 1024u) { if (stack16) RWR_SHADOW_LAUNCH(true, true, node_bytes + fixed); else RWR_SHADOW_LAUNCH(true, false, node_bytes + fixed); }
-    else { if (stack16) RWR_SHADOW_LAUNCH(false, true, fixed); else RWR_SHADOW_LAUNCH(false, false, fixed); }
-#undef RWR_SHADOW_LAUNCH
+    const LaneLdsPlan l = lane_lds_plan(bvh, fp, false);   // (no 1 024-thread form here)
+    hipLaunchKernelGGL(kShadowForms[ShadowForms::encode({l.nodes_in_lds, l.stack16})], grid, dim3(256), l.bytes, s, fp, tris, bvh, wf, shadow, n_tiles,
+                       sample_count, n_shares, lights);
     return hipGetLastError();
 }
 

@@ -628,7 +628,10 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
                         ctx->wf_packet_dense_rays, wide_lane ? 1u : 0u};
     // RWR_FLAG_MIRRORS: this slot's copy of the surface table — a record per part, then one per sphere index — refreshed on the
     // frame's stream (ahead of the fork below: every queue's kernels read it) when the context's attributes have changed since the slot's last copy
-    WfMirror mirror{nullptr, 0u, 0u, nullptr};
+    // (ft: what the frame's kernels know, WfFeatures — the surfaces and the sky here, a queue's shadow records per launch group,
+    // emit per generation)
+    WfFeatures ft;
+    ft.surf = rq.glass ? kSurfGlass : rq.mirrors ? kSurfMirrors : kSurfNone;
     const uint32_t modes = (rq.mirrors ? 1u : 0u) | (rq.glass ? 2u : 0u);   // whose records the frame's copy holds: a flag switches its own surfaces on
     if (modes) {
         const size_t n_parts = ctx->part_mirrors.size(), n_recs = n_parts + RWR_MAX_SPHERES;
@@ -652,19 +655,19 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
             W.mirror_version = ctx->mirror_version;
             W.mirror_modes = modes;
         }
-        mirror = WfMirror{W.d_mirror.ptr, (uint32_t)n_parts, 0u, nullptr};
+        ft.mirror = WfMirror{W.d_mirror.ptr, (uint32_t)n_parts, 0u, nullptr};
         if (rq.glass) {   // the frame's three event counters start from zero
             RWR_HIP_CHECK(W.d_glass_counts.ensure(3));
             RWR_HIP_CHECK(hipMemsetAsync(W.d_glass_counts.ptr, 0, 3 * sizeof(unsigned long long), stream));
-            mirror.glass_counts = W.d_glass_counts.ptr;
+            ft.mirror.glass_counts = W.d_glass_counts.ptr;
         }
     }
     if (overlap) {   // the other streams start behind this frame's setup (and so behind the previous frame's resolve)
         RWR_HIP_CHECK(hipEventRecord(W.fork, stream));
         for (size_t q = 1; q < n_queues; q++) RWR_HIP_CHECK(hipStreamWaitEvent(W.streams[q], W.fork, 0));
     }
-    WfSky sky{};
-    if (rq.sky) std::memcpy(&sky, &ctx->sky, sizeof sky);
+    if (rq.sky) std::memcpy(&ft.sky, &ctx->sky, sizeof ft.sky);
+    ft.sky_on = rq.sky;
     const uint32_t *last_counters = nullptr;
     // (global sample indices: an accumulating frame traces [accum_before, accum_before + spp), keyed like one frame of them all)
     for (uint32_t s0 = 0, g = 0; s0 < ap.trace_spp; s0 += group, g++) {
@@ -672,12 +675,12 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
         const size_t q = g % n_queues;
         hipStream_t gs = q ? W.streams[q].h : stream;
         const size_t mask_words = (size_t)n_tiles * group * 8u;
-        const WfShadow sw{rq.shadows ? W.d_shadow_recs.ptr + q * slots : nullptr, rq.shadows ? W.d_shadow_masks.ptr + q * mask_words : nullptr,
-                          W.d_shadow_counts.ptr};
+        if (rq.shadows) ft.shadow = WfShadow{W.d_shadow_recs.ptr + q * slots, W.d_shadow_masks.ptr + q * mask_words, W.d_shadow_counts.ptr};
+        ft.shadows = ft.shadow.recs != nullptr;
         RWR_HIP_CHECK(launch_wf_primary(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg, wfq[q],
-                                        (uint32_t)ap.before + s0, cnt, z_split, rq.shadows ? &sw : nullptr, modes ? &mirror : nullptr, rq.glass));
+                                        (uint32_t)ap.before + s0, cnt, z_split, ft));
         if (rq.shadows)   // h0's shadow rays
-            RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], sw, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
+            RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
         // the bounce stage: one generation of rays per bounce (RWR_FLAG_MULTI_BOUNCE: up to RWR_MAX_BOUNCES).  Generation k traces
         // ray k of every path that is still alive — the sort and trace kernels run again over the same fixed slots — and, unless
         // it is the last, writes ray k + 1 back into the slot of every hit, with its bit in the other ballot array.
@@ -687,15 +690,15 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
             if (gen > 1u)   // the sort counts this generation's live pools from zero (the primary stage zeroed the set of four for the first)
                 RWR_HIP_CHECK(hipMemsetAsync(wg.counters, 0, 4u * sizeof(uint32_t), gs));
             const bool emit = gen < rp.max_bounces;
-            const WfEmit em{masks_next, 2u + 16u * gen, (uint32_t)ap.before + s0};
+            ft.emits = emit;
+            ft.emit = emit ? WfEmit{masks_next, 2u + 16u * gen, (uint32_t)ap.before + s0} : WfEmit{nullptr, 0u, 0u};
             if (emit) RWR_HIP_CHECK(hipMemsetAsync(masks_next, 0, (size_t)n_tiles * group * 8u * sizeof(unsigned long long), gs));
-            if (rq.shadows) RWR_HIP_CHECK(hipMemsetAsync(sw.masks, 0, mask_words * sizeof(unsigned long long), gs));   // the trace kernels set bits
+            if (rq.shadows) RWR_HIP_CHECK(hipMemsetAsync(ft.shadow.masks, 0, mask_words * sizeof(unsigned long long), gs));   // the trace kernels set bits
             RWR_HIP_CHECK(launch_wf_bounce(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh, tex0, wg, n_tiles, cnt,
                                            (uint32_t)std::fmax(1.0f, std::ceil(ctx->wf_packet_fill * (float)(cnt * kWfTilePixels))),
-                                           W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles,
-                                           emit ? &em : nullptr, rq.shadows ? &sw : nullptr, rq.sky ? &sky : nullptr, modes ? &mirror : nullptr, rq.glass));
+                                           W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles, ft));
             if (rq.shadows)   // this generation's hits
-                RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, sw, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
+                RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
             if (emit) std::swap(wg.masks, masks_next);
         }
         if (rp.max_bounces && s0 + group >= rp.spp) last_counters = wfq[q].counters;   // the last group's live-pool counts, for the next frame's split

@@ -340,6 +340,21 @@ struct WfMirror {
     unsigned long long *glass_counts;
 };
 constexpr int kSurfNone = 0, kSurfMirrors = 1, kSurfGlass = 2;   // the kernels' SURF argument: no table, mirrors alone, mirrors and glass
+// What the kernels of one launch group know: the four argument structs above — all zero where the frame lacks the flag, and that
+// is what the kernels then get — and the switches the launchers pick the kernels' forms by.  render.cpp fills it once per launch
+// group; `emit` and `emits` change per generation (a generation that is not the path's last: the trace kernels' EMIT forms).
+struct WfFeatures {
+    WfEmit emit{nullptr, 0u, 0u};
+    WfShadow shadow{nullptr, nullptr, nullptr};
+    WfSky sky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    WfMirror mirror{nullptr, 0u, 0u, nullptr};
+    bool emits = false, shadows = false, sky_on = false;
+    int surf = kSurfNone;   // the surface models of the frame's flags (kSurfGlass: the table may hold glass records)
+    // The two rules for SURF.  The surface forms differ where a ray is emitted and nowhere else: the primary stage has one only
+    // when the frame bounces at all, a trace kernel only in a generation that emits (a kernel that ends a path has none).
+    int primary_surf(const FrameParams &fp) const { return fp.bounces != 0u ? surf : kSurfNone; }
+    int trace_surf() const { return emits ? surf : kSurfNone; }
+};
 struct BvhNode4;
 struct BvhDevice {
     const BvhNode4 *nodes;
@@ -376,22 +391,20 @@ hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriReco
                              hipEvent_t ev_stop = nullptr, const FusedSetup *fused = nullptr, const RayPlane *plane = nullptr);
 // grid rows the fused form puts in front of the frame's strips for `n_blocks` record-making workgroups
 uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks);
+// ft (WfFeatures): ft.shadows — the SHADOW forms, which read ft.shadow; ft.primary_surf(fp) — SURF, the forms that read ft.mirror
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg,
-                             const WfBuffers &wf, uint32_t sample_begin, uint32_t sample_count, uint32_t z_split,
-                             const WfShadow *shadow = nullptr, const WfMirror *mirror = nullptr, bool glass = false);
+                             const WfBuffers &wf, uint32_t sample_begin, uint32_t sample_count, uint32_t z_split, const WfFeatures &ft);
 // once per frame, ahead of the primary stage, when the frame is expected to show little: fills live_list / live_count / tile_live
 hipError_t launch_wf_classify(hipStream_t s, const FrameParams &fp, const FrameTri *ftris, const Targets &tg, uint32_t tiles_x,
                               uint32_t *live_list, uint32_t *live_count, uint32_t *tile_live);
-// emit: one generation of a deeper path that is not its last — the trace kernels' EMIT forms write every hit's next ray back
-// into its slot; null: the kernels that end the path.  sky: RWR_FLAG_SKY — the SKY forms, a ray that hits nothing adds the sky's term.
-// mirror: RWR_FLAG_MIRRORS / RWR_FLAG_GLASS — the surface forms of the EMIT kernels (a path's last generation emits nothing: its
-// kernels are the same); glass: the table may hold glass records (the SURF = 2 forms)
+// One generation of rays: the sort, then the trace kernels in the forms of ft (WfFeatures) — ft.emits: a generation of a deeper
+// path that is not its last, the EMIT forms write every hit's next ray back into its slot; else the kernels that end the path.
+// ft.shadows: the SHADOW forms; ft.sky_on: the SKY forms, a ray that hits nothing adds the sky's term; ft.trace_surf(): SURF.
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf,
                             uint32_t n_tiles, uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list,
-                            const WfEmit *emit = nullptr, const WfShadow *shadow = nullptr, const WfSky *sky = nullptr,
-                            const WfMirror *mirror = nullptr, bool glass = false);
+                            const WfFeatures &ft);
 // RWR_FLAG_SHADOWS: traces the shadow records the kernels of one stage left in the queue (the primary stage's, or one generation's
 // trace kernels') and adds the light's part of every term whose ray got through.  light_mesh / light_sphere: the unit directions
 // towards the reference's two lights; expected_tiles: how many tiles are expected to hold records (sizes the work items only).
