@@ -293,7 +293,7 @@ enum {
                                           multi-GPU gather keep their contracts.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or
                                           single-triangle passes: RWR_ERR_UNSUPPORTED, whatever max_bounces is and whether or not a
                                           mirror is set (the refusal comes first, as RWR_FLAG_SKY's). */
-    RWR_FLAG_GLASS = 1u << 11       /* extension: glass surfaces — a scene part or a sphere marked as glass (rwr_scene_set_part_glass,
+    RWR_FLAG_GLASS = 1u << 11,      /* extension: glass surfaces — a scene part or a sphere marked as glass (rwr_scene_set_part_glass,
                                        rwr_scene_set_sphere_glass) of index eta and tint C reflects by Fresnel's law (Schlick's form),
                                        refracts by Snell's, and reflects totally on the way out beyond the critical angle.  Independent
                                        of RWR_FLAG_MIRRORS: each flag switches its own surfaces on; a glass surface in a frame without
@@ -331,6 +331,57 @@ enum {
                                           flight, row bands, strips and the multi-GPU gather keep their contracts.  With
                                           RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED, whatever
                                           max_bounces is and whether or not a surface is glass. */
+    RWR_FLAG_REPROJECT = 1u << 12   /* extension: temporal reprojection — a low-sample frame is blended with the context's history of
+                                       the frames before it, fetched where the point a pixel sees was seen last frame, while the
+                                       camera moves (RWR_FLAG_ACCUMULATE converges only while it rests).  Without the flag every
+                                       frame is what it was, byte for byte, with no further launch or allocation.  With it the frame
+                                       is frame k = 0, 1, ... of the context's history:
+                                       1. The frame always takes the path integrator and is rendered as if RWR_FLAG_AUX_OUTPUTS were
+                                          set (as with RWR_FLAG_DENOISE).  It is traced exactly as the frame without the flag whose
+                                          seed is params.seed + k (mod 2^32): c_now is that frame's resolved color_f32 plane; depth,
+                                          obj_id, hit_t and the render, shadow and glass stats are that frame's, bit for bit.  The
+                                          caller keeps seed fixed; the frames decorrelate through k.
+                                       2. The history goes on while the screen, spp, max_bounces, seed, the effective flags but the
+                                          RWR_FLAG_DENOISE bit, frames in flight, the scene (every accepted setter of a scene
+                                          attribute changes it), the sky's parameters while the sky lights the frame, and
+                                          rwr_reproject_params equal the previous reprojecting frame's.  The camera is NOT part of
+                                          this key.  Anything else starts over at k = 0: rwr_resize, rwr_reproject_reset, a frame
+                                          without the flag in between, an accepted rwr_reproject_set_params (also one that sets the
+                                          values it already has).
+                                       3. Per frame, from the camera uniform alone, in f32 with no contraction: W(x_nds, y_nds) =
+                                          pixelToRay's world_vec before the normalise; c0 = W(0,0), cx = W(1,0) - c0,
+                                          cy = W(0,1) - c0, nrm = cross3(cx, cy).  These, the origin o and the screen are what the
+                                          history keeps of a frame's camera (primed below).
+                                       4. Pixel p = (x, y) of frame k >= 1, id = obj_id(p), t = hit_t(p); the previous frame's history
+                                          planes: colour h, length n, id', t'.  id = -1: out = c_now, n' = 0 (background).
+                                          Otherwise P = O + t Dc on the PIXEL-CENTRE ray (pixelToRay at +0.5, +0.5, not sample 0's
+                                          jittered ray: under a resting camera P lands on p's own centre), d = P - o',
+                                          den = dot3(nrm', d), mu = dot3(nrm', c0') / den; no history unless mu > 0 (false for NaN).
+                                          r = mu d - c0', xn = dot3(cross3(r, cy'), nrm') / dot3(nrm', nrm'),
+                                          yn = dot3(cross3(cx', r), nrm') / dot3(nrm', nrm'), fx = (xn + 1) 0.5 W - 0.5,
+                                          fy = (yn + 1) 0.5 H - 0.5, te = sqrtf(dot3(d, d)).  Taps q = (x0, y0), (x0+1, y0),
+                                          (x0, y0+1), (x0+1, y0+1) with x0 = floorf(fx), a = fx - x0 and the bilinear weights
+                                          (1-a or a) * (1-b or b).  A tap counts if it lies inside the frame (a tap outside is
+                                          skipped, never clamped), id'(q) == id or both ids >= 0 and
+                                          dot3(nhat[id], nhat[id'(q)]) >= normal_cos_min, and fabsf(te - t'(q)) <= depth_rel * te.
+                                          Over the counting taps in tap order: sw += w, sc += w h(q) per channel, sn += w n(q).
+                                          Not sw > 0, or fx / fy not finite: out = c_now, n' = 1 (fresh).  Else hist = sc / sw,
+                                          n' = fminf(sn / sw + 1, (float)max_history), out = hist + (c_now - hist) / n' per channel
+                                          (reused) — and c_now itself when n' == 1: max_history = 1 is the plain frame byte for
+                                          byte.  Frame 0: every hit pixel is fresh.  Alpha is c_now's.  tests/reproject_ref.c pins
+                                          the operation order.
+                                       5. color_f32 = out, the rgba8 plane its conversion as the resolve's; the history stores out, n',
+                                          id, t and this frame's camera.  With RWR_FLAG_DENOISE the filter runs after this stage, on
+                                          out; the history never sees the filter.
+                                       6. The history is the context's, not a frame slot's: the stages run in frame order behind an
+                                          event while tracing overlaps across frames in flight; every number of frames in flight
+                                          gives the same bytes.
+                                       7. RWR_ERR_UNSUPPORTED: together with RWR_FLAG_ACCUMULATE (two histories); rwr_render_rows /
+                                          rwr_render_strips that do not cover the whole frame (taps reach into other ranks' rows);
+                                          RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH, single-triangle passes.  Everything else keeps its
+                                          contract: deeper paths, shadows, sky, mirrors, glass, normal maps, RWR_FLAG_NO_CULL,
+                                          instances and parts — the stage only sees their resolved frame.  The scene is static
+                                          between setters, so no motion vectors are needed. */
 };
 
 #define RWR_MAX_BOUNCES 8u
@@ -633,6 +684,30 @@ typedef struct rwr_sky_params {
 #define RWR_SKY_COMPONENT_MAX 16.0f                                 /* the largest component rwr_sky_set_params takes */
 RWR_API int rwr_sky_set_params(rwr_context *ctx, const rwr_sky_params *params);
 RWR_API int rwr_sky_get_params(rwr_context *ctx, rwr_sky_params *out);
+
+/* RWR_FLAG_REPROJECT: the stage's parameters, per context.  max_history 1 ... 1024 (default 32): the longest history a pixel's
+ * blend weighs in, out = hist + (c_now - hist) / n' with n' <= max_history; normal_cos_min finite and in [-1, 1] (default 0.95) and
+ * depth_rel finite and >= 0 (default 0.05): the tap tests of the flag's item 4, the denoiser's defaults.  Anything else, NaN
+ * included: RWR_ERR_INVALID_ARGUMENT, and the parameters stay as they were.  params = NULL restores the defaults.  Host-side,
+ * waits for nothing.  Every accepted call starts a new history, also one that sets the values the context already has. */
+typedef struct rwr_reproject_params {
+    uint32_t max_history;
+    float normal_cos_min, depth_rel;
+} rwr_reproject_params;
+RWR_API int rwr_reproject_set_params(rwr_context *ctx, const rwr_reproject_params *params);
+RWR_API int rwr_reproject_get_params(rwr_context *ctx, rwr_reproject_params *out);
+/* rwr_reproject_reset: the next reprojecting frame starts a new history, k = 0 (host-side only, nothing waits).
+ * rwr_reproject_frames: how many frames the history of the frame rendered last holds — k + 1, and 0 when that frame did not
+ * reproject.  Host-side, does not wait.
+ * rwr_last_reproject_stats: pixels of the last render call that blended with the history (reused), hit pixels that found none
+ * (fresh) and background pixels; exact counts, reused + fresh + background = width * height (zeros when that frame did not
+ * reproject).  Waits for the frame, as rwr_last_render_stats does.
+ * rwr_reproject_readback: the width * height f32 plane n' of the frame rendered last (RWR_ERR_NOT_READY when it did not
+ * reproject).  It synchronises, as rwr_readback does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_reproject_reset(rwr_context *ctx);
+RWR_API int rwr_reproject_frames(rwr_context *ctx, uint64_t *frames);
+RWR_API int rwr_last_reproject_stats(rwr_context *ctx, uint64_t *reused, uint64_t *fresh, uint64_t *background);
+RWR_API int rwr_reproject_readback(rwr_context *ctx, float *history_len);
 
 /* Self-test of the kernels' short exact forms ("Numerics"): the frame kernel replaces the
  * shader's  ((1/d) - (1/kNear)) / ((1/kFar) - (1/kNear))  (compute.wgsl:78-80) and the three divisions

@@ -52,6 +52,8 @@ FLAG_SKY = 1 << 9            # bounce rays that leave the scene return the sky's
 SKY_PARAMS_DTYPE = np.dtype([("zenith", "<f4", 3), ("horizon", "<f4", 3)])
 FLAG_MIRRORS = 1 << 10       # parts and spheres marked as mirrors reflect the ray that found them (include/rwr_hip.h)
 FLAG_GLASS = 1 << 11         # parts and spheres marked as glass reflect by Fresnel's law and refract by Snell's (include/rwr_hip.h)
+FLAG_REPROJECT = 1 << 12     # temporal reprojection of the context's history while the camera moves; implies FLAG_AUX_OUTPUTS (include/rwr_hip.h)
+REPROJECT_PARAMS_DTYPE = np.dtype([("max_history", "<u4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
 MAX_BOUNCES = 8
 FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
 KEY_FORWARD, KEY_BACKWARD, KEY_LEFT, KEY_RIGHT, KEY_UP, KEY_DOWN = 1, 2, 4, 8, 16, 32
@@ -118,6 +120,8 @@ def lib() -> C.CDLL:
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
         "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
+        "rwr_reproject_set_params": [vp, vp], "rwr_reproject_get_params": [vp, vp], "rwr_reproject_reset": [vp],
+        "rwr_reproject_frames": [vp, vp], "rwr_last_reproject_stats": [vp, vp, vp, vp], "rwr_reproject_readback": [vp, vp],
         "rwr_scene_set_part_mirror": [vp, u32, vp], "rwr_scene_set_sphere_mirror": [vp, u32, vp],
         "rwr_scene_get_part_mirror": [vp, u32, vp, vp], "rwr_scene_get_sphere_mirror": [vp, u32, vp, vp],
         "rwr_scene_set_part_glass": [vp, u32, f32, vp], "rwr_scene_set_sphere_glass": [vp, u32, f32, vp],
@@ -142,7 +146,9 @@ def lib() -> C.CDLL:
     _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats",
                            "rwr_sky_set_params", "rwr_sky_get_params", "rwr_scene_set_part_mirror", "rwr_scene_set_sphere_mirror",
                            "rwr_scene_get_part_mirror", "rwr_scene_get_sphere_mirror", "rwr_scene_set_part_glass", "rwr_scene_set_sphere_glass",
-                           "rwr_scene_get_part_glass", "rwr_scene_get_sphere_glass", "rwr_last_glass_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_scene_get_part_glass", "rwr_scene_get_sphere_glass", "rwr_last_glass_stats",
+                           "rwr_reproject_set_params", "rwr_reproject_get_params", "rwr_reproject_reset", "rwr_reproject_frames",
+                           "rwr_last_reproject_stats", "rwr_reproject_readback")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -726,6 +732,46 @@ class Context:
         _check(lib().rwr_denoise_get_params(self._h, _p(p)))
         return {"iterations": int(p["iterations"][0]), "sigma_color": float(p["sigma_color"][0]),
                 "normal_cos_min": float(p["normal_cos_min"][0]), "depth_rel": float(p["depth_rel"][0])}
+
+    def set_reproject_params(self, max_history=None, normal_cos_min=None, depth_rel=None):
+        """The FLAG_REPROJECT stage's parameters (rwr_reproject_set_params); an argument left out keeps its value, no argument at all
+        restores the defaults.  Out of range or NaN: RwrError(ERR_INVALID_ARGUMENT), and the parameters stay.  Every accepted call
+        starts a new history."""
+        given = {"max_history": max_history, "normal_cos_min": normal_cos_min, "depth_rel": depth_rel}
+        if all(v is None for v in given.values()):
+            _check(lib().rwr_reproject_set_params(self._h, None))
+            return
+        p = np.zeros(1, dtype=REPROJECT_PARAMS_DTYPE)
+        for k, v in self.reproject_params().items():
+            p[k] = v if given[k] is None else given[k]
+        _check(lib().rwr_reproject_set_params(self._h, _p(p)))
+
+    def reproject_params(self) -> dict:
+        p = np.zeros(1, dtype=REPROJECT_PARAMS_DTYPE)
+        _check(lib().rwr_reproject_get_params(self._h, _p(p)))
+        return {"max_history": int(p["max_history"][0]), "normal_cos_min": float(p["normal_cos_min"][0]), "depth_rel": float(p["depth_rel"][0])}
+
+    def reproject_reset(self):
+        """The next FLAG_REPROJECT frame starts a new history."""
+        _check(lib().rwr_reproject_reset(self._h))
+
+    def reproject_frames(self) -> int:
+        """Frames the history of the frame rendered last holds, k + 1 (0: it did not reproject)."""
+        n = C.c_uint64()
+        _check(lib().rwr_reproject_frames(self._h, C.byref(n)))
+        return n.value
+
+    def last_reproject_stats(self) -> tuple[int, int, int]:
+        """(reused, fresh, background) pixels of the last render call; they add up to width * height (rwr_last_reproject_stats)."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rwr_last_reproject_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def reproject_history(self) -> np.ndarray:
+        """The (H, W) float32 plane n' of the frame rendered last (rwr_reproject_readback); it synchronises."""
+        out = np.zeros((self.height, self.width), np.float32)
+        _check(lib().rwr_reproject_readback(self._h, _p(out)))
+        return out
 
     def sky_set_params(self, zenith=None, horizon=None):
         """The FLAG_SKY sky's two colours (rwr_sky_set_params), each three floats in [0, 16]; an argument left out keeps its value,

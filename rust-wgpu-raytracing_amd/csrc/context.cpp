@@ -224,6 +224,8 @@ int rwr_resize(rwr_context *ctx, const rwr_screen *screen)
     RWR_HIP_CHECK(sync_all(ctx));
     ctx->screen = *screen;
     ctx->accum.reset();   // (the key holds the screen size too)
+    ctx->reproj.reset();  // (likewise; a resize to the same size starts a new history too)
+    ctx->last_reproject_frames = 0;
     for (uint32_t i = 0; i < ctx->n_slots; i++) {
         RWR_HIP_CHECK(ensure_slot_targets(ctx, i));
         ctx->slots[i].aux_valid = false;
@@ -460,6 +462,73 @@ int rwr_denoise_get_params(rwr_context *ctx, rwr_denoise_params *out)
 {
     if (!ctx || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
     *out = ctx->denoise;
+    return RWR_OK;
+}
+
+// every accepted call starts a new history, also one that sets the values the context has (as the mirror setters change the scene)
+int rwr_reproject_set_params(rwr_context *ctx, const rwr_reproject_params *params)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    rwr_reproject_params p = kReprojectDefaults;
+    if (params) p = *params;
+    if (p.max_history < 1u || p.max_history > 1024u) return set_error(RWR_ERR_INVALID_ARGUMENT, "reproject max_history %u: 1 ... 1024", p.max_history);
+    if (!(p.normal_cos_min >= -1.0f && p.normal_cos_min <= 1.0f))   // (false for NaN)
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "reproject normal_cos_min %g: finite, -1 ... 1", (double)p.normal_cos_min);
+    if (!(p.depth_rel >= 0.0f) || !std::isfinite(p.depth_rel))
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "reproject depth_rel %g: finite, >= 0", (double)p.depth_rel);
+    ctx->reproject = p;
+    ctx->reproj.key.clear();
+    return RWR_OK;
+}
+
+int rwr_reproject_get_params(rwr_context *ctx, rwr_reproject_params *out)
+{
+    if (!ctx || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = ctx->reproject;
+    return RWR_OK;
+}
+
+int rwr_reproject_reset(rwr_context *ctx)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    ctx->reproj.key.clear();
+    return RWR_OK;
+}
+
+int rwr_reproject_frames(rwr_context *ctx, uint64_t *frames)
+{
+    if (!ctx || !frames) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *frames = ctx->last_reproject_frames;
+    return RWR_OK;
+}
+
+int rwr_last_reproject_stats(rwr_context *ctx, uint64_t *reused, uint64_t *fresh, uint64_t *background)
+{
+    if (!ctx || !reused || !fresh || !background) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    unsigned long long counts[3] = {0ull, 0ull, 0ull};
+    if (ctx->last_reproject_frames != 0 && ctx->reproj.d_counts.ptr) {
+        DeviceGuard g(ctx->device);
+        RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
+        RWR_HIP_CHECK(hipMemcpy(counts, ctx->reproj.d_counts.ptr + 3u * ctx->last_reproject_set, sizeof counts, hipMemcpyDeviceToHost));
+    }
+    *reused = counts[0];
+    *fresh = counts[1];
+    *background = counts[2];
+    return RWR_OK;
+}
+
+int rwr_reproject_readback(rwr_context *ctx, float *history_len)
+{
+    if (!ctx || !history_len) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    const DeviceBuffer<float4> &plane = ctx->reproj.d_colour[ctx->last_reproject_set];
+    const size_t n = (size_t)ctx->screen.width * ctx->screen.height;
+    if (ctx->last_reproject_frames == 0 || !plane.ptr || plane.count < n)
+        return set_error(RWR_ERR_NOT_READY, "the last render did not set RWR_FLAG_REPROJECT");
+    DeviceGuard g(ctx->device);
+    RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
+    std::vector<float4> records(n);   // n' is the fourth float of the history's colour records
+    RWR_HIP_CHECK(hipMemcpy(records.data(), plane.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) history_len[i] = records[i].w;
     return RWR_OK;
 }
 

@@ -18,6 +18,7 @@ struct FrameRequest {
     uint32_t row_begin, row_end, row_pitch;
     bool aux, accumulate, shadows;
     bool denoise;     // RWR_FLAG_DENOISE: the filter runs behind the resolve (rp.flags holds the effective flags: AUX implied, this bit cleared)
+    bool reproject;   // RWR_FLAG_REPROJECT: the reprojection stage runs behind the resolve, ahead of the filter (AUX implied, this bit cleared)
     bool mirrors;     // RWR_FLAG_MIRRORS with at least one bounce and one mirror surface: the MIRROR forms (else the bit is cleared from rp.flags)
     bool glass;       // RWR_FLAG_GLASS with at least one bounce and one glass surface: the glass forms (else the bit is cleared from rp.flags)
     bool sky;         // RWR_FLAG_SKY with at least one bounce: the trace kernels' SKY forms (without a bounce the bit is cleared from rp.flags)
@@ -31,6 +32,12 @@ struct AccumPlan {
     AccumMode mode = AccumMode::kFirst;
     uint64_t before = 0;      // samples the history holds before this frame
     uint32_t trace_spp = 0;   // samples this frame traces
+};
+
+// Temporal reprojection: what this frame does with the context's history.
+struct ReprojectPlan {
+    std::vector<unsigned char> key;
+    uint64_t k = 0;           // the frame's number in the history: 0 starts a new one
 };
 
 // The kernel that renders a frame.  Decided once (choose_kernel); every other question about the frame's form is asked of it.
@@ -79,6 +86,18 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
                              "every %u-th strip is a part of it", row_begin, row_end, row_pitch / kStripRows);
         rp.flags = (rp.flags & ~(uint32_t)RWR_FLAG_DENOISE) | RWR_FLAG_AUX_OUTPUTS;
     }
+    // the reprojection stage gathers from the whole previous frame and blends over the whole of this one, behind the integrator's
+    // resolve: the filter's rules (rwr_hip.h, RWR_FLAG_REPROJECT item 7).  Its bit is not part of the flags the frame is traced with.
+    const bool reproject = (rp.flags & RWR_FLAG_REPROJECT) != 0;
+    if (reproject) {
+        if (accumulate) return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_REPROJECT with RWR_FLAG_ACCUMULATE: a context blends one history, not two");
+        if ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0)
+            return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_REPROJECT: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
+        if (row_begin != 0u || row_end != ctx->screen.height || row_pitch != kStripRows)
+            return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_REPROJECT: the stage needs the whole frame (its taps land anywhere in the previous one); rows [%u,%u) "
+                             "every %u-th strip is a part of it", row_begin, row_end, row_pitch / kStripRows);
+        rp.flags = (rp.flags & ~(uint32_t)RWR_FLAG_REPROJECT) | RWR_FLAG_AUX_OUTPUTS;
+    }
     // the refusal first: it holds whatever max_bounces is (rwr_hip.h, RWR_FLAG_SKY item 7)
     if ((rp.flags & RWR_FLAG_SKY) && ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0))
         return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_SKY: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
@@ -108,11 +127,11 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
     const bool glass = (rp.flags & RWR_FLAG_GLASS) != 0;
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
     // with shadow rays (the integrator's stages trace them) or one the filter follows (it runs behind the integrator's resolve)
-    const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate || shadows || denoise;
+    const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate || shadows || denoise || reproject;
     const bool dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;
     if (dormant && (wavefront || (rp.flags & RWR_FLAG_USE_BVH)))
         return set_error(RWR_ERR_UNSUPPORTED, "single-triangle passes and RWR_FLAG_ORTHO_RAYS apply to the reference frame (spp 1, no bounce, no RWR_FLAG_USE_BVH)");
-    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, denoise, mirrors, glass, sky, wavefront, dormant};
+    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, denoise, reproject, mirrors, glass, sky, wavefront, dormant};
     return RWR_OK;
 }
 
@@ -152,6 +171,69 @@ int plan_accumulation(rwr_context *ctx, const rwr_camera_inv_uniform &cam, const
     }
     ap.trace_spp = ap.mode == AccumMode::kShow ? 0u : rq.rp.spp;
     return RWR_OK;
+}
+
+// What a reprojecting frame must share with the one before for the history to go on (rwr_hip.h RWR_FLAG_REPROJECT item 2): the
+// screen, spp, bounces, seed, the effective flags (the DENOISE and REPROJECT bits are not among them), frames in flight, the scene,
+// the stage's parameters and, while the sky lights the frame, the sky's.  NOT the camera.
+std::vector<unsigned char> reproject_key_of(const rwr_context *ctx, const FrameRequest &rq)
+{
+    const uint32_t words[7] = {ctx->screen.width, ctx->screen.height, rq.rp.spp, rq.rp.max_bounces, rq.rp.seed, rq.rp.flags, ctx->n_slots};
+    std::vector<unsigned char> key(sizeof words + sizeof ctx->scene_generation + sizeof ctx->reproject + (rq.sky ? sizeof ctx->sky : 0u));
+    unsigned char *at = key.data();
+    std::memcpy(at, words, sizeof words); at += sizeof words;
+    std::memcpy(at, &ctx->scene_generation, sizeof ctx->scene_generation); at += sizeof ctx->scene_generation;
+    std::memcpy(at, &ctx->reproject, sizeof ctx->reproject); at += sizeof ctx->reproject;
+    if (rq.sky) std::memcpy(at, &ctx->sky, sizeof ctx->sky);
+    return key;
+}
+
+// Temporal reprojection: does this frame go on with the context's history or start a new one?  A frame without the flag ends it.
+// Frame k is traced with seed + k (mod 2^32).  Committed once the stage is enqueued.
+void plan_reprojection(rwr_context *ctx, FrameRequest &rq, ReprojectPlan &pp)
+{
+    if (rq.reproject) {
+        pp.key = reproject_key_of(ctx, rq);
+        if (pp.key == ctx->reproj.key && ctx->reproj.frames != 0) pp.k = ctx->reproj.frames;
+        rq.rp.seed += (uint32_t)pp.k;
+    } else {
+        ctx->reproj.key.clear();
+        ctx->reproj.frames = 0;
+        ctx->last_reproject_frames = 0;
+    }
+}
+
+// What the history keeps of a frame's camera (rwr_hip.h RWR_FLAG_REPROJECT item 3), in the oracle's f32 operations (this unit is
+// built without contraction): W(x_nds, y_nds) is pixelToRay's world_vec before the normalise, compute.wgsl:151-159.
+RpCamera reproject_camera(const rwr_camera_inv_uniform &cam)
+{
+    auto mul = [](const float (&m)[4][4], const float (&v)[4], float (&r)[4]) {
+        for (int i = 0; i < 4; i++) r[i] = m[0][i] * v[0] + m[1][i] * v[1] + m[2][i] * v[2] + m[3][i] * v[3];
+    };
+    auto world_vec = [&](float x_nds, float y_nds, float (&w)[4]) {
+        const float proj_vec[4] = {x_nds, y_nds, 1.0f, 1.0f};
+        float view_vec[4];
+        mul(cam.proj_inv, proj_vec, view_vec);
+        view_vec[3] = 0.0f;
+        mul(cam.viewmodel_inv, view_vec, w);
+    };
+    float c0[4], wx[4], wy[4];
+    world_vec(0.0f, 0.0f, c0);
+    world_vec(1.0f, 0.0f, wx);
+    world_vec(0.0f, 1.0f, wy);
+    RpCamera rc{};
+    for (int i = 0; i < 3; i++) {
+        rc.o[i] = cam.origin[i];
+        rc.c0[i] = c0[i];
+        rc.cx[i] = wx[i] - c0[i];
+        rc.cy[i] = wy[i] - c0[i];
+    }
+    rc.nrm[0] = rc.cx[1] * rc.cy[2] - rc.cx[2] * rc.cy[1];
+    rc.nrm[1] = rc.cx[2] * rc.cy[0] - rc.cx[0] * rc.cy[2];
+    rc.nrm[2] = rc.cx[0] * rc.cy[1] - rc.cx[1] * rc.cy[0];
+    rc.nc0 = rc.nrm[0] * rc.c0[0] + rc.nrm[1] * rc.c0[1] + rc.nrm[2] * rc.c0[2];
+    rc.nn = rc.nrm[0] * rc.nrm[0] + rc.nrm[1] * rc.nrm[1] + rc.nrm[2] * rc.nrm[2];
+    return rc;
 }
 
 FrameKernel choose_kernel(const rwr_context *ctx, const FrameRequest &rq, const FrameConsts &fc)
@@ -487,8 +569,8 @@ int enqueue_reference(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, F
 // A frame of the wavefront integrator: the samples are traced in launch groups; per group the primary stage (all of the
 // group's samples of every pixel, rays into the fixed-slot queue) then the bounce stage (one workgroup per
 // 64x8-pixel tile and its ray pool)
-int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, AccumPlan &ap, FrameConsts &fc, const Targets &tg,
-                      FrameTiming &timing)
+int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, AccumPlan &ap, ReprojectPlan &pp, FrameConsts &fc,
+                      const Targets &tg, FrameTiming &timing)
 {
     FrameParams &fp = fc.fp;
     const rwr_render_params &rp = rq.rp;
@@ -733,7 +815,35 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
         ctx->last_accum_samples = total;
     }
     W.fix_clean = true;   // (the resolve zeroes what it reads; rows outside the band were never touched)
-    // RWR_FLAG_DENOISE: the filter, behind either resolve on the slot's stream.  (An accumulating frame: behind the event the next
+    // RWR_FLAG_REPROJECT: the stage, behind the resolve on the slot's stream.  The history is the context's, not the slot's: frames
+    // in flight trace side by side, their stages run in frame order behind an event.  Frame k gathers from set (k - 1) & 1 and
+    // writes set k & 1 — the set frame k - 1 read from, which that frame's stage (the event) has finished with.
+    if (rq.reproject) {
+        Reproject &R = ctx->reproj;
+        const uint32_t set = (uint32_t)(pp.k & 1u);
+        for (uint32_t i = 0; i < 2u; i++) {
+            RWR_HIP_CHECK(R.d_colour[i].ensure(n));
+            RWR_HIP_CHECK(R.d_guide[i].ensure(n));
+            RWR_HIP_CHECK(R.d_id[i].ensure(n));
+        }
+        RWR_HIP_CHECK(R.d_counts.ensure(6));
+        if (!R.done) RWR_HIP_CHECK(hipEventCreateWithFlags(&R.done.h, hipEventDisableTiming));
+        if (R.done_recorded) RWR_HIP_CHECK(hipStreamWaitEvent(stream, R.done, 0));
+        RWR_HIP_CHECK(hipMemsetAsync(R.d_counts.ptr + 3u * set, 0, 3 * sizeof(unsigned long long), stream));
+        const RpHistory from{R.d_colour[set ^ 1u].ptr, R.d_guide[set ^ 1u].ptr, R.d_id[set ^ 1u].ptr};
+        const RpHistory to{R.d_colour[set].ptr, R.d_guide[set].ptr, R.d_id[set].ptr};
+        RWR_HIP_CHECK(launch_wf_reproject(stream, fp.width, fp.height, ctx->d_tris.ptr, tg, fp.cam, pp.k ? &R.camera : nullptr, ctx->reproject,
+                                          from, to, R.d_counts.ptr + 3u * set));
+        RWR_HIP_CHECK(hipEventRecord(R.done, stream));
+        R.done_recorded = true;
+        R.camera = reproject_camera(fp.cam);
+        R.key.swap(pp.key);
+        R.frames = pp.k + 1u;
+        ctx->last_reproject_frames = R.frames;
+        ctx->last_reproject_set = set;
+    }
+    // RWR_FLAG_DENOISE: the filter, behind either resolve (and the reprojection stage: it filters `out`, and runs behind the event
+    // the next stage waits for — the history never sees the filter) on the slot's stream.  (An accumulating frame: behind the event the next
     // accumulating resolve waits for — the history never sees the filter, and no other slot waits for it.)
     if (rq.denoise) {
         RWR_HIP_CHECK(sl.d_dn_guide.ensure(n));
@@ -756,6 +866,8 @@ int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const r
     if (rc != RWR_OK) return rc;
     AccumPlan ap;
     if ((rc = plan_accumulation(ctx, *camera, rq, ap)) != RWR_OK) return rc;
+    ReprojectPlan pp;
+    plan_reprojection(ctx, rq, pp);
 
     DeviceGuard g(ctx->device);
     if ((rc = rebuild_tris(ctx)) != RWR_OK) return rc;
@@ -790,7 +902,7 @@ int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const r
     const FrameKernel kernel = choose_kernel(ctx, rq, fc);
 
     FrameTiming timing;
-    rc = kernel == FrameKernel::kWavefront ? enqueue_wavefront(ctx, sl, rq, ap, fc, tg, timing)
+    rc = kernel == FrameKernel::kWavefront ? enqueue_wavefront(ctx, sl, rq, ap, pp, fc, tg, timing)
                                            : enqueue_reference(ctx, sl, rq, kernel, fc, tg, timing);
     if (rc != RWR_OK) return rc;
 

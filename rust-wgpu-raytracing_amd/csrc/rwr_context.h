@@ -121,6 +121,7 @@ struct FrameSlot {
 };
 constexpr uint32_t kMaxFramesInFlight = 3;
 constexpr rwr_denoise_params kDenoiseDefaults{5u, 0.04f, 0.95f, 0.05f};   // RWR_FLAG_DENOISE: DESIGN.md §6 says why these
+constexpr rwr_reproject_params kReprojectDefaults{32u, 0.95f, 0.05f};   // RWR_FLAG_REPROJECT: the tap tests are the denoiser's
 constexpr rwr_sky_params kSkyDefaults = RWR_SKY_DEFAULTS;   // RWR_FLAG_SKY
 constexpr uint32_t kWfMaxQueues = 4;
 
@@ -174,6 +175,28 @@ struct Accum {
     void reset()
     {
         Accum fresh;
+        fresh.done = std::move(done);
+        fresh.done_recorded = done_recorded;
+        *this = std::move(fresh);
+    }
+};
+
+// Temporal reprojection (RWR_FLAG_REPROJECT): ONE history per context, as the accumulation's.  Two sets alternate — frame k reads
+// set (k - 1) & 1 and writes set k & 1 — allocated by the first reprojecting frame; `key` is everything a frame must share with the
+// one before for the history to go on (render.cpp reproject_key_of; the camera is not in it), empty when the next frame starts over.
+struct Reproject {
+    DeviceBuffer<float4> d_colour[2], d_guide[2];   // {r, g, b, n}, {nhat.xyz or zeros, t} (RpHistory)
+    DeviceBuffer<int32_t> d_id[2];
+    DeviceBuffer<unsigned long long> d_counts;      // {reused, fresh, background} per set
+    std::vector<unsigned char> key;
+    uint64_t frames = 0;               // frames the history holds
+    RpCamera camera{};                 // of the frame that wrote the history last
+    OwnedEvent done;                   // recorded after every stage: the next one waits for it (frames in flight)
+    bool done_recorded = false;
+    // a new screen size: the history goes, the event and what it has seen stay
+    void reset()
+    {
+        Reproject fresh;
         fresh.done = std::move(done);
         fresh.done_recorded = done_recorded;
         *this = std::move(fresh);
@@ -259,6 +282,10 @@ struct rwr_context {
     rwr::Accum accum;
     uint64_t accum_max = 1u << 24;         // samples per pixel at most (f32 holds the divisor exactly); RWR_ACCUM_MAX_SAMPLES lowers it
     uint64_t last_accum_samples = 0;       // rwr_accum_samples: of the frame rendered last, 0 when it did not accumulate
+    rwr::Reproject reproj;
+    rwr_reproject_params reproject = rwr::kReprojectDefaults;   // RWR_FLAG_REPROJECT (rwr_reproject_set_params)
+    uint64_t last_reproject_frames = 0;    // rwr_reproject_frames: of the frame rendered last, 0 when it did not reproject
+    uint32_t last_reproject_set = 0;       // ... and the history set it wrote (rwr_reproject_readback, rwr_last_reproject_stats)
     rwr_denoise_params denoise = rwr::kDenoiseDefaults;   // RWR_FLAG_DENOISE (rwr_denoise_set_params)
     rwr_sky_params sky = rwr::kSkyDefaults;               // RWR_FLAG_SKY (rwr_sky_set_params)
     uint64_t scene_generation = 0;         // bumped by every change of the scene (an accumulation does not survive one)

@@ -440,6 +440,24 @@ hipError_t launch_wf_resolve_accum(hipStream_t s, const FrameParams &fp, const T
 hipError_t launch_wf_denoise(hipStream_t s, uint32_t width, uint32_t height, const TriRecord *tris, const Targets &tg,
                              const rwr_denoise_params &dp, float4 *guide, float4 *plane_a, float4 *plane_b);
 
+// RWR_FLAG_REPROJECT (kernels_wf_reproject.hip).  RpCamera: what the history keeps of a frame's camera (rwr_hip.h item 3), made on
+// the host in the oracle's f32 operations (render.cpp reproject_camera); nc0 = dot3(nrm, c0), nn = dot3(nrm, nrm).
+struct RpCamera {
+    float o[3], c0[3], cx[3], cy[3], nrm[3];
+    float nc0, nn;
+};
+// One history set, width * height records each: {r, g, b, n}, {nhat.xyz of the face or zeros, t}, the object id
+struct RpHistory {
+    float4 *colour;
+    float4 *guide;
+    int32_t *id;
+};
+// The stage behind the frame's resolve: tg holds the resolved frame with its aux planes; prev = nullptr: frame 0 of a history
+// (`from` is not read); counts: {reused, fresh, background}, zeroed by the caller.
+hipError_t launch_wf_reproject(hipStream_t s, uint32_t width, uint32_t height, const TriRecord *tris, const Targets &tg,
+                               const rwr_camera_inv_uniform &cam, const RpCamera *prev, const rwr_reproject_params &rp,
+                               const RpHistory &from, const RpHistory &to, unsigned long long *counts);
+
 // per-frame records and tables (kernels_primary.hip): FrameTri + tnum per face, ray tables per column pair / row
 struct FrameSetupOut {
     FrameTri *ftris;   // n_tris

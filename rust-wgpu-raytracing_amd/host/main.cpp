@@ -6,7 +6,8 @@
 //              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows]
 //              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]]
 //              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]...
-//              [--glass-sphere N[:ior[:r,g,b]]]... [--show-params] [--out frame.png] [--time]
+//              [--glass-sphere N[:ior[:r,g,b]]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]]
+//              [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
 // (KEY in W A S D Up Down Left Right Space LShift, or '-' for no key).  After the script,
@@ -15,7 +16,9 @@
 // (0-based, counted over the whole run) -> State::resize (lib.rs:772-989, 1323-1330), including its quirk: the
 // camera's aspect is recomputed from the size BEFORE the resize.  --accumulate (extension): every frame sets
 // RWR_FLAG_ACCUMULATE, so the image converges while the camera rests (any change starts over); the program prints
-// `samples N` for the final frame.
+// `samples N` for the final frame.  --reproject (extension): every frame sets RWR_FLAG_REPROJECT, so every frame — every key step's
+// too — is blended with the history of the frames before it while the camera moves; the program prints `history K` for the
+// final frame.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -49,6 +52,15 @@ int main(int argc, char **argv)
     bool timing = false, accumulate = false, shadows = false, denoise = false;
     int denoise_iterations = 0;      // 0: the library's default
     float denoise_sigma = 0.0f;      // 0: the library's default
+    bool reproject = false, reproject_set = false;
+    rwr_reproject_params reproject_params{32u, 0.95f, 0.05f};   // the library's defaults
+    // a number and nothing else (no "nan", no "inf", no trailing text)
+    auto parse_number = [](const char *text, double &out) {
+        if (!((*text >= '0' && *text <= '9') || *text == '.' || *text == '-' || *text == '+')) return false;
+        char *end = nullptr;
+        out = std::strtod(text, &end);
+        return end != text && *end == '\0' && out == out && out - out == 0.0;
+    };
     bool sky = false, sky_zenith_set = false, sky_horizon_set = false, show_params = false;
     rwr_sky_params sky_params = RWR_SKY_DEFAULTS;   // the library's defaults
     // "r,g,b": three numbers and nothing else, each finite and in [0, 16] (rwr_sky_set_params' range)
@@ -131,6 +143,22 @@ int main(int argc, char **argv)
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-iterations") { denoise = true; denoise_iterations = std::atoi(next()); }
         else if (a == "--denoise-sigma") { denoise = true; denoise_sigma = (float)std::atof(next()); }
+        else if (a == "--reproject") reproject = true;
+        else if (a == "--reproject-history" || a == "--reproject-normal" || a == "--reproject-depth") {
+            double v = 0.0;
+            const bool ok = parse_number(next(), v);
+            if (a == "--reproject-history") {
+                if (!ok || v != (double)(uint32_t)v || v < 1.0 || v > 1024.0) { std::fprintf(stderr, "--reproject-history N: a whole number in [1, 1024]\n"); return 2; }
+                reproject_params.max_history = (uint32_t)v;
+            } else if (a == "--reproject-normal") {
+                if (!ok || v < -1.0 || v > 1.0) { std::fprintf(stderr, "--reproject-normal C: a number in [-1, 1]\n"); return 2; }
+                reproject_params.normal_cos_min = (float)v;
+            } else {
+                if (!ok || v < 0.0 || !((float)v - (float)v == 0.0f)) { std::fprintf(stderr, "--reproject-depth X: a finite number >= 0\n"); return 2; }
+                reproject_params.depth_rel = (float)v;
+            }
+            reproject = reproject_set = true;
+        }
         else if (a == "--sky") sky = true;
         else if (a == "--sky-zenith" || a == "--sky-horizon") {
             const bool zenith = a == "--sky-zenith";
@@ -173,7 +201,8 @@ int main(int argc, char **argv)
                         "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] "
                         "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
                         "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]... "
-                        "[--glass-sphere N[:ior[:r,g,b]]]... [--show-params] [--out frame.png] [--time]\n"
+                        "[--glass-sphere N[:ior[:r,g,b]]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]] "
+                        "[--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
                         "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n"
                         "  --shadows     every hit casts a shadow ray towards its light (RWR_FLAG_SHADOWS); works with --spp, --bounces "
@@ -190,6 +219,10 @@ int main(int argc, char **argv)
                         "refraction ior in [1, 4] (1.5 when left out) and tint r,g,b in [0, 1] (1,1,1 when left out): it reflects by Fresnel's law and "
                         "refracts by Snell's (RWR_FLAG_GLASS, implied; needs --bounces >= 1, and several for a ray to get through; "
                         "rwr_scene_set_part_glass / rwr_scene_set_sphere_glass); repeatable\n"
+                        "  --reproject   every frame is blended with the history of the frames before it, fetched where its points were seen "
+                        "last frame, while the camera moves (RWR_FLAG_REPROJECT; with --keys every key step's frame feeds the next one's history): "
+                        "at most N frames of history per pixel (1-1024), taps of faces whose normals' cosine is at least C and whose distance "
+                        "differs by at most X of itself (rwr_reproject_set_params); a value implies --reproject; prints `history K` for the final frame\n"
                         "  --show-params prints the render parameters the arguments give and exits, without a device\n");
             return 0;
         } else {
@@ -199,8 +232,12 @@ int main(int argc, char **argv)
     }
     const uint32_t flags = (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u) |   // more than one bounce: the deeper paths
                            (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u) | (denoise ? (uint32_t)RWR_FLAG_DENOISE : 0u) | (sky ? (uint32_t)RWR_FLAG_SKY : 0u) |
-                           (mirrors.empty() ? 0u : (uint32_t)RWR_FLAG_MIRRORS) | (glasses.empty() ? 0u : (uint32_t)RWR_FLAG_GLASS);
+                           (mirrors.empty() ? 0u : (uint32_t)RWR_FLAG_MIRRORS) | (glasses.empty() ? 0u : (uint32_t)RWR_FLAG_GLASS) |
+                           (reproject ? (uint32_t)RWR_FLAG_REPROJECT : 0u);
     if (show_params) {
+        if (reproject)   // (a line of its own, ahead of the line every run prints)
+            std::printf("reproject 1 history %u normal %g depth %g\n", reproject_params.max_history, (double)reproject_params.normal_cos_min,
+                        (double)reproject_params.depth_rel);
         std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g glass %zu", spp, bounces, flags, sky ? 1 : 0,
                     (double)sky_params.zenith[0], (double)sky_params.zenith[1], (double)sky_params.zenith[2],
                     (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2], glasses.size());
@@ -251,6 +288,9 @@ int main(int argc, char **argv)
             if (rc == RWR_OK) rc = rwr_denoise_set_params(state.context(), &dp);
             if (rc != RWR_OK) { std::fprintf(stderr, "--denoise: %s\n", rwr_last_error_string()); return 2; }
         }
+        if (reproject_set) {
+            if (rwr_reproject_set_params(state.context(), &reproject_params) != RWR_OK) { std::fprintf(stderr, "--reproject: %s\n", rwr_last_error_string()); return 2; }
+        }
         uint64_t rendered = 0;
         const auto t0 = std::chrono::steady_clock::now();
         auto frame = [&]() {  // [Resized: resize()] then RedrawRequested: update() then render() (lib.rs:1323-1337)
@@ -272,6 +312,7 @@ int main(int argc, char **argv)
         std::printf("frames %llu  eye (%.6f, %.6f, %.6f)  target (%.6f, %.6f, %.6f)  size %ux%u  aspect %.9g\n", (unsigned long long)rendered,
                     c.eye.x, c.eye.y, c.eye.z, c.target.x, c.target.y, c.target.z, state.size().width, state.size().height, (double)c.aspect);
         if (accumulate) std::printf("samples %llu\n", (unsigned long long)state.accumulated_samples());
+        if (reproject) std::printf("history %llu\n", (unsigned long long)state.reprojected_frames());
         if (timing) std::printf("%.3f ms/frame over %llu frames (update + render, host wall clock)\n", sec * 1e3 / (double)rendered,
                                 (unsigned long long)rendered);
         if (!out.empty()) {

@@ -136,6 +136,14 @@ public:
         return n;
     }
 
+    // extension (RWR_FLAG_REPROJECT): frames the history of the frame rendered last holds, 0 when it did not reproject
+    uint64_t reprojected_frames()
+    {
+        uint64_t n = 0;
+        check(rwr_reproject_frames(ctx_, &n));
+        return n;
+    }
+
     // the blit's job (screenquad.wgsl + sRGB swapchain, lib.rs:1186-1224): framebuffer -> PNG
     void present(const std::string &png_path)
     {
