@@ -642,6 +642,20 @@ RWR_API int rwr_frame_setup_launches(rwr_context *ctx, uint64_t *launches);
  * bytes either way.  Host-side, does not wait.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_ray_plane_stats(rwr_context *ctx, uint64_t *builds, uint64_t *frames);
 
+/* The tile classes of the frame rendered last.  With the per-tile face sets (above), k_frame_setup leaves one class word per
+ * 32x4-pixel tile of the two-pixel frame kernel's grid, and the kernel takes one of three ways through a tile by it: a tile no
+ * face and no sphere can show in stores the clear values; a tile with exactly one face and no sphere tests and shades that face
+ * without the state of earlier passes; every other tile runs the whole kernel.  A word holds
+ *   bits 0-1    0: no face survives the tile's culling, or the tile lies outside the mesh's screen rectangle; 1: one; 2: more
+ *   bits 8-15   the face's index when bits 0-1 are 1
+ *   bits 16-23  bit s set: sphere s's silhouette rectangle touches the tile
+ * grid_x, grid_y: the kernel's grid of 64x8-pixel workgroups for the frame's rows; classes (may be NULL: the dimensions alone)
+ * receives 4 * grid_x * grid_y words, word 4 * (by * grid_x + bx) + w for the tile at pixel (64 bx + 32 (w & 1), first row of
+ * strip by + 4 (w >> 1)); capacity: words `classes` has room for.  Waits for that frame alone.  RWR_TILE_CLASS=0 (read when the
+ * context is created) makes the kernel ignore the words — frames are the same bytes either way — the setup writes them all the
+ * same.  RWR_ERR_NOT_READY when the last frame has none (another kernel or form, more than 256 faces, RWR_TILE_LISTS=0). */
+RWR_API int rwr_debug_tile_classes(rwr_context *ctx, uint32_t *classes, size_t capacity, uint32_t *grid_x, uint32_t *grid_y);
+
 /* RWR_FLAG_SHADOWS: shadow rays traced by the last render call (= hits shaded: primary hits and the bounce hits of every
  * generation; an accumulating frame: its own samples; 0 without the flag) and how many of them were occluded.  Exact counts.
  * Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */

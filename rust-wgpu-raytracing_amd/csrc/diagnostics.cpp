@@ -37,6 +37,25 @@ int rwr_selftest_exact_div(rwr_context *ctx, uint32_t count, uint32_t seed, uint
     return run_selftest(ctx, out4, [&](unsigned long long *d) { return launch_selftest_exact_div(ctx->stream, d, count, seed); });
 }
 
+int rwr_debug_tile_classes(rwr_context *ctx, uint32_t *classes, size_t capacity, uint32_t *grid_x, uint32_t *grid_y)
+{
+    if (!ctx || !grid_x || !grid_y) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    const rwr_context::LastClasses lc = ctx->last_classes;
+    const size_t n = (size_t)lc.gx * lc.gy * 4u;
+    if (n == 0 || lc.slot >= ctx->n_slots || ctx->slots[lc.slot].d_tile_lists.count < tile_list_words(lc.gx, lc.gy))
+        return set_error(RWR_ERR_NOT_READY, "the frame rendered last has no tile classes (they come with the per-tile face sets of the "
+                         "two-pixel frame kernel's two-launch form: a scene of at most %u faces, culled)", kTileListMaxFaces);
+    *grid_x = lc.gx;
+    *grid_y = lc.gy;
+    if (!classes) return RWR_OK;
+    if (capacity < n) return set_error(RWR_ERR_INVALID_ARGUMENT, "room for %zu class words, the frame has %zu", capacity, n);
+    DeviceGuard g(ctx->device);
+    FrameSlot &sl = ctx->slots[lc.slot];
+    RWR_HIP_CHECK(hipMemcpyAsync(classes, sl.d_tile_lists.ptr + n * kTileListWords, n * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+    RWR_HIP_CHECK(hipStreamSynchronize(sl.stream));   // that frame's stream alone
+    return RWR_OK;
+}
+
 int rwr_measure_valu_clock(rwr_context *ctx, uint32_t waves_per_simd, double out4[4])
 {
     if (!ctx || !out4) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");

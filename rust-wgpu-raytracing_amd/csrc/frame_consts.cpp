@@ -17,6 +17,7 @@ void build_tex_quads(const uint8_t *rgba8, uint32_t w, uint32_t h, uint32_t *out
         x = std::min<int64_t>(std::max<int64_t>(x, 0), (int64_t)w - 1);
         y = std::min<int64_t>(std::max<int64_t>(y, 0), (int64_t)h - 1);
         const uint8_t *t = rgba8 + 4u * ((size_t)y * w + (size_t)x);
+        // (three bytes at bits 2-9, 12-19, 22-29: bits 0-1, 10-11, 20-21 and 30-31 are clear, which quad_texel relies on)
         return (uint32_t)t[0] << 2 | (uint32_t)t[1] << 12 | (uint32_t)t[2] << 22;
     };
     for (uint32_t py = 0; py <= h; py++)

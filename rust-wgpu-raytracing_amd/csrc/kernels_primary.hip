@@ -142,29 +142,30 @@ hipError_t launch_prebake(hipStream_t s, const rwr_model_vertex_small *verts, co
 // Per-frame setup, one launch: blocks [0, nb_tris) make one face each per thread (the culling record
 // of rwr_cull.h and the ray-independent numerator of the plane distance), the blocks after them fill
 // the ray tables (FrameParams::ray_colp / ray_row), one column pair or one row per thread, and the last
-// out.list_blocks blocks (if any) make the two-pixel frame kernel's per-tile face sets.
+// out.list_blocks blocks (if any) make the two-pixel frame kernel's per-tile face sets and, with tc.classes, the tiles' class words.
 __global__ void __launch_bounds__(256)
 k_frame_setup(const CullConsts cc, const rwr_camera_inv_uniform cam, uint32_t width, uint32_t height,
               const CullRec *__restrict__ cull, const TriRecord *__restrict__ tris, uint32_t n_tris, uint32_t nb_tris,
-              uint32_t nb_setup, const FrameSetupOut out)
+              uint32_t nb_setup, const FrameSetupOut out, const TileClassIn tc)
 {
     // The launch runs while the other frame slot's frame kernel fills every SIMD, and its end starts this slot's frame kernel:
     // its waves (a few hundred dependent instructions each) take issue priority over the frame kernel's.
     __builtin_amdgcn_s_setprio(3);
-    if (blockIdx.x >= nb_setup) frame_tile_lists_block(blockIdx.x - nb_setup, cc, cull, n_tris, out);   // rwr_frame_setup.h
+    if (blockIdx.x >= nb_setup) frame_tile_lists_block(blockIdx.x - nb_setup, cc, cull, n_tris, out, tc);   // rwr_frame_setup.h
     else frame_setup_block(blockIdx.x, nb_setup, cc, cam, width, height, cull, tris, n_tris, nb_tris, out);
 }
 
 hipError_t launch_frame_setup(hipStream_t s, const CullConsts &cc, const rwr_camera_inv_uniform &cam, uint32_t width,
                               uint32_t height, const CullRec *cull, const TriRecord *tris, uint32_t n_tris,
-                              const FrameSetupOut &out)
+                              const FrameSetupOut &out, const TileClassIn &tc)
 {
     const uint32_t nb_tris = (n_tris + 255u) / 256u, nb_tab = (out.ray_pairs + out.ray_rows + 255u) / 256u;
     if (out.tile_lists && (n_tris == 0 || n_tris > kTileListMaxFaces || out.list_blocks == 0)) return hipErrorInvalidValue;
+    if (tc.classes && (!out.tile_lists || tc.n_spheres > RWR_MAX_SPHERES)) return hipErrorInvalidValue;   // (the class words come with the sets)
     const uint32_t nb_lists = out.tile_lists ? out.list_blocks : 0u;
     if (nb_tris + nb_tab + nb_lists == 0) return hipSuccess;
     hipLaunchKernelGGL(k_frame_setup, dim3(nb_tris + nb_tab + nb_lists), dim3(256), 0, s, cc, cam, width, height, cull, tris, n_tris,
-                       nb_tris, nb_tris + nb_tab, out);
+                       nb_tris, nb_tris + nb_tab, out, tc);
     return hipGetLastError();
 }
 

@@ -33,6 +33,10 @@ namespace rwr {
 // (rwr_internal.h RayPlane, filled by k_ray_plane from the same function) instead of computed from the ray tables.  The form has
 // no use for the tables, and the plane's two arrays arrive in the tables' arguments (ray_colp: RayPlane::xy, ray_row:
 // RayPlane::z), so that the kernel's arguments, and with them the code of every other form, stay what they were.
+// Tile classes (the forms that walk per-tile face sets: CULL, not FUSED; RWR_FLAG_TILE_CLASS): the setup leaves a class word
+// with every tile's set (rwr_internal.h kTileFaces*), and a wave takes one of three ways through its tile by it — clear values
+// for a tile nothing can show in, a straight path for exactly one face and no sphere, the whole kernel otherwise.  The ways
+// meet again at the stores: one tail, so that the form's registers are those of the general path alone.
 template <bool AUX, bool CULL, bool NMAP, bool FUSED = false, bool PLANE = false>
 __global__ void __launch_bounds__(256, (AUX || NMAP) ? 4 : RWR_P2_OCC)
 // (the first eleven arguments repeat FrameParams fields: they are what a wave needs first, and the Makefile
@@ -145,6 +149,11 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
         for (uint32_t k = 0; k < kTileListWords; k++) set[k] = rec[k];
         n_list = 0u;
     }
+    // ... and, requested with it, the tile's class word (rwr_internal.h kTileFaces*; a parallel array behind the grid's sets): what
+    // the compares below and the set's population would tell, found out by the setup.  RWR_TILE_CLASS=0: never looked at.
+    const bool classed = lists && (p.flags & RWR_FLAG_TILE_CLASS) != 0u;   // (uniform)
+    uint32_t cls = 0u;
+    if (classed) cls = to_const_space(p.tile_lists)[gridDim.x * gridDim.y * 4u * kTileListWords + (by * gridDim.x + blockIdx.x) * 4u + wu];
     __shared__ float4 s_rec[CULL ? 4 : 1][CULL ? 256 : 1];   // round's culling records, one plane per 16 B of FrameTri
     __shared__ uint32_t s_face[CULL ? 256 : 1];              // ... and their face indices
     __shared__ float s_lut[256];                             // sRGB decode table of the quad texels (rwr_internal.h QuadTex)
@@ -179,15 +188,128 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
         D = pixel_pair_ray_dir_tab(p.cam, ray_colp, ray_row, px0, py);
     }
 
+    // where the pair's results go, and the stores (every way through a tile ends in them)
+    struct PairSlot { bool in_frame, both, pair_store; uint32_t o; };
+    auto pair_slot = [&](uint32_t px0, uint32_t py) {
+        PairSlot ps;
+        ps.in_frame = py < p.row_end && px0 < p.width;
+        ps.o = py * p.width + px0;  // < 2^30 pixels (rwr_resize)
+        ps.both = px0 + 1u < p.width;
+        ps.pair_store = ps.both && (ps.o & 1u) == 0u;
+        return ps;
+    };
+    // depth plane first (nothing behind it needs it): 8-byte aligned pair whenever the width is even
+    auto store_depth = [&](const PairSlot &ps, f2 depth_tex) {
+        if (ps.in_frame) {
+            if (ps.pair_store) {
+                // streaming stores: the targets are written once and never read here; they must not push the
+                // texture and the face records out of the L2 (3.7 % of the frame rate)
+                __builtin_nontemporal_store(depth_tex, reinterpret_cast<f2 *>(tg.depth + ps.o));
+            } else {
+                tg.depth[ps.o] = depth_tex.x;
+                if (ps.both) tg.depth[ps.o + 1] = depth_tex.y;
+            }
+        }
+    };
+    auto store_colour = [&](const PairSlot &ps, const uint32_t (&rgba)[2], const float4 (&cf)[2], i2 obj, f2 win_t, uint32_t dbg_listed,
+                            uint32_t dbg_tested) {
+        if (ps.in_frame) {
+            const uint32_t o = ps.o;
+            if (ps.pair_store) {
+                __builtin_nontemporal_store(u2{rgba[0], rgba[1]}, reinterpret_cast<u2 *>(reinterpret_cast<uint32_t *>(tg.color) + o));
+            } else {
+                reinterpret_cast<uint32_t *>(tg.color)[o] = rgba[0];
+                if (ps.both) reinterpret_cast<uint32_t *>(tg.color)[o + 1] = rgba[1];
+            }
+            if (AUX) {
+                const bool dbg = (p.flags & RWR_FLAG_DEBUG_COUNTS) != 0;
+                reinterpret_cast<float4 *>(tg.color_f32)[o] = cf[0];
+                tg.obj_id[o] = dbg ? (int32_t)dbg_listed : obj.x;
+                tg.hit_t[o] = dbg ? (float)dbg_tested : win_t.x;
+                if (ps.both) {
+                    reinterpret_cast<float4 *>(tg.color_f32)[o + 1] = cf[1];
+                    tg.obj_id[o + 1] = dbg ? (int32_t)dbg_listed : obj.y;
+                    tg.hit_t[o + 1] = dbg ? (float)dbg_tested : win_t.y;
+                }
+            }
+        }
+    };
+    // the mesh winners' colours as rgba8unorm (rwr_device.h; alpha 2.0 -> 255) over what the pair holds
+    auto pack_mesh = [&](i2 obj, f2 cr, f2 cg, f2 cb, uint32_t (&rgba)[2], float4 (&cf)[2]) {
+        const f2 sr = cr * 255.0f, sg = cg * 255.0f, sb = cb * 255.0f;
+        const uint32_t m0 = pack_rgba8_scaled(sr.x, sg.x, sb.x, 0xff000000u);
+        const uint32_t m1 = pack_rgba8_scaled(sr.y, sg.y, sb.y, 0xff000000u);
+        rgba[0] = obj.x >= 0 ? m0 : rgba[0];
+        rgba[1] = obj.y >= 0 ? m1 : rgba[1];
+        if (AUX) {
+            if (obj.x >= 0) cf[0] = make_float4(cr.x, cg.x, cb.x, 2.0f);
+            if (obj.y >= 0) cf[1] = make_float4(cr.y, cg.y, cb.y, 2.0f);
+        }
+    };
+
+    // -- the tile's class, known to the setup: three ways through the tile, chosen once per wave (uniform), which meet again where
+    // the pair's results are stored ----------------------------------------------------------------------------------------------
+    constexpr uint32_t kWayNone = 0u, kWayOne = 1u, kWayAll = 2u;
+    const uint32_t tile_class = cls & (kTileFacesMask | kTileSphereMask);
+    const uint32_t way = !classed ? kWayAll
+                         : tile_class == kTileFacesNone ? kWayNone
+                         : (tile_class == kTileFacesOne && !NMAP && !(p.n_materials > 1u)) ? kWayOne : kWayAll;
     // framebuffer state of the two pixels, as the reference's cleared textures hold it
     f2 depth_tex = splat(0.0f), win_t = splat(0.0f);
     i2 obj = i2{-1, -1};
+    MeshHit2 best;
+    best.have = i2{0, 0};
+    best.t = best.u = best.v = best.ndotd = splat(0.0f);
+    best.idx = u2{0u, 0u};
+    uint32_t dbg_listed = 0, dbg_tested = 0;
+    uint32_t n_tested = 0;  // wave-uniform
+    uint32_t last_idx = 0;  // (wave-uniform) the face tested last: a wave that tested exactly one face loads its shading
+                            // record for the shading step, into scalar registers (carried through the loop, the record's
+                            // 11 dwords lived in vector registers)
+    ShadeRec one_shade = {};   // (kWayOne: that record, requested with the face's other records)
+    if (way == kWayNone) {
+        // no face and no sphere can show: the cleared frame.  No sphere pass, no mesh pass, no shading, no use for the ray; the
+        // wave still meets its workgroup at the table's barrier.
+        rwait();
+        __syncthreads();
+    } else if (way == kWayOne) {
+        // exactly one face and no sphere: the straight path.  The face's index is in the class word, so its records — the hit
+        // test's, the numerator and the shading's — are requested at once, ahead of the table's barrier; there is no state of an
+        // earlier pass to composite with: the framebuffer holds the clear values, the first hit is the nearest.  The arithmetic is
+        // the general path's own functions, which therefore give its bits.
+        const uint32_t idx = (cls >> kTileFaceShift) & 0xffu;
+        const TriRecord T = tris[idx];
+        const float tnum = to_const_space(p.tnum)[idx];
+        one_shade = shade[idx];
+        rwait();   // (the table's barrier)
+        __syncthreads();
+        f2 u, v;
+        best.have = triangle_hit(T, tnum, O, D, best.t, u, v, best.ndotd);
+        best.u = best.have ? u : splat(0.0f);   // (a pair without a hit shades texel (0, 0) and drops the result, as ever)
+        best.v = best.have ? v : splat(0.0f);
+        best.idx = u2{idx, idx};
+        last_idx = idx;
+        n_tested = 1u;
+        if (AUX) dbg_listed = dbg_tested = 1u;
+        // the depth test against the cleared plane: current_depth = 1 - 0 (compute.wgsl:210)
+        const bool fast = !__any(any2(best.have & ~depth_fast_domain(best.t)));
+        const f2 depth = fast ? to_non_linear_depth_fast(best.t) : to_non_linear_depth(best.t);
+        const i2 win = best.have & ~(depth >= 1.0f);
+        depth_tex = win ? (1.0f - depth) : splat(0.0f);
+        obj = win ? i2{(int)idx, (int)idx} : i2{-1, -1};
+        win_t = win ? best.t : splat(0.0f);
+    } else {
+    // -- every other tile ---------------------------------------------------------------------------------------------------
 
     // -- analytic sphere passes, in order (lib.rs:1106-1173) -----------------
+    // (classed: the setup made the rectangle compares, bit s of the word's sphere field says "not outside"; a tile that touches
+    // no sphere does not enter the loop, nor what the compiler hoists out of it)
     const float tx0 = (float)tile_x0, ty0 = (float)tile_y0;
-    for (uint32_t s = 0; s < p.n_spheres; s++) {
-        if (CULL && ((tx0 + kTileWf < p.sphere_rect[s][0]) || (tx0 > p.sphere_rect[s][2]) ||
-                     (ty0 + kTileHf < p.sphere_rect[s][1]) || (ty0 > p.sphere_rect[s][3])))
+    const uint32_t sph = classed ? (cls >> kTileSphereShift) & 0xffu : 0xffu;
+    for (uint32_t s = 0; sph != 0u && s < p.n_spheres; s++) {
+        if (classed ? ((sph >> s) & 1u) == 0u
+                    : (CULL && ((tx0 + kTileWf < p.sphere_rect[s][0]) || (tx0 > p.sphere_rect[s][2]) ||
+                                (ty0 + kTileHf < p.sphere_rect[s][1]) || (ty0 > p.sphere_rect[s][3]))))
             continue;
         f2 t = splat(0.0f);
         const i2 hit = sphere_ray_intersect_t(ld3(p.spheres[s].center), p.spheres[s].radius, O, D, t);
@@ -202,15 +324,6 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
     }
 
     // -- mesh pass (lib.rs:1174-1184) -----------------------------------------
-    MeshHit2 best;
-    best.have = i2{0, 0};
-    best.t = best.u = best.v = best.ndotd = splat(0.0f);
-    best.idx = u2{0u, 0u};
-    uint32_t dbg_listed = 0, dbg_tested = 0;
-    uint32_t n_tested = 0;  // wave-uniform
-    uint32_t last_idx = 0;  // (wave-uniform) the face tested last: a wave that tested exactly one face loads its shading
-                            // record for the shading step, into scalar registers (carried through the loop, the record's
-                            // 11 dwords lived in vector registers)
     if constexpr (CULL) {
         // Each wave culls the round's records for its own tile, 64 at a time, one per lane (rwr_cull.h), and walks the
         // survivors in ascending face order.  Every wave reaches every barrier: n_list is the workgroup's (a wave
@@ -295,22 +408,10 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
         obj = win ? i2{(int)best.idx.x, (int)best.idx.y} : obj;
         win_t = win ? best.t : win_t;
     }
+    }   // (kWayAll)
 
-    // depth plane first (nothing below needs it): 8-byte aligned pair whenever the width is even
-    const bool in_frame = py < p.row_end && px0 < p.width;
-    const uint32_t o = py * p.width + px0;  // < 2^30 pixels (rwr_resize)
-    const bool both = px0 + 1u < p.width;
-    const bool pair_store = both && (o & 1u) == 0u;
-    if (in_frame) {
-        if (pair_store) {
-            // streaming stores: the targets are written once and never read here; they must not push the
-            // texture and the face records out of the L2 (3.7 % of the frame rate)
-            __builtin_nontemporal_store(depth_tex, reinterpret_cast<f2 *>(tg.depth + o));
-        } else {
-            tg.depth[o] = depth_tex.x;
-            if (both) tg.depth[o + 1] = depth_tex.y;
-        }
-    }
+    const PairSlot ps = pair_slot(px0, py);
+    store_depth(ps, depth_tex);
 
     // -- shade the winners and store --------------------------------------------
     // Sphere winners first (few tiles; one pixel at a time), straight to their packed form, so that the
@@ -342,40 +443,12 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
         else if (p.n_materials > 1u) shade_mesh_pair<true, false, false, FrameParams, QuadTex>(p, shade, qt, obj, unused, best, D, cr, cg, cb);
         else if (n_tested == 1u) {
             // the one face the wave tested (so the scene has faces and the record array exists): every mesh winner shows it
-            const ShadeRec last_shade = FUSED ? load_shade_record(shade_c + last_idx) : shade[last_idx];
+            const ShadeRec last_shade = way == kWayOne ? one_shade : FUSED ? load_shade_record(shade_c + last_idx) : shade[last_idx];
             shade_mesh_pair<false, true, false, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);
         } else shade_mesh_pair<false, false, false, FrameParams, QuadTex>(p, shade, qt, obj, unused, best, D, cr, cg, cb);
-        // rgba8unorm conversion of both pixels (rwr_device.h); alpha 2.0 -> 255
-        const f2 sr = cr * 255.0f, sg = cg * 255.0f, sb = cb * 255.0f;
-        const uint32_t m0 = pack_rgba8_scaled(sr.x, sg.x, sb.x, 0xff000000u);
-        const uint32_t m1 = pack_rgba8_scaled(sr.y, sg.y, sb.y, 0xff000000u);
-        rgba[0] = obj.x >= 0 ? m0 : rgba[0];
-        rgba[1] = obj.y >= 0 ? m1 : rgba[1];
-        if (AUX) {
-            if (obj.x >= 0) cf[0] = make_float4(cr.x, cg.x, cb.x, 2.0f);
-            if (obj.y >= 0) cf[1] = make_float4(cr.y, cg.y, cb.y, 2.0f);
-        }
+        pack_mesh(obj, cr, cg, cb, rgba, cf);
     }
-
-    if (in_frame) {
-        if (pair_store) {
-            __builtin_nontemporal_store(u2{rgba[0], rgba[1]}, reinterpret_cast<u2 *>(reinterpret_cast<uint32_t *>(tg.color) + o));
-        } else {
-            reinterpret_cast<uint32_t *>(tg.color)[o] = rgba[0];
-            if (both) reinterpret_cast<uint32_t *>(tg.color)[o + 1] = rgba[1];
-        }
-        if (AUX) {
-            const bool dbg = (p.flags & RWR_FLAG_DEBUG_COUNTS) != 0;
-            reinterpret_cast<float4 *>(tg.color_f32)[o] = cf[0];
-            tg.obj_id[o] = dbg ? (int32_t)dbg_listed : obj.x;
-            tg.hit_t[o] = dbg ? (float)dbg_tested : win_t.x;
-            if (both) {
-                reinterpret_cast<float4 *>(tg.color_f32)[o + 1] = cf[1];
-                tg.obj_id[o + 1] = dbg ? (int32_t)dbg_listed : obj.y;
-                tg.hit_t[o + 1] = dbg ? (float)dbg_tested : win_t.y;
-            }
-        }
-    }
+    store_colour(ps, rgba, cf, obj, win_t, dbg_listed, dbg_tested);
 }
 
 uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks)

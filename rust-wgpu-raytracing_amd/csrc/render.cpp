@@ -294,9 +294,25 @@ struct RecordsKey {
     const void *cull, *tris, *ftris, *tnum, *ray_colp, *ray_row, *zero_a, *zero_b, *tile_lists;
     uint32_t width, height, n_tris, ray_pairs, ray_rows, n_zero_a, n_zero_b, list_gx, list_gy, list_row_begin, list_row_pitch, list_blocks;
     uint32_t row_begin, row_end, row_pitch, pad;   // the launch's rows, with or without face sets: a change of rows is a change of key
+    TileClassIn tc;   // the tiles' class words: where they go, and the mesh rectangle, sphere count and sphere rectangles they record
 };
-static_assert(sizeof(RecordsKey) == sizeof(rwr_camera_inv_uniform) + sizeof(CullConsts) + 8 + 9 * sizeof(void *) + 16 * 4, "RecordsKey has no padding");
+static_assert(sizeof(RecordsKey) == sizeof(rwr_camera_inv_uniform) + sizeof(CullConsts) + 8 + 9 * sizeof(void *) + 16 * 4 + sizeof(TileClassIn),
+              "RecordsKey has no padding");
 static_assert(sizeof(FrameSetupOut) == 96, "a new member of FrameSetupOut belongs in RecordsKey");
+static_assert(sizeof(TileClassIn) == 160, "a new member of TileClassIn is a new input of k_frame_setup: RecordsKey holds the whole struct");
+
+// The class words' inputs for a launch whose sets go to so.tile_lists (rwr_internal.h: the words lie behind the sets); all zero
+// for a launch without sets.
+TileClassIn tile_class_in(const FrameParams &fp, const FrameSetupOut &so)
+{
+    TileClassIn tc{};
+    if (!so.tile_lists) return tc;
+    tc.classes = so.tile_lists + (size_t)so.list_gx * so.list_gy * 4u * kTileListWords;
+    for (int k = 0; k < 4; k++) tc.mesh_px[k] = fp.mesh_px[k];
+    tc.n_spheres = fp.n_spheres;
+    std::memcpy(tc.sphere_rect, fp.sphere_rect, sizeof tc.sphere_rect);
+    return tc;
+}
 
 // Every k_frame_setup goes through here.  The slot's records are a pure function of the launch's key, so a launch whose key is
 // the one the slot's records were made from is not made: camera, screen, rows and scene stand still on most frames of a redraw
@@ -312,13 +328,13 @@ hipError_t launch_records(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc
     const RecordsKey key{fp.cam, fc.cc, ctx->scene_generation, ctx->d_cull.ptr, ctx->d_tris.ptr, so.ftris, so.tnum, so.ray_colp, so.ray_row,
                          so.zero_a, so.zero_b, so.tile_lists, fp.width, fp.height, ctx->n_tris, so.ray_pairs, so.ray_rows, so.n_zero_a,
                          so.n_zero_b, so.list_gx, so.list_gy, so.list_row_begin, so.list_row_pitch, so.list_blocks,
-                         fp.row_begin, fp.row_end, fp.row_pitch, 0u};
+                         fp.row_begin, fp.row_end, fp.row_pitch, 0u, tile_class_in(fp, so)};
     const unsigned char *bytes = reinterpret_cast<const unsigned char *>(&key);
     const bool pure = so.n_zero_a == 0u && so.n_zero_b == 0u;
     if (!captured && pure && sl.records_key.size() == sizeof key && std::memcmp(sl.records_key.data(), bytes, sizeof key) == 0)
         return hipSuccess;
     sl.records_key.clear();
-    const hipError_t e = launch_frame_setup(sl.stream, fc.cc, fp.cam, fp.width, fp.height, ctx->d_cull.ptr, ctx->d_tris.ptr, ctx->n_tris, so);
+    const hipError_t e = launch_frame_setup(sl.stream, fc.cc, fp.cam, fp.width, fp.height, ctx->d_cull.ptr, ctx->d_tris.ptr, ctx->n_tris, so, key.tc);
     if (e != hipSuccess || captured) return e;
     ctx->setup_launches++;
     if (ctx->setup_cache) sl.records_key.assign(bytes, bytes + sizeof key);   // (RWR_SETUP_CACHE=0: never a key, never a hit)
@@ -526,15 +542,21 @@ int enqueue_reference(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, F
         so.list_row_pitch = fp.row_pitch;
         const uint32_t regions = ((so.list_gx + kListRegionWgs - 1u) / kListRegionWgs) * ((so.list_gy + kListRegionWgs - 1u) / kListRegionWgs);
         so.list_blocks = (regions + 4u * kListRegionsPerWave - 1u) / (4u * kListRegionsPerWave);
-        RWR_HIP_CHECK(sl.d_tile_lists.ensure((size_t)so.list_gx * so.list_gy * 4u * kTileListWords));
+        RWR_HIP_CHECK(sl.d_tile_lists.ensure(tile_list_words(so.list_gx, so.list_gy)));   // (the sets, then the tiles' class words)
         so.tile_lists = sl.d_tile_lists.ptr;
         fp.tile_lists = so.tile_lists;
     }
+    // the frame kernel takes a tile by its class word (RWR_TILE_CLASS=0: it looks at none; the setup writes them all the same)
+    fp.flags &= ~RWR_FLAG_TILE_CLASS;
+    if (so.tile_lists && ctx->tile_class) fp.flags |= RWR_FLAG_TILE_CLASS;
+    ctx->last_classes = rwr_context::LastClasses{so.tile_lists ? ctx->cur : 0u, so.list_gx, so.tile_lists ? so.list_gy : 0u};
     const QuadTex quad_tex{ctx->d_quads.empty() ? nullptr : ctx->d_quads[0].ptr, ctx->d_mat_quads.ptr, ctx->d_srgb_lut.ptr};
     const bool plain = small_culled && !rq.aux && !ctx->timing_every;   // nothing but records + frame kernel on the stream
     if (plain && ctx->frame_graph) return launch_frame_graph(ctx, sl, fc, so, quad_tex, tg);   // (an empty band too: captured as it is)
-    if (plain && ctx->fused_setup && fused_pays(ctx, fp) && !(fp.flags & RWR_FLAG_NORMAL_MAP) && band)
+    if (plain && ctx->fused_setup && fused_pays(ctx, fp) && !(fp.flags & RWR_FLAG_NORMAL_MAP) && band) {
+        ctx->last_classes = rwr_context::LastClasses{};   // (the fused form makes no sets)
         return launch_fused_frame(ctx, sl, fc, so, quad_tex, tg);
+    }
     if ((rc = enqueue_records(ctx, sl, kernel, fc, so, timing)) != RWR_OK) return rc;
     switch (kernel) {
     case FrameKernel::kDormant: {
@@ -902,6 +924,7 @@ int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const r
     const FrameKernel kernel = choose_kernel(ctx, rq, fc);
 
     FrameTiming timing;
+    ctx->last_classes = rwr_context::LastClasses{};   // (enqueue_reference: a frame whose setup makes class words)
     rc = kernel == FrameKernel::kWavefront ? enqueue_wavefront(ctx, sl, rq, ap, pp, fc, tg, timing)
                                            : enqueue_reference(ctx, sl, rq, kernel, fc, tg, timing);
     if (rc != RWR_OK) return rc;

@@ -244,6 +244,9 @@ struct rwr_context {
     uint64_t setup_launches = 0;                        // k_frame_setup launches put on a stream so far (rwr_frame_setup_launches)
     bool ray_plane = true;                              // a slot keeps its pixels' ray directions while the camera rests (FrameSlot::d_ray_plane); RWR_RAY_PLANE=0: computed every frame
     uint64_t ray_plane_builds = 0, ray_plane_frames = 0;   // k_ray_plane launches / frames that loaded their rays from a plane, so far (rwr_ray_plane_stats)
+    bool tile_class = true;                             // the two-pixel kernel takes a tile by the class word k_frame_setup left with its face set; RWR_TILE_CLASS=0: it ignores the words
+    struct LastClasses { uint32_t slot = 0, gx = 0, gy = 0; };   // the class words of the frame rendered last: its slot and the frame kernel's grid (gy == 0: it has none)
+    LastClasses last_classes;                           // (rwr_debug_tile_classes)
     // BVH over the (flattened) world-space faces, for bounce rays
     rwr::DeviceBuffer<rwr::BvhNode4> d_bvh_nodes;
     rwr::DeviceBuffer<uint32_t> d_bvh_leaf_faces;

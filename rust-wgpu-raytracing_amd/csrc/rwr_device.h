@@ -281,7 +281,9 @@ RWR_DEV QuadTap quad_tap(uint32_t qw, float wmax, float hmax, f2 fxy)
 RWR_DEV float4 quad_texel(const float *lut, uint32_t w)
 {
     const char *l = reinterpret_cast<const char *>(lut);
-    return make_float4(*reinterpret_cast<const float *>(l + (w & 0x3fcu)), *reinterpret_cast<const float *>(l + ((w >> 10) & 0x3fcu)),
+    // (g: bits 10-11 of a texel are clear — build_tex_quads shifts a byte to bits 2-9 — so the ten bits from bit 10 are the
+    // offset as they stand: one bit-field extract instead of a shift and a mask)
+    return make_float4(*reinterpret_cast<const float *>(l + (w & 0x3fcu)), *reinterpret_cast<const float *>(l + ((w >> 10) & 0x3ffu)),
                        *reinterpret_cast<const float *>(l + (w >> 20)), 0.0f);
 }
 RWR_DEV f3 quad_filter(const uint4 *__restrict__ quad, const float *lut, const QuadTap &t)

@@ -218,6 +218,29 @@ RWR_DEV void intersect_and_select(const TriRecord &T, float tnum, uint32_t idx, 
     best.ndotd = take ? ndotd : best.ndotd;
     best.idx = take ? u2{idx, idx} : best.idx;
 }
+// The test alone, for a tile's first and only face (kernels_primary_p2.hip, the straight path): the mask of hits and, whether hit
+// or not, what the test computed on the way.  The lines above, operation for operation — a change there is a change here (the
+// function above does not call this one: written that way, the compiler lays out every kernel that inlines it differently).
+RWR_DEV i2 triangle_hit(const TriRecord &T, float tnum, f3 O, v3 D, f2 &t, f2 &u, f2 &v, f2 &ndotd)
+{
+    const f3 N1 = ld3(T.N);
+    const v3 N = splat3(N1);
+    ndotd = dot3(N, D);
+    const f2 abs_ndotd = abs2(ndotd);
+    i2 hit = ~(abs_ndotd < kEpsilon);                         // :94
+    t = hit_t(tnum, ndotd, abs_ndotd);                        // :99-102, same bits as tnum / ndotd
+    hit &= ~(t < 0.0f);                                       // :105
+    const v3 P = along(splat3(O), t, D);                      // :110
+    v3 C = cross3(splat3(ld3(T.e0)), sub3(P, splat3(ld3(T.p0))));
+    hit &= ~(dot3(N, C) < 0.0f);                              // :118
+    C = cross3(splat3(ld3(T.e1)), sub3(P, splat3(ld3(T.p1))));
+    u = dot3(N, C);
+    hit &= ~(u < 0.0f);                                       // :127
+    C = cross3(splat3(ld3(T.e2)), sub3(P, splat3(ld3(T.p2))));
+    v = dot3(N, C);
+    hit &= ~(v < 0.0f);                                       // :136
+    return hit;
+}
 
 // Scene data read at wave-uniform addresses goes through the CONSTANT address space: in a kernel that also stores to global
 // memory (ray queues, atomics) the compiler no longer dares to use scalar loads for plain global pointers (it cannot see that

@@ -66,8 +66,14 @@ RWR_DEV void frame_setup_block(uint32_t block, uint32_t n_blocks, const CullCons
 // each edge's dmax = fma(xs, ex, fma(ys, ey, ea)) takes corner coordinates no larger in xs * ex and ys * ey, so its exact value
 // is no larger and, rounding being monotone, neither is the rounded one (a NaN at r' needs an infinite term that r has too, and
 // then r's compare fails as well).  A face culled for the region is culled for each of its tiles.
+//
+// With tc.classes each lane also leaves its tile's class word (rwr_internal.h kTileFaces*): everything the frame kernel would find
+// out about the tile before it looks at a ray — how many faces the set holds (and which, when it is one), whether the tile lies
+// in the mesh's pixel rectangle (the kernel's `live`: the same integer compares on the same integers), and which spheres'
+// rectangles it touches (the kernel's float compares on the same floats: tx0 / ty0 are formed here as the kernel forms them,
+// and the rectangles are the frame's own).
 RWR_DEV void frame_tile_lists_block(uint32_t block, const CullConsts &cc, const CullRec *__restrict__ cull, uint32_t n_tris,
-                                    const FrameSetupOut &out)
+                                    const FrameSetupOut &out, const TileClassIn &tc)
 {
     __shared__ float4 s_ft[4][kTileListMaxFaces];   // the faces' FrameTris, one plane per 16 B
     for (uint32_t i = threadIdx.x; i < n_tris; i += 256u) {
@@ -117,6 +123,23 @@ RWR_DEV void frame_tile_lists_block(uint32_t block, const CullConsts &cc, const 
             uint4 *dst = reinterpret_cast<uint4 *>(out.tile_lists + ((size_t)(by * out.list_gx + bx) * 4u + w) * kTileListWords);
             dst[0] = make_uint4(set[0], set[1], set[2], set[3]);
             dst[1] = make_uint4(set[4], set[5], set[6], set[7]);
+            if (tc.classes) {
+                uint32_t n = 0, one = 0;
+#pragma unroll
+                for (uint32_t k = 0; k < kTileListWords; k++) {
+                    n += (uint32_t)__popc(set[k]);
+                    if (set[k]) one = 32u * k + (uint32_t)__builtin_ctz(set[k]);   // (the face, when n == 1)
+                }
+                const int32_t sx0 = (int32_t)(bx * 64u + (w & 1u) * 32u), sy0 = (int32_t)(out.list_row_begin + by * out.list_row_pitch + (w >> 1) * 4u);
+                const bool live = !(sx0 + 32 < tc.mesh_px[0] || sx0 > tc.mesh_px[2] || sy0 + 4 < tc.mesh_px[1] || sy0 > tc.mesh_px[3]);
+                uint32_t cls = !live || n == 0u ? kTileFacesNone : n == 1u ? (kTileFacesOne | one << kTileFaceShift) : kTileFacesMore;
+                for (uint32_t s = 0; s < tc.n_spheres; s++) {   // (uniform; launch_frame_setup: at most RWR_MAX_SPHERES)
+                    const bool off = (tx0 + 32.0f < tc.sphere_rect[s][0]) || (tx0 > tc.sphere_rect[s][2]) ||
+                                     (ty0 + 4.0f < tc.sphere_rect[s][1]) || (ty0 > tc.sphere_rect[s][3]);
+                    if (!off) cls |= 1u << (kTileSphereShift + s);
+                }
+                tc.classes[(size_t)(by * out.list_gx + bx) * 4u + w] = cls;
+            }
         }
     }
 }

@@ -16,6 +16,9 @@ constexpr uint32_t RWR_FLAG_DEBUG_COUNTS = 1u << 16;
 // Internal: render frames with the one-pixel-per-lane kernel (k_primary) instead of the
 // two-pixels-per-lane one (k_primary_p2); both must give identical results.
 constexpr uint32_t RWR_FLAG_ONE_PIXEL_PER_LANE = 1u << 17;
+// Internal, set by render.cpp alone (a caller's bit is cleared): the frame's per-tile face sets come with class words
+// (TileClassIn below) and the two-pixel frame kernel branches on them.  Clear (RWR_TILE_CLASS=0): the kernel never loads one.
+constexpr uint32_t RWR_FLAG_TILE_CLASS = 1u << 18;
 
 // ---------------------------------------------------------------------------
 // Device-side scene records (data layout in HBM, see DESIGN.md §"Data layout").
@@ -163,6 +166,18 @@ constexpr uint32_t kStripRows = 8;   // rows of a strip = of every render kernel
 // (made by waves of k_frame_setup that cover kListRegionsPerWave regions of kListRegionWgs x kListRegionWgs workgroups each)
 constexpr uint32_t kTileListMaxFaces = 256, kTileListWords = kTileListMaxFaces / 32;
 constexpr uint32_t kListRegionWgs = 4, kListRegionsPerWave = 1;
+// One class word per tile, a parallel array behind the sets in the same buffer (word 8 * tiles + tile, tiles = 4 * workgroups of
+// the frame kernel's grid; tile = 4 * workgroup + wave, as the sets), made by the same lane of k_frame_setup that makes the set
+// (rwr_frame_setup.h) from the compares the frame kernel would make itself:
+//   bits 0-1   faces: kTileFacesNone / One / More — the set's population, and None for a tile outside the mesh's pixel rectangle
+//              (FrameParams::mesh_px, the kernel's `live`)
+//   bits 8-15  the face's index when there is exactly one
+//   bits 16-23 spheres: bit s set <=> s < n_spheres and the tile's rectangle touches sphere s's (FrameParams::sphere_rect)
+// The kernel (kernels_primary_p2.hip) takes one of three ways through a tile by it, once per wave.
+constexpr uint32_t kTileFacesNone = 0u, kTileFacesOne = 1u, kTileFacesMore = 2u, kTileFacesMask = 3u;
+constexpr uint32_t kTileFaceShift = 8u, kTileSphereShift = 16u, kTileSphereMask = 0xffu << kTileSphereShift;
+static_assert(RWR_MAX_SPHERES <= 8 && kTileListMaxFaces <= 256, "a class word has 8 bits for the spheres and 8 for a face index");
+inline size_t tile_list_words(uint32_t gx, uint32_t gy) { return (size_t)gx * gy * 4u * (kTileListWords + 1u); }   // sets, then class words
 
 struct FrameParams {
     rwr_camera_inv_uniform cam;
@@ -474,6 +489,17 @@ struct FrameSetupOut {
     uint32_t *tile_lists;
     uint32_t list_gx, list_gy, list_row_begin, list_row_pitch, list_blocks;
 };
+// What the blocks that make the face sets need on top for the tiles' class words (kTileFaces* above): where the words go (null:
+// no sets this frame) and the frame kernel's own operands of the compares they record — FrameParams::mesh_px, n_spheres and
+// sphere_rect.  An argument of k_frame_setup of its own, so that FusedSetup (which holds a FrameSetupOut) and with it the fused
+// frame kernel's arguments stay what they were.
+struct TileClassIn {
+    uint32_t *classes;
+    int32_t mesh_px[4];
+    uint32_t n_spheres, pad;
+    float sphere_rect[RWR_MAX_SPHERES][4];
+};
+static_assert(sizeof(TileClassIn) == 8 + 16 + 8 + RWR_MAX_SPHERES * 16, "TileClassIn has no padding");
 // The frame kernel's FUSED form (one launch per frame, kernels_primary_p2.hip): the grid's first rows are workgroups that make
 // the frame's records and tables (the work of k_frame_setup), the others wait until all of them have finished.
 struct FusedSetup {
@@ -524,7 +550,7 @@ hipError_t launch_measure_valu(hipStream_t s, int mode, ulonglong2 *d_out, uint3
 
 hipError_t launch_frame_setup(hipStream_t s, const CullConsts &cc, const rwr_camera_inv_uniform &cam, uint32_t width,
                               uint32_t height, const CullRec *cull, const TriRecord *tris, uint32_t n_tris,
-                              const FrameSetupOut &out);
+                              const FrameSetupOut &out, const TileClassIn &tc);
 // count -> scan -> fill; *total_out (device) receives the entries the frame's lists need
 hipError_t launch_bin_faces(hipStream_t s, const FrameTri *ftris, uint32_t n_tris, uint32_t row_begin, uint32_t *lists,
                             uint32_t *counts, uint32_t *offsets, uint32_t *total_out, uint32_t bins_x, uint32_t bins_y, uint32_t capacity,
