@@ -331,7 +331,7 @@ enum {
                                           flight, row bands, strips and the multi-GPU gather keep their contracts.  With
                                           RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED, whatever
                                           max_bounces is and whether or not a surface is glass. */
-    RWR_FLAG_REPROJECT = 1u << 12   /* extension: temporal reprojection — a low-sample frame is blended with the context's history of
+    RWR_FLAG_REPROJECT = 1u << 12,  /* extension: temporal reprojection — a low-sample frame is blended with the context's history of
                                        the frames before it, fetched where the point a pixel sees was seen last frame, while the
                                        camera moves (RWR_FLAG_ACCUMULATE converges only while it rests).  Without the flag every
                                        frame is what it was, byte for byte, with no further launch or allocation.  With it the frame
@@ -382,6 +382,41 @@ enum {
                                           contract: deeper paths, shadows, sky, mirrors, glass, normal maps, RWR_FLAG_NO_CULL,
                                           instances and parts — the stage only sees their resolved frame.  The scene is static
                                           between setters, so no motion vectors are needed. */
+    RWR_FLAG_GLOSSY = 1u << 13      /* extension: glossy surfaces — a scene part or a sphere marked as glossy (rwr_scene_set_part_gloss,
+                                       rwr_scene_set_sphere_gloss) of reflectance R and roughness rho sends on a direction between the
+                                       mirror reflection and the diffuse ray the hit would otherwise have sent: brushed metal, a
+                                       polished floor, a satin ball.  Independent of RWR_FLAG_MIRRORS and RWR_FLAG_GLASS: each flag
+                                       switches its own surfaces on; a glossy surface in a frame without this flag is the diffuse
+                                       surface it was.  Without the flag every frame is what it was, byte for byte, with no further
+                                       launch or allocation.  With it, at a hit h a path goes on from (h0, or h_k with
+                                       k < max_bounces) on a glossy surface, all in f32 with no contraction:
+                                       1. Dh = normalize3(D), the oracle's routine; D is the direction of the ray that found h, of any
+                                          length (at h0 it is unit already and normalised all the same: one rule for every generation).
+                                       2. n is the reference's HitRecord normal: a face's normal flipped towards the ray, a sphere's
+                                          outward normal; normal maps never change it.  Rf = reflect_direction(n, Dh): d = dot3(n, Dh),
+                                          Rf = Dh - (2 d) n per component.
+                                       3. X = bounce_direction(n, pixel, sample, seed, d0), bit for bit the diffuse ray the same hit
+                                          would have emitted, with d0 the first dimension of the generation's block (2 for the ray that
+                                          leaves h0, 2 + 16 k for the one that leaves h_k); the block's dimensions are read exactly as a
+                                          diffuse hit reads them.
+                                       4. om = 1.0f - rho; S = om Rf + rho X per component (om*Rf.x + rho*X.x: two products, one sum).
+                                          At rho = 1 every component of S equals X's.
+                                       5. !(dot3(S, S) > 0.0f) — a vanishing sum, or NaN: S = Rf.
+                                       6. The next ray: direction S, not re-normalised; origin P + 1e-4 n, operation for operation the
+                                          diffuse, mirror and shadow rays' origin; throughput T * R (T0 = R at a glossy h0).  The local
+                                          term of h is unchanged, E(h) or the shadowed E(h): a coated surface, as a mirror.  Primary-stage
+                                          sums, sample-0 planes, h0's shadow records and generation 1's ray count do not depend on the
+                                          flag; the nearest-hit rule, the clamps, the sky's term at a miss and (R <= 1) the integrator's
+                                          range analysis are untouched.
+                                       7. max_bounces = 0, or no part of the scene and none of its spheres (indices below the count
+                                          rwr_scene_set_spheres gave) is glossy: the flag is ignored — cleared before the frame's kernels
+                                          are chosen — and the frame is the frame without it, byte for byte, in the same kernels.
+                                       8. RWR_FLAG_ACCUMULATE: this bit (after item 7) is part of the key, and of RWR_FLAG_REPROJECT's
+                                          effective flags; every accepted call of the gloss setters changes the scene's generation, a
+                                          refused one changes nothing.  rwr_last_gloss_stats counts the rays item 6 emitted.  Every
+                                          other flag, instances, parts, frames in flight, row bands, strips and the multi-GPU gather keep
+                                          their contracts.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
+                                          RWR_ERR_UNSUPPORTED, whatever max_bounces is and whether or not a surface is glossy. */
 };
 
 #define RWR_MAX_BOUNCES 8u
@@ -479,6 +514,19 @@ RWR_API int rwr_scene_set_part_glass(rwr_context *ctx, uint32_t part, float ior,
 RWR_API int rwr_scene_set_sphere_glass(rwr_context *ctx, uint32_t sphere, float ior, const float *tint);
 RWR_API int rwr_scene_get_part_glass(rwr_context *ctx, uint32_t part, int *is_glass, float *ior, float tint[3]);
 RWR_API int rwr_scene_get_sphere_glass(rwr_context *ctx, uint32_t sphere, int *is_glass, float *ior, float tint[3]);
+
+/* RWR_FLAG_GLOSSY: the gloss attribute of a scene part or of a sphere index, with the mirror attribute's index and reset rules.
+ * reflectance: 3 floats, each finite and in [0, 1]; NULL = not glossy (roughness is then ignored).  roughness: finite, in
+ * [2^-10, 1] (a perfect mirror is the mirror setter's job).  Anything else, NaN included: RWR_ERR_INVALID_ARGUMENT and the old state
+ * stays.  A surface has one model: an accepted call of a gloss setter clears the surface's mirror and glass attribute, an accepted
+ * call of a mirror or glass setter its gloss (with NULL any of them makes the surface diffuse).  Every accepted call changes the
+ * scene's generation.  The surface keeps 1.0f + roughness; the roughness the frame uses, and the getters return, is that minus
+ * 1.0f (a multiple of 2^-23).  The getters return *is_glossy = 0 / 1 and, for a glossy surface, its reflectance and roughness
+ * (zeros otherwise); every output may be NULL. */
+RWR_API int rwr_scene_set_part_gloss(rwr_context *ctx, uint32_t part, const float *reflectance, float roughness);
+RWR_API int rwr_scene_set_sphere_gloss(rwr_context *ctx, uint32_t sphere, const float *reflectance, float roughness);
+RWR_API int rwr_scene_get_part_gloss(rwr_context *ctx, uint32_t part, int *is_glossy, float reflectance[3], float *roughness);
+RWR_API int rwr_scene_get_sphere_gloss(rwr_context *ctx, uint32_t sphere, int *is_glossy, float reflectance[3], float *roughness);
 
 /* Replaces Sphere::new's uniform, one per analytic sphere pass, composited in
  * array order before the mesh (src/lib.rs:532-534, 1106-1173).  n <= RWR_MAX_SPHERES. */
@@ -665,6 +713,11 @@ RWR_API int rwr_last_shadow_stats(rwr_context *ctx, uint64_t *shadow_rays, uint6
  * reflections (an accumulating frame: its own samples; zeros for a frame the flag did nothing to).  Exact counts.  Waits for the
  * frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_last_glass_stats(rwr_context *ctx, uint64_t *reflected, uint64_t *transmitted, uint64_t *tir);
+
+/* RWR_FLAG_GLOSSY: the rays the glossy hits of the last render call sent on (an accumulating frame: its own samples; zero for a
+ * frame the flag did nothing to).  An exact count.  Waits for the frame, as rwr_last_render_stats does.  A NULL argument is
+ * RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_last_gloss_stats(rwr_context *ctx, uint64_t *glossy_rays);
 
 /* Progressive accumulation (RWR_FLAG_ACCUMULATE).  One context holds one accumulation.
  * rwr_accum_reset: the next accumulating frame starts over at N = 0 (host-side only, nothing waits).

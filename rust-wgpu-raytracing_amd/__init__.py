@@ -53,6 +53,7 @@ SKY_PARAMS_DTYPE = np.dtype([("zenith", "<f4", 3), ("horizon", "<f4", 3)])
 FLAG_MIRRORS = 1 << 10       # parts and spheres marked as mirrors reflect the ray that found them (include/rwr_hip.h)
 FLAG_GLASS = 1 << 11         # parts and spheres marked as glass reflect by Fresnel's law and refract by Snell's (include/rwr_hip.h)
 FLAG_REPROJECT = 1 << 12     # temporal reprojection of the context's history while the camera moves; implies FLAG_AUX_OUTPUTS (include/rwr_hip.h)
+FLAG_GLOSSY = 1 << 13        # parts and spheres marked as glossy send on a ray between the mirror reflection and the diffuse ray (include/rwr_hip.h)
 REPROJECT_PARAMS_DTYPE = np.dtype([("max_history", "<u4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
 MAX_BOUNCES = 8
 FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
@@ -128,6 +129,9 @@ def lib() -> C.CDLL:
         "rwr_scene_set_part_glass": [vp, u32, f32, vp], "rwr_scene_set_sphere_glass": [vp, u32, f32, vp],
         "rwr_scene_get_part_glass": [vp, u32, vp, vp, vp], "rwr_scene_get_sphere_glass": [vp, u32, vp, vp, vp],
         "rwr_last_glass_stats": [vp, vp, vp, vp],
+        "rwr_scene_set_part_gloss": [vp, u32, vp, f32], "rwr_scene_set_sphere_gloss": [vp, u32, vp, f32],
+        "rwr_scene_get_part_gloss": [vp, u32, vp, vp, vp], "rwr_scene_get_sphere_gloss": [vp, u32, vp, vp, vp],
+        "rwr_last_gloss_stats": [vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
         "rwr_load_model_compute": [C.c_char_p, C.c_char_p, vp], "rwr_model_free": [vp],
         "rwr_model_info": [vp, vp, vp, vp, vp, vp, vp], "rwr_scene_upload_model": [vp, vp],
@@ -149,7 +153,8 @@ def lib() -> C.CDLL:
                            "rwr_scene_get_part_mirror", "rwr_scene_get_sphere_mirror", "rwr_scene_set_part_glass", "rwr_scene_set_sphere_glass",
                            "rwr_scene_get_part_glass", "rwr_scene_get_sphere_glass", "rwr_last_glass_stats",
                            "rwr_reproject_set_params", "rwr_reproject_get_params", "rwr_reproject_reset", "rwr_reproject_frames",
-                           "rwr_last_reproject_stats", "rwr_reproject_readback")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_last_reproject_stats", "rwr_reproject_readback", "rwr_scene_set_part_gloss", "rwr_scene_set_sphere_gloss",
+                           "rwr_scene_get_part_gloss", "rwr_scene_get_sphere_gloss", "rwr_last_gloss_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -510,6 +515,39 @@ class Context:
         a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(lib().rwr_last_glass_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
+
+    def set_part_gloss(self, part: int, roughness: float = 0.25, reflectance=(1.0, 1.0, 1.0)):
+        """FLAG_GLOSSY: scene part `part` is glossy, of this roughness (in [2**-10, 1]) and reflectance (three floats in [0, 1]);
+        reflectance None: not glossy.  Out of range or NaN: RwrError(ERR_INVALID_ARGUMENT), and the old state stays.  An accepted
+        call clears the part's mirror and glass attribute (rwr_scene_set_part_gloss)."""
+        r = self._reflectance(reflectance)
+        _check(lib().rwr_scene_set_part_gloss(self._h, part, _p(r), roughness))
+
+    def set_sphere_gloss(self, sphere: int, roughness: float = 0.25, reflectance=(1.0, 1.0, 1.0)):
+        """FLAG_GLOSSY: the sphere of index `sphere` (< 8, kept whatever set_spheres holds) is glossy; reflectance None: not glossy."""
+        r = self._reflectance(reflectance)
+        _check(lib().rwr_scene_set_sphere_gloss(self._h, sphere, _p(r), roughness))
+
+    def _get_gloss(self, fn, index: int):
+        on = C.c_int(0)
+        rough = C.c_float(0.0)
+        r = np.zeros(3, np.float32)
+        _check(fn(self._h, index, C.byref(on), _p(r), C.byref(rough)))
+        return (float(rough.value), r) if on.value else None
+
+    def get_part_gloss(self, part: int):
+        """(roughness, reflectance float32[3]) when the part is glossy, else None (rwr_scene_get_part_gloss)."""
+        return self._get_gloss(lib().rwr_scene_get_part_gloss, part)
+
+    def get_sphere_gloss(self, sphere: int):
+        """(roughness, reflectance float32[3]) when the sphere index is glossy, else None (rwr_scene_get_sphere_gloss)."""
+        return self._get_gloss(lib().rwr_scene_get_sphere_gloss, sphere)
+
+    def last_gloss_stats(self):
+        """The rays the glossy hits of the last render call sent on (rwr_last_gloss_stats)."""
+        a = C.c_uint64(0)
+        _check(lib().rwr_last_gloss_stats(self._h, C.byref(a)))
+        return int(a.value)
 
     def set_triangles(self, triangles):
         """Single-triangle passes (the reference's dormant models/triangle), after the spheres."""

@@ -440,6 +440,19 @@ int rwr_last_glass_stats(rwr_context *ctx, uint64_t *reflected, uint64_t *transm
     return RWR_OK;
 }
 
+int rwr_last_gloss_stats(rwr_context *ctx, uint64_t *glossy_rays)
+{
+    if (!ctx || !glossy_rays) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    unsigned long long count = 0ull;
+    if (ctx->last_gloss && ctx->wf_state[ctx->last_wf_state].d_glass_counts.ptr) {
+        DeviceGuard g(ctx->device);
+        RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
+        RWR_HIP_CHECK(hipMemcpy(&count, ctx->wf_state[ctx->last_wf_state].d_glass_counts.ptr + 3, sizeof count, hipMemcpyDeviceToHost));
+    }
+    *glossy_rays = count;
+    return RWR_OK;
+}
+
 int rwr_denoise_set_params(rwr_context *ctx, const rwr_denoise_params *params)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");

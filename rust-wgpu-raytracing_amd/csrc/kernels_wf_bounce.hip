@@ -275,14 +275,24 @@ k_wf_sort(const WfBuffers wf, PoolInfo *__restrict__ info, uint32_t *__restrict_
 // Glass forms (RWR_FLAG_GLASS; SURF == kSurfGlass), a hit on glass (`eta` != 0, its index): direction and side by
 // refract_or_reflect with the generation's first random number, origin P + 1e-4 m, thr is T * C — computed here, where the
 // traversal's registers are dead.  Returns the glass event (0 reflected, 1 transmitted, 2 totally reflected), 3 for no glass hit.
+// Glossy forms (RWR_FLAG_GLOSSY; SURF == kSurfGloss), a hit on a glossy surface (`rho` != 0, its roughness): the diffuse direction
+// of the same dimensions goes through gloss_direction — computed for every lane that draws a diffuse direction and selected, so
+// that the lanes stay together — thr is T * R.  Returns kEventGlossy for such a hit.
+constexpr uint32_t kEventGlossy = 4u;
 template <int SURF = kSurfNone>
 RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const WfEmit &em, const TriRecord *__restrict__ tris, uint32_t tile,
-                               uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr, bool mirror = false, float eta = 0.0f)
+                               uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr, bool mirror = false, float eta = 0.0f,
+                               float rho = 0.0f)
 {
     f3 n;
     f3 O1 = hit_exit_point(p, tris, O, D, obj, t, ndotd, n);
     f3 D1;
     uint32_t event = 3u;
+    // glossy forms: a ray that starts at P + 1e-4 n (every one but a glass hit's) has its origin and the first two channels of its
+    // throughput stored ahead of the direction's arithmetic — five registers fewer across the disk loop and the rule, which these
+    // forms hold live together
+    if (SURF == kSurfGloss && eta == 0.0f)
+        wf.rays[2u * ((size_t)tile * wf.group * kWfTilePixels + e)] = make_float4(O1.x, O1.y, O1.z, wf_pack_unorm16x2(thr.x, thr.y));
     if (SURF != kSurfNone && mirror) {
         D1 = reflect_direction(n, D);
     } else {
@@ -290,18 +300,26 @@ RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const 
         const uint32_t r = e & (kWfTilePixels - 1u), w = r >> 7, k = (r >> 6) & 1u, l = r & 63u;
         const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (w & 1u) * 32u + 2u * (l & 15u) + k;
         const uint32_t py = p.row_begin + (tile / wf.tiles_x) * p.row_pitch + (w >> 1) * 4u + (l >> 4);
-        if (SURF == kSurfGlass && eta != 0.0f) {
+        if ((SURF == kSurfGlass || SURF == kSurfGloss) && eta != 0.0f) {
             const float u = rng_uniform(py * p.width + px, em.sample_base + e / kWfTilePixels, em.next_dim, p.seed);
             f3 m;
             event = refract_or_reflect(n, D, obj >= 0, ndotd, eta, u, D1, m);
             const f3 P = along(O, t, D);
             O1 = mk3(P.x + m.x * 1e-4f, P.y + m.y * 1e-4f, P.z + m.z * 1e-4f);
         } else {
+            f3 Rf = D;
+            if (SURF == kSurfGloss) Rf = gloss_reflection(n, D);   // (gloss_direction's first half, ahead of the disk loop: fewer registers across it)
             D1 = bounce_direction(n, py * p.width + px, em.sample_base + e / kWfTilePixels, p.seed, em.next_dim);
+            if (SURF == kSurfGloss) {
+                const bool glossy = rho != 0.0f;
+                const f3 S = gloss_blend(Rf, D1, rho);
+                D1 = mk3(glossy ? S.x : D1.x, glossy ? S.y : D1.y, glossy ? S.z : D1.z);
+                event = glossy ? kEventGlossy : event;
+            }
         }
     }
     const size_t slot = (size_t)tile * wf.group * kWfTilePixels + e;
-    wf.rays[2u * slot] = make_float4(O1.x, O1.y, O1.z, wf_pack_unorm16x2(thr.x, thr.y));
+    if (SURF != kSurfGloss || eta != 0.0f) wf.rays[2u * slot] = make_float4(O1.x, O1.y, O1.z, wf_pack_unorm16x2(thr.x, thr.y));
     wf.rays[2u * slot + 1u] = make_float4(D1.x, D1.y, D1.z, wf_pack_unorm16x2(thr.z, 0.0f));
     wf.bins[slot] = (uint16_t)wf_direction_bin(D1);
     atomicOr(&em.masks_out[(size_t)tile * wf.group * 8u + (e >> 6)], 1ull << (e & 63u));
@@ -310,6 +328,8 @@ RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const 
 
 // Glass forms: a wave's glass events into the frame's three counters (WfMirror::glass_counts) — ballots and popcounts, added by
 // the wave's first active lane, one atomic per event kind the wave saw.  Call where the wave's lanes have come together again.
+// GLOSS (the glossy forms): the glossy rays too, into the fourth counter behind them.
+template <bool GLOSS = false>
 RWR_DEV void count_glass_events(unsigned long long *__restrict__ counts, uint32_t ev0, uint32_t ev1 = 3u)
 {
     const unsigned long long active = __ballot(true);
@@ -318,6 +338,10 @@ RWR_DEV void count_glass_events(unsigned long long *__restrict__ counts, uint32_
     for (uint32_t k = 0; k < 3u; k++) {
         const uint32_t n = (uint32_t)__popcll(__ballot(ev0 == k)) + (uint32_t)__popcll(__ballot(ev1 == k));
         if (n && lane == (uint32_t)__builtin_ctzll(active)) atomicAdd(&counts[k], (unsigned long long)n);
+    }
+    if (GLOSS) {
+        const uint32_t n = (uint32_t)__popcll(__ballot(ev0 == kEventGlossy)) + (uint32_t)__popcll(__ballot(ev1 == kEventGlossy));
+        if (n && lane == (uint32_t)__builtin_ctzll(active)) atomicAdd(&counts[3], (unsigned long long)n);
     }
 }
 
@@ -420,8 +444,9 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // SKY: RWR_FLAG_SKY — a ray that hits nothing adds the sky's term (add_sky); separate instantiations for the same reason.
 // MIRROR: RWR_FLAG_MIRRORS — of the EMIT forms alone: a hit on a mirror surface sends the reflected ray on, with T * R
 // (emit_next_ray); separate instantiations for the same reason.
-// SURF: which surface models the EMIT form knows — kSurfNone, kSurfMirrors (RWR_FLAG_MIRRORS alone: the MIRROR forms) or kSurfGlass
-// (RWR_FLAG_GLASS, with or without mirrors: a hit on glass sends on a reflected or a refracted ray with T * C and is counted).
+// SURF: which surface models the EMIT form knows — kSurfNone, kSurfMirrors (RWR_FLAG_MIRRORS alone: the MIRROR forms), kSurfGlass
+// (RWR_FLAG_GLASS, with or without mirrors: a hit on glass sends on a reflected or a refracted ray with T * C and is counted) or
+// kSurfGloss (RWR_FLAG_GLOSSY, with or without the other two: a glossy hit sends on gloss_direction's ray with T * R and is counted).
 // Which combinations exist, and how launch_wf_bounce picks one: LaneForms and PacketForms below, behind the kernels.
 template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false, bool SKY = false,
           int SURF = kSurfNone>
@@ -503,15 +528,18 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                                   mk3(thr.x * s1.albedo.x, thr.y * s1.albedo.y, thr.z * s1.albedo.z));
                 if (EMIT && MIRROR) {
                     const float4 m = mirror_record(p, mir, shade, obj);
-                    const bool mirror = SURF == kSurfGlass ? m.w > 0.0f : m.w != 0.0f, glass = SURF == kSurfGlass && m.w < 0.0f;
-                    const f3 next = (mirror || glass) ? mk3(m.x, m.y, m.z) : s1.albedo;
+                    const bool gloss = SURF == kSurfGloss && m.w > 1.0f;   // (w = 1 + roughness, in (1, 2]; the other forms never see one)
+                    const bool mirror = SURF == kSurfNone || SURF == kSurfMirrors ? m.w != 0.0f : m.w > 0.0f && !gloss;
+                    const bool glass = (SURF == kSurfGlass || SURF == kSurfGloss) && m.w < 0.0f;
+                    const f3 next = (mirror || glass || gloss) ? mk3(m.x, m.y, m.z) : s1.albedo;
                     event = emit_next_ray<SURF>(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd, mk3(thr.x * next.x, thr.y * next.y, thr.z * next.z),
-                                                mirror, glass ? -m.w : 0.0f);
+                                                mirror, glass ? -m.w : 0.0f, gloss ? m.w - 1.0f : 0.0f);
                 }
             } else if (SKY) {
                 add_sky(sh, sky, e, D.y, thr);
             }
             if (SURF == kSurfGlass) count_glass_events(mir.glass_counts, event);
+            if (SURF == kSurfGloss) count_glass_events<true>(mir.glass_counts, event);
             if (EMIT) {   // rays written for the next generation (lanes past the pool's end have left the iteration)
                 const unsigned long long em = __ballot(have);
                 if (em && (tid & 63u) == (uint32_t)__builtin_ctzll(em)) atomicAdd(&wf.wave_total[tile * 4u], (uint32_t)__popcll(em));
@@ -601,8 +629,13 @@ RWR_DEV i2 sphere_pair_intersect_t(f3 center, float radius, v3 O, v3 D, f2 &t_ou
 #ifndef RWR_PACKET_OCC
 #define RWR_PACKET_OCC 4
 #endif
+// The glossy EMIT + SKY forms without shadow rays need close to 140 VGPRs: held to four waves (128) they spill, as their mirror and glass
+// twins do, so these two forms alone are bound to three waves and spill nothing (measured: profiles/gloss_probe.txt, section 4).
+#ifndef RWR_GLOSS_SKY_PACKET_OCC
+#define RWR_GLOSS_SKY_PACKET_OCC 3
+#endif
 template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false, int SURF = kSurfNone>   // EMIT, SHADOW, SKY, SURF: see k_wf_trace_lane
-__global__ void __launch_bounds__(256, RWR_PACKET_OCC)
+__global__ void __launch_bounds__(256, (SURF == kSurfGloss && SKY && !SHADOW) ? RWR_GLOSS_SKY_PACKET_OCC : RWR_PACKET_OCC)
 k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                   uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
@@ -772,6 +805,12 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
             obj = take ? i2{(int)best.idx.x, (int)best.idx.y} : obj;
         }
 
+        // (glossy forms: the sky's terms first — integer sums, any order gives the same bytes — so that the packet's ray numbers and a
+        // missed ray's throughput are dead while the hits' next rays are made: the registers the disk loop and the rule need)
+        if (SKY && SURF == kSurfGloss) {
+            if (i0 < last && !have.x) add_sky(sh, sky, e0, R.D.y.x, mk3(thr.x.x, thr.y.x, thr.z.x));
+            if (i1 < last && !have.y) add_sky(sh, sky, e1, R.D.y.y, mk3(thr.x.y, thr.y.y, thr.z.y));
+        }
         // -- shade the second hit, add albedo(h0) * E(h1) to the pixel's sums --------------------------------------
         if (__any(any2(have))) {
             f2 er = splat(0.0f), eg = splat(0.0f), eb = splat(0.0f);
@@ -828,21 +867,24 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
                     if (k ? have.y : have.x) {
                         const int32_t o = k ? obj.y : obj.x;
                         const float4 m = mirror_record(p, mir, shade, o);
-                        const bool mirror = SURF == kSurfGlass ? m.w > 0.0f : m.w != 0.0f, glass = SURF == kSurfGlass && m.w < 0.0f;
-                        const f3 next = (mirror || glass) ? mk3(m.x, m.y, m.z) : (k ? mk3(ar.y, ag.y, ab.y) : mk3(ar.x, ag.x, ab.x));
+                        const bool gloss = SURF == kSurfGloss && m.w > 1.0f;
+                        const bool mirror = SURF == kSurfNone || SURF == kSurfMirrors ? m.w != 0.0f : m.w > 0.0f && !gloss;
+                        const bool glass = (SURF == kSurfGlass || SURF == kSurfGloss) && m.w < 0.0f;
+                        const f3 next = (mirror || glass || gloss) ? mk3(m.x, m.y, m.z) : (k ? mk3(ar.y, ag.y, ab.y) : mk3(ar.x, ag.x, ab.x));
                         const f3 t = k ? mk3(thr.x.y, thr.y.y, thr.z.y) : mk3(thr.x.x, thr.y.x, thr.z.x);
                         event[k] = emit_next_ray<SURF>(p, wf, em, tris, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), o, k ? best_t.y : best_t.x,
                                                        k ? best.ndotd.y : best.ndotd.x, mk3(t.x * next.x, t.y * next.y, t.z * next.z), mirror,
-                                                       glass ? -m.w : 0.0f);
+                                                       glass ? -m.w : 0.0f, gloss ? m.w - 1.0f : 0.0f);
                     }
                 if (SURF == kSurfGlass) count_glass_events(mir.glass_counts, event[0], event[1]);
+                if (SURF == kSurfGloss) count_glass_events<true>(mir.glass_counts, event[0], event[1]);
             }
             if (EMIT) {
                 const uint32_t n_emit = (uint32_t)__popcll(__ballot(have.x != 0)) + (uint32_t)__popcll(__ballot(have.y != 0));
                 if (lane == 0u) atomicAdd(&wf.wave_total[tile * 4u], n_emit);
             }
         }
-        if (SKY) {   // per ray, not per wave: every ray of the packet (not the padding of its last lanes: i0, i1 < last) that found nothing
+        if (SKY && SURF != kSurfGloss) {   // per ray, not per wave: every ray of the packet (not the padding of its last lanes: i0, i1 < last) that found nothing
             if (i0 < last && !have.x) add_sky(sh, sky, e0, R.D.y.x, mk3(thr.x.x, thr.y.x, thr.z.x));
             if (i1 < last && !have.y) add_sky(sh, sky, e1, R.D.y.y, mk3(thr.x.y, thr.y.y, thr.z.y));
         }
@@ -864,7 +906,7 @@ struct SortForms {
 };
 struct PacketForms {
     struct Form { bool nmap, emit, shadow, sky; int surf; };
-    static constexpr uint32_t kRange = 16u * 3u;
+    static constexpr uint32_t kRange = 16u * 4u;
     static constexpr uint32_t encode(Form f) { return f.nmap + 2u * f.emit + 4u * f.shadow + 8u * f.sky + 16u * (uint32_t)f.surf; }
     static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (int)(i >> 4)}; }
     static constexpr bool valid(Form f) { return f.emit || f.surf == kSurfNone; }
@@ -878,7 +920,7 @@ struct PacketForms {
 // WIDE — 1 024 threads around one copy of the nodelets — only with the nodelets in LDS, 16-bit stacks and no normal map (LaneLdsPlan)
 struct LaneForms {
     struct Form { bool nodes_in_lds, nmap, stack16, wide, emit, shadow, sky; int surf; };
-    static constexpr uint32_t kRange = 128u * 3u;
+    static constexpr uint32_t kRange = 128u * 4u;
     static constexpr uint32_t encode(Form f)
     {
         return f.nodes_in_lds + 2u * f.nmap + 4u * f.stack16 + 8u * f.wide + 16u * f.emit + 32u * f.shadow + 64u * f.sky + 128u * (uint32_t)f.surf;
@@ -899,8 +941,8 @@ struct LaneForms {
 static constexpr auto kSortForms = form_table<SortForms>();
 static constexpr auto kPacketForms = form_table<PacketForms>();
 static constexpr auto kLaneForms = form_table<LaneForms>();
-static_assert(check_forms<SortForms>(2) && check_forms<PacketForms>(32), "packets: NMAP x (4 path-ending + 12 EMIT forms)");
-static_assert(check_forms<LaneForms>(144) && count_forms<LaneForms>(LaneForms::is_wide) == 16, "per lane: 8 x 16 with 256 threads, 16 wide");
+static_assert(check_forms<SortForms>(2) && check_forms<PacketForms>(40), "packets: NMAP x (4 path-ending + 16 EMIT forms)");
+static_assert(check_forms<LaneForms>(180) && count_forms<LaneForms>(LaneForms::is_wide) == 20, "per lane: 8 x 20 with 256 threads, 20 wide");
 
 // RWR_WF_STATS=1 (wf.dbg set): launches of the packet kernel, the per-lane kernel and its WIDE form, by this process
 static std::atomic<uint64_t> g_trace_launches[3];

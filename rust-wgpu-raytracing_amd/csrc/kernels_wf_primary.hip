@@ -127,6 +127,19 @@ RWR_DEV v3 bounce_direction_pair(v3 n, u2 base, i2 want)
     return normalize3(d);
 }
 
+// gloss_direction (rwr_device.h) for a pixel pair: X is the pair's diffuse direction (bounce_direction_pair), rho each pixel's
+// roughness.  Elements that are not glossy still compute; the caller selects.
+RWR_DEV v3 gloss_direction_pair(v3 n, v3 D, v3 X, f2 rho)
+{
+    const v3 Dh = normalize3(D);
+    const f2 two_d = 2.0f * dot3(n, Dh);
+    const v3 Rf = v3{Dh.x - two_d * n.x, Dh.y - two_d * n.y, Dh.z - two_d * n.z};
+    const f2 om = 1.0f - rho;
+    const v3 S = v3{om * Rf.x + rho * X.x, om * Rf.y + rho * X.y, om * Rf.z + rho * X.z};
+    const i2 ok = dot3(S, S) > 0.0f;
+    return v3{ok ? S.x : Rf.x, ok ? S.y : Rf.y, ok ? S.z : Rf.z};
+}
+
 #ifndef RWR_WF_OCC
 #define RWR_WF_OCC 4
 #endif
@@ -168,6 +181,8 @@ RWR_DEV f3 ld3(kernarg<float> *q) { return mk3(q[0], q[1], q[2]); }
 // SURF (rwr_internal.h): kSurfNone, kSurfMirrors — the MIRROR forms — or kSurfGlass (RWR_FLAG_GLASS, with or without mirrors): a hit
 // on glass emits the reflected or the refracted ray of refract_or_reflect from P + 1e-4 m with throughput C, decided per pixel too.
 // A tile without a glass hit skips that arithmetic, a tile whose emitting pixels are all specular skips the RNG disk loop.
+// kSurfGloss (RWR_FLAG_GLOSSY, with or without the other two): a glossy hit draws the diffuse direction like a diffuse one and
+// sends gloss_direction_pair's ray on with throughput R; a tile without a glossy hit skips that arithmetic.
 template <bool AUX, bool CULL, bool NMAP, bool LIST = false, bool SHADOW = false, int SURF = kSurfNone>
 // (LIST — frames that show little — keeps an item loop's state on top of everything else and needs 142 registers: three waves
 // per SIMD like the AUX / NMAP forms; such a frame does not fill the chip anyway.  MIRROR does not loosen the bound: the plain
@@ -175,7 +190,7 @@ template <bool AUX, bool CULL, bool NMAP, bool LIST = false, bool SHADOW = false
 __global__ void __launch_bounds__(256, (AUX || NMAP || LIST || SHADOW) ? 3 : RWR_WF_OCC)
 k_wf_primary(const WfPrimaryArgs a)
 {
-    constexpr bool MIRROR = SURF != kSurfNone, GLASS = SURF == kSurfGlass;
+    constexpr bool MIRROR = SURF != kSurfNone, GLASS = SURF == kSurfGlass || SURF == kSurfGloss, GLOSS = SURF == kSurfGloss;
     kernarg<WfPrimaryArgs> *const ka = (kernarg<WfPrimaryArgs> *)__builtin_amdgcn_kernarg_segment_ptr();
     const uint32_t sample_begin = a.sample_begin, sample_count = a.sample_count, z_split = a.z_split;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -337,8 +352,11 @@ k_wf_primary(const WfPrimaryArgs a)
             depth_plane[pix0] = depth_tex.x;
             if (AUX) { qt->tg.obj_id[pix0] = obj.x; qt->tg.hit_t[pix0] = win_t.x; }
             if (in1) {
-                depth_plane[pix0 + 1u] = depth_tex.y;
-                if (AUX) { qt->tg.obj_id[pix0 + 1u] = obj.y; qt->tg.hit_t[pix0 + 1u] = win_t.y; }
+                uint32_t pix1 = pix0 + 1u;
+                // (glossy forms: the right pixel's index is made here, once per frame, not kept in a register pair across the sample loop)
+                if (GLOSS) asm volatile("" : "+v"(pix1));
+                depth_plane[pix1] = depth_tex.y;
+                if (AUX) { qt->tg.obj_id[pix1] = obj.y; qt->tg.hit_t[pix1] = win_t.y; }
             }
         }
 
@@ -475,8 +493,9 @@ k_wf_primary(const WfPrimaryArgs a)
                     float r0 = tab[0], r1 = tab[1], r2 = tab[2], r3 = tab[3];
                     asm volatile("" : "+s"(r0), "+s"(r1), "+s"(r2), "+s"(r3));   // (pinned to scalar registers: not folded into the per-lane read)
                     const float4 m0 = make_float4(r0, r1, r2, r3);
-                    i2 mir = i2{0, 0}, gl = i2{0, 0};
+                    i2 mir = i2{0, 0}, gl = i2{0, 0}, gs = i2{0, 0};
                     f2 eta = splat(0.0f);   // GLASS: the index of a pixel's glass hit
+                    f2 rho = splat(0.0f);   // GLOSS: the roughness of a pixel's glossy hit
 #pragma unroll
                     for (int k = 0; k < 2; k++) {
                         const int o = k ? obj.y : obj.x;
@@ -490,6 +509,8 @@ k_wf_primary(const WfPrimaryArgs a)
                                 if (k) { tr.y = m.x; tgc.y = m.y; tb.y = m.z; } else { tr.x = m.x; tgc.x = m.y; tb.x = m.z; }
                                 if (GLASS && m.w < 0.0f) {
                                     if (k) { gl.y = -1; eta.y = -m.w; } else { gl.x = -1; eta.x = -m.w; }
+                                } else if (GLOSS && m.w > 1.0f) {   // (w = 1 + roughness; it draws the diffuse direction too)
+                                    if (k) { gs.y = -1; rho.y = m.w - 1.0f; } else { gs.x = -1; rho.x = m.w - 1.0f; }
                                 } else {
                                     if (k) mir.y = -1; else mir.x = -1;
                                 }
@@ -504,6 +525,18 @@ k_wf_primary(const WfPrimaryArgs a)
                         Dm = v3{D.x - two_d * n.x, D.y - two_d * n.y, D.z - two_d * n.z};
                     }
                     D1 = v3{mir ? Dm.x : Dd.x, mir ? Dm.y : Dd.y, mir ? Dm.z : Dd.z};
+                    if (GLOSS) {
+                        if (__any(any2(gs))) {
+                            const v3 S = gloss_direction_pair(n, D, Dd, rho);
+                            D1 = v3{gs ? S.x : D1.x, gs ? S.y : D1.y, gs ? S.z : D1.z};
+                            // the wave's glossy rays into the frame's counter behind the glass events: ballots and popcounts, one atomic.
+                            // Lane 0 is the wave's first active lane here, as for the glass counters above: every branch down to
+                            // this one is wave-uniform (m0 | m1, bounces, __any), so all 64 lanes of the pixel-pair wave are live;
+                            // and cnt > 0, since __any(any2(gs)) holds.
+                            const uint32_t cnt = (uint32_t)__popcll(__ballot(gs.x != 0)) + (uint32_t)__popcll(__ballot(gs.y != 0));
+                            if (lane == 0u) atomicAdd(&wf_args_again(ka)->mr.glass_counts[3], (unsigned long long)cnt);
+                        }
+                    }
                     if (GLASS) {
                         uint32_t ev[2] = {3u, 3u};
                         if (__any(any2(gl))) {   // (rwr_device.h refract_or_reflect, one pixel of the pair after the other; dimension 2 of the sample)
@@ -574,7 +607,7 @@ k_wf_primary(const WfPrimaryArgs a)
 // with every such (CULL, LIST) — (1, 1), (1, 0), (0, 0) — so it adds no condition of its own.
 struct PrimaryForms {
     struct Form { bool aux, cull, nmap, list, shadow; int surf; };
-    static constexpr uint32_t kRange = 32u * 3u;
+    static constexpr uint32_t kRange = 32u * 4u;
     static constexpr uint32_t encode(Form f) { return f.aux + 2u * f.cull + 4u * f.nmap + 8u * f.list + 16u * f.shadow + 32u * (uint32_t)f.surf; }
     static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (i & 16u) != 0, (int)(i >> 5)}; }
     static constexpr bool valid(Form f) { return !f.list || f.cull; }
@@ -586,7 +619,7 @@ struct PrimaryForms {
     }
 };
 static constexpr auto kPrimaryForms = form_table<PrimaryForms>();
-static_assert(check_forms<PrimaryForms>(72), "8 plain + 4 LIST + 12 SHADOW forms, times three surface models");
+static_assert(check_forms<PrimaryForms>(96), "8 plain + 4 LIST + 12 SHADOW forms, times four surface models");
 
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg, const WfBuffers &wf,

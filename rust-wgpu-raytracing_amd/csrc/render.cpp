@@ -21,6 +21,7 @@ struct FrameRequest {
     bool reproject;   // RWR_FLAG_REPROJECT: the reprojection stage runs behind the resolve, ahead of the filter (AUX implied, this bit cleared)
     bool mirrors;     // RWR_FLAG_MIRRORS with at least one bounce and one mirror surface: the MIRROR forms (else the bit is cleared from rp.flags)
     bool glass;       // RWR_FLAG_GLASS with at least one bounce and one glass surface: the glass forms (else the bit is cleared from rp.flags)
+    bool gloss;       // RWR_FLAG_GLOSSY with at least one bounce and one glossy surface: the glossy forms (else the bit is cleared from rp.flags)
     bool sky;         // RWR_FLAG_SKY with at least one bounce: the trace kernels' SKY forms (without a bounce the bit is cleared from rp.flags)
     bool wavefront;   // the wavefront integrator renders it (several samples, a bounce, or an accumulation)
     bool dormant;     // the reference's dormant parts (single-triangle passes, orthographic rays) have their own plain kernel
@@ -110,8 +111,8 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
         return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_MIRRORS: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
     if (rp.flags & RWR_FLAG_MIRRORS) {
         bool any = false;
-        for (const MirrorRec &m : ctx->part_mirrors) any = any || m.on > 0.0f;
-        for (uint32_t i = 0; i < ctx->n_spheres; i++) any = any || ctx->sphere_mirrors[i].on > 0.0f;
+        for (const MirrorRec &m : ctx->part_mirrors) any = any || m.on == 1.0f;
+        for (uint32_t i = 0; i < ctx->n_spheres; i++) any = any || ctx->sphere_mirrors[i].on == 1.0f;
         if (rp.max_bounces == 0u || !any) rp.flags &= ~(uint32_t)RWR_FLAG_MIRRORS;
     }
     const bool mirrors = (rp.flags & RWR_FLAG_MIRRORS) != 0;
@@ -125,20 +126,30 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
         if (rp.max_bounces == 0u || !any) rp.flags &= ~(uint32_t)RWR_FLAG_GLASS;
     }
     const bool glass = (rp.flags & RWR_FLAG_GLASS) != 0;
+    // glossy surfaces: the same two rules (rwr_hip.h, RWR_FLAG_GLOSSY items 8 and 7); a glossy record is one with on > 1
+    if ((rp.flags & RWR_FLAG_GLOSSY) && ((rp.flags & (RWR_FLAG_ORTHO_RAYS | RWR_FLAG_USE_BVH)) || ctx->n_triangles != 0))
+        return set_error(RWR_ERR_UNSUPPORTED, "RWR_FLAG_GLOSSY: RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH and single-triangle passes apply to the reference frame only");
+    if (rp.flags & RWR_FLAG_GLOSSY) {
+        bool any = false;
+        for (const MirrorRec &m : ctx->part_mirrors) any = any || m.on > 1.0f;
+        for (uint32_t i = 0; i < ctx->n_spheres; i++) any = any || ctx->sphere_mirrors[i].on > 1.0f;
+        if (rp.max_bounces == 0u || !any) rp.flags &= ~(uint32_t)RWR_FLAG_GLOSSY;
+    }
+    const bool gloss = (rp.flags & RWR_FLAG_GLOSSY) != 0;
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
     // with shadow rays (the integrator's stages trace them) or one the filter follows (it runs behind the integrator's resolve)
     const bool wavefront = rp.spp != 1 || rp.max_bounces != 0 || accumulate || shadows || denoise || reproject;
     const bool dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;
     if (dormant && (wavefront || (rp.flags & RWR_FLAG_USE_BVH)))
         return set_error(RWR_ERR_UNSUPPORTED, "single-triangle passes and RWR_FLAG_ORTHO_RAYS apply to the reference frame (spp 1, no bounce, no RWR_FLAG_USE_BVH)");
-    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, denoise, reproject, mirrors, glass, sky, wavefront, dormant};
+    rq = FrameRequest{rp, row_begin, row_end, row_pitch, (rp.flags & RWR_FLAG_AUX_OUTPUTS) != 0, accumulate, shadows, denoise, reproject, mirrors, glass, gloss, sky, wavefront, dormant};
     return RWR_OK;
 }
 
 // What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
 // camera uniform's bytes, the screen, the rows, bounces, seed, flags but the ACCUMULATE bit, frames in flight and the scene — and, while
 // the frame is lit by the sky (RWR_FLAG_SKY), the sky's parameters.  (Mirror surfaces, RWR_FLAG_MIRRORS: the flag is one of the
-// flags, and every call of their setters changes the scene's generation; glass surfaces, RWR_FLAG_GLASS, likewise.)
+// flags, and every call of their setters changes the scene's generation; glass surfaces, RWR_FLAG_GLASS, and glossy ones, RWR_FLAG_GLOSSY, likewise.)
 std::vector<unsigned char> accum_key_of(const rwr_context *ctx, const rwr_camera_inv_uniform &cam, const FrameRequest &rq)
 {
     const uint32_t words[9] = {ctx->screen.width, ctx->screen.height, rq.row_begin, rq.row_end, rq.row_pitch, rq.rp.max_bounces, rq.rp.seed,
@@ -735,8 +746,8 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
     // (ft: what the frame's kernels know, WfFeatures — the surfaces and the sky here, a queue's shadow records per launch group,
     // emit per generation)
     WfFeatures ft;
-    ft.surf = rq.glass ? kSurfGlass : rq.mirrors ? kSurfMirrors : kSurfNone;
-    const uint32_t modes = (rq.mirrors ? 1u : 0u) | (rq.glass ? 2u : 0u);   // whose records the frame's copy holds: a flag switches its own surfaces on
+    ft.surf = rq.gloss ? kSurfGloss : rq.glass ? kSurfGlass : rq.mirrors ? kSurfMirrors : kSurfNone;
+    const uint32_t modes = (rq.mirrors ? 1u : 0u) | (rq.glass ? 2u : 0u) | (rq.gloss ? 4u : 0u);   // whose records the frame's copy holds: a flag switches its own surfaces on
     if (modes) {
         const size_t n_parts = ctx->part_mirrors.size(), n_recs = n_parts + RWR_MAX_SPHERES;
         if (W.mirror_version != ctx->mirror_version || W.mirror_modes != modes || W.d_mirror.count < n_recs) {
@@ -749,7 +760,7 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
             RWR_HIP_CHECK(W.d_mirror.ensure(n_recs));
             if (!W.mirror_copied) RWR_HIP_CHECK(hipEventCreateWithFlags(&W.mirror_copied.h, hipEventDisableTiming));
             auto visible = [&](const MirrorRec &m) {   // a surface whose flag the frame lacks is the diffuse surface it was
-                const bool on = m.on > 0.0f ? rq.mirrors : m.on < 0.0f ? rq.glass : false;
+                const bool on = m.on > 1.0f ? rq.gloss : m.on > 0.0f ? rq.mirrors : m.on < 0.0f ? rq.glass : false;
                 return on ? m : MirrorRec{0.0f, 0.0f, 0.0f, 0.0f};
             };
             for (size_t i = 0; i < n_parts; i++) W.h_mirror.h[i] = visible(ctx->part_mirrors[i]);
@@ -760,9 +771,11 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
             W.mirror_modes = modes;
         }
         ft.mirror = WfMirror{W.d_mirror.ptr, (uint32_t)n_parts, 0u, nullptr};
-        if (rq.glass) {   // the frame's three event counters start from zero
-            RWR_HIP_CHECK(W.d_glass_counts.ensure(3));
-            RWR_HIP_CHECK(hipMemsetAsync(W.d_glass_counts.ptr, 0, 3 * sizeof(unsigned long long), stream));
+        // (intended: a frame with RWR_FLAG_GLASS alone also holds and zeroes four counters now, 8 bytes more than its three — one
+        // buffer of one size for either flag, so that a context alternating between them never reallocates; no launch is added)
+        if (rq.glass || rq.gloss) {   // the frame's event counters — three of glass, then the glossy rays — start from zero
+            RWR_HIP_CHECK(W.d_glass_counts.ensure(4));
+            RWR_HIP_CHECK(hipMemsetAsync(W.d_glass_counts.ptr, 0, 4 * sizeof(unsigned long long), stream));
             ft.mirror.glass_counts = W.d_glass_counts.ptr;
         }
     }
@@ -940,6 +953,7 @@ int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const r
     ctx->last_primary = (uint64_t)ctx->screen.width * band_rows(fc.fp) * ap.trace_spp;
     ctx->last_shadows = rq.shadows;
     ctx->last_glass = rq.wavefront && rq.glass && ap.trace_spp != 0u;
+    ctx->last_gloss = rq.wavefront && rq.gloss && ap.trace_spp != 0u;
     ctx->last_bounce = 0;  // filled in lazily by rwr_last_render_stats from the pass counters
     return RWR_OK;
 }

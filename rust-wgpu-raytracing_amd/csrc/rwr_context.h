@@ -63,7 +63,7 @@ using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
 using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
 using OwnedGraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
 using PinnedWords = Owned<uint32_t *, free_pinned_words>;
-struct MirrorRec { float r, g, b, on; };   // a surface's record, a float4 of WfMirror::table — on = 1: a mirror of reflectance r, g, b (RWR_FLAG_MIRRORS); on = -ior: glass of tint r, g, b (RWR_FLAG_GLASS); 0: neither
+struct MirrorRec { float r, g, b, on; };   // a surface's record, a float4 of WfMirror::table — on = 1: a mirror of reflectance r, g, b (RWR_FLAG_MIRRORS); on = -ior: glass of tint r, g, b (RWR_FLAG_GLASS); on = 1 + roughness, in (1, 2]: glossy, reflectance r, g, b (RWR_FLAG_GLOSSY); 0: neither
 static_assert(sizeof(MirrorRec) == sizeof(float4), "MirrorRec is a float4");
 inline hipError_t free_pinned_mirror(MirrorRec *p) { return hipHostFree(p); }
 using PinnedMirror = Owned<MirrorRec *, free_pinned_mirror>;
@@ -155,8 +155,8 @@ struct WfState {
     size_t h_mirror_count = 0;
     OwnedEvent mirror_copied;
     uint64_t mirror_version = 0;
-    uint32_t mirror_modes = 0;                // which surfaces that copy holds: 1 mirrors, 2 glass (WfMirror, rwr_internal.h)
-    DeviceBuffer<unsigned long long> d_glass_counts;   // RWR_FLAG_GLASS: reflected, transmitted, totally reflected; zeroed per frame
+    uint32_t mirror_modes = 0;                // which surfaces that copy holds: 1 mirrors, 2 glass, 4 glossy (WfMirror, rwr_internal.h)
+    DeviceBuffer<unsigned long long> d_glass_counts;   // RWR_FLAG_GLASS: reflected, transmitted, totally reflected; RWR_FLAG_GLOSSY: then the glossy rays; zeroed per frame
 };
 
 // Progressive accumulation (RWR_FLAG_ACCUMULATE): ONE accumulation per context.  Its sums and the first frame's sample-0 planes
@@ -324,6 +324,7 @@ struct rwr_context {
 
     uint64_t last_primary = 0, last_bounce = 0;
     bool last_shadows = false;      // the last render call traced shadow rays (RWR_FLAG_SHADOWS): their counters are in its WfState
+    bool last_gloss = false;        // the last render call ran the glossy forms (RWR_FLAG_GLOSSY): their counter is the fourth of d_glass_counts
     bool last_glass = false;        // the last render call ran the glass forms (RWR_FLAG_GLASS): their counters are in its WfState
     // optional per-kernel timing (rwr_ctx_set_kernel_timing)
     uint32_t timing_every = 0;

@@ -518,6 +518,22 @@ RWR_DEV uint32_t refract_or_reflect(f3 n, f3 D, bool face, float ndotd, float et
     return tir ? 2u : reflect ? 0u : 1u;
 }
 
+// RWR_FLAG_GLOSSY: the ray that leaves a hit on a glossy surface of roughness rho (rwr_hip.h, RWR_FLAG_GLOSSY items 1-5) — between
+// the mirror reflection Rf of the normalised D and X, the diffuse ray the same hit would have sent (bounce_direction of the same
+// dimensions): S = (1 - rho) Rf + rho X per component, two products and one sum; a vanishing or NaN sum gives Rf.  n: the
+// HitRecord normal hit_exit_point builds; D: the direction of the ray that found the hit, of any length.  Not re-normalised.
+// f32 operations in this order, no contraction; selects, no branches.  In two halves, so that a kernel can take the reflection
+// before it draws X (D is dead across the disk loop then) and blend after it: the same operations either way.
+RWR_DEV f3 gloss_reflection(f3 n, f3 D) { return reflect_direction(n, normalize3(D)); }
+RWR_DEV f3 gloss_blend(f3 Rf, f3 X, float rho)
+{
+    const float om = 1.0f - rho;
+    const f3 S = mk3(om * Rf.x + rho * X.x, om * Rf.y + rho * X.y, om * Rf.z + rho * X.z);
+    const bool ok = dot3(S, S) > 0.0f;
+    return mk3(ok ? S.x : Rf.x, ok ? S.y : Rf.y, ok ? S.z : Rf.z);
+}
+RWR_DEV f3 gloss_direction(f3 n, f3 D, f3 X, float rho) { return gloss_blend(gloss_reflection(n, D), X, rho); }
+
 // Wavefront integrator: the key a tile's ray pool is sorted by (kernels_wf_primary.hip stores it, kernels_wf_bounce.hip sorts).
 // Direction bin: 3 bits of octant (Gray-coded so that neighbours share two signs) and 2 x kWfDirCellBits bits of position
 // inside the octant's triangle of the octahedral map (Morton order of a 2^bits x 2^bits grid).

@@ -348,13 +348,16 @@ static_assert(sizeof(WfSky) == sizeof(rwr_sky_params), "WfSky is rwr_sky_params"
 // glass of index -on and tint r, g, b.  A slot's copy holds the surfaces of the flags its frame has, the others' records are
 // zero there, so no kernel looks at a flag.  glass_counts: the frame's three event counters (reflected, transmitted, totally
 // reflected), one atomic per wave; null in the mirror forms.
+// Glossy surfaces (RWR_FLAG_GLOSSY; the glossy forms, SURF = 3) share it too: on = 1 + roughness, in (1, 2], marks a glossy surface
+// of reflectance r, g, b — on == 1 stays a mirror.  Their one counter, the glossy rays emitted, is glass_counts[3], behind the
+// three glass counters (four are allocated whenever any is).
 struct WfMirror {
     const float4 *table;
     uint32_t n_parts;
     uint32_t pad;
     unsigned long long *glass_counts;
 };
-constexpr int kSurfNone = 0, kSurfMirrors = 1, kSurfGlass = 2;   // the kernels' SURF argument: no table, mirrors alone, mirrors and glass
+constexpr int kSurfNone = 0, kSurfMirrors = 1, kSurfGlass = 2, kSurfGloss = 3;   // the kernels' SURF argument: no table, mirrors alone, mirrors and glass, those and glossy
 // What the kernels of one launch group know: the four argument structs above — all zero where the frame lacks the flag, and that
 // is what the kernels then get — and the switches the launchers pick the kernels' forms by.  render.cpp fills it once per launch
 // group; `emit` and `emits` change per generation (a generation that is not the path's last: the trace kernels' EMIT forms).
@@ -364,7 +367,7 @@ struct WfFeatures {
     WfSky sky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     WfMirror mirror{nullptr, 0u, 0u, nullptr};
     bool emits = false, shadows = false, sky_on = false;
-    int surf = kSurfNone;   // the surface models of the frame's flags (kSurfGlass: the table may hold glass records)
+    int surf = kSurfNone;   // the surface models of the frame's flags (kSurfGlass: the table may hold glass records; kSurfGloss: glossy ones too)
     // The two rules for SURF.  The surface forms differ where a ray is emitted and nowhere else: the primary stage has one only
     // when the frame bounces at all, a trace kernel only in a generation that emits (a kernel that ends a path has none).
     int primary_surf(const FrameParams &fp) const { return fp.bounces != 0u ? surf : kSurfNone; }

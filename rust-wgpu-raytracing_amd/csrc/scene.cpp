@@ -245,7 +245,7 @@ int rwr_scene_set_part_mirror(rwr_context *ctx, uint32_t part, const float *refl
     const int rc = mirror_from(reflectance, "part", part, m);
     if (rc != RWR_OK) return rc;   // (a refused call changes nothing, the scene's generation included)
     ctx->scene_generation++;
-    ctx->part_mirrors[part] = m;   // (a surface has one model: this replaces a glass attribute too)
+    ctx->part_mirrors[part] = m;   // (a surface has one model: this replaces a glass or gloss attribute too)
     ctx->mirror_version++;
     return RWR_OK;
 }
@@ -258,14 +258,14 @@ int rwr_scene_set_sphere_mirror(rwr_context *ctx, uint32_t sphere, const float *
     const int rc = mirror_from(reflectance, "sphere", sphere, m);
     if (rc != RWR_OK) return rc;
     ctx->scene_generation++;
-    ctx->sphere_mirrors[sphere] = m;   // (a surface has one model: this replaces a glass attribute too)
+    ctx->sphere_mirrors[sphere] = m;   // (a surface has one model: this replaces a glass or gloss attribute too)
     ctx->mirror_version++;
     return RWR_OK;
 }
 
 static void mirror_out(const MirrorRec &m, int *is_mirror, float reflectance[3])
 {
-    const bool on = m.on > 0.0f;   // (on < 0: glass, rwr_scene_set_part_glass)
+    const bool on = m.on == 1.0f;   // (on < 0: glass, rwr_scene_set_part_glass; on > 1: glossy, rwr_scene_set_part_gloss)
     if (is_mirror) *is_mirror = on ? 1 : 0;
     if (reflectance) { reflectance[0] = on ? m.r : 0.0f; reflectance[1] = on ? m.g : 0.0f; reflectance[2] = on ? m.b : 0.0f; }
 }
@@ -311,7 +311,7 @@ int rwr_scene_set_part_glass(rwr_context *ctx, uint32_t part, float ior, const f
     const int rc = glass_from(ior, tint, "part", part, m);
     if (rc != RWR_OK) return rc;   // (a refused call changes nothing, the scene's generation included)
     ctx->scene_generation++;
-    ctx->part_mirrors[part] = m;   // (a surface has one model: this replaces a mirror attribute too)
+    ctx->part_mirrors[part] = m;   // (a surface has one model: this replaces a mirror or gloss attribute too)
     ctx->mirror_version++;
     return RWR_OK;
 }
@@ -324,7 +324,7 @@ int rwr_scene_set_sphere_glass(rwr_context *ctx, uint32_t sphere, float ior, con
     const int rc = glass_from(ior, tint, "sphere", sphere, m);
     if (rc != RWR_OK) return rc;
     ctx->scene_generation++;
-    ctx->sphere_mirrors[sphere] = m;   // (a surface has one model: this replaces a mirror attribute too)
+    ctx->sphere_mirrors[sphere] = m;   // (a surface has one model: this replaces a mirror or gloss attribute too)
     ctx->mirror_version++;
     return RWR_OK;
 }
@@ -350,6 +350,74 @@ int rwr_scene_get_sphere_glass(rwr_context *ctx, uint32_t sphere, int *is_glass,
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
     if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
     glass_out(ctx->sphere_mirrors[sphere], is_glass, ior, tint);
+    return RWR_OK;
+}
+
+// RWR_FLAG_GLOSSY: a surface's attribute from the caller's three floats of reflectance (NULL: not glossy) and its roughness.
+// The record is the mirror attribute's: {reflectance r, g, b, 1 + roughness} — on in (1, 2] marks a glossy surface, on == 1 a
+// mirror, on < 0 glass, 0 neither.  The roughness the kernels and the getters use is on - 1, a multiple of 2^-23.
+static int gloss_from(const float *reflectance, float roughness, const char *what, uint32_t index, MirrorRec &out)
+{
+    if (!reflectance) {
+        out = MirrorRec{0.0f, 0.0f, 0.0f, 0.0f};
+        return RWR_OK;
+    }
+    if (!(roughness >= 0x1p-10f && roughness <= 1.0f))   // (false for NaN)
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: roughness %g: finite, 2^-10 ... 1", what, index, (double)roughness);
+    for (int c = 0; c < 3; c++)
+        if (!(reflectance[c] >= 0.0f && reflectance[c] <= 1.0f))
+            return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: reflectance[%d] %g: finite, 0 ... 1", what, index, c, (double)reflectance[c]);
+    out = MirrorRec{reflectance[0], reflectance[1], reflectance[2], 1.0f + roughness};
+    return RWR_OK;
+}
+
+int rwr_scene_set_part_gloss(rwr_context *ctx, uint32_t part, const float *reflectance, float roughness)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
+    MirrorRec m;
+    const int rc = gloss_from(reflectance, roughness, "part", part, m);
+    if (rc != RWR_OK) return rc;   // (a refused call changes nothing, the scene's generation included)
+    ctx->scene_generation++;
+    ctx->part_mirrors[part] = m;   // (a surface has one model: this replaces a mirror or glass attribute too)
+    ctx->mirror_version++;
+    return RWR_OK;
+}
+
+int rwr_scene_set_sphere_gloss(rwr_context *ctx, uint32_t sphere, const float *reflectance, float roughness)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
+    MirrorRec m;
+    const int rc = gloss_from(reflectance, roughness, "sphere", sphere, m);
+    if (rc != RWR_OK) return rc;
+    ctx->scene_generation++;
+    ctx->sphere_mirrors[sphere] = m;   // (a surface has one model: this replaces a mirror or glass attribute too)
+    ctx->mirror_version++;
+    return RWR_OK;
+}
+
+static void gloss_out(const MirrorRec &m, int *is_glossy, float reflectance[3], float *roughness)
+{
+    const bool on = m.on > 1.0f;
+    if (is_glossy) *is_glossy = on ? 1 : 0;
+    if (reflectance) { reflectance[0] = on ? m.r : 0.0f; reflectance[1] = on ? m.g : 0.0f; reflectance[2] = on ? m.b : 0.0f; }
+    if (roughness) *roughness = on ? m.on - 1.0f : 0.0f;
+}
+
+int rwr_scene_get_part_gloss(rwr_context *ctx, uint32_t part, int *is_glossy, float reflectance[3], float *roughness)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
+    gloss_out(ctx->part_mirrors[part], is_glossy, reflectance, roughness);
+    return RWR_OK;
+}
+
+int rwr_scene_get_sphere_gloss(rwr_context *ctx, uint32_t sphere, int *is_glossy, float reflectance[3], float *roughness)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
+    gloss_out(ctx->sphere_mirrors[sphere], is_glossy, reflectance, roughness);
     return RWR_OK;
 }
 

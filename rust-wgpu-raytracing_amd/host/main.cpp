@@ -6,7 +6,7 @@
 //              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows]
 //              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]]
 //              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]...
-//              [--glass-sphere N[:ior[:r,g,b]]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]]
+//              [--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]]
 //              [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
@@ -122,6 +122,33 @@ int main(int argc, char **argv)
         for (int c = 0; c < 3; c++) g.tint[c] = v[c];
         return true;
     };
+    // --gloss-part / --gloss-sphere "N:rough" or "N:rough:r,g,b": an index, a roughness in [2^-10, 1] and a reflectance in [0, 1]^3
+    // (1,1,1 when left out)
+    struct Gloss { bool sphere; uint32_t index; float rough; float r[3]; };
+    std::vector<Gloss> glosses;
+    auto parse_gloss = [](const char *text, Gloss &g) {
+        char *end = nullptr;
+        if (*text < '0' || *text > '9') return false;
+        const unsigned long idx = std::strtoul(text, &end, 10);
+        if (end == text || idx > 0xfffffffful) return false;
+        g.index = (uint32_t)idx;
+        g.r[0] = g.r[1] = g.r[2] = 1.0f;
+        if (*end != ':') return false;   // (the roughness is not optional: a surface without one is a mirror)
+        const char *rough_text = end + 1;
+        if (!((*rough_text >= '0' && *rough_text <= '9') || *rough_text == '.')) return false;   // (no sign, no "nan", no "inf")
+        const float rough = std::strtof(rough_text, &end);
+        if (end == rough_text || !(rough >= 0x1p-10f && rough <= 1.0f)) return false;
+        g.rough = rough;
+        if (*end == '\0') return true;
+        if (*end != ':') return false;
+        float v[3];
+        char tail = 0;
+        if (std::sscanf(end + 1, "%f,%f,%f%c", &v[0], &v[1], &v[2], &tail) != 3) return false;
+        for (int c = 0; c < 3; c++)
+            if (!(v[c] >= 0.0f && v[c] <= 1.0f)) return false;
+        for (int c = 0; c < 3; c++) g.r[c] = v[c];
+        return true;
+    };
     struct Resize { uint64_t frame; uint32_t w, h; };
     std::vector<Resize> resizes;
     for (int i = 1; i < argc; i++) {
@@ -186,6 +213,15 @@ int main(int argc, char **argv)
             }
             glasses.push_back(g);
         }
+        else if (a == "--gloss-part" || a == "--gloss-sphere") {
+            Gloss g{a == "--gloss-sphere", 0u, 0.25f, {1.0f, 1.0f, 1.0f}};
+            if (!parse_gloss(next(), g) || (g.sphere && g.index >= RWR_MAX_SPHERES)) {
+                std::fprintf(stderr, "%s N:rough[:r,g,b]: an index%s, a roughness in [2^-10, 1] and three numbers in [0, 1]\n", a.c_str(),
+                             g.sphere ? " below 8" : "");
+                return 2;
+            }
+            glosses.push_back(g);
+        }
         else if (a == "--show-params") show_params = true;
         else if (a == "--resize") {
             Resize r{0, 0, 0};
@@ -201,7 +237,8 @@ int main(int argc, char **argv)
                         "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] "
                         "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
                         "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]... "
-                        "[--glass-sphere N[:ior[:r,g,b]]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]] "
+                        "[--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... "
+                        "[--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]] "
                         "[--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
                         "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n"
@@ -219,6 +256,11 @@ int main(int argc, char **argv)
                         "refraction ior in [1, 4] (1.5 when left out) and tint r,g,b in [0, 1] (1,1,1 when left out): it reflects by Fresnel's law and "
                         "refracts by Snell's (RWR_FLAG_GLASS, implied; needs --bounces >= 1, and several for a ray to get through; "
                         "rwr_scene_set_part_glass / rwr_scene_set_sphere_glass); repeatable\n"
+                        "  --gloss-part N:rough[:r,g,b], --gloss-sphere N:rough[:r,g,b]  part N of the scene / sphere N is glossy, of roughness rough "
+                        "in [2^-10, 1] (towards 0 a mirror, 1 diffuse) and reflectance r,g,b in [0, 1] (1,1,1 when left out): it sends on a ray between "
+                        "the mirror reflection and the diffuse ray (RWR_FLAG_GLOSSY, implied; needs --bounces >= 1; rwr_scene_set_part_gloss / "
+                        "rwr_scene_set_sphere_gloss); repeatable; prints `glossy rays N` for the final frame.  Mirror, glass and gloss options "
+                        "are applied in that order: of several for one surface the last of these wins\n"
                         "  --reproject   every frame is blended with the history of the frames before it, fetched where its points were seen "
                         "last frame, while the camera moves (RWR_FLAG_REPROJECT; with --keys every key step's frame feeds the next one's history): "
                         "at most N frames of history per pixel (1-1024), taps of faces whose normals' cosine is at least C and whose distance "
@@ -233,14 +275,18 @@ int main(int argc, char **argv)
     const uint32_t flags = (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u) |   // more than one bounce: the deeper paths
                            (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u) | (denoise ? (uint32_t)RWR_FLAG_DENOISE : 0u) | (sky ? (uint32_t)RWR_FLAG_SKY : 0u) |
                            (mirrors.empty() ? 0u : (uint32_t)RWR_FLAG_MIRRORS) | (glasses.empty() ? 0u : (uint32_t)RWR_FLAG_GLASS) |
+                           (glosses.empty() ? 0u : (uint32_t)RWR_FLAG_GLOSSY) |
                            (reproject ? (uint32_t)RWR_FLAG_REPROJECT : 0u);
     if (show_params) {
         if (reproject)   // (a line of its own, ahead of the line every run prints)
             std::printf("reproject 1 history %u normal %g depth %g\n", reproject_params.max_history, (double)reproject_params.normal_cos_min,
                         (double)reproject_params.depth_rel);
-        std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g glass %zu", spp, bounces, flags, sky ? 1 : 0,
+        std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g gloss %zu", spp, bounces, flags, sky ? 1 : 0,
                     (double)sky_params.zenith[0], (double)sky_params.zenith[1], (double)sky_params.zenith[2],
-                    (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2], glasses.size());
+                    (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2], glosses.size());
+        for (const Gloss &g : glosses)
+            std::printf(" %s %u:%g:%g,%g,%g", g.sphere ? "sphere" : "part", g.index, (double)g.rough, (double)g.r[0], (double)g.r[1], (double)g.r[2]);
+        std::printf(" glass %zu", glasses.size());
         for (const Glass &g : glasses)
             std::printf(" %s %u:%g:%g,%g,%g", g.sphere ? "sphere" : "part", g.index, (double)g.ior, (double)g.tint[0], (double)g.tint[1], (double)g.tint[2]);
         std::printf(" mirrors %zu", mirrors.size());
@@ -280,6 +326,10 @@ int main(int argc, char **argv)
             const int rc = g.sphere ? rwr_scene_set_sphere_glass(state.context(), g.index, g.ior, g.tint) : rwr_scene_set_part_glass(state.context(), g.index, g.ior, g.tint);
             if (rc != RWR_OK) { std::fprintf(stderr, "%s: %s\n", g.sphere ? "--glass-sphere" : "--glass-part", rwr_last_error_string()); return 2; }
         }
+        for (const Gloss &g : glosses) {   // (after the mirrors and the glass: the later option wins)
+            const int rc = g.sphere ? rwr_scene_set_sphere_gloss(state.context(), g.index, g.r, g.rough) : rwr_scene_set_part_gloss(state.context(), g.index, g.r, g.rough);
+            if (rc != RWR_OK) { std::fprintf(stderr, "%s: %s\n", g.sphere ? "--gloss-sphere" : "--gloss-part", rwr_last_error_string()); return 2; }
+        }
         if (denoise_iterations != 0 || denoise_sigma != 0.0f) {
             rwr_denoise_params dp;
             int rc = rwr_denoise_get_params(state.context(), &dp);
@@ -313,6 +363,7 @@ int main(int argc, char **argv)
                     c.eye.x, c.eye.y, c.eye.z, c.target.x, c.target.y, c.target.z, state.size().width, state.size().height, (double)c.aspect);
         if (accumulate) std::printf("samples %llu\n", (unsigned long long)state.accumulated_samples());
         if (reproject) std::printf("history %llu\n", (unsigned long long)state.reprojected_frames());
+        if (!glosses.empty()) std::printf("glossy rays %llu\n", (unsigned long long)state.glossy_rays());
         if (timing) std::printf("%.3f ms/frame over %llu frames (update + render, host wall clock)\n", sec * 1e3 / (double)rendered,
                                 (unsigned long long)rendered);
         if (!out.empty()) {

@@ -144,6 +144,14 @@ public:
         return n;
     }
 
+    // extension (RWR_FLAG_GLOSSY): the rays the glossy hits of the frame rendered last sent on
+    uint64_t glossy_rays()
+    {
+        uint64_t n = 0;
+        check(rwr_last_gloss_stats(ctx_, &n));
+        return n;
+    }
+
     // the blit's job (screenquad.wgsl + sRGB swapchain, lib.rs:1186-1224): framebuffer -> PNG
     void present(const std::string &png_path)
     {
