@@ -704,6 +704,22 @@ RWR_API int rwr_ray_plane_stats(rwr_context *ctx, uint64_t *builds, uint64_t *fr
  * same.  RWR_ERR_NOT_READY when the last frame has none (another kernel or form, more than 256 faces, RWR_TILE_LISTS=0). */
 RWR_API int rwr_debug_tile_classes(rwr_context *ctx, uint32_t *classes, size_t capacity, uint32_t *grid_x, uint32_t *grid_y);
 
+/* The cover words of the frame rendered last: one word per tile beside the class words (same grid, same order, same arguments as
+ * rwr_debug_tile_classes).  A frame that finds its slot's records made (rwr_frame_setup_launches: it adds no launch) runs the
+ * tiles of class "one face, no sphere" and, where the kernel's own hit test finds that every pixel pair of the tile hits that
+ * face, wins the depth test and stays in the domain of the short division and depth forms, sets the tile's word to 1; the slot's
+ * later frames with the same records take such a tile without the edge-0 product, the compares and the selects that could only
+ * confirm it — t, u, v, depth, shading and texture are computed as ever, frames are the same bytes.  Every k_frame_setup launch
+ * zeroes the words it reaches, so they stand exactly as long as the records they were learnt from; a frame that made its records
+ * neither reads nor writes them.  RWR_TILE_COVER=0 (read when the context is created): no frame does, the words stay 0.
+ * Waits for that frame alone.  RWR_ERR_NOT_READY when the last frame has no class words. */
+RWR_API int rwr_debug_tile_cover(rwr_context *ctx, uint32_t *cover, size_t capacity, uint32_t *grid_x, uint32_t *grid_y);
+
+/* frames: frames of this context so far that looked at cover words (above).  tiles_last: tiles the frame rendered last took as
+ * covered (0 when it did not look, and for a slot's first such frame, which learns them); counted on the host from the words, so
+ * it waits for that frame when it is not 0 by rule.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_tile_cover_stats(rwr_context *ctx, uint64_t *frames, uint64_t *tiles_last);
+
 /* RWR_FLAG_SHADOWS: shadow rays traced by the last render call (= hits shaded: primary hits and the bounce hits of every
  * generation; an accumulating frame: its own samples; 0 without the flag) and how many of them were occluded.  Exact counts.
  * Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */

@@ -119,6 +119,7 @@ def lib() -> C.CDLL:
         "rwr_timer_begin": [vp], "rwr_timer_end": [vp, vp], "rwr_timer_stop": [vp], "rwr_timer_elapsed": [vp, vp], "rwr_last_render_stats": [vp, vp, vp],
         "rwr_last_shadow_stats": [vp, vp, vp], "rwr_frame_setup_launches": [vp, vp], "rwr_ray_plane_stats": [vp, vp, vp],
         "rwr_debug_tile_classes": [vp, vp, C.c_size_t, vp, vp],
+        "rwr_debug_tile_cover": [vp, vp, C.c_size_t, vp, vp], "rwr_tile_cover_stats": [vp, vp, vp],
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
         "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
@@ -148,7 +149,7 @@ def lib() -> C.CDLL:
         "rwr_dist_loopback_deposit": [vp, u32, u32, i32], "rwr_dist_loopback_finish": [vp, u32, i32],
         "rwr_measure_valu_clock": [vp, u32, vp], "rwr_clock_probe_start": [vp, u32], "rwr_clock_probe_read": [vp, vp],
     }
-    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats", "rwr_debug_tile_classes",
+    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats", "rwr_debug_tile_classes", "rwr_debug_tile_cover", "rwr_tile_cover_stats",
                            "rwr_sky_set_params", "rwr_sky_get_params", "rwr_scene_set_part_mirror", "rwr_scene_set_sphere_mirror",
                            "rwr_scene_get_part_mirror", "rwr_scene_get_sphere_mirror", "rwr_scene_set_part_glass", "rwr_scene_set_sphere_glass",
                            "rwr_scene_get_part_glass", "rwr_scene_get_sphere_glass", "rwr_last_glass_stats",
@@ -748,6 +749,22 @@ class Context:
         words = np.empty(4 * gx.value * gy.value, np.uint32)
         _check(lib().rwr_debug_tile_classes(self._h, _p(words), words.size, C.byref(gx), C.byref(gy)))
         return np.ascontiguousarray(words.reshape(gy.value, gx.value, 2, 2).transpose(0, 2, 1, 3).reshape(2 * gy.value, 2 * gx.value))
+
+    def tile_cover(self) -> np.ndarray:
+        """The cover words of the frame rendered last (rwr_debug_tile_cover), laid out like tile_classes(): 1 where a frame served
+        from the slot's kept records found every pixel pair of a one-face tile hitting, 0 elsewhere and after every setup launch."""
+        gx, gy = C.c_uint32(), C.c_uint32()
+        _check(lib().rwr_debug_tile_cover(self._h, None, 0, C.byref(gx), C.byref(gy)))
+        words = np.empty(4 * gx.value * gy.value, np.uint32)
+        _check(lib().rwr_debug_tile_cover(self._h, _p(words), words.size, C.byref(gx), C.byref(gy)))
+        return np.ascontiguousarray(words.reshape(gy.value, gx.value, 2, 2).transpose(0, 2, 1, 3).reshape(2 * gy.value, 2 * gx.value))
+
+    def tile_cover_stats(self) -> tuple[int, int]:
+        """(frames of this context so far that looked at cover words, tiles the frame rendered last took as covered)
+        (rwr_tile_cover_stats); (0, 0) for ever with RWR_TILE_COVER=0."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(lib().rwr_tile_cover_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def last_shadow_stats(self) -> tuple[int, int]:
         """(shadow rays traced by the last render call, how many of them were occluded); (0, 0) without FLAG_SHADOWS."""

@@ -56,6 +56,42 @@ int rwr_debug_tile_classes(rwr_context *ctx, uint32_t *classes, size_t capacity,
     return RWR_OK;
 }
 
+int rwr_debug_tile_cover(rwr_context *ctx, uint32_t *cover, size_t capacity, uint32_t *grid_x, uint32_t *grid_y)
+{
+    if (!ctx || !grid_x || !grid_y) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    const rwr_context::LastClasses lc = ctx->last_classes;
+    const size_t n = (size_t)lc.gx * lc.gy * 4u;
+    if (n == 0 || lc.slot >= ctx->n_slots || ctx->slots[lc.slot].d_tile_lists.count < tile_list_words(lc.gx, lc.gy))
+        return set_error(RWR_ERR_NOT_READY, "the frame rendered last has no cover words (they lie beside the tile classes: rwr_debug_tile_classes)");
+    *grid_x = lc.gx;
+    *grid_y = lc.gy;
+    if (!cover) return RWR_OK;
+    if (capacity < n) return set_error(RWR_ERR_INVALID_ARGUMENT, "room for %zu cover words, the frame has %zu", capacity, n);
+    DeviceGuard g(ctx->device);
+    FrameSlot &sl = ctx->slots[lc.slot];
+    RWR_HIP_CHECK(hipMemcpyAsync(cover, sl.d_tile_lists.ptr + n * (kTileListWords + 1u), n * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+    RWR_HIP_CHECK(hipStreamSynchronize(sl.stream));   // that frame's stream alone
+    return RWR_OK;
+}
+
+int rwr_tile_cover_stats(rwr_context *ctx, uint64_t *frames, uint64_t *tiles_last)
+{
+    if (!ctx || !frames || !tiles_last) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *frames = ctx->tile_cover_frames;
+    *tiles_last = 0;
+    // The last frame took covered exactly the tiles whose words were set before it: none when it was its slot's first frame with
+    // the flag since a setup (it learnt them), else the words as they stand (what a tile's tests say does not change while the
+    // records stand, so every frame after the first finds and leaves the same words) — counted here, not by the kernel.
+    if (ctx->last_cover_frames < 2u) return RWR_OK;
+    uint32_t gx = 0, gy = 0;
+    int rc = rwr_debug_tile_cover(ctx, nullptr, 0, &gx, &gy);
+    if (rc != RWR_OK) return rc;
+    std::vector<uint32_t> words((size_t)gx * gy * 4u);
+    if ((rc = rwr_debug_tile_cover(ctx, words.data(), words.size(), &gx, &gy)) != RWR_OK) return rc;
+    for (uint32_t w : words) *tiles_last += w == kTileCovered ? 1u : 0u;
+    return RWR_OK;
+}
+
 int rwr_measure_valu_clock(rwr_context *ctx, uint32_t waves_per_simd, double out4[4])
 {
     if (!ctx || !out4) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");

@@ -37,7 +37,9 @@ namespace rwr {
 // with every tile's set (rwr_internal.h kTileFaces*), and a wave takes one of three ways through its tile by it — clear values
 // for a tile nothing can show in, a straight path for exactly one face and no sphere, the whole kernel otherwise.  The ways
 // meet again at the stores: one tail, so that the form's registers are those of the general path alone.
-template <bool AUX, bool CULL, bool NMAP, bool FUSED = false, bool PLANE = false>
+// COVER: a frame served from the slot's kept records (RWR_FLAG_TILE_COVER, render.cpp) — the straight path reads and learns the
+// tiles' cover words (rwr_internal.h kTileCovered).  An instantiation of its own, so that every other frame runs the code it ran.
+template <bool AUX, bool CULL, bool NMAP, bool FUSED = false, bool PLANE = false, bool COVER = false>
 __global__ void __launch_bounds__(256, (AUX || NMAP) ? 4 : RWR_P2_OCC)
 // (the first eleven arguments repeat FrameParams fields: they are what a wave needs first, and the Makefile
 // has their 14 dwords preloaded into SGPRs)
@@ -48,6 +50,7 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
              const QuadTex tex, const Targets tg, const FusedSetup fs)
 {
     static_assert(!PLANE || (CULL && !NMAP && !FUSED), "the loading form exists for the culled two-launch frame without normal maps");
+    static_assert(!COVER || (CULL && !NMAP && !FUSED), "cover words lie beside the face sets of the culled two-launch frame; normal maps take the general path");
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     uint32_t by = blockIdx.y;
     const_ptr<TriRecord> tris_c = nullptr;
@@ -281,23 +284,57 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
         const TriRecord T = tris[idx];
         const float tnum = to_const_space(p.tnum)[idx];
         one_shade = shade[idx];
+        // ... and with them, on a frame served from the slot's kept records (RWR_FLAG_TILE_COVER, render.cpp), the tile's cover word
+        // (rwr_internal.h kTileCovered; the third parallel array): what the tests below said about the tile on an earlier frame
+        // with these records.  Without the flag the word is neither read nor written.
+        // (cov: the word, or kTileNotCovering without the flag — one scalar register carries both facts across the test)
+        constexpr uint32_t kTileNotCovering = 2u;
+        auto cover_at = [&](uint32_t w) { return gridDim.x * gridDim.y * 4u * (kTileListWords + 1u) + (by * gridDim.x + blockIdx.x) * 4u + w; };
+        uint32_t cov = kTileNotCovering;
+        if constexpr (COVER) {
+            if ((p.flags & RWR_FLAG_TILE_COVER) != 0u) cov = to_const_space(p.tile_lists)[cover_at(wu)];
+        }
         rwait();   // (the table's barrier)
+        // (p0 and e0 are read by one of the two branches below alone; left to itself the compiler moves their loads into that
+        // branch, behind the barrier, where nothing hides them: keep the whole record requested ahead of it)
+        if constexpr (COVER) asm volatile("" ::"s"(T.p0[0]), "s"(T.p0[1]), "s"(T.p0[2]), "s"(T.e0[0]), "s"(T.e0[1]), "s"(T.e0[2]));
         __syncthreads();
-        f2 u, v;
-        best.have = triangle_hit(T, tnum, O, D, best.t, u, v, best.ndotd);
-        best.u = best.have ? u : splat(0.0f);   // (a pair without a hit shades texel (0, 0) and drops the result, as ever)
-        best.v = best.have ? v : splat(0.0f);
         best.idx = u2{idx, idx};
         last_idx = idx;
         n_tested = 1u;
         if (AUX) dbg_listed = dbg_tested = 1u;
-        // the depth test against the cleared plane: current_depth = 1 - 0 (compute.wgsl:210)
-        const bool fast = !__any(any2(best.have & ~depth_fast_domain(best.t)));
-        const f2 depth = fast ? to_non_linear_depth_fast(best.t) : to_non_linear_depth(best.t);
-        const i2 win = best.have & ~(depth >= 1.0f);
-        depth_tex = win ? (1.0f - depth) : splat(0.0f);
-        obj = win ? i2{(int)idx, (int)idx} : i2{-1, -1};
-        win_t = win ? best.t : splat(0.0f);
+        if (COVER && cov == kTileCovered) {
+            // ... and the cover word says what the lines of the other branch found on an earlier frame with these very records and
+            // rays: every pair hits, wins, and both short forms are in their domain.  What feeds colour and depth is computed as
+            // there; what could only confirm the word is not.
+            triangle_covered(T, tnum, O, D, best.t, best.u, best.v, best.ndotd);
+            best.have = i2{-1, -1};
+            depth_tex = 1.0f - to_non_linear_depth_fast(best.t);
+            obj = i2{(int)idx, (int)idx};
+            win_t = best.t;
+        } else {
+            f2 u, v;
+            best.have = triangle_hit(T, tnum, O, D, best.t, u, v, best.ndotd);
+            best.u = best.have ? u : splat(0.0f);   // (a pair without a hit shades texel (0, 0) and drops the result, as ever)
+            best.v = best.have ? v : splat(0.0f);
+            // the depth test against the cleared plane: current_depth = 1 - 0 (compute.wgsl:210)
+            const bool fast = !__any(any2(best.have & ~depth_fast_domain(best.t)));
+            const f2 depth = fast ? to_non_linear_depth_fast(best.t) : to_non_linear_depth(best.t);
+            const i2 win = best.have & ~(depth >= 1.0f);
+            depth_tex = win ? (1.0f - depth) : splat(0.0f);
+            obj = win ? i2{(int)idx, (int)idx} : i2{-1, -1};
+            win_t = win ? best.t : splat(0.0f);
+            if (COVER && cov != kTileNotCovering) {
+                // learn the word: the masks these lines decided, compared once per wave (hit_t's own two domain tests again, the
+                // same expressions).  One lane stores, with a plain vector store; the slot's stream orders it against the slot's
+                // next launch, and no other wave reads this word.
+                const bool all = fast && hit_div_num_domain(tnum) && hit_div_lanes_in_domain(abs2(best.ndotd)) &&
+                                 __builtin_amdgcn_ballot_w64((win.x & win.y) != 0) == __builtin_amdgcn_read_exec();
+                uint32_t w = wu;
+                asm volatile("" : "+s"(w));   // (the address is formed again here, once per tile and key, not carried through the test)
+                if (all && lane == 0u) const_cast<uint32_t *>(p.tile_lists)[cover_at(w)] = kTileCovered;
+            }
+        }
     } else {
     // -- every other tile ---------------------------------------------------------------------------------------------------
 
@@ -476,11 +513,14 @@ hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriReco
     fp.n_tris, fp.row_begin, fp.bins.enabled, fp.row_pitch, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3], fp, tris, shade, tex, tg, fs)
     if (plane) {   // (a resting camera's frame: render.cpp ray_plane_step)
         if (fused || nmap || !do_cull || !plane->xy || !plane->z) return hipErrorInvalidValue;
+        const bool cover = (fp.flags & RWR_FLAG_TILE_COVER) != 0u;
         const float4 *const pxy = plane->xy, *const pz = reinterpret_cast<const float4 *>(plane->z);   // in the ray tables' arguments
-#define RWR_P2_LAUNCH_PLANE(A) hipExtLaunchKernelGGL((k_primary_p2<A, true, false, false, true>), grid, block, 0, s, ev_start, ev_stop, 0, ftris, pxy, pz, \
+#define RWR_P2_LAUNCH_PLANE(A, V) hipExtLaunchKernelGGL((k_primary_p2<A, true, false, false, true, V>), grid, block, 0, s, ev_start, ev_stop, 0, ftris, pxy, pz, \
     fp.n_tris, fp.row_begin, fp.bins.enabled, fp.row_pitch, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3], fp, tris, shade, tex, tg, fs)
-        if (aux) RWR_P2_LAUNCH_PLANE(true);
-        else RWR_P2_LAUNCH_PLANE(false);
+        if (aux && cover) RWR_P2_LAUNCH_PLANE(true, true);
+        else if (aux) RWR_P2_LAUNCH_PLANE(true, false);
+        else if (cover) RWR_P2_LAUNCH_PLANE(false, true);
+        else RWR_P2_LAUNCH_PLANE(false, false);
 #undef RWR_P2_LAUNCH_PLANE
     } else if (fused) {   // (the plain reference frame only: context.cpp)
         RWR_P2_LAUNCH(false, true, false, true);
@@ -489,6 +529,13 @@ hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriReco
         else if (aux) RWR_P2_LAUNCH(true, false, true, false);
         else if (do_cull) RWR_P2_LAUNCH(false, true, true, false);
         else RWR_P2_LAUNCH(false, false, true, false);
+    } else if ((fp.flags & RWR_FLAG_TILE_COVER) != 0u) {   // (a resting camera's frame without a plane: RWR_RAY_PLANE=0, a frame too large for one)
+        if (!do_cull) return hipErrorInvalidValue;
+#define RWR_P2_LAUNCH_COVER(A) hipExtLaunchKernelGGL((k_primary_p2<A, true, false, false, false, true>), grid, block, 0, s, ev_start, ev_stop, 0, ftris, fp.ray_colp, fp.ray_row, \
+    fp.n_tris, fp.row_begin, fp.bins.enabled, fp.row_pitch, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3], fp, tris, shade, tex, tg, fs)
+        if (aux) RWR_P2_LAUNCH_COVER(true);
+        else RWR_P2_LAUNCH_COVER(false);
+#undef RWR_P2_LAUNCH_COVER
     } else {
         if (aux && do_cull) RWR_P2_LAUNCH(true, true, false, false);
         else if (aux) RWR_P2_LAUNCH(true, false, false, false);

@@ -310,7 +310,7 @@ struct RecordsKey {
 static_assert(sizeof(RecordsKey) == sizeof(rwr_camera_inv_uniform) + sizeof(CullConsts) + 8 + 9 * sizeof(void *) + 16 * 4 + sizeof(TileClassIn),
               "RecordsKey has no padding");
 static_assert(sizeof(FrameSetupOut) == 96, "a new member of FrameSetupOut belongs in RecordsKey");
-static_assert(sizeof(TileClassIn) == 160, "a new member of TileClassIn is a new input of k_frame_setup: RecordsKey holds the whole struct");
+static_assert(sizeof(TileClassIn) == 168, "a new member of TileClassIn is a new input of k_frame_setup: RecordsKey holds the whole struct");
 
 // The class words' inputs for a launch whose sets go to so.tile_lists (rwr_internal.h: the words lie behind the sets); all zero
 // for a launch without sets.
@@ -319,6 +319,7 @@ TileClassIn tile_class_in(const FrameParams &fp, const FrameSetupOut &so)
     TileClassIn tc{};
     if (!so.tile_lists) return tc;
     tc.classes = so.tile_lists + (size_t)so.list_gx * so.list_gy * 4u * kTileListWords;
+    tc.cover = tc.classes + (size_t)so.list_gx * so.list_gy * 4u;
     for (int k = 0; k < 4; k++) tc.mesh_px[k] = fp.mesh_px[k];
     tc.n_spheres = fp.n_spheres;
     std::memcpy(tc.sphere_rect, fp.sphere_rect, sizeof tc.sphere_rect);
@@ -333,8 +334,11 @@ TileClassIn tile_class_in(const FrameParams &fp, const FrameSetupOut &so)
 // records whenever they run — made, not counted (launch_frame_graph counts replays), and it leaves no key.
 // This is the only place that leaves a key behind; whatever else writes the slot's records clears it (launch_frame_graph,
 // launch_fused_frame, and ensure_frame_buffers when a buffer moves outside a frame).
-hipError_t launch_records(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc, const FrameSetupOut &so, bool captured = false)
+// *kept (may be null): the launch was not made, the slot's records — and the tiles' class and cover words among them — are the
+// ones an earlier launch with this key left.
+hipError_t launch_records(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc, const FrameSetupOut &so, bool captured = false, bool *kept = nullptr)
 {
+    if (kept) *kept = false;
     const FrameParams &fp = fc.fp;
     const RecordsKey key{fp.cam, fc.cc, ctx->scene_generation, ctx->d_cull.ptr, ctx->d_tris.ptr, so.ftris, so.tnum, so.ray_colp, so.ray_row,
                          so.zero_a, so.zero_b, so.tile_lists, fp.width, fp.height, ctx->n_tris, so.ray_pairs, so.ray_rows, so.n_zero_a,
@@ -342,9 +346,12 @@ hipError_t launch_records(rwr_context *ctx, FrameSlot &sl, const FrameConsts &fc
                          fp.row_begin, fp.row_end, fp.row_pitch, 0u, tile_class_in(fp, so)};
     const unsigned char *bytes = reinterpret_cast<const unsigned char *>(&key);
     const bool pure = so.n_zero_a == 0u && so.n_zero_b == 0u;
-    if (!captured && pure && sl.records_key.size() == sizeof key && std::memcmp(sl.records_key.data(), bytes, sizeof key) == 0)
+    if (!captured && pure && sl.records_key.size() == sizeof key && std::memcmp(sl.records_key.data(), bytes, sizeof key) == 0) {
+        if (kept) *kept = true;
         return hipSuccess;
+    }
     sl.records_key.clear();
+    sl.cover_frames = 0;   // (the launch zeroes the cover words it reaches: what the frames since the last one learnt is forgotten)
     const hipError_t e = launch_frame_setup(sl.stream, fc.cc, fp.cam, fp.width, fp.height, ctx->d_cull.ptr, ctx->d_tris.ptr, ctx->n_tris, so, key.tc);
     if (e != hipSuccess || captured) return e;
     ctx->setup_launches++;
@@ -414,11 +421,12 @@ bool ray_plane_step(rwr_context *ctx, FrameSlot &sl, const FrameParams &fp, RayP
 }
 
 // k_frame_setup, the screen bins of a large scene, and the start of the frame's timing pair.
-int enqueue_records(rwr_context *ctx, FrameSlot &sl, FrameKernel kernel, FrameConsts &fc, const FrameSetupOut &so, FrameTiming &timing)
+int enqueue_records(rwr_context *ctx, FrameSlot &sl, FrameKernel kernel, FrameConsts &fc, const FrameSetupOut &so, FrameTiming &timing,
+                    bool *kept = nullptr)
 {
     FrameParams &fp = fc.fp;
     const hipStream_t stream = sl.stream;
-    RWR_HIP_CHECK(launch_records(ctx, sl, fc, so));
+    RWR_HIP_CHECK(launch_records(ctx, sl, fc, so, false, kept));
     if (ctx->n_tris > ctx->bin_min_faces && !(fp.flags & RWR_FLAG_NO_CULL)) {
         // more faces than one 256-wide batch: bin them per 64x32-pixel screen region, once per frame.  The lists
         // are sized by a count pass on the device; the buffer keeps what the previous frames needed (read back a
@@ -558,9 +566,10 @@ int enqueue_reference(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, F
         fp.tile_lists = so.tile_lists;
     }
     // the frame kernel takes a tile by its class word (RWR_TILE_CLASS=0: it looks at none; the setup writes them all the same)
-    fp.flags &= ~RWR_FLAG_TILE_CLASS;
+    fp.flags &= ~(RWR_FLAG_TILE_CLASS | RWR_FLAG_TILE_COVER);
     if (so.tile_lists && ctx->tile_class) fp.flags |= RWR_FLAG_TILE_CLASS;
     ctx->last_classes = rwr_context::LastClasses{so.tile_lists ? ctx->cur : 0u, so.list_gx, so.tile_lists ? so.list_gy : 0u};
+    ctx->last_cover_frames = 0;   // (set below, by the one form that looks at cover words)
     const QuadTex quad_tex{ctx->d_quads.empty() ? nullptr : ctx->d_quads[0].ptr, ctx->d_mat_quads.ptr, ctx->d_srgb_lut.ptr};
     const bool plain = small_culled && !rq.aux && !ctx->timing_every;   // nothing but records + frame kernel on the stream
     if (plain && ctx->frame_graph) return launch_frame_graph(ctx, sl, fc, so, quad_tex, tg);   // (an empty band too: captured as it is)
@@ -568,7 +577,8 @@ int enqueue_reference(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, F
         ctx->last_classes = rwr_context::LastClasses{};   // (the fused form makes no sets)
         return launch_fused_frame(ctx, sl, fc, so, quad_tex, tg);
     }
-    if ((rc = enqueue_records(ctx, sl, kernel, fc, so, timing)) != RWR_OK) return rc;
+    bool kept = false;
+    if ((rc = enqueue_records(ctx, sl, kernel, fc, so, timing, &kept)) != RWR_OK) return rc;
     switch (kernel) {
     case FrameKernel::kDormant: {
         SingleTriangles st{};
@@ -590,6 +600,16 @@ int enqueue_reference(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, F
         RayPlane plane{};
         const bool can_load = !(fp.flags & RWR_FLAG_NO_CULL) && !((fp.flags & RWR_FLAG_NORMAL_MAP) && fp.tangents);
         const bool load = can_load && ray_plane_step(ctx, sl, fp, plane);
+        // Cover words (rwr_internal.h kTileCovered): only a frame served from the slot's kept records looks at them — the first
+        // such frame learns them with the straight path's own tests, the frames after it skip those tests on the tiles learnt —
+        // so a frame that made its records (a moving camera, RWR_SETUP_CACHE=0) neither reads nor writes one.  RWR_TILE_COVER=0:
+        // no frame does.
+        // (can_load: no normal maps; one material — the frames whose one-face tiles take the straight path at all)
+        if (kept && (fp.flags & RWR_FLAG_TILE_CLASS) && ctx->tile_cover && can_load && fp.n_materials <= 1u) {
+            fp.flags |= RWR_FLAG_TILE_COVER;
+            ctx->tile_cover_frames++;
+            ctx->last_cover_frames = ++sl.cover_frames;
+        }
         RWR_HIP_CHECK(launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, quad_tex, tg,
                                         timing.dispatch ? ctx->timing_events[2 * ctx->timing_pairs].h : nullptr,
                                         timing.dispatch ? ctx->timing_events[2 * ctx->timing_pairs + 1].h : nullptr, nullptr,
@@ -938,6 +958,7 @@ int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const r
 
     FrameTiming timing;
     ctx->last_classes = rwr_context::LastClasses{};   // (enqueue_reference: a frame whose setup makes class words)
+    ctx->last_cover_frames = 0;
     rc = kernel == FrameKernel::kWavefront ? enqueue_wavefront(ctx, sl, rq, ap, pp, fc, tg, timing)
                                            : enqueue_reference(ctx, sl, rq, kernel, fc, tg, timing);
     if (rc != RWR_OK) return rc;

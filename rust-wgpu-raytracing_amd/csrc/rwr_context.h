@@ -97,6 +97,7 @@ struct FrameSlot {
     // what the records, tables and face sets above were made from, byte for byte (render.cpp launch_records), while they stand:
     // a frame with the same key on this slot finds them made and launches no k_frame_setup.  Empty: nothing to rely on
     std::vector<unsigned char> records_key;
+    uint32_t cover_frames = 0;   // frames with RWR_FLAG_TILE_COVER on this slot since its last k_frame_setup (which zeroes the cover words)
     // The kept plane of ray directions (rwr_internal.h RayPlane; render.cpp ray_plane_step), allocated by the slot's first build:
     // the xy array, then the z array.  ray_plane_key: the plane key (camera, screen, rows, addresses) of the slot's last frame
     // that could use a plane, empty when there is nothing to rely on; ray_plane_built: d_ray_plane holds that key's directions
@@ -247,6 +248,9 @@ struct rwr_context {
     bool tile_class = true;                             // the two-pixel kernel takes a tile by the class word k_frame_setup left with its face set; RWR_TILE_CLASS=0: it ignores the words
     struct LastClasses { uint32_t slot = 0, gx = 0, gy = 0; };   // the class words of the frame rendered last: its slot and the frame kernel's grid (gy == 0: it has none)
     LastClasses last_classes;                           // (rwr_debug_tile_classes)
+    bool tile_cover = true;                             // a frame served from a slot's kept records learns and uses the tiles' cover words (rwr_internal.h kTileCovered); RWR_TILE_COVER=0: no frame looks at them
+    uint64_t tile_cover_frames = 0;                     // frames that ran with RWR_FLAG_TILE_COVER so far (rwr_tile_cover_stats)
+    uint32_t last_cover_frames = 0;                     // the frame rendered last: 0 without the flag, else its slot's FrameSlot::cover_frames (1: it learnt, more: it used what was learnt)
     // BVH over the (flattened) world-space faces, for bounce rays
     rwr::DeviceBuffer<rwr::BvhNode4> d_bvh_nodes;
     rwr::DeviceBuffer<uint32_t> d_bvh_leaf_faces;

@@ -192,6 +192,7 @@ struct MeshHit2 {
 // triangleRayIntersect + selection (compute.wgsl:82-148, 198-201), branch-free, for a pixel pair
 // against a wave-uniform record (cf. intersect_and_select).
 // tnum = -(dot(N, O) + d), the ray-independent numerator of :99-102 (k_frame_setup).
+// (triangle_hit and triangle_covered below repeat these lines: a change here is a change there.)
 RWR_DEV void intersect_and_select(const TriRecord &T, float tnum, uint32_t idx, f3 O, v3 D, MeshHit2 &best)
 {
     const f3 N1 = ld3(T.N);
@@ -240,6 +241,22 @@ RWR_DEV i2 triangle_hit(const TriRecord &T, float tnum, f3 O, v3 D, f2 &t, f2 &u
     v = dot3(N, C);
     hit &= ~(v < 0.0f);                                       // :136
     return hit;
+}
+// What the test computes for a tile whose every pair is known to hit (kernels_primary_p2.hip, the covered way: triangle_hit itself
+// said so for these very operands in an earlier frame, and said that tnum and every lane's ndotd lie in the short division's
+// domain): t, u, v and ndotd — the lines of triangle_hit, operation for operation, minus the mask, its compares, the edge-0
+// product (of which only the sign was used) and the domain tests of hit_t.  A change there is a change here.
+RWR_DEV void triangle_covered(const TriRecord &T, float tnum, f3 O, v3 D, f2 &t, f2 &u, f2 &v, f2 &ndotd)
+{
+    const f3 N1 = ld3(T.N);
+    const v3 N = splat3(N1);
+    ndotd = dot3(N, D);
+    t = div_fast(splat(tnum), ndotd);                         // :99-102, hit_t's short form
+    const v3 P = along(splat3(O), t, D);                      // :110
+    v3 C = cross3(splat3(ld3(T.e1)), sub3(P, splat3(ld3(T.p1))));
+    u = dot3(N, C);
+    C = cross3(splat3(ld3(T.e2)), sub3(P, splat3(ld3(T.p2))));
+    v = dot3(N, C);
 }
 
 // Scene data read at wave-uniform addresses goes through the CONSTANT address space: in a kernel that also stores to global

@@ -139,6 +139,7 @@ RWR_DEV void frame_tile_lists_block(uint32_t block, const CullConsts &cc, const 
                     if (!off) cls |= 1u << (kTileSphereShift + s);
                 }
                 tc.classes[(size_t)(by * out.list_gx + bx) * 4u + w] = cls;
+                tc.cover[(size_t)(by * out.list_gx + bx) * 4u + w] = 0u;   // what a frame kernel learnt about the tile (kTileCovered) goes with the records it learnt it from
             }
         }
     }

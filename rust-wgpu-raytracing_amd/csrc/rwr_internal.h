@@ -19,6 +19,10 @@ constexpr uint32_t RWR_FLAG_ONE_PIXEL_PER_LANE = 1u << 17;
 // Internal, set by render.cpp alone (a caller's bit is cleared): the frame's per-tile face sets come with class words
 // (TileClassIn below) and the two-pixel frame kernel branches on them.  Clear (RWR_TILE_CLASS=0): the kernel never loads one.
 constexpr uint32_t RWR_FLAG_TILE_CLASS = 1u << 18;
+// Internal, set by render.cpp alone (a caller's bit is cleared), only beside RWR_FLAG_TILE_CLASS and only on a frame that found its
+// slot's records made (launch_records: a key hit): the kernel reads the tiles' cover words (kTileCovered below) and writes the ones
+// it learns.  Clear (a key miss, RWR_TILE_COVER=0, any other form): the kernel neither reads nor writes them.
+constexpr uint32_t RWR_FLAG_TILE_COVER = 1u << 19;
 
 // ---------------------------------------------------------------------------
 // Device-side scene records (data layout in HBM, see DESIGN.md §"Data layout").
@@ -177,7 +181,14 @@ constexpr uint32_t kListRegionWgs = 4, kListRegionsPerWave = 1;
 constexpr uint32_t kTileFacesNone = 0u, kTileFacesOne = 1u, kTileFacesMore = 2u, kTileFacesMask = 3u;
 constexpr uint32_t kTileFaceShift = 8u, kTileSphereShift = 16u, kTileSphereMask = 0xffu << kTileSphereShift;
 static_assert(RWR_MAX_SPHERES <= 8 && kTileListMaxFaces <= 256, "a class word has 8 bits for the spheres and 8 for a face index");
-inline size_t tile_list_words(uint32_t gx, uint32_t gy) { return (size_t)gx * gy * 4u * (kTileListWords + 1u); }   // sets, then class words
+// One cover word per tile, a third parallel array behind the class words (word 9 * tiles + tile).  The setup lane that writes a
+// tile's class word zeroes it; the frame kernel of a frame served from the slot's kept records (RWR_FLAG_TILE_COVER) sets it to
+// kTileCovered when its own hit test found, for a tile of class "one face, no sphere", that every pixel pair of the tile hit the
+// face, won the depth test and stayed in the domain of both short forms (division, depth) — a pure function of what RecordsKey
+// holds, so it stands exactly as long as the class word beside it — and from the next such frame on takes the tile without the
+// tests that could only confirm it.
+constexpr uint32_t kTileCovered = 1u;
+inline size_t tile_list_words(uint32_t gx, uint32_t gy) { return (size_t)gx * gy * 4u * (kTileListWords + 2u); }   // sets, then class words, then cover words
 
 struct FrameParams {
     rwr_camera_inv_uniform cam;
@@ -498,11 +509,12 @@ struct FrameSetupOut {
 // frame kernel's arguments stay what they were.
 struct TileClassIn {
     uint32_t *classes;
+    uint32_t *cover;   // the tiles' cover words (kTileCovered above), zeroed with every class word written
     int32_t mesh_px[4];
     uint32_t n_spheres, pad;
     float sphere_rect[RWR_MAX_SPHERES][4];
 };
-static_assert(sizeof(TileClassIn) == 8 + 16 + 8 + RWR_MAX_SPHERES * 16, "TileClassIn has no padding");
+static_assert(sizeof(TileClassIn) == 8 + 8 + 16 + 8 + RWR_MAX_SPHERES * 16, "TileClassIn has no padding");
 // The frame kernel's FUSED form (one launch per frame, kernels_primary_p2.hip): the grid's first rows are workgroups that make
 // the frame's records and tables (the work of k_frame_setup), the others wait until all of them have finished.
 struct FusedSetup {
