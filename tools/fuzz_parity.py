@@ -12,6 +12,11 @@ seconds, the walk ends early once that time is up and says how far it came.
 --path --glass: glass_cases.glass_case(g) for g in [first, first + count) (default: the 64 cases after the committed list) against
 glass_ref.c with glass_cases.compare, the three glass event counts included; the cases of glass_cases.ROUNDED_THROUGHPUT against
 the reference that rounds the throughput to unorm16 (glass_cases.compare_rounded); the walk stops at the first mismatch.
+    python tools/fuzz_parity.py --path --gloss [first] [count] [seconds]      see tests/gloss_cases.py
+--path --gloss: gloss_cases.gloss_case(q) for q in [first, first + count) (default: the 64 cases after the committed 96) against
+gloss_ref.c with gloss_cases.compare, the glossy-ray count and the three glass event counts included; otherwise as --glass (the
+cases of gloss_cases.ROUNDED_THROUGHPUT, the first mismatch, the error against the rounded reference where it stops), and the last
+line also gives the worst case's error against the rounded reference.
 """
 import os
 import sys
@@ -27,10 +32,11 @@ r = g.load_package()
 far = "--far" in sys.argv[1:]
 rest = "--rest" in sys.argv[1:]
 path = "--path" in sys.argv[1:]
-glass = "--glass" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a not in ("--far", "--rest", "--path", "--glass")]
+gloss = "--gloss" in sys.argv[1:]
+glass = "--glass" in sys.argv[1:] or gloss      # the gloss walk is the glass walk over another list, with one more count
+args = [a for a in sys.argv[1:] if a not in ("--far", "--rest", "--path", "--glass", "--gloss")]
 if glass and not path:
-    sys.exit("--glass goes with --path")
+    sys.exit("--glass and --gloss go with --path")
 if path:
     import tempfile
 
@@ -41,7 +47,12 @@ if path:
         def mktemp(name):
             return tempfile.mkdtemp(prefix=name)
 
-    if glass:     # the list, its reference, its comparison; the glass walk stops at the first mismatch
+    if gloss:
+        import gloss_cases as cases
+        import gloss_ref
+
+        L, make, n_listed, what = gloss_ref.lib(_Tmp), cases.gloss_case, cases.N_GLOSS_CASES, "gloss"
+    elif glass:   # the list, its reference, its comparison; the glass walk stops at the first mismatch
         import glass_cases as cases
         import glass_ref
 
@@ -55,10 +66,10 @@ if path:
     first = int(args[0]) if len(args) > 0 else n_listed
     count = int(args[1]) if len(args) > 1 else 64
     t_end = time.time() + float(args[2]) if len(args) > 2 else None
-    worst = worst_ratio = 0.0
+    worst = worst_ratio = worst_rounded = 0.0
     at = None
     t0 = time.time()
-    done, failed, ctx, with_events, events = 0, [], None, 0, [0, 0, 0]
+    done, failed, ctx, with_events, events, with_glossy, glossy = 0, [], None, 0, [0, 0, 0], 0, 0
     for i in range(first, first + count):
         if t_end is not None and time.time() >= t_end:
             break
@@ -72,7 +83,7 @@ if path:
             got = cases.gpu_frame(r, c, ctx)
             if glass and i in cases.ROUNDED_THROUGHPUT:      # held to the reference that rounds the throughput, as the GPU test holds it
                 err, against_plain = cases.compare_rounded(got, L, orc, c)
-                print(f"glass case {i}: colour error {against_plain:.3g} against the plain reference, {err:.3g} against the one that rounds the "
+                print(f"{what} case {i}: colour error {against_plain:.3g} against the plain reference, {err:.3g} against the one that rounds the "
                       f"throughput to unorm16 ({err / path_cases.color_bar(c):.2f} of its bar)", flush=True)
             else:
                 err = cases.compare(got, cases.reference(L, orc, c), c)
@@ -84,16 +95,21 @@ if path:
             if glass:     # where it stops it also says what the reference that rounds the throughput would have said
                 try:
                     err, _ = cases.compare_rounded(got, L, orc, c)
-                    print(f"glass case {i}: every integer equal; against the reference that rounds the throughput to unorm16 {err:.3g} "
+                    print(f"{what} case {i}: every integer equal; against the reference that rounds the throughput to unorm16 {err:.3g} "
                           f"({err / path_cases.color_bar(c):.2f} of its bar)", flush=True)
                 except AssertionError as e2:
-                    print(f"glass case {i}: no match with the reference that rounds the throughput either: {e2}", flush=True)
+                    print(f"{what} case {i}: no match with the reference that rounds the throughput either: {e2}", flush=True)
                 break
             err = 0.0
+        if gloss and err / path_cases.color_bar(c) >= worst_ratio:      # the worst so far: what the rounded reference says of it
+            worst_rounded = float(abs(got["color_f32"] - cases.reference(L, orc, c, thr_unorm16=True)["color_f32"]).max())
         cases.forget(c)
         if glass:
             with_events += sum(got["glass"]) > 0
             events = [a + b for a, b in zip(events, got["glass"])]
+        if gloss:
+            with_glossy += got["glossy"] > 0
+            glossy += got["glossy"]
         if err / path_cases.color_bar(c) >= worst_ratio:
             worst, worst_ratio, at = err, err / path_cases.color_bar(c), i
         done += 1
@@ -102,8 +118,11 @@ if path:
     if ctx is not None:
         ctx.close()
     seen = f" {with_events} with glass events (reflected, transmitted, totally reflected: {tuple(events)})," if glass else ""
+    if gloss:
+        seen = f" {with_glossy} with glossy rays ({glossy} of them)," + seen
     print(f"{'ok' if not failed else 'FAILED ' + str(failed)}: {done} {what} cases ({first} ... {first + done - 1}) in {time.time() - t0:.0f} s,{seen} "
-          f"worst colour error {worst:.2e} (case {at}, {worst_ratio:.2f} of its bar)")
+          f"worst colour error {worst:.2e} (case {at}, {worst_ratio:.2f} of its bar)" +
+          (f", {worst_rounded:.2e} against the reference that rounds the throughput to unorm16" if gloss else ""))
     sys.exit(1 if failed else 0)
 seed = int(args[0]) if len(args) > 0 else 1
 seconds = float(args[1]) if len(args) > 1 else 30.0
