@@ -1,7 +1,7 @@
 // C-ABI implementation: the context's life cycle, targets, timers and statistics.
 // Replaces the wgpu plumbing of State (the reference's src/lib.rs:260-1231) with
 // one HIP stream and a handful of device buffers.  The scene, the frame, the self-tests and the
-// multi-GPU gather have their own units (scene.cpp, render.cpp, diagnostics.cpp, dist.cpp).
+// multi-GPU gather have their own units (scene.cpp, the frame units of rwr_frame.h, diagnostics.cpp, dist.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

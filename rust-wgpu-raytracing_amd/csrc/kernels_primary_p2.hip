@@ -29,7 +29,7 @@ namespace rwr {
 // order of their flattened index, so the record makers are running before a waiting one exists; the wait is BOUNDED all the
 // same: a wave whose wait runs out flags the frame as incomplete and leaves, it never hangs).  Saves the host one of its two
 // launches per frame and the device the boundary between them.
-// PLANE: the camera rests (render.cpp ray_plane_step) — the pairs' ray directions are loaded from the slot's kept plane
+// PLANE: the camera rests (frame_records.cpp ray_plane_step) — the pairs' ray directions are loaded from the slot's kept plane
 // (rwr_internal.h RayPlane, filled by k_ray_plane from the same function) instead of computed from the ray tables.  The form has
 // no use for the tables, and the plane's two arrays arrive in the tables' arguments (ray_colp: RayPlane::xy, ray_row:
 // RayPlane::z), so that the kernel's arguments, and with them the code of every other form, stay what they were.
@@ -37,7 +37,7 @@ namespace rwr {
 // with every tile's set (rwr_internal.h kTileFaces*), and a wave takes one of three ways through its tile by it — clear values
 // for a tile nothing can show in, a straight path for exactly one face and no sphere, the whole kernel otherwise.  The ways
 // meet again at the stores: one tail, so that the form's registers are those of the general path alone.
-// COVER: a frame served from the slot's kept records (RWR_FLAG_TILE_COVER, render.cpp) — the straight path reads and learns the
+// COVER: a frame served from the slot's kept records (RWR_FLAG_TILE_COVER, render_reference.cpp) — the straight path reads and learns the
 // tiles' cover words (rwr_internal.h kTileCovered).  An instantiation of its own, so that every other frame runs the code it ran.
 template <bool AUX, bool CULL, bool NMAP, bool FUSED = false, bool PLANE = false, bool COVER = false>
 __global__ void __launch_bounds__(256, (AUX || NMAP) ? 4 : RWR_P2_OCC)
@@ -284,7 +284,7 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
         const TriRecord T = tris[idx];
         const float tnum = to_const_space(p.tnum)[idx];
         one_shade = shade[idx];
-        // ... and with them, on a frame served from the slot's kept records (RWR_FLAG_TILE_COVER, render.cpp), the tile's cover word
+        // ... and with them, on a frame served from the slot's kept records (RWR_FLAG_TILE_COVER, render_reference.cpp), the tile's cover word
         // (rwr_internal.h kTileCovered; the third parallel array): what the tests below said about the tile on an earlier frame
         // with these records.  Without the flag the word is neither read nor written.
         // (cov: the word, or kTileNotCovering without the flag — one scalar register carries both facts across the test)
@@ -511,7 +511,7 @@ hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriReco
     const FusedSetup fs = fused ? *fused : FusedSetup{};
 #define RWR_P2_LAUNCH(A, C, N, F) hipExtLaunchKernelGGL((k_primary_p2<A, C, N, F>), grid, block, 0, s, ev_start, ev_stop, 0, ftris, fp.ray_colp, fp.ray_row, \
     fp.n_tris, fp.row_begin, fp.bins.enabled, fp.row_pitch, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3], fp, tris, shade, tex, tg, fs)
-    if (plane) {   // (a resting camera's frame: render.cpp ray_plane_step)
+    if (plane) {   // (a resting camera's frame: frame_records.cpp ray_plane_step)
         if (fused || nmap || !do_cull || !plane->xy || !plane->z) return hipErrorInvalidValue;
         const bool cover = (fp.flags & RWR_FLAG_TILE_COVER) != 0u;
         const float4 *const pxy = plane->xy, *const pz = reinterpret_cast<const float4 *>(plane->z);   // in the ray tables' arguments

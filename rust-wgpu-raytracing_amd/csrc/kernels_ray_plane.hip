@@ -15,7 +15,7 @@ k_ray_plane(const float4 *__restrict__ ray_colp, const float4 *__restrict__ ray_
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     uint32_t px0, py;
     p2_lane_pixel(wave, lane, blockIdx.x * 64u, row_begin + blockIdx.y * row_pitch, px0, py);
-    // (lanes off the frame too: the tables cover whole workgroup columns and 8 rows below any band, render.cpp frame_tables)
+    // (lanes off the frame too: the tables cover whole workgroup columns and 8 rows below any band, frame_records.cpp frame_tables)
     const v3 D = pixel_pair_ray_dir_tab(cam, ray_colp, ray_row, px0, py);
     const uint32_t i = (blockIdx.y * gridDim.x + blockIdx.x) * 256u + threadIdx.x;   // < 2^24 (kRayPlaneMaxW x kRayPlaneMaxH)
     plane.xy[i] = make_float4(D.x.x, D.x.y, D.y.x, D.y.y);

@@ -1,5 +1,5 @@
 // The context behind the C ABI (include/rwr_hip.h) and what its units share: context.cpp (life cycle, targets, timers),
-// scene.cpp, render.cpp, diagnostics.cpp, dist.cpp.  The units read the context's members directly.
+// scene.cpp, the frame units (rwr_frame.h), diagnostics.cpp, dist.cpp.  The units read the context's members directly.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -63,10 +63,38 @@ using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
 using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
 using OwnedGraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
 using PinnedWords = Owned<uint32_t *, free_pinned_words>;
-struct MirrorRec { float r, g, b, on; };   // a surface's record, a float4 of WfMirror::table — on = 1: a mirror of reflectance r, g, b (RWR_FLAG_MIRRORS); on = -ior: glass of tint r, g, b (RWR_FLAG_GLASS); on = 1 + roughness, in (1, 2]: glossy, reflectance r, g, b (RWR_FLAG_GLOSSY); 0: neither
+// A surface's record, a float4 of WfMirror::table: r, g, b and the surface's model in `on` (SurfaceModel below).
+struct MirrorRec { float r, g, b, on; };
 static_assert(sizeof(MirrorRec) == sizeof(float4), "MirrorRec is a float4");
 inline hipError_t free_pinned_mirror(MirrorRec *p) { return hipHostFree(p); }
 using PinnedMirror = Owned<MirrorRec *, free_pinned_mirror>;
+
+// The one statement of MirrorRec::on.  A surface has one model:
+//   kDiffuse  on = 0               neither of the others (r, g, b are zero)
+//   kMirror   on = 1               reflectance r, g, b (RWR_FLAG_MIRRORS)
+//   kGlass    on = -ior            tint r, g, b; ior in [1, 4] (RWR_FLAG_GLASS)
+//   kGloss    on = 1 + roughness   reflectance r, g, b; roughness in [2^-10, 1], a multiple of 2^-23 once stored (RWR_FLAG_GLOSSY)
+// Invariant: every record a setter can write (scene.cpp, through the makers below) has on in {0} U {1} U [-4, -1] U [1 + 2^-10, 2].
+// So `on == 1` and `on > 0 && !(on > 1)` name the same records, and so do `on > 1` and `on >= 1 + 2^-10`: whichever comparison
+// a reader of the table uses (the kernels decode m.w themselves, rwr_internal.h WfMirror), it agrees with surface_model.
+enum class SurfaceModel { kDiffuse, kMirror, kGlass, kGloss };
+inline SurfaceModel surface_model(const MirrorRec &m)
+{
+    return m.on > 1.0f ? SurfaceModel::kGloss : m.on > 0.0f ? SurfaceModel::kMirror : m.on < 0.0f ? SurfaceModel::kGlass : SurfaceModel::kDiffuse;
+}
+constexpr float kGlassIorMin = 1.0f, kGlassIorMax = 4.0f, kGlossRoughnessMin = 0x1p-10f, kGlossRoughnessMax = 1.0f;
+constexpr MirrorRec kDiffuseRec{0.0f, 0.0f, 0.0f, 0.0f};
+// the record makers: rgb in [0, 1] each, ior and roughness in the ranges above (the setters refuse anything else before they call)
+inline MirrorRec mirror_rec(const float rgb[3]) { return MirrorRec{rgb[0], rgb[1], rgb[2], 1.0f}; }
+inline MirrorRec glass_rec(const float rgb[3], float ior) { return MirrorRec{rgb[0], rgb[1], rgb[2], -ior}; }
+inline MirrorRec gloss_rec(const float rgb[3], float roughness) { return MirrorRec{rgb[0], rgb[1], rgb[2], 1.0f + roughness}; }
+// ... and what a glass record holds of its ior, a glossy one of its roughness (a diffuse record: 0)
+inline float surface_param(const MirrorRec &m) { return m.on < 0.0f ? -m.on : m.on > 1.0f ? m.on - 1.0f : 0.0f; }
+// A model's bit in the words that say which models a table holds (WfState::mirror_modes): 1 mirrors, 2 glass, 4 glossy
+constexpr uint32_t surface_mode(SurfaceModel s)
+{
+    return s == SurfaceModel::kMirror ? 1u : s == SurfaceModel::kGlass ? 2u : s == SurfaceModel::kGloss ? 4u : 0u;
+}
 
 // Everything one frame in flight owns: its stream, its targets and the per-frame records / tables.
 // Frames alternate between slots (rwr_ctx_set_frames_in_flight), so the ramp-up of one frame's kernel
@@ -94,11 +122,11 @@ struct FrameSlot {
     // hipGraph of this slot — replayed as it is while camera and parameters stay the same, updated in place when they change
     OwnedGraphExec frame_graph;
     std::vector<unsigned char> frame_graph_key;
-    // what the records, tables and face sets above were made from, byte for byte (render.cpp launch_records), while they stand:
+    // what the records, tables and face sets above were made from, byte for byte (frame_records.cpp launch_records), while they stand:
     // a frame with the same key on this slot finds them made and launches no k_frame_setup.  Empty: nothing to rely on
     std::vector<unsigned char> records_key;
     uint32_t cover_frames = 0;   // frames with RWR_FLAG_TILE_COVER on this slot since its last k_frame_setup (which zeroes the cover words)
-    // The kept plane of ray directions (rwr_internal.h RayPlane; render.cpp ray_plane_step), allocated by the slot's first build:
+    // The kept plane of ray directions (rwr_internal.h RayPlane; frame_records.cpp ray_plane_step), allocated by the slot's first build:
     // the xy array, then the z array.  ray_plane_key: the plane key (camera, screen, rows, addresses) of the slot's last frame
     // that could use a plane, empty when there is nothing to rely on; ray_plane_built: d_ray_plane holds that key's directions
     DeviceBuffer<float2> d_ray_plane;
@@ -184,7 +212,7 @@ struct Accum {
 
 // Temporal reprojection (RWR_FLAG_REPROJECT): ONE history per context, as the accumulation's.  Two sets alternate — frame k reads
 // set (k - 1) & 1 and writes set k & 1 — allocated by the first reprojecting frame; `key` is everything a frame must share with the
-// one before for the history to go on (render.cpp reproject_key_of; the camera is not in it), empty when the next frame starts over.
+// one before for the history to go on (frame_request.cpp reproject_key_of; the camera is not in it), empty when the next frame starts over.
 struct Reproject {
     DeviceBuffer<float4> d_colour[2], d_guide[2];   // {r, g, b, n}, {nhat.xyz or zeros, t} (RpHistory)
     DeviceBuffer<int32_t> d_id[2];
@@ -260,7 +288,7 @@ struct rwr_context {
     uint32_t wf_min_packet_pools = 64;    // tunable: RWR_WF_MIN_PACKET_POOLS (a quarter share of configs[4]'s frame has about 100 packet pools of 30 000 rays
                                           // and is 5 % faster with them as packets, an eighth share has 50 and is 10 % faster per lane: tools/share_probe.py)
     uint32_t wf_lane_items = 0;           // tunable: RWR_WF_LANE_ITEMS (0: chosen per frame, see the BvhDevice of the wavefront path)
-    int32_t wf_wide_lane = -1;            // the per-lane trace kernel as 1 024-thread workgroups: -1 by itself (render.cpp), tunable: RWR_WF_WIDE_LANE=0/1
+    int32_t wf_wide_lane = -1;            // the per-lane trace kernel as 1 024-thread workgroups: -1 by itself (render_wavefront.cpp wf_schedule), tunable: RWR_WF_WIDE_LANE=0/1
     uint32_t wf_packet_dense_rays = 16384;   // a pool of at least this many rays (32 samples of a full tile) is traced as packets
                                              // however far apart its rays start; tunable: RWR_WF_PACKET_RAYS (0: never).  Measured
                                              // (tools/packet_rays_sweep.sh): configs[4]'s frame, 64 samples per group, 2.11 -> 1.75
@@ -378,11 +406,20 @@ inline hipError_t sync_all(rwr_context *ctx)
 // faces the kernels see: every face of the mesh once per instance (no instances: once); at most 2^31 - 1 in a scene that was accepted
 inline uint64_t instanced_faces(uint64_t n_faces, uint32_t n_instances) { return n_faces * (n_instances ? n_instances : 1u); }
 
+// which surface models the context's parts and its spheres in use hold, as surface_mode bits
+inline uint32_t surface_modes(const rwr_context *ctx)
+{
+    uint32_t modes = 0;
+    for (const MirrorRec &m : ctx->part_mirrors) modes |= surface_mode(surface_model(m));
+    for (uint32_t i = 0; i < ctx->n_spheres; i++) modes |= surface_mode(surface_model(ctx->sphere_mirrors[i]));
+    return modes;
+}
+
 // context.cpp: per-frame buffers of every active slot for the current scene and screen
 hipError_t ensure_frame_buffers(rwr_context *ctx);
 // scene.cpp: the world-space records and the BVH, when the mesh or its instances have changed
 int rebuild_tris(rwr_context *ctx);
-// render.cpp: a frame of the fused frame kernel in idle slot `i` is complete
+// render_reference.cpp: a frame of the fused frame kernel in idle slot `i` is complete
 int check_fused_frame(rwr_context *ctx, uint32_t i);
 
 }  // namespace rwr

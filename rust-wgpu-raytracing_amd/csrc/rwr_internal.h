@@ -16,10 +16,10 @@ constexpr uint32_t RWR_FLAG_DEBUG_COUNTS = 1u << 16;
 // Internal: render frames with the one-pixel-per-lane kernel (k_primary) instead of the
 // two-pixels-per-lane one (k_primary_p2); both must give identical results.
 constexpr uint32_t RWR_FLAG_ONE_PIXEL_PER_LANE = 1u << 17;
-// Internal, set by render.cpp alone (a caller's bit is cleared): the frame's per-tile face sets come with class words
+// Internal, set by render_reference.cpp alone (a caller's bit is cleared): the frame's per-tile face sets come with class words
 // (TileClassIn below) and the two-pixel frame kernel branches on them.  Clear (RWR_TILE_CLASS=0): the kernel never loads one.
 constexpr uint32_t RWR_FLAG_TILE_CLASS = 1u << 18;
-// Internal, set by render.cpp alone (a caller's bit is cleared), only beside RWR_FLAG_TILE_CLASS and only on a frame that found its
+// Internal, set by render_reference.cpp alone (a caller's bit is cleared), only beside RWR_FLAG_TILE_CLASS and only on a frame that found its
 // slot's records made (launch_records: a key hit): the kernel reads the tiles' cover words (kTileCovered below) and writes the ones
 // it learns.  Clear (a key miss, RWR_TILE_COVER=0, any other form): the kernel neither reads nor writes them.
 constexpr uint32_t RWR_FLAG_TILE_COVER = 1u << 19;
@@ -370,7 +370,7 @@ struct WfMirror {
 };
 constexpr int kSurfNone = 0, kSurfMirrors = 1, kSurfGlass = 2, kSurfGloss = 3;   // the kernels' SURF argument: no table, mirrors alone, mirrors and glass, those and glossy
 // What the kernels of one launch group know: the four argument structs above — all zero where the frame lacks the flag, and that
-// is what the kernels then get — and the switches the launchers pick the kernels' forms by.  render.cpp fills it once per launch
+// is what the kernels then get — and the switches the launchers pick the kernels' forms by.  render_wavefront.cpp fills it once per launch
 // group; `emit` and `emits` change per generation (a generation that is not the path's last: the trace kernels' EMIT forms).
 struct WfFeatures {
     WfEmit emit{nullptr, 0u, 0u};
@@ -397,7 +397,7 @@ struct BvhDevice {
     uint32_t wide_lane;         // the per-lane trace kernel may run as 1 024-thread workgroups sharing one LDS copy of the nodelets
 };
 
-// A frame slot's kept plane of ray directions (render.cpp ray_plane_step): the normalised directions of the two-pixel frame
+// A frame slot's kept plane of ray directions (frame_records.cpp ray_plane_step): the normalised directions of the two-pixel frame
 // kernel's pixel pairs, 24 bytes per lane of its grid — xy[i] = {x.x, x.y, y.x, y.y}, z[i] = {z.x, z.y} of the pair whose lane
 // is thread i % 256 of workgroup i / 256 (workgroups in the order of their flattened index).  Every lane of the grid has an
 // entry, on or off the frame, so neither the kernel that fills it nor the one that loads from it tests a bound.
@@ -470,7 +470,7 @@ hipError_t launch_wf_denoise(hipStream_t s, uint32_t width, uint32_t height, con
                              const rwr_denoise_params &dp, float4 *guide, float4 *plane_a, float4 *plane_b);
 
 // RWR_FLAG_REPROJECT (kernels_wf_reproject.hip).  RpCamera: what the history keeps of a frame's camera (rwr_hip.h item 3), made on
-// the host in the oracle's f32 operations (render.cpp reproject_camera); nc0 = dot3(nrm, c0), nn = dot3(nrm, nrm).
+// the host in the oracle's f32 operations (frame_request.cpp reproject_camera); nc0 = dot3(nrm, c0), nn = dot3(nrm, nrm).
 struct RpCamera {
     float o[3], c0[3], cx[3], cy[3], nrm[3];
     float nc0, nn;

@@ -144,7 +144,7 @@ int rwr_scene_add_mesh(rwr_context *ctx, const rwr_model_vertex_small *verts, ui
     M.nmap = nullptr; M.nmap_w = M.nmap_h = 0u;
     ctx->st_materials.push_back(M);
     ctx->d_nmaps.emplace_back();
-    ctx->part_mirrors.push_back(MirrorRec{0.0f, 0.0f, 0.0f, 0.0f});
+    ctx->part_mirrors.push_back(kDiffuseRec);
     ctx->mirror_version++;
     if (mid == 0) ctx->material = *material;
     return RWR_OK;
@@ -223,203 +223,75 @@ int rwr_scene_set_normal_map(rwr_context *ctx, uint32_t part, const uint8_t *rgb
     return RWR_OK;
 }
 
-// RWR_FLAG_MIRRORS: a surface's attribute from the caller's three floats (NULL: not a mirror)
-static int mirror_from(const float *reflectance, const char *what, uint32_t index, MirrorRec &out)
+// The surface models (RWR_FLAG_MIRRORS, _GLASS, _GLOSSY; rwr_context.h SurfaceModel).  A part or a sphere index has one record,
+// so the twelve entry points — set and get, part and sphere, three models — are one lookup, one setter and one getter.
+
+// the record of part / sphere `index`; NULL: refused, RWR_ERR_INVALID_ARGUMENT is set
+static MirrorRec *surface_at(rwr_context *ctx, bool sphere, uint32_t index)
 {
-    if (!reflectance) {
-        out = MirrorRec{0.0f, 0.0f, 0.0f, 0.0f};
-        return RWR_OK;
+    if (!ctx) {
+        set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    } else if (sphere) {
+        if (index < RWR_MAX_SPHERES) return &ctx->sphere_mirrors[index];
+        set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", index, RWR_MAX_SPHERES);
+    } else {
+        if (index < ctx->part_mirrors.size()) return &ctx->part_mirrors[index];
+        set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", index, ctx->part_mirrors.size());
     }
-    for (int c = 0; c < 3; c++)
-        if (!(reflectance[c] >= 0.0f && reflectance[c] <= 1.0f))   // (false for NaN)
-            return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: reflectance[%d] %g: finite, 0 ... 1", what, index, c, (double)reflectance[c]);
-    out = MirrorRec{reflectance[0], reflectance[1], reflectance[2], 1.0f};
-    return RWR_OK;
+    return nullptr;
 }
 
-int rwr_scene_set_part_mirror(rwr_context *ctx, uint32_t part, const float *reflectance)
+// rgb: the mirror's or the glossy surface's reflectance, the glass's tint (NULL: the surface is none of the three); param: the
+// glass's ior, the glossy surface's roughness.  The record replaces whichever attribute the surface had.
+static int set_surface(rwr_context *ctx, bool sphere, uint32_t index, SurfaceModel model, const float *rgb, float param)
 {
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
-    MirrorRec m;
-    const int rc = mirror_from(reflectance, "part", part, m);
-    if (rc != RWR_OK) return rc;   // (a refused call changes nothing, the scene's generation included)
-    ctx->scene_generation++;
-    ctx->part_mirrors[part] = m;   // (a surface has one model: this replaces a glass or gloss attribute too)
-    ctx->mirror_version++;
-    return RWR_OK;
-}
-
-int rwr_scene_set_sphere_mirror(rwr_context *ctx, uint32_t sphere, const float *reflectance)
-{
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
-    MirrorRec m;
-    const int rc = mirror_from(reflectance, "sphere", sphere, m);
-    if (rc != RWR_OK) return rc;
-    ctx->scene_generation++;
-    ctx->sphere_mirrors[sphere] = m;   // (a surface has one model: this replaces a glass or gloss attribute too)
-    ctx->mirror_version++;
-    return RWR_OK;
-}
-
-static void mirror_out(const MirrorRec &m, int *is_mirror, float reflectance[3])
-{
-    const bool on = m.on == 1.0f;   // (on < 0: glass, rwr_scene_set_part_glass; on > 1: glossy, rwr_scene_set_part_gloss)
-    if (is_mirror) *is_mirror = on ? 1 : 0;
-    if (reflectance) { reflectance[0] = on ? m.r : 0.0f; reflectance[1] = on ? m.g : 0.0f; reflectance[2] = on ? m.b : 0.0f; }
-}
-
-int rwr_scene_get_part_mirror(rwr_context *ctx, uint32_t part, int *is_mirror, float reflectance[3])
-{
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
-    mirror_out(ctx->part_mirrors[part], is_mirror, reflectance);
-    return RWR_OK;
-}
-
-int rwr_scene_get_sphere_mirror(rwr_context *ctx, uint32_t sphere, int *is_mirror, float reflectance[3])
-{
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
-    mirror_out(ctx->sphere_mirrors[sphere], is_mirror, reflectance);
-    return RWR_OK;
-}
-
-// RWR_FLAG_GLASS: a surface's attribute from the caller's index of refraction and three floats of tint (tint NULL: not glass).
-// The record is the mirror attribute's: {tint r, g, b, -ior} — on < 0 marks glass, on > 0 a mirror, 0 neither.
-static int glass_from(float ior, const float *tint, const char *what, uint32_t index, MirrorRec &out)
-{
-    if (!tint) {
-        out = MirrorRec{0.0f, 0.0f, 0.0f, 0.0f};
-        return RWR_OK;
+    MirrorRec *at = surface_at(ctx, sphere, index);
+    if (!at) return RWR_ERR_INVALID_ARGUMENT;
+    const char *what = sphere ? "sphere" : "part";
+    MirrorRec m = kDiffuseRec;
+    if (rgb) {   // (the range tests are false for NaN)
+        if (model == SurfaceModel::kGlass && !(param >= kGlassIorMin && param <= kGlassIorMax))
+            return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: ior %g: finite, 1 ... 4", what, index, (double)param);
+        if (model == SurfaceModel::kGloss && !(param >= kGlossRoughnessMin && param <= kGlossRoughnessMax))
+            return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: roughness %g: finite, 2^-10 ... 1", what, index, (double)param);
+        for (int c = 0; c < 3; c++)
+            if (!(rgb[c] >= 0.0f && rgb[c] <= 1.0f))
+                return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: %s[%d] %g: finite, 0 ... 1", what, index,
+                                 model == SurfaceModel::kGlass ? "tint" : "reflectance", c, (double)rgb[c]);
+        m = model == SurfaceModel::kGlass ? glass_rec(rgb, param) : model == SurfaceModel::kGloss ? gloss_rec(rgb, param) : mirror_rec(rgb);
     }
-    if (!(ior >= 1.0f && ior <= 4.0f))   // (false for NaN)
-        return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: ior %g: finite, 1 ... 4", what, index, (double)ior);
-    for (int c = 0; c < 3; c++)
-        if (!(tint[c] >= 0.0f && tint[c] <= 1.0f))
-            return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: tint[%d] %g: finite, 0 ... 1", what, index, c, (double)tint[c]);
-    out = MirrorRec{tint[0], tint[1], tint[2], -ior};
-    return RWR_OK;
-}
-
-int rwr_scene_set_part_glass(rwr_context *ctx, uint32_t part, float ior, const float *tint)
-{
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
-    MirrorRec m;
-    const int rc = glass_from(ior, tint, "part", part, m);
-    if (rc != RWR_OK) return rc;   // (a refused call changes nothing, the scene's generation included)
-    ctx->scene_generation++;
-    ctx->part_mirrors[part] = m;   // (a surface has one model: this replaces a mirror or gloss attribute too)
+    ctx->scene_generation++;   // (a refused call never gets here: it changes nothing, the scene's generation included)
+    *at = m;
     ctx->mirror_version++;
     return RWR_OK;
 }
 
-int rwr_scene_set_sphere_glass(rwr_context *ctx, uint32_t sphere, float ior, const float *tint)
+// is the surface of `model`, and if so its r, g, b and its parameter (zeros if not; any of the three pointers may be NULL)
+static int get_surface(rwr_context *ctx, bool sphere, uint32_t index, SurfaceModel model, int *is_model, float rgb[3], float *param)
 {
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
-    MirrorRec m;
-    const int rc = glass_from(ior, tint, "sphere", sphere, m);
-    if (rc != RWR_OK) return rc;
-    ctx->scene_generation++;
-    ctx->sphere_mirrors[sphere] = m;   // (a surface has one model: this replaces a mirror or gloss attribute too)
-    ctx->mirror_version++;
+    const MirrorRec *at = surface_at(ctx, sphere, index);
+    if (!at) return RWR_ERR_INVALID_ARGUMENT;
+    const bool on = surface_model(*at) == model;
+    const MirrorRec m = on ? *at : kDiffuseRec;
+    if (is_model) *is_model = on ? 1 : 0;
+    if (rgb) { rgb[0] = m.r; rgb[1] = m.g; rgb[2] = m.b; }
+    if (param) *param = surface_param(m);
     return RWR_OK;
 }
 
-static void glass_out(const MirrorRec &m, int *is_glass, float *ior, float tint[3])
-{
-    const bool on = m.on < 0.0f;
-    if (is_glass) *is_glass = on ? 1 : 0;
-    if (ior) *ior = on ? -m.on : 0.0f;
-    if (tint) { tint[0] = on ? m.r : 0.0f; tint[1] = on ? m.g : 0.0f; tint[2] = on ? m.b : 0.0f; }
-}
 
-int rwr_scene_get_part_glass(rwr_context *ctx, uint32_t part, int *is_glass, float *ior, float tint[3])
-{
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
-    glass_out(ctx->part_mirrors[part], is_glass, ior, tint);
-    return RWR_OK;
-}
-
-int rwr_scene_get_sphere_glass(rwr_context *ctx, uint32_t sphere, int *is_glass, float *ior, float tint[3])
-{
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
-    glass_out(ctx->sphere_mirrors[sphere], is_glass, ior, tint);
-    return RWR_OK;
-}
-
-// RWR_FLAG_GLOSSY: a surface's attribute from the caller's three floats of reflectance (NULL: not glossy) and its roughness.
-// The record is the mirror attribute's: {reflectance r, g, b, 1 + roughness} — on in (1, 2] marks a glossy surface, on == 1 a
-// mirror, on < 0 glass, 0 neither.  The roughness the kernels and the getters use is on - 1, a multiple of 2^-23.
-static int gloss_from(const float *reflectance, float roughness, const char *what, uint32_t index, MirrorRec &out)
-{
-    if (!reflectance) {
-        out = MirrorRec{0.0f, 0.0f, 0.0f, 0.0f};
-        return RWR_OK;
-    }
-    if (!(roughness >= 0x1p-10f && roughness <= 1.0f))   // (false for NaN)
-        return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: roughness %g: finite, 2^-10 ... 1", what, index, (double)roughness);
-    for (int c = 0; c < 3; c++)
-        if (!(reflectance[c] >= 0.0f && reflectance[c] <= 1.0f))
-            return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: reflectance[%d] %g: finite, 0 ... 1", what, index, c, (double)reflectance[c]);
-    out = MirrorRec{reflectance[0], reflectance[1], reflectance[2], 1.0f + roughness};
-    return RWR_OK;
-}
-
-int rwr_scene_set_part_gloss(rwr_context *ctx, uint32_t part, const float *reflectance, float roughness)
-{
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
-    MirrorRec m;
-    const int rc = gloss_from(reflectance, roughness, "part", part, m);
-    if (rc != RWR_OK) return rc;   // (a refused call changes nothing, the scene's generation included)
-    ctx->scene_generation++;
-    ctx->part_mirrors[part] = m;   // (a surface has one model: this replaces a mirror or glass attribute too)
-    ctx->mirror_version++;
-    return RWR_OK;
-}
-
-int rwr_scene_set_sphere_gloss(rwr_context *ctx, uint32_t sphere, const float *reflectance, float roughness)
-{
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
-    MirrorRec m;
-    const int rc = gloss_from(reflectance, roughness, "sphere", sphere, m);
-    if (rc != RWR_OK) return rc;
-    ctx->scene_generation++;
-    ctx->sphere_mirrors[sphere] = m;   // (a surface has one model: this replaces a mirror or glass attribute too)
-    ctx->mirror_version++;
-    return RWR_OK;
-}
-
-static void gloss_out(const MirrorRec &m, int *is_glossy, float reflectance[3], float *roughness)
-{
-    const bool on = m.on > 1.0f;
-    if (is_glossy) *is_glossy = on ? 1 : 0;
-    if (reflectance) { reflectance[0] = on ? m.r : 0.0f; reflectance[1] = on ? m.g : 0.0f; reflectance[2] = on ? m.b : 0.0f; }
-    if (roughness) *roughness = on ? m.on - 1.0f : 0.0f;
-}
-
-int rwr_scene_get_part_gloss(rwr_context *ctx, uint32_t part, int *is_glossy, float reflectance[3], float *roughness)
-{
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (part >= ctx->part_mirrors.size()) return set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", part, ctx->part_mirrors.size());
-    gloss_out(ctx->part_mirrors[part], is_glossy, reflectance, roughness);
-    return RWR_OK;
-}
-
-int rwr_scene_get_sphere_gloss(rwr_context *ctx, uint32_t sphere, int *is_glossy, float reflectance[3], float *roughness)
-{
-    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (sphere >= RWR_MAX_SPHERES) return set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", sphere, RWR_MAX_SPHERES);
-    gloss_out(ctx->sphere_mirrors[sphere], is_glossy, reflectance, roughness);
-    return RWR_OK;
-}
+int rwr_scene_set_part_mirror(rwr_context *ctx, uint32_t part, const float *reflectance) { return set_surface(ctx, false, part, SurfaceModel::kMirror, reflectance, 0.0f); }
+int rwr_scene_set_sphere_mirror(rwr_context *ctx, uint32_t sphere, const float *reflectance) { return set_surface(ctx, true, sphere, SurfaceModel::kMirror, reflectance, 0.0f); }
+int rwr_scene_get_part_mirror(rwr_context *ctx, uint32_t part, int *is_mirror, float reflectance[3]) { return get_surface(ctx, false, part, SurfaceModel::kMirror, is_mirror, reflectance, nullptr); }
+int rwr_scene_get_sphere_mirror(rwr_context *ctx, uint32_t sphere, int *is_mirror, float reflectance[3]) { return get_surface(ctx, true, sphere, SurfaceModel::kMirror, is_mirror, reflectance, nullptr); }
+int rwr_scene_set_part_glass(rwr_context *ctx, uint32_t part, float ior, const float *tint) { return set_surface(ctx, false, part, SurfaceModel::kGlass, tint, ior); }
+int rwr_scene_set_sphere_glass(rwr_context *ctx, uint32_t sphere, float ior, const float *tint) { return set_surface(ctx, true, sphere, SurfaceModel::kGlass, tint, ior); }
+int rwr_scene_get_part_glass(rwr_context *ctx, uint32_t part, int *is_glass, float *ior, float tint[3]) { return get_surface(ctx, false, part, SurfaceModel::kGlass, is_glass, tint, ior); }
+int rwr_scene_get_sphere_glass(rwr_context *ctx, uint32_t sphere, int *is_glass, float *ior, float tint[3]) { return get_surface(ctx, true, sphere, SurfaceModel::kGlass, is_glass, tint, ior); }
+int rwr_scene_set_part_gloss(rwr_context *ctx, uint32_t part, const float *reflectance, float roughness) { return set_surface(ctx, false, part, SurfaceModel::kGloss, reflectance, roughness); }
+int rwr_scene_set_sphere_gloss(rwr_context *ctx, uint32_t sphere, const float *reflectance, float roughness) { return set_surface(ctx, true, sphere, SurfaceModel::kGloss, reflectance, roughness); }
+int rwr_scene_get_part_gloss(rwr_context *ctx, uint32_t part, int *is_glossy, float reflectance[3], float *roughness) { return get_surface(ctx, false, part, SurfaceModel::kGloss, is_glossy, reflectance, roughness); }
+int rwr_scene_get_sphere_gloss(rwr_context *ctx, uint32_t sphere, int *is_glossy, float reflectance[3], float *roughness) { return get_surface(ctx, true, sphere, SurfaceModel::kGloss, is_glossy, reflectance, roughness); }
 
 int rwr_scene_upload_mesh(rwr_context *ctx, const rwr_model_vertex_small *verts, uint32_t n_verts,
                           const rwr_model_face_small *faces, uint32_t n_faces, const rwr_material_data *material,

@@ -1,5 +1,5 @@
 """Oracle parity for frames served from a slot's kept state (test infrastructure): a frame slot keeps k_frame_setup's records
-while their key stands still (render.cpp launch_records) and, from the third frame at rest, the two-pixel frame kernel loads its
+while their key stands still (frame_records.cpp launch_records) and, from the third frame at rest, the two-pixel frame kernel loads its
 ray directions from a plane the slot keeps (ray_plane_step).  tests/test_gpu_setup_cache.py and tests/test_gpu_ray_plane.py
 compare that state with the library itself (on against off); here every frame served from it is compared with the CPU oracle,
 at the project's bar: obj_id, hit_t and depth bit for bit, color_f32 within 1e-4.  Used by tests/test_gpu_rest_parity.py (a

@@ -1,5 +1,5 @@
 """While the camera rests, the two-pixel frame kernel loads the normalised ray directions of its pixel pairs from a plane the
-frame slot keeps (render.cpp ray_plane_step; k_ray_plane fills it with the frame kernel's own ray function) instead of computing
+frame slot keeps (frame_records.cpp ray_plane_step; k_ray_plane fills it with the frame kernel's own ray function) instead of computing
 them.  Every sequence here is rendered in two contexts, the plane on and RWR_RAY_PLANE=0, given the same calls: every plane of
 every frame must be the same bytes in both — no tolerance, both sides run the same function — and rwr_ray_plane_stats must show
 exactly the builds and the loading frames the sequence implies.

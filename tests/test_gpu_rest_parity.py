@@ -1,4 +1,4 @@
-"""Frames served from a frame slot's kept state — k_frame_setup's records (render.cpp launch_records) and the plane of ray
+"""Frames served from a frame slot's kept state — k_frame_setup's records (frame_records.cpp launch_records) and the plane of ray
 directions the two-pixel frame kernel loads from (ray_plane_step, k_ray_plane) — compared with the CPU oracle; the helper and
 its model of the slots are tests/rest_common.py.  The bar is the project's: obj_id, hit_t and depth bit for bit, color_f32
 within 1e-4, a plain frame's RGBA8 equal to the aux frame's.

@@ -1,5 +1,5 @@
 """A frame slot keeps its per-frame records (k_frame_setup: culling records, ray tables, per-tile face sets) while camera,
-screen, the call's rows and the scene stand still, and a frame that finds them made launches no setup (render.cpp
+screen, the call's rows and the scene stand still, and a frame that finds them made launches no setup (frame_records.cpp
 launch_records).  Every sequence here is rendered in two contexts, the cache on and RWR_SETUP_CACHE=0: each frame must be the same
 bytes in both, and rwr_frame_setup_launches must show exactly the hits and misses the sequence implies.
 
