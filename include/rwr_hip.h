@@ -720,6 +720,14 @@ RWR_API int rwr_debug_tile_cover(rwr_context *ctx, uint32_t *cover, size_t capac
  * it waits for that frame when it is not 0 by rule.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_tile_cover_stats(rwr_context *ctx, uint64_t *frames, uint64_t *tiles_last);
 
+/* frames: frames of this context so far that the frame kernel's lean resting form rendered: a frame that looks at cover words
+ * (above), loads its rays from the slot's kept plane and writes colour and depth alone — a resting camera's plain frame of a scene
+ * with per-tile face sets and one material.  The form has no culling records in LDS and no workgroup barrier and stays within the
+ * scalar registers at which a CU holds eight of its workgroups; frames are the same bytes as the cover form's.
+ * RWR_LEAN_REST=0 (read when the context is created): such frames run the cover form, the count stays 0.
+ * A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_lean_rest_stats(rwr_context *ctx, uint64_t *frames);
+
 /* RWR_FLAG_SHADOWS: shadow rays traced by the last render call (= hits shaded: primary hits and the bounce hits of every
  * generation; an accumulating frame: its own samples; 0 without the flag) and how many of them were occluded.  Exact counts.
  * Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */

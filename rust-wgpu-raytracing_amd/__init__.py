@@ -119,7 +119,7 @@ def lib() -> C.CDLL:
         "rwr_timer_begin": [vp], "rwr_timer_end": [vp, vp], "rwr_timer_stop": [vp], "rwr_timer_elapsed": [vp, vp], "rwr_last_render_stats": [vp, vp, vp],
         "rwr_last_shadow_stats": [vp, vp, vp], "rwr_frame_setup_launches": [vp, vp], "rwr_ray_plane_stats": [vp, vp, vp],
         "rwr_debug_tile_classes": [vp, vp, C.c_size_t, vp, vp],
-        "rwr_debug_tile_cover": [vp, vp, C.c_size_t, vp, vp], "rwr_tile_cover_stats": [vp, vp, vp],
+        "rwr_debug_tile_cover": [vp, vp, C.c_size_t, vp, vp], "rwr_tile_cover_stats": [vp, vp, vp], "rwr_lean_rest_stats": [vp, vp],
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
         "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
@@ -149,7 +149,7 @@ def lib() -> C.CDLL:
         "rwr_dist_loopback_deposit": [vp, u32, u32, i32], "rwr_dist_loopback_finish": [vp, u32, i32],
         "rwr_measure_valu_clock": [vp, u32, vp], "rwr_clock_probe_start": [vp, u32], "rwr_clock_probe_read": [vp, vp],
     }
-    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats", "rwr_debug_tile_classes", "rwr_debug_tile_cover", "rwr_tile_cover_stats",
+    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats", "rwr_debug_tile_classes", "rwr_debug_tile_cover", "rwr_tile_cover_stats", "rwr_lean_rest_stats",
                            "rwr_sky_set_params", "rwr_sky_get_params", "rwr_scene_set_part_mirror", "rwr_scene_set_sphere_mirror",
                            "rwr_scene_get_part_mirror", "rwr_scene_get_sphere_mirror", "rwr_scene_set_part_glass", "rwr_scene_set_sphere_glass",
                            "rwr_scene_get_part_glass", "rwr_scene_get_sphere_glass", "rwr_last_glass_stats",
@@ -765,6 +765,13 @@ class Context:
         a, b = C.c_uint64(), C.c_uint64()
         _check(lib().rwr_tile_cover_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def lean_rest_stats(self) -> int:
+        """Frames of this context so far that the frame kernel's lean resting form rendered (rwr_lean_rest_stats); 0 for ever with
+        RWR_LEAN_REST=0."""
+        a = C.c_uint64()
+        _check(lib().rwr_lean_rest_stats(self._h, C.byref(a)))
+        return a.value
 
     def last_shadow_stats(self) -> tuple[int, int]:
         """(shadow rays traced by the last render call, how many of them were occluded); (0, 0) without FLAG_SHADOWS."""

@@ -90,6 +90,7 @@ void read_tunables(rwr_context *ctx)
     env_flag("RWR_RAY_PLANE", &ctx->ray_plane);
     env_flag("RWR_TILE_CLASS", &ctx->tile_class);
     env_flag("RWR_TILE_COVER", &ctx->tile_cover);
+    env_flag("RWR_LEAN_REST", &ctx->lean_rest);
     env_f32("RWR_AUTO_BVH_FACE_PX", &ctx->auto_bvh_face_px);
     if (env_u32("RWR_WF_GROUP", &ctx->wf_group)) ctx->wf_group = std::min(kWfMaxGroup, std::max(1u, ctx->wf_group));
     bool stats = false, wide = false;

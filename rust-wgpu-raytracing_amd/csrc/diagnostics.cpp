@@ -92,6 +92,13 @@ int rwr_tile_cover_stats(rwr_context *ctx, uint64_t *frames, uint64_t *tiles_las
     return RWR_OK;
 }
 
+int rwr_lean_rest_stats(rwr_context *ctx, uint64_t *frames)
+{
+    if (!ctx || !frames) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *frames = ctx->lean_rest_frames;
+    return RWR_OK;
+}
+
 int rwr_measure_valu_clock(rwr_context *ctx, uint32_t waves_per_simd, double out4[4])
 {
     if (!ctx || !out4) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");

@@ -156,10 +156,13 @@ int enqueue_reference(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, F
             ctx->tile_cover_frames++;
             ctx->last_cover_frames = ++sl.cover_frames;
         }
+        // (the lean resting form where the frame is one of its kind — launch_primary_p2's rule; RWR_LEAN_REST=0: never)
+        bool lean = ctx->lean_rest;
         RWR_HIP_CHECK(launch_primary_p2(stream, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, quad_tex, tg,
                                         timing.dispatch ? ctx->timing_events[2 * ctx->timing_pairs].h : nullptr,
                                         timing.dispatch ? ctx->timing_events[2 * ctx->timing_pairs + 1].h : nullptr, nullptr,
-                                        load ? &plane : nullptr));
+                                        load ? &plane : nullptr, &lean));
+        if (lean) ctx->lean_rest_frames++;
     }
     }
     return RWR_OK;

@@ -279,6 +279,8 @@ struct rwr_context {
     bool tile_cover = true;                             // a frame served from a slot's kept records learns and uses the tiles' cover words (rwr_internal.h kTileCovered); RWR_TILE_COVER=0: no frame looks at them
     uint64_t tile_cover_frames = 0;                     // frames that ran with RWR_FLAG_TILE_COVER so far (rwr_tile_cover_stats)
     uint32_t last_cover_frames = 0;                     // the frame rendered last: 0 without the flag, else its slot's FrameSlot::cover_frames (1: it learnt, more: it used what was learnt)
+    bool lean_rest = true;                              // a resting camera's plain frame runs the frame kernel's lean form (kernels_primary_p2.hip k_primary_p2_lean); RWR_LEAN_REST=0: the cover form
+    uint64_t lean_rest_frames = 0;                      // frames launched in the lean form so far (rwr_lean_rest_stats)
     // BVH over the (flattened) world-space faces, for bounce rays
     rwr::DeviceBuffer<rwr::BvhNode4> d_bvh_nodes;
     rwr::DeviceBuffer<uint32_t> d_bvh_leaf_faces;

@@ -415,9 +415,12 @@ hipError_t preload_kernels_ray_plane();
 struct FusedSetup;
 // plane (may be null): the frame's ray directions are loaded from it instead of computed (the culled frame without normal
 // maps, two launches per frame: anything else with a plane is hipErrorInvalidValue)
+// lean (may be null): in, whether the lean resting form (k_primary_p2_lean) may be launched where the frame is one of its kind —
+// a plane frame with RWR_FLAG_TILE_COVER, tile sets, one material, no extra outputs; out, whether it was
 hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const QuadTex &tex, const Targets &tg, hipEvent_t ev_start = nullptr,
-                             hipEvent_t ev_stop = nullptr, const FusedSetup *fused = nullptr, const RayPlane *plane = nullptr);
+                             hipEvent_t ev_stop = nullptr, const FusedSetup *fused = nullptr, const RayPlane *plane = nullptr,
+                             bool *lean = nullptr);
 // grid rows the fused form puts in front of the frame's strips for `n_blocks` record-making workgroups
 uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks);
 // ft (WfFeatures): ft.shadows — the SHADOW forms, which read ft.shadow; ft.primary_surf(fp) — SURF, the forms that read ft.mirror
