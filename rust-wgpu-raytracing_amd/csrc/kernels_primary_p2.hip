@@ -61,6 +61,10 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
     constexpr bool LISTS = false;
     const auto tl = [&]() { return p.tile_lists; };   // the tiles' sets, class words and cover words (read where the body asks)
     const float *const lut_src = tex.lut;
+    // the tile arrays' strides and the numerators, read where the body asks (the grid from the dispatch packet's copy)
+    const auto grid_x = [&]() { return gridDim.x; };
+    const auto grid_tiles = [&]() { return gridDim.x * gridDim.y * 4u; };
+    const auto tnum_ptr = [&]() { return p.tnum; };
 #include "rwr_primary_p2_body.h"
 }
 
@@ -68,11 +72,15 @@ k_primary_p2(const FrameTri *__restrict__ ftris, const float4 *__restrict__ ray_
 // workgroups of 256 threads only up to 80 scalar registers a wave (.sgpr_count; 82-96: seven — measured,
 // profiles/r12_residency_census.txt).  The allocator knows that rule, but per declared wave count: k_primary_p2 declares
 // RWR_P2_OCC = 7 waves per SIMD and is given 96, this form declares 8 and is held to 80 (amdgpu_num_sgpr(82) on top of it changes
-// no instruction).  Its first ten argument dwords — the plane, the tiles' words, the table, the band — are preloaded like
-// k_primary_p2's.
+// no instruction).  Its first fourteen argument dwords — the plane, the tiles' words, the table, the band, the numerators and the
+// tile arrays' strides — are preloaded like k_primary_p2's.
+// tnum (FrameParams::tnum), tiles_x, n_tiles (the launch's gridDim.x and gridDim.x * gridDim.y * 4, from launch_primary_p2): what a
+// wave needs to ask for its tile's words arrives in registers, so that no load stands between the dispatch and that request
+// (gridDim itself is a load from the hidden arguments, FrameParams::tnum one from the argument block).
 __global__ void __launch_bounds__(256, 8)
 k_primary_p2_lean(const float4 *__restrict__ ray_colp, const float4 *__restrict__ ray_row, const uint32_t *__restrict__ tile_lists,
                   const float *__restrict__ lut_src, uint32_t row_begin, uint32_t row_pitch,
+                  const float *__restrict__ tnum, uint32_t tiles_x, uint32_t n_tiles,
                   const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const QuadTex tex, const Targets tg)
 {
@@ -83,6 +91,9 @@ k_primary_p2_lean(const float4 *__restrict__ ray_colp, const float4 *__restrict_
     const int32_t mesh_x0 = 0, mesh_y0 = 0, mesh_x1 = 0, mesh_y1 = 0;
     const FusedSetup fs{};
     const auto tl = [&]() { return tile_lists; };
+    const auto grid_x = [&]() { return tiles_x; };
+    const auto grid_tiles = [&]() { return n_tiles; };
+    const auto tnum_ptr = [&]() { return tnum; };
 #include "rwr_primary_p2_body.h"
 }
 
@@ -120,7 +131,7 @@ hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriReco
         // the lean resting form: everything it takes for granted holds (it reads the tiles' words without a null test)
         if (lean_allowed && cover && !aux && fp.tile_lists && (fp.flags & RWR_FLAG_TILE_CLASS) != 0u && fp.n_materials <= 1u) {
             hipExtLaunchKernelGGL(k_primary_p2_lean, grid, block, 0, s, ev_start, ev_stop, 0, pxy, pz, fp.tile_lists, tex.lut, fp.row_begin, fp.row_pitch,
-                                  fp, tris, shade, tex, tg);
+                                  fp.tnum, grid.x, grid.x * grid.y * 4u, fp, tris, shade, tex, tg);
             *lean = true;
         } else if (aux && cover) RWR_P2_LAUNCH_PLANE(true, true);
         else if (aux) RWR_P2_LAUNCH_PLANE(true, false);

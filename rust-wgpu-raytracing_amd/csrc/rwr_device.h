@@ -291,6 +291,12 @@ RWR_DEV f3 quad_filter(const uint4 *__restrict__ quad, const float *lut, const Q
     const uint4 q = quad[t.idx];
     return tex_blend(quad_texel(lut, q.x), quad_texel(lut, q.y), quad_texel(lut, q.z), quad_texel(lut, q.w), t.a);
 }
+// quad_filter in its two halves, for a caller that requests several records before it decodes the first (rwr_shade_p2.h)
+RWR_DEV uint4 quad_fetch(const uint4 *__restrict__ quad, const QuadTap &t) { return quad[t.idx]; }
+RWR_DEV f3 quad_decode(const uint4 &q, const float *lut, const QuadTap &t)
+{
+    return tex_blend(quad_texel(lut, q.x), quad_texel(lut, q.y), quad_texel(lut, q.z), quad_texel(lut, q.w), t.a);
+}
 
 // Mesh shading, triangle_list/compute.wgsl:217-234 (colour path: see the header), in three steps
 // so that callers with two pixels per lane can run the middle one packed.

@@ -1,7 +1,9 @@
 // The statements of the two-pixel frame kernel (kernels_primary_p2.hip), included into the body of each of its entry points,
 // k_primary_p2<...> and k_primary_p2_lean: no include guard, nothing at file scope.  It names the entry point's arguments
 // (k_primary_p2's list), the form's compile-time facts AUX, CULL, NMAP, FUSED, PLANE, COVER, LISTS, and two pointers the entry point
-// makes: tl() (the tiles' sets, class words and cover words: FrameParams::tile_lists) and lut_src (QuadTex::lut).
+// makes: tl() (the tiles' sets, class words and cover words: FrameParams::tile_lists) and lut_src (QuadTex::lut); and three facts of the
+// launch it reads through the entry point: grid_x() and grid_tiles() (workgroups per row of the grid, tiles of the grid: the strides
+// of the tile arrays) and tnum_ptr() (FrameParams::tnum).
     static_assert(!LISTS || (PLANE && COVER && !AUX), "the lean form is the resting frame's: rays from the plane, cover words, no extra outputs");
     static_assert(!PLANE || (CULL && !NMAP && !FUSED), "the loading form exists for the culled two-launch frame without normal maps");
     static_assert(!COVER || (CULL && !NMAP && !FUSED), "cover words lie beside the face sets of the culled two-launch frame; normal maps take the general path");
@@ -104,7 +106,7 @@
     uint32_t set[kTileListWords] = {};
     if (lists) {
         if constexpr (!LISTS) {
-            const const_ptr<uint32_t> rec = to_const_space(tl()) + ((by * gridDim.x + blockIdx.x) * 4u + wu) * kTileListWords;
+            const const_ptr<uint32_t> rec = to_const_space(tl()) + ((by * grid_x() + blockIdx.x) * 4u + wu) * kTileListWords;
 #pragma unroll
             for (uint32_t k = 0; k < kTileListWords; k++) set[k] = rec[k];
         }
@@ -114,7 +116,13 @@
     // the compares below and the set's population would tell, found out by the setup.  RWR_TILE_CLASS=0: never looked at.
     const bool classed = LISTS || (lists && (p.flags & RWR_FLAG_TILE_CLASS) != 0u);   // (uniform)
     uint32_t cls = 0u;
-    if (classed) cls = to_const_space(tl())[gridDim.x * gridDim.y * 4u * kTileListWords + (by * gridDim.x + blockIdx.x) * 4u + wu];
+    if (classed) cls = to_const_space(tl())[grid_tiles() * kTileListWords + (by * grid_x() + blockIdx.x) * 4u + wu];
+    // (LISTS: the tile's cover word leaves with the class word — its address needs the same indices and nothing of the class — so
+    // that the straight path below finds it there instead of asking for it a round trip later.  A tile of another class has read a
+    // word it does not use; the array holds one for every tile of the grid.)
+    auto cover_at = [&](uint32_t w) { return grid_tiles() * (kTileListWords + 1u) + (by * grid_x() + blockIdx.x) * 4u + w; };
+    uint32_t cov_entry = 0u;
+    if constexpr (LISTS) cov_entry = to_const_space(tl())[cover_at(wu)];
     // (LISTS: the setup made `live`'s compares and put their outcome in the word — a tile outside the mesh's rectangle has class
     // "no face", rwr_frame_setup.h frame_tile_lists_block — and a tile with a face in its class lies inside)
     if constexpr (LISTS) live = (cls & kTileFacesMask) != kTileFacesNone;
@@ -168,7 +176,7 @@
     const f3 O = ld3(p.cam.origin);
     v3 D;
     if constexpr (PLANE) {   // requested where the table loads are: ahead of the LDS table's wait, behind the same work
-        const uint32_t i = (by * gridDim.x + blockIdx.x) * 256u + threadIdx.x;   // this lane's entry (k_ray_plane's index)
+        const uint32_t i = (by * grid_x() + blockIdx.x) * 256u + threadIdx.x;   // this lane's entry (k_ray_plane's index)
         const float4 dxy = ray_colp[i];
         const float2 dz = reinterpret_cast<const float2 *>(ray_row)[i];
         D = v3{f2{dxy.x, dxy.y}, f2{dxy.z, dxy.w}, f2{dz.x, dz.y}};
@@ -267,17 +275,17 @@
         // the general path's own functions, which therefore give its bits.
         const uint32_t idx = (cls >> kTileFaceShift) & 0xffu;
         const TriRecord T = tris[idx];
-        const float tnum = to_const_space(p.tnum)[idx];
+        const float tnum = to_const_space(tnum_ptr())[idx];
         one_shade = shade[idx];
         // ... and with them, on a frame served from the slot's kept records (RWR_FLAG_TILE_COVER, render_reference.cpp), the tile's cover word
         // (rwr_internal.h kTileCovered; the third parallel array): what the tests below said about the tile on an earlier frame
         // with these records.  Without the flag the word is neither read nor written.
         // (cov: the word, or kTileNotCovering without the flag — one scalar register carries both facts across the test)
         constexpr uint32_t kTileNotCovering = 2u;
-        auto cover_at = [&](uint32_t w) { return gridDim.x * gridDim.y * 4u * (kTileListWords + 1u) + (by * gridDim.x + blockIdx.x) * 4u + w; };
         uint32_t cov = kTileNotCovering;
         if constexpr (COVER) {
-            if (LISTS || (p.flags & RWR_FLAG_TILE_COVER) != 0u) cov = to_const_space(tl())[cover_at(wu)];
+            if constexpr (LISTS) cov = cov_entry;   // (requested at entry)
+            else if ((p.flags & RWR_FLAG_TILE_COVER) != 0u) cov = to_const_space(tl())[cover_at(wu)];
         }
         rwait();   // (the table's barrier)
         // (p0 and e0 are read by one of the two branches below alone; left to itself the compiler moves their loads into that
@@ -318,13 +326,18 @@
                                  __builtin_amdgcn_ballot_w64((win.x & win.y) != 0) == __builtin_amdgcn_read_exec();
                 uint32_t w = wu;
                 asm volatile("" : "+s"(w));   // (the address is formed again here, once per tile and key, not carried through the test)
-                if (all && lane == 0u) const_cast<uint32_t *>(tl())[cover_at(w)] = kTileCovered;
+                if constexpr (LISTS) {
+                    // (the strides again from the dispatch's own grid, a load on this way alone — a tile learns once per key —
+                    // instead of two argument registers held across the test on every way)
+                    if (all && lane == 0u)
+                        const_cast<uint32_t *>(tl())[gridDim.x * gridDim.y * 4u * (kTileListWords + 1u) + (by * gridDim.x + blockIdx.x) * 4u + w] = kTileCovered;
+                } else if (all && lane == 0u) const_cast<uint32_t *>(tl())[cover_at(w)] = kTileCovered;
             }
         }
     } else {
     // -- every other tile ---------------------------------------------------------------------------------------------------
     if constexpr (LISTS) {   // (the tile's set: requested on this way alone, ahead of the sphere passes and the table's wait)
-        const const_ptr<uint32_t> rec = to_const_space(tl()) + ((by * gridDim.x + blockIdx.x) * 4u + wu) * kTileListWords;
+        const const_ptr<uint32_t> rec = to_const_space(tl()) + ((by * grid_x() + blockIdx.x) * 4u + wu) * kTileListWords;
 #pragma unroll
         for (uint32_t k = 0; k < kTileListWords; k++) set[k] = rec[k];
     }
@@ -366,7 +379,7 @@
                 while (m) {
                     const uint32_t idx = 64u * k + (uint32_t)__builtin_ctzll(m);
                     m &= m - 1ull;
-                    intersect_and_select(tris[idx], to_const_space(p.tnum)[idx], idx, O, D, best);
+                    intersect_and_select(tris[idx], to_const_space(tnum_ptr())[idx], idx, O, D, best);
                     last_idx = idx;
                     n_tested++;
                     if (AUX) dbg_tested++;
@@ -398,7 +411,7 @@
                     // wave-uniform face index: the record comes in through scalar loads
                     const uint32_t idx = (uint32_t)__builtin_amdgcn_readlane((int)my_face, (int)bit);
                     if (FUSED) intersect_and_select(load_tri_record(tris_c + idx), tnum_c[idx], idx, O, D, best);
-                    else intersect_and_select(tris[idx], to_const_space(p.tnum)[idx], idx, O, D, best);
+                    else intersect_and_select(tris[idx], to_const_space(tnum_ptr())[idx], idx, O, D, best);
                     last_idx = idx;
                     n_tested++;
                     if (AUX) dbg_tested++;
@@ -420,7 +433,7 @@
             while (m) {
                 const uint32_t idx = base + (uint32_t)__builtin_ctzll(m);
                 m &= m - 1ull;
-                intersect_and_select(tris[idx], to_const_space(p.tnum)[idx], idx, O, D, best);
+                intersect_and_select(tris[idx], to_const_space(tnum_ptr())[idx], idx, O, D, best);
                 last_idx = idx;
                 n_tested++;
                 if (AUX) dbg_tested++;
@@ -440,6 +453,9 @@
     }   // (kWayAll)
 
     const PairSlot ps = pair_slot(px0, py);
+    // (the store counts in the wave's vector-memory counter, so the shading's first texel wait covers it.  The lean form with the
+    // store at the end, beside the colour's, measured the same frame time with four more vector registers:
+    // profiles/r13_lean_chain_ab.txt)
     store_depth(ps, depth_tex);
 
     // -- shade the winners and store --------------------------------------------
@@ -473,7 +489,13 @@
         else if (n_tested == 1u) {
             // the one face the wave tested (so the scene has faces and the record array exists): every mesh winner shows it
             const ShadeRec last_shade = way == kWayOne ? one_shade : FUSED ? load_shade_record(shade_c + last_idx) : shade[last_idx];
-            shade_mesh_pair<false, true, false, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);
+            if constexpr (LISTS) {   // (both quad records requested before the first is decoded)
+                f2 tr, tgr, tb;
+                shade_mesh_pair<false, true, false, FrameParams, QuadTex, true>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb, tr, tgr, tb);
+            } else shade_mesh_pair<false, true, false, FrameParams, QuadTex>(p, shade, qt, obj, last_shade, best, D, cr, cg, cb);
+        } else if constexpr (LISTS) {
+            f2 tr, tgr, tb;
+            shade_mesh_pair<false, false, false, FrameParams, QuadTex, true>(p, shade, qt, obj, unused, best, D, cr, cg, cb, tr, tgr, tb);
         } else shade_mesh_pair<false, false, false, FrameParams, QuadTex>(p, shade, qt, obj, unused, best, D, cr, cg, cb);
         pack_mesh(obj, cr, cg, cb, rgba, cf);
     }

@@ -28,12 +28,16 @@ template <> struct TexArg<const float4 *> { typedef const float4 *__restrict__ t
 // P: FrameParams, or FrameParams in the kernel-argument (constant) address space — a caller inside a long loop reads the fields
 // through a pointer it has just re-derived, so that they are loaded where they are used instead of living in scalar registers
 // for the whole loop (kernels_wf_primary.hip).
-template <bool MULTI, bool UNIFORM, bool NMAP = false, typename P = FrameParams, typename TX = const float4 *>
+// BOTH (QuadTex only; the frame kernel's lean resting form): both pixels' quad records are requested before the first is decoded,
+// one round trip to memory instead of two in a row; decoding stays one pixel after the other, the same operations in the same
+// order.
+template <bool MULTI, bool UNIFORM, bool NMAP = false, typename P = FrameParams, typename TX = const float4 *, bool BOTH = false>
 RWR_DEV void shade_mesh_pair(const P &p, const ShadeRec *__restrict__ shade, typename TexArg<TX>::type tex,
                              i2 obj, const ShadeRec &uS, const MeshHit2 &best, v3 D, f2 &cr, f2 &cg, f2 &cb,
                              f2 &tr, f2 &tg, f2 &tb)
 {
     static_assert(!(NMAP && UNIFORM), "the normal-mapped path fetches per-pixel records");
+    static_assert(!BOTH || std::is_same<TX, QuadTex>::value, "both records in flight: the quad form's single fetch per pixel");
     constexpr bool QUAD = std::is_same<TX, QuadTex>::value;
     static_assert(QUAD || std::is_same<TX, const float4 *>::value, "texture form");
     using Tap = typename std::conditional<QUAD, QuadTap, TexTaps>::type;
@@ -86,6 +90,15 @@ RWR_DEV void shade_mesh_pair(const P &p, const ShadeRec *__restrict__ shade, typ
     }
     // phase 2, one pixel after the other (the scheduling barriers keep 12, not 24, texel registers live)
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (BOTH) {
+        const uint4 q0 = quad_fetch(texk[0], taps[0]), q1 = quad_fetch(texk[1], taps[1]);
+        __builtin_amdgcn_sched_barrier(0);
+        const f3 t0 = quad_decode(q0, tex.lut, taps[0]);
+        tr.x = t0.x; tg.x = t0.y; tb.x = t0.z;
+        __builtin_amdgcn_sched_barrier(0);
+        const f3 t1 = quad_decode(q1, tex.lut, taps[1]);
+        tr.y = t1.x; tg.y = t1.y; tb.y = t1.z;
+    } else {
     {
         f3 t;
         if constexpr (QUAD) t = quad_filter(texk[0], tex.lut, taps[0]);
@@ -99,6 +112,7 @@ RWR_DEV void shade_mesh_pair(const P &p, const ShadeRec *__restrict__ shade, typ
         else t = tex_filter(texk[1], taps[1]);
         tr.y = t.x; tg.y = t.y; tb.y = t.z;
     }
+    }   // (!BOTH)
     f2 sp = hn * hn;  // pow(., 32) by five squarings (rwr_device.h pow32)
     sp = sp * sp; sp = sp * sp; sp = sp * sp; sp = sp * sp;
     cr = fma2(ksr, sp, fma2(tr, ndl, kar));                  // :231-233
@@ -106,12 +120,12 @@ RWR_DEV void shade_mesh_pair(const P &p, const ShadeRec *__restrict__ shade, typ
     cb = fma2(ksb, sp, fma2(tb, ndl, kab));
 }
 
-template <bool MULTI, bool UNIFORM, bool NMAP = false, typename P = FrameParams, typename TX = const float4 *>
+template <bool MULTI, bool UNIFORM, bool NMAP = false, typename P = FrameParams, typename TX = const float4 *, bool BOTH = false>
 RWR_DEV void shade_mesh_pair(const P &p, const ShadeRec *__restrict__ shade, typename TexArg<TX>::type tex,
                              i2 obj, const ShadeRec &uS, const MeshHit2 &best, v3 D, f2 &cr, f2 &cg, f2 &cb)
 {
     f2 tr, tg, tb;
-    shade_mesh_pair<MULTI, UNIFORM, NMAP, P, TX>(p, shade, tex, obj, uS, best, D, cr, cg, cb, tr, tg, tb);
+    shade_mesh_pair<MULTI, UNIFORM, NMAP, P, TX, BOTH>(p, shade, tex, obj, uS, best, D, cr, cg, cb, tr, tg, tb);
 }
 
 }  // namespace rwr

@@ -1,7 +1,8 @@
-"""Three-arm A/B of the benchmark on one GPU, arms interleaved run by run (the procedure of the r11 and r12 rounds):
-  parent  a build of the parent commit, loaded through RWR_HIP_LIB
-  change  this tree's library
-  off     this tree's library with a knob switched off (KNOB=0)
+"""Four-arm A/B of the benchmark on one GPU, arms interleaved run by run (the procedure of the r11 to r13 rounds):
+  parent      a build of the parent commit, loaded through RWR_HIP_LIB
+  change      this tree's library
+  off         this tree's library with a knob switched off (KNOB=0)
+  parent_off  the parent's library with the same knob switched off: what `off` must read as when the change lives behind the knob
 Each round runs `bench.py`, `bench.py --config loop` and `bench.py --config cfg2b` in every arm.  Prints every ms_per_step in run
 order, then min / median / max per config and arm and the verdict by the standing claim rule: every change run faster than every
 parent run, and the ratio of medians beyond three times the parent's own max/min spread.
@@ -39,7 +40,8 @@ def main():
     ap.add_argument("--limit", type=float, default=120.0, help="seconds one bench.py run may take")
     ap.add_argument("bench_args", nargs="*", help="passed on to bench.py (after --)")
     args = ap.parse_args()
-    arms = [("parent", {"RWR_HIP_LIB": os.path.abspath(args.parent_lib)}), ("change", {}), ("off", {args.knob: "0"})]
+    parent = {"RWR_HIP_LIB": os.path.abspath(args.parent_lib)}
+    arms = [("parent", parent), ("change", {}), ("off", {args.knob: "0"}), ("parent_off", dict(parent, **{args.knob: "0"}))]
     configs = args.configs.split(",")
     lines, res = [], {}
     for _ in range(args.rounds):
@@ -54,16 +56,17 @@ def main():
     for config in configs:
         for arm, _ in arms:
             v = [1e3 * x for x in res[(config, arm)]]
-            lines.append(f"# {config:<6} {arm:<7} n={len(v)}  {min(v):6.2f} / {statistics.median(v):6.2f} / {max(v):6.2f}")
-        p, c, o = (res[(config, a)] for a in ("parent", "change", "off"))
+            lines.append(f"# {config:<6} {arm:<10} n={len(v)}  {min(v):6.2f} / {statistics.median(v):6.2f} / {max(v):6.2f}")
+        p, c, o, po = (res[(config, a)] for a in ("parent", "change", "off", "parent_off"))
         spread = max(p) / min(p)
         ratio = statistics.median(c) / statistics.median(p)
         all_faster = max(c) < min(p)
         claimed = all_faster and (1.0 - ratio) > 3.0 * (spread - 1.0)
         lines.append(f"# {config:<6} change / parent, ratio of medians: {ratio:.3f}   off / parent: {statistics.median(o) / statistics.median(p):.3f}   "
+                     f"off / parent_off: {statistics.median(o) / statistics.median(po):.3f}   "
                      f"(parent's spread max/min: {spread:.3f}; {'every change run faster than every parent run' if all_faster else 'change runs NOT all faster than the parent runs'}; "
                      f"claim rule: {'met' if claimed else 'NOT met'})")
-    print("\n".join(lines[len(lines) - 2 - 4 * len(configs):]))
+    print("\n".join(lines[len(lines) - 2 - (len(arms) + 1) * len(configs):]))
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
