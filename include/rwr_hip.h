@@ -382,7 +382,7 @@ enum {
                                           contract: deeper paths, shadows, sky, mirrors, glass, normal maps, RWR_FLAG_NO_CULL,
                                           instances and parts — the stage only sees their resolved frame.  The scene is static
                                           between setters, so no motion vectors are needed. */
-    RWR_FLAG_GLOSSY = 1u << 13      /* extension: glossy surfaces — a scene part or a sphere marked as glossy (rwr_scene_set_part_gloss,
+    RWR_FLAG_GLOSSY = 1u << 13,     /* extension: glossy surfaces — a scene part or a sphere marked as glossy (rwr_scene_set_part_gloss,
                                        rwr_scene_set_sphere_gloss) of reflectance R and roughness rho sends on a direction between the
                                        mirror reflection and the diffuse ray the hit would otherwise have sent: brushed metal, a
                                        polished floor, a satin ball.  Independent of RWR_FLAG_MIRRORS and RWR_FLAG_GLASS: each flag
@@ -417,6 +417,40 @@ enum {
                                           other flag, instances, parts, frames in flight, row bands, strips and the multi-GPU gather keep
                                           their contracts.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED, whatever max_bounces is and whether or not a surface is glossy. */
+    RWR_FLAG_SOFT_SHADOWS = 1u << 14 /* extension: soft shadows — RWR_FLAG_SHADOWS' two lights get a finite angular size
+                                       (rwr_shadow_set_params), so that shadow edges become penumbrae: sharp at the contact, wide far
+                                       from the occluder.  The radius r of a light is the tangent of the half-angle under which a hit
+                                       sees it (0: the point light at infinity; 0.0047: the sun).  Without the flag every frame is what
+                                       it was, byte for byte.  With RWR_FLAG_SHADOWS and this flag, the shadow ray of hit h_k (k = 0 for
+                                       h0, k for the hit of bounce ray k) keeps its origin P + 1e-4 n, operation for operation; its
+                                       direction S is, in f32 with no contraction:
+                                       1. L = -normalize3(kLightDir) of the shader that shaded the hit, as without the flag; r is that
+                                          light's radius (mesh_light_radius for a face hit, sphere_light_radius for a sphere hit).
+                                       2. (a, b): bounce_direction's rejection loop over the unit disk, operation for operation — 8 tries,
+                                          ua = 2 u - 1, accepted on ua*ua + ub*ub <= 1.0f, a = b = 0 when all eight are refused — on the
+                                          RNG dimensions d_s + 2 j, d_s + 1 + 2 j of (global pixel, global sample, seed), with
+                                          d_s = 2 + 16 RWR_MAX_BOUNCES + 16 k = 130 + 16 k.  The block lies behind every block a path
+                                          reads: no primary, bounce or glass random number changes.
+                                       3. b1, b2: bounce_direction's basis about L — sign = copysignf(1, L.z), aa = -1 / (sign + L.z),
+                                          bb = L.x L.y aa, b1 = (1 + sign L.x L.x aa, sign bb, -sign L.x), b2 = (bb, sign + L.y L.y aa,
+                                          -L.y) — constant per light, the bits of this f32 evaluation.
+                                       4. S.c = L.c + r * (a*b1.c + b*b2.c) per component: two products and a sum inside, one product, one
+                                          sum.  S is not re-normalised (|S| >= 1; the hit tests take a direction of any length).  With
+                                          r = 0 it is L exactly.
+                                       5. occluded(h) is "any sphere or any face is hit by (origin, S)" in the reference's intersection
+                                          arithmetic: no distance limit, no face excluded.  E(h) is still shaded with the fixed L — only
+                                          visibility becomes stochastic; the ambient part, the clamps, the records and the counts of
+                                          rwr_last_shadow_stats are RWR_FLAG_SHADOWS', and a soft frame traces as many shadow rays as the
+                                          hard one.
+                                       6. Without RWR_FLAG_SHADOWS, or with both radii 0, the flag is ignored — cleared before the frame's
+                                          kernels are chosen — and the frame is the frame without it, byte for byte, in the same kernels
+                                          (the flag alone at spp 1 without a bounce: the reference frame).
+                                       7. While the flag is effective, its bit and the 8 bytes of rwr_shadow_params are part of
+                                          RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's; without it rwr_shadow_set_params
+                                          disturbs neither.  A reprojecting frame k is traced with seed + k, so its penumbra is drawn
+                                          anew.  RNG keys are global pixel and global sample: frames in flight, row bands, strips, the
+                                          multi-GPU gather and every schedule give the same bytes; every other flag keeps its contract.
+                                          With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
 };
 
 #define RWR_MAX_BOUNCES 8u
@@ -775,6 +809,19 @@ typedef struct rwr_sky_params {
 #define RWR_SKY_COMPONENT_MAX 16.0f                                 /* the largest component rwr_sky_set_params takes */
 RWR_API int rwr_sky_set_params(rwr_context *ctx, const rwr_sky_params *params);
 RWR_API int rwr_sky_get_params(rwr_context *ctx, rwr_sky_params *out);
+
+/* RWR_FLAG_SOFT_SHADOWS: the angular size of the two lights, per context.  A radius is the tangent of the half-angle under which a
+ * hit sees the light: mesh_light_radius for the mesh shader's light (face hits), sphere_light_radius for the sphere shader's.
+ * Defaults 0.05 and 0.05; params = NULL restores them.  Each radius must be finite and in [0, 1]; anything else, NaN included:
+ * RWR_ERR_INVALID_ARGUMENT, and the parameters stay as they were.  Host-side, waits for nothing; frames rendered after the call
+ * use the new values. */
+typedef struct rwr_shadow_params {
+    float mesh_light_radius, sphere_light_radius;
+} rwr_shadow_params;
+#define RWR_SHADOW_DEFAULTS {0.05f, 0.05f}   /* an initialiser of rwr_shadow_params: what NULL restores */
+#define RWR_SHADOW_RADIUS_MAX 1.0f            /* the largest radius rwr_shadow_set_params takes */
+RWR_API int rwr_shadow_set_params(rwr_context *ctx, const rwr_shadow_params *params);
+RWR_API int rwr_shadow_get_params(rwr_context *ctx, rwr_shadow_params *out);
 
 /* RWR_FLAG_REPROJECT: the stage's parameters, per context.  max_history 1 ... 1024 (default 32): the longest history a pixel's
  * blend weighs in, out = hist + (c_now - hist) / n' with n' <= max_history; normal_cos_min finite and in [-1, 1] (default 0.95) and

@@ -54,6 +54,8 @@ FLAG_MIRRORS = 1 << 10       # parts and spheres marked as mirrors reflect the r
 FLAG_GLASS = 1 << 11         # parts and spheres marked as glass reflect by Fresnel's law and refract by Snell's (include/rwr_hip.h)
 FLAG_REPROJECT = 1 << 12     # temporal reprojection of the context's history while the camera moves; implies FLAG_AUX_OUTPUTS (include/rwr_hip.h)
 FLAG_GLOSSY = 1 << 13        # parts and spheres marked as glossy send on a ray between the mirror reflection and the diffuse ray (include/rwr_hip.h)
+FLAG_SOFT_SHADOWS = 1 << 14  # FLAG_SHADOWS' two lights get an angular size: penumbrae (include/rwr_hip.h)
+SHADOW_PARAMS_DTYPE = np.dtype([("mesh_light_radius", "<f4"), ("sphere_light_radius", "<f4")])
 REPROJECT_PARAMS_DTYPE = np.dtype([("max_history", "<u4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
 MAX_BOUNCES = 8
 FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
@@ -123,6 +125,7 @@ def lib() -> C.CDLL:
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
         "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
+        "rwr_shadow_set_params": [vp, vp], "rwr_shadow_get_params": [vp, vp],
         "rwr_reproject_set_params": [vp, vp], "rwr_reproject_get_params": [vp, vp], "rwr_reproject_reset": [vp],
         "rwr_reproject_frames": [vp, vp], "rwr_last_reproject_stats": [vp, vp, vp, vp], "rwr_reproject_readback": [vp, vp],
         "rwr_scene_set_part_mirror": [vp, u32, vp], "rwr_scene_set_sphere_mirror": [vp, u32, vp],
@@ -155,7 +158,8 @@ def lib() -> C.CDLL:
                            "rwr_scene_get_part_glass", "rwr_scene_get_sphere_glass", "rwr_last_glass_stats",
                            "rwr_reproject_set_params", "rwr_reproject_get_params", "rwr_reproject_reset", "rwr_reproject_frames",
                            "rwr_last_reproject_stats", "rwr_reproject_readback", "rwr_scene_set_part_gloss", "rwr_scene_set_sphere_gloss",
-                           "rwr_scene_get_part_gloss", "rwr_scene_get_sphere_gloss", "rwr_last_gloss_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_scene_get_part_gloss", "rwr_scene_get_sphere_gloss", "rwr_last_gloss_stats",
+                           "rwr_shadow_set_params", "rwr_shadow_get_params")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -864,6 +868,25 @@ class Context:
         p = np.zeros(1, dtype=SKY_PARAMS_DTYPE)
         _check(lib().rwr_sky_get_params(self._h, _p(p)))
         return {"zenith": p["zenith"][0].copy(), "horizon": p["horizon"][0].copy()}
+
+    def shadow_set_params(self, mesh=None, sphere=None):
+        """The FLAG_SOFT_SHADOWS radii of the two lights (rwr_shadow_set_params): `mesh` the mesh shader's light, `sphere` the sphere
+        shader's, each the tangent of the half-angle a hit sees the light under, in [0, 1]; an argument left out keeps its value, no
+        argument at all restores the defaults.  Out of range or NaN: RwrError(ERR_INVALID_ARGUMENT), and the parameters stay."""
+        if mesh is None and sphere is None:
+            _check(lib().rwr_shadow_set_params(self._h, None))
+            return
+        p = np.zeros(1, dtype=SHADOW_PARAMS_DTYPE)
+        now = self.shadow_get_params()
+        p["mesh_light_radius"] = now["mesh"] if mesh is None else np.float32(mesh)
+        p["sphere_light_radius"] = now["sphere"] if sphere is None else np.float32(sphere)
+        _check(lib().rwr_shadow_set_params(self._h, _p(p)))
+
+    def shadow_get_params(self) -> dict:
+        """{"mesh": float32, "sphere": float32} (rwr_shadow_get_params)."""
+        p = np.zeros(1, dtype=SHADOW_PARAMS_DTYPE)
+        _check(lib().rwr_shadow_get_params(self._h, _p(p)))
+        return {"mesh": np.float32(p["mesh_light_radius"][0]), "sphere": np.float32(p["sphere_light_radius"][0])}
 
 
 def csrc_tree() -> str:

@@ -573,6 +573,29 @@ int rwr_sky_get_params(rwr_context *ctx, rwr_sky_params *out)
     return RWR_OK;
 }
 
+int rwr_shadow_set_params(rwr_context *ctx, const rwr_shadow_params *params)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (!params) {
+        ctx->shadow = kShadowDefaults;
+        return RWR_OK;
+    }
+    const rwr_shadow_params p = *params;
+    if (!(p.mesh_light_radius >= 0.0f && p.mesh_light_radius <= RWR_SHADOW_RADIUS_MAX))   // (false for NaN)
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "shadow mesh_light_radius %g: finite, 0 ... 1", (double)p.mesh_light_radius);
+    if (!(p.sphere_light_radius >= 0.0f && p.sphere_light_radius <= RWR_SHADOW_RADIUS_MAX))
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "shadow sphere_light_radius %g: finite, 0 ... 1", (double)p.sphere_light_radius);
+    ctx->shadow = p;
+    return RWR_OK;
+}
+
+int rwr_shadow_get_params(rwr_context *ctx, rwr_shadow_params *out)
+{
+    if (!ctx || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = ctx->shadow;
+    return RWR_OK;
+}
+
 int rwr_accum_reset(rwr_context *ctx)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");

@@ -13,7 +13,7 @@ namespace {
 // id / t planes, so RWR_FLAG_AUX_OUTPUTS is implied, and its own bit is not part of rp.flags from there on (nor of a history's key).
 // mode: a surface flag switches on the surfaces of its model (surface_mode's bit).
 struct FlagRule { uint32_t flag; const char *name, *stage, *why; uint32_t mode; };
-constexpr FlagRule kFlagRules[8] = {
+constexpr FlagRule kFlagRules[9] = {
     {RWR_FLAG_ACCUMULATE, "RWR_FLAG_ACCUMULATE", nullptr, nullptr, 0u},
     {RWR_FLAG_SHADOWS, "RWR_FLAG_SHADOWS", nullptr, nullptr, 0u},
     {RWR_FLAG_DENOISE, "RWR_FLAG_DENOISE", "filter", "its taps reach 62 pixels", 0u},
@@ -21,37 +21,41 @@ constexpr FlagRule kFlagRules[8] = {
     {RWR_FLAG_SKY, "RWR_FLAG_SKY", nullptr, nullptr, 0u},
     {RWR_FLAG_MIRRORS, "RWR_FLAG_MIRRORS", nullptr, nullptr, surface_mode(SurfaceModel::kMirror)},
     {RWR_FLAG_GLASS, "RWR_FLAG_GLASS", nullptr, nullptr, surface_mode(SurfaceModel::kGlass)},
-    {RWR_FLAG_GLOSSY, "RWR_FLAG_GLOSSY", nullptr, nullptr, surface_mode(SurfaceModel::kGloss)}};
+    {RWR_FLAG_GLOSSY, "RWR_FLAG_GLOSSY", nullptr, nullptr, surface_mode(SurfaceModel::kGloss)},
+    {RWR_FLAG_SOFT_SHADOWS, "RWR_FLAG_SOFT_SHADOWS", nullptr, nullptr, 0u}};
 constexpr uint32_t kSurfaceFlags = RWR_FLAG_MIRRORS | RWR_FLAG_GLASS | RWR_FLAG_GLOSSY;
 
 // What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
 // camera uniform's bytes, the screen, the rows, bounces, seed, flags but the ACCUMULATE bit, frames in flight and the scene — and, while
-// the frame is lit by the sky (RWR_FLAG_SKY), the sky's parameters.  (Mirror surfaces, RWR_FLAG_MIRRORS: the flag is one of the
+// the frame is lit by the sky (RWR_FLAG_SKY), the sky's parameters, and while its lights have a size (RWR_FLAG_SOFT_SHADOWS), theirs.  (Mirror surfaces, RWR_FLAG_MIRRORS: the flag is one of the
 // flags, and every call of their setters changes the scene's generation; glass surfaces, RWR_FLAG_GLASS, and glossy ones, RWR_FLAG_GLOSSY, likewise.)
 std::vector<unsigned char> accum_key_of(const rwr_context *ctx, const rwr_camera_inv_uniform &cam, const FrameRequest &rq)
 {
     const uint32_t words[9] = {ctx->screen.width, ctx->screen.height, rq.row_begin, rq.row_end, rq.row_pitch, rq.rp.max_bounces, rq.rp.seed,
                                rq.rp.flags & ~(uint32_t)RWR_FLAG_ACCUMULATE, ctx->n_slots};
-    std::vector<unsigned char> key(sizeof cam + sizeof words + sizeof ctx->scene_generation + (rq.sky ? sizeof ctx->sky : 0u));
-    std::memcpy(key.data(), &cam, sizeof cam);
-    std::memcpy(key.data() + sizeof cam, words, sizeof words);
-    std::memcpy(key.data() + sizeof cam + sizeof words, &ctx->scene_generation, sizeof ctx->scene_generation);
-    if (rq.sky) std::memcpy(key.data() + sizeof cam + sizeof words + sizeof ctx->scene_generation, &ctx->sky, sizeof ctx->sky);
+    std::vector<unsigned char> key(sizeof cam + sizeof words + sizeof ctx->scene_generation + (rq.sky ? sizeof ctx->sky : 0u) + (rq.soft ? sizeof ctx->shadow : 0u));
+    unsigned char *at = key.data();
+    std::memcpy(at, &cam, sizeof cam); at += sizeof cam;
+    std::memcpy(at, words, sizeof words); at += sizeof words;
+    std::memcpy(at, &ctx->scene_generation, sizeof ctx->scene_generation); at += sizeof ctx->scene_generation;
+    if (rq.sky) { std::memcpy(at, &ctx->sky, sizeof ctx->sky); at += sizeof ctx->sky; }
+    if (rq.soft) std::memcpy(at, &ctx->shadow, sizeof ctx->shadow);   // (the flag's bit is among the words: the two optional tails cannot be taken for each other)
     return key;
 }
 
 // What a reprojecting frame must share with the one before for the history to go on (rwr_hip.h RWR_FLAG_REPROJECT item 2): the
 // screen, spp, bounces, seed, the effective flags (the DENOISE and REPROJECT bits are not among them), frames in flight, the scene,
-// the stage's parameters and, while the sky lights the frame, the sky's.  NOT the camera.
+// the stage's parameters and, while the sky lights the frame, the sky's, while the lights have a size, theirs.  NOT the camera.
 std::vector<unsigned char> reproject_key_of(const rwr_context *ctx, const FrameRequest &rq)
 {
     const uint32_t words[7] = {ctx->screen.width, ctx->screen.height, rq.rp.spp, rq.rp.max_bounces, rq.rp.seed, rq.rp.flags, ctx->n_slots};
-    std::vector<unsigned char> key(sizeof words + sizeof ctx->scene_generation + sizeof ctx->reproject + (rq.sky ? sizeof ctx->sky : 0u));
+    std::vector<unsigned char> key(sizeof words + sizeof ctx->scene_generation + sizeof ctx->reproject + (rq.sky ? sizeof ctx->sky : 0u) + (rq.soft ? sizeof ctx->shadow : 0u));
     unsigned char *at = key.data();
     std::memcpy(at, words, sizeof words); at += sizeof words;
     std::memcpy(at, &ctx->scene_generation, sizeof ctx->scene_generation); at += sizeof ctx->scene_generation;
     std::memcpy(at, &ctx->reproject, sizeof ctx->reproject); at += sizeof ctx->reproject;
-    if (rq.sky) std::memcpy(at, &ctx->sky, sizeof ctx->sky);
+    if (rq.sky) { std::memcpy(at, &ctx->sky, sizeof ctx->sky); at += sizeof ctx->sky; }
+    if (rq.soft) std::memcpy(at, &ctx->shadow, sizeof ctx->shadow);
     return key;
 }
 
@@ -101,10 +105,12 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
         for (const FlagRule &f : kFlagRules)
             if (f.mode && !(modes & f.mode)) rp.flags &= ~f.flag;
     }
+    // Soft shadows change the direction of shadow rays and nothing else: without shadow rays, or with two point lights, there is nothing to change
+    if (!(asked & RWR_FLAG_SHADOWS) || (ctx->shadow.mesh_light_radius == 0.0f && ctx->shadow.sphere_light_radius == 0.0f)) rp.flags &= ~(uint32_t)RWR_FLAG_SOFT_SHADOWS;
     auto has = [](uint32_t flags, uint32_t flag) { return (flags & flag) != 0; };
     rq = FrameRequest{rp, row_begin, row_end, row_pitch, has(rp.flags, RWR_FLAG_AUX_OUTPUTS), has(asked, RWR_FLAG_ACCUMULATE), has(asked, RWR_FLAG_SHADOWS),
                       has(asked, RWR_FLAG_DENOISE), has(asked, RWR_FLAG_REPROJECT), has(rp.flags, RWR_FLAG_MIRRORS), has(rp.flags, RWR_FLAG_GLASS),
-                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), false, false};
+                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), false, false};
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
     // with shadow rays (the integrator's stages trace them) or one the filter follows (it runs behind the integrator's resolve)
     rq.wavefront = rp.spp != 1 || rp.max_bounces != 0 || rq.accumulate || rq.shadows || rq.denoise || rq.reproject;

@@ -13,7 +13,14 @@
 // origin terms, node, stack, face records — is per lane, as in k_wf_trace_lane.  A word whose records want both lights (a sphere
 // hit among mesh hits) is traced once per light.
 // The origin and the two hit tests are written operation for operation like the oracle; boxes only skip what cannot be hit.
+// SOFT forms (RWR_FLAG_SOFT_SHADOWS; definition: include/rwr_hip.h): the lights have an angular size, and a ray runs towards a
+// point of its light's disk, S = L + r (a b1 + b b2).  A lane finds its global pixel and sample from (tile, slot) the way
+// emit_next_ray does and draws (a, b) by bounce_direction's rejection loop ONCE, ahead of the two-light loop (two registers
+// across it; the basis and the radius of a light are wave-uniform scalars, WfSoft); per light it forms S and its own slab
+// constants (make_slab_ray) and walks the same any-hit traversal with a per-lane direction.  The hard forms keep their code: what
+// the SOFT forms need arrives in a kernel argument of its own behind the others.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <type_traits>
 
@@ -25,10 +32,10 @@ namespace rwr {
 
 struct ShadowLights { float dir[2][3]; SlabDir slab[2]; };   // [0] the mesh shader's light, [1] the sphere shader's
 
-template <bool NODES_IN_LDS, bool STACK16>
+template <bool NODES_IN_LDS, bool STACK16, bool SOFT>
 __global__ void __launch_bounds__(256)
 k_wf_shadow(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDevice bvh, const WfBuffers wf, const WfShadow sw,
-            uint32_t n_tiles, uint32_t sample_count, uint32_t n_shares, const ShadowLights lights)
+            uint32_t n_tiles, uint32_t sample_count, uint32_t n_shares, const ShadowLights lights, const WfSoft soft)
 {
     __shared__ TraceShared sh;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
@@ -74,12 +81,30 @@ k_wf_shadow(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDe
                 ra = src[0]; rb = src[1];
             }
             const f3 O = mk3(__uint_as_float(ra.x), __uint_as_float(ra.y), __uint_as_float(ra.z));
+            float da = 0.0f, db = 0.0f;   // SOFT: the lane's point on the unit disk
+            if (SOFT) {
+                // the slot's pixel (as add_contribution maps it) and sample, as emit_next_ray finds them
+                const uint32_t r = e & (kWfTilePixels - 1u), wv = r >> 7, k = (r >> 6) & 1u, l = r & 63u;
+                const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (wv & 1u) * 32u + 2u * (l & 15u) + k;
+                const uint32_t py = p.row_begin + (tile / wf.tiles_x) * p.row_pitch + (wv >> 1) * 4u + (l >> 4);
+                const uint32_t pixel = py * p.width + px, sample = soft.sample_base + e / kWfTilePixels;
+                for (uint32_t j = 0; j < 8u; j++) {   // bounce_direction's rejection loop, operation for operation
+                    const float ua = 2.0f * rng_uniform(pixel, sample, soft.dim0 + 2u * j, p.seed) - 1.0f;
+                    const float ub = 2.0f * rng_uniform(pixel, sample, soft.dim0 + 1u + 2u * j, p.seed) - 1.0f;
+                    if (ua * ua + ub * ub <= 1.0f) { da = ua; db = ub; break; }
+                }
+            }
             bool occluded = false;
 #pragma unroll
             for (uint32_t kind = 0; kind < 2u; kind++) {
                 const bool mine = live && (ra.w & 1u) == kind;
                 if (!__any(mine)) continue;   // uniform
-                const f3 L = mk3(lights.dir[kind][0], lights.dir[kind][1], lights.dir[kind][2]);
+                f3 L = mk3(lights.dir[kind][0], lights.dir[kind][1], lights.dir[kind][2]);
+                if (SOFT) {   // S = L + r (a b1 + b b2): two products and a sum inside, one product, one sum; not re-normalised
+                    const float rl = soft.radius[kind];
+                    L = mk3(L.x + rl * (da * soft.b1[kind][0] + db * soft.b2[kind][0]), L.y + rl * (da * soft.b1[kind][1] + db * soft.b2[kind][1]),
+                            L.z + rl * (da * soft.b1[kind][2] + db * soft.b2[kind][2]));
+                }
                 bool occ = false;
                 for (uint32_t s = 0; s < p.n_spheres; s++) {   // spheres first, literal sphereRayIntersect
                     float ts;
@@ -88,7 +113,11 @@ k_wf_shadow(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDe
                 if (p.n_tris) {
                     const bool go = mine && !occ;
                     bool o2;
-                    if (NODES_IN_LDS) o2 = bvh_occluded(s_nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, L, lights.slab[kind], go);
+                    if (SOFT) {   // a direction per lane: its own reciprocals and near planes
+                        const SlabRay sr = make_slab_ray(O, L);
+                        if (NODES_IN_LDS) o2 = bvh_occluded(s_nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, L, sr, go);
+                        else o2 = bvh_occluded(bvh.nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, L, sr, go);
+                    } else if (NODES_IN_LDS) o2 = bvh_occluded(s_nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, L, lights.slab[kind], go);
                     else o2 = bvh_occluded(bvh.nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, L, lights.slab[kind], go);
                     occ = occ || (go && o2);
                 }
@@ -112,20 +141,20 @@ k_wf_shadow(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDe
 }
 
 struct ShadowForms {   // rwr_wf_forms.h
-    struct Form { bool nodes_in_lds, stack16; };
-    static constexpr uint32_t kRange = 4u;
-    static constexpr uint32_t encode(Form f) { return f.nodes_in_lds + 2u * f.stack16; }
-    static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0}; }
+    struct Form { bool nodes_in_lds, stack16, soft; };
+    static constexpr uint32_t kRange = 8u;
+    static constexpr uint32_t encode(Form f) { return f.nodes_in_lds + 2u * f.stack16 + 4u * f.soft; }
+    static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0}; }
     static constexpr bool valid(Form) { return true; }
-    using Kernel = decltype(&k_wf_shadow<false, false>);
-    template <uint32_t I> static constexpr Kernel kernel() { return &k_wf_shadow<decode(I).nodes_in_lds, decode(I).stack16>; }
+    using Kernel = decltype(&k_wf_shadow<false, false, false>);
+    template <uint32_t I> static constexpr Kernel kernel() { return &k_wf_shadow<decode(I).nodes_in_lds, decode(I).stack16, decode(I).soft>; }
 };
 static constexpr auto kShadowForms = form_table<ShadowForms>();
-static_assert(check_forms<ShadowForms>(4), "nodelets in LDS or not, 16-bit stacks or not");
+static_assert(check_forms<ShadowForms>(8), "nodelets in LDS or not, 16-bit stacks or not, lights of a size or not");
 
 hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
                             const WfShadow &shadow, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count, const float light_mesh[3],
-                            const float light_sphere[3])
+                            const float light_sphere[3], uint32_t gen, uint32_t sample_base, const rwr_shadow_params *soft)
 {
     if (n_tiles == 0 || sample_count == 0) return hipSuccess;
     ShadowLights lights;
@@ -137,6 +166,20 @@ hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecor
         for (int k = 0; k < 3; k++) { uint32_t u; std::memcpy(&u, &inv[k], 4); sign[k] = u >> 31; }
         lights.slab[l] = SlabDir{inv[0], inv[1], inv[2], 3u * sign[0], 3u * sign[1] + 1u, 3u * sign[2] + 2u};
     }
+    WfSoft sf{};
+    if (soft) {   // bounce_direction's basis about each light (rwr_device.h), the same f32 operations (this unit is built without contraction)
+        for (int l = 0; l < 2; l++) {
+            const float *n = lights.dir[l];
+            const float sign = std::copysign(1.0f, n[2]);
+            const float aa = -1.0f / (sign + n[2]);
+            const float bb = n[0] * n[1] * aa;
+            sf.b1[l][0] = 1.0f + sign * n[0] * n[0] * aa; sf.b1[l][1] = sign * bb; sf.b1[l][2] = -sign * n[0];
+            sf.b2[l][0] = bb; sf.b2[l][1] = sign + n[1] * n[1] * aa; sf.b2[l][2] = -n[1];
+        }
+        sf.radius[0] = soft->mesh_light_radius; sf.radius[1] = soft->sphere_light_radius;
+        sf.dim0 = 2u + 16u * RWR_MAX_BOUNCES + 16u * gen;
+        sf.sample_base = sample_base;
+    }
     // enough work items to fill the chip a few times over when the tiles with work are few — expected_tiles: the live tiles of
     // the frame before when this frame walks a live list, else all of them (a share zeroes and flushes 12 KiB of sums; any
     // split gives the same frame)
@@ -144,15 +187,15 @@ hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecor
     const uint32_t n_shares = std::max(1u, std::min(std::min(32u, sample_count * 8u), 4096u / work_tiles));
     const dim3 grid((uint32_t)std::min<uint64_t>(2048u, (uint64_t)n_tiles * n_shares));
     const LaneLdsPlan l = lane_lds_plan(bvh, fp, false);   // (no 1 024-thread form here)
-    hipLaunchKernelGGL(kShadowForms[ShadowForms::encode({l.nodes_in_lds, l.stack16})], grid, dim3(256), l.bytes, s, fp, tris, bvh, wf, shadow, n_tiles,
-                       sample_count, n_shares, lights);
+    hipLaunchKernelGGL(kShadowForms[ShadowForms::encode({l.nodes_in_lds, l.stack16, soft != nullptr})], grid, dim3(256), l.bytes, s, fp, tris, bvh, wf, shadow,
+                       n_tiles, sample_count, n_shares, lights, sf);
     return hipGetLastError();
 }
 
 hipError_t preload_kernels_wf_shadow()
 {
     hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>((&k_wf_shadow<true, true>)));
+    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>((&k_wf_shadow<true, true, false>)));
 }
 
 }  // namespace rwr

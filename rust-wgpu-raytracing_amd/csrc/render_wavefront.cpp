@@ -231,6 +231,8 @@ int WfFrame::trace_groups(const AccumPlan &ap)
     }
     if (rq.sky) std::memcpy(&ft.sky, &ctx->sky, sizeof ft.sky);
     ft.sky_on = rq.sky;
+    ft.soft = rq.soft;
+    const rwr_shadow_params *soft = ft.soft ? &ctx->shadow : nullptr;
     // (global sample indices: an accumulating frame traces [accum_before, accum_before + spp), keyed like one frame of them all)
     for (uint32_t s0 = 0, g = 0; s0 < ap.trace_spp; s0 += group, g++) {
         const uint32_t cnt = std::min(group, rp.spp - s0);
@@ -241,7 +243,8 @@ int WfFrame::trace_groups(const AccumPlan &ap)
         RWR_HIP_CHECK(launch_wf_primary(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg, wfq[q],
                                         (uint32_t)ap.before + s0, cnt, z_split, ft));
         if (rq.shadows)   // h0's shadow rays
-            RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
+            RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere, 0u,
+                                           (uint32_t)ap.before + s0, soft));
         // the bounce stage: one generation of rays per bounce (RWR_FLAG_MULTI_BOUNCE: up to RWR_MAX_BOUNCES).  Generation k traces
         // ray k of every path that is still alive — the sort and trace kernels run again over the same fixed slots — and, unless
         // it is the last, writes ray k + 1 back into the slot of every hit, with its bit in the other ballot array.
@@ -259,7 +262,8 @@ int WfFrame::trace_groups(const AccumPlan &ap)
                                            (uint32_t)std::fmax(1.0f, std::ceil(ctx->wf_packet_fill * (float)(cnt * kWfTilePixels))),
                                            W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles, ft));
             if (rq.shadows)   // this generation's hits
-                RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere));
+                RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere, gen,
+                                               (uint32_t)ap.before + s0, soft));
             if (emit) std::swap(wg.masks, masks_next);
         }
         if (rp.max_bounces && s0 + group >= rp.spp) last_counters = wfq[q].counters;

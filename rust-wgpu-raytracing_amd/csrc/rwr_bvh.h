@@ -216,14 +216,13 @@ RWR_DEV SlabRay slab_ray_from(const SlabDir &d, f3 O)
     return r;
 }
 
-// One ray per lane, all in the SAME direction D (wave-uniform: rays towards a directional light; sd: its slab constants), lanes
-// with `active` unset only keep the wave company.  Per lane: the origin terms, the node, the stack.  A node's surviving children
-// are visited nearest first (bvh_inner_step's per-lane key minimum, as for any ray).  nodes, stack: as bvh_nearest.
+// One ray per lane with its slab constants sr (make_slab_ray, or slab_ray_from below); lanes with `active` unset only keep the
+// wave company.  Per lane: the node, the stack.  A node's surviving children are visited nearest first (bvh_inner_step's per-lane
+// key minimum, as for any ray).  nodes, stack: as bvh_nearest.
 template <typename NodePtr, typename StackT>
 RWR_DEV bool bvh_occluded(NodePtr nodes, const uint32_t *__restrict__ leaf_faces, const TriRecord *__restrict__ tris,
-                          uint32_t n_faces, StackT *stack, f3 O, f3 D, const SlabDir &sd, bool active)
+                          uint32_t n_faces, StackT *stack, f3 O, f3 D, const SlabRay &sr, bool active)
 {
-    const SlabRay sr = slab_ray_from(sd, O);
     const uint32_t stride = blockDim.x;
     StackT *sp = stack + threadIdx.x;
     StackT *const sp0 = sp;
@@ -244,6 +243,15 @@ RWR_DEV bool bvh_occluded(NodePtr nodes, const uint32_t *__restrict__ leaf_faces
         }
     }
     return occluded;
+}
+
+// ... all in the SAME direction D (wave-uniform: rays towards a directional light of no size; sd: its slab constants): only the
+// origin terms of the slab test are per lane.
+template <typename NodePtr, typename StackT>
+RWR_DEV bool bvh_occluded(NodePtr nodes, const uint32_t *__restrict__ leaf_faces, const TriRecord *__restrict__ tris,
+                          uint32_t n_faces, StackT *stack, f3 O, f3 D, const SlabDir &sd, bool active)
+{
+    return bvh_occluded(nodes, leaf_faces, tris, n_faces, stack, O, D, slab_ray_from(sd, O), active);
 }
 
 // Host side: the dynamic LDS of a kernel that walks the BVH per lane (k_wf_trace_lane, k_wf_shadow), [nodelets][traversal stacks].

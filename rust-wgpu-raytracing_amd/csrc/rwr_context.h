@@ -152,6 +152,7 @@ constexpr uint32_t kMaxFramesInFlight = 3;
 constexpr rwr_denoise_params kDenoiseDefaults{5u, 0.04f, 0.95f, 0.05f};   // RWR_FLAG_DENOISE: DESIGN.md §6 says why these
 constexpr rwr_reproject_params kReprojectDefaults{32u, 0.95f, 0.05f};   // RWR_FLAG_REPROJECT: the tap tests are the denoiser's
 constexpr rwr_sky_params kSkyDefaults = RWR_SKY_DEFAULTS;   // RWR_FLAG_SKY
+constexpr rwr_shadow_params kShadowDefaults = RWR_SHADOW_DEFAULTS;   // RWR_FLAG_SOFT_SHADOWS
 constexpr uint32_t kWfMaxQueues = 4;
 
 // The wavefront integrator's device state, one set per frame slot: a frame of the integrator then shares nothing with the
@@ -325,6 +326,7 @@ struct rwr_context {
     uint32_t last_reproject_set = 0;       // ... and the history set it wrote (rwr_reproject_readback, rwr_last_reproject_stats)
     rwr_denoise_params denoise = rwr::kDenoiseDefaults;   // RWR_FLAG_DENOISE (rwr_denoise_set_params)
     rwr_sky_params sky = rwr::kSkyDefaults;               // RWR_FLAG_SKY (rwr_sky_set_params)
+    rwr_shadow_params shadow = rwr::kShadowDefaults;      // RWR_FLAG_SOFT_SHADOWS (rwr_shadow_set_params)
     uint64_t scene_generation = 0;         // bumped by every change of the scene (an accumulation does not survive one)
     // one decoded texture per scene part (texels decoded to linear f32 at upload, Rgba8UnormSrgb semantics)
     std::vector<rwr::DeviceBuffer<float4>> d_texs;

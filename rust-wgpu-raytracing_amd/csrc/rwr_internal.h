@@ -342,6 +342,14 @@ struct WfShadow {
     unsigned long long *masks;
     unsigned long long *counts;
 };
+// Soft shadows (RWR_FLAG_SOFT_SHADOWS; the SOFT forms of k_wf_shadow): per light ([0] the mesh shader's, [1] the sphere shader's)
+// bounce_direction's basis about the unit vector towards it and its radius; the first of the 16 RNG dimensions this launch's disk
+// draws read (130 + 16 k behind generation k: behind every block a path reads) and the global sample index of the launch group's
+// first sample.  A kernel argument of its own behind the others (cf. WfEmit), so that the hard forms keep their code.
+struct WfSoft {
+    float b1[2][3], b2[2][3], radius[2];
+    uint32_t dim0, sample_base;
+};
 // Sky light (RWR_FLAG_SKY; the SKY forms of the trace kernels, kernels_wf_bounce.hip): the context's rwr_sky_params.  A kernel
 // argument of its own behind the others (cf. WfEmit), so that the six floats are scalar registers and the kernels without the
 // flag keep their code.
@@ -378,6 +386,7 @@ struct WfFeatures {
     WfSky sky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     WfMirror mirror{nullptr, 0u, 0u, nullptr};
     bool emits = false, shadows = false, sky_on = false;
+    bool soft = false;   // RWR_FLAG_SOFT_SHADOWS: k_wf_shadow's SOFT forms (no other kernel looks)
     int surf = kSurfNone;   // the surface models of the frame's flags (kSurfGlass: the table may hold glass records; kSurfGloss: glossy ones too)
     // The two rules for SURF.  The surface forms differ where a ray is emitted and nowhere else: the primary stage has one only
     // when the frame bounces at all, a trace kernel only in a generation that emits (a kernel that ends a path has none).
@@ -440,9 +449,11 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
 // RWR_FLAG_SHADOWS: traces the shadow records the kernels of one stage left in the queue (the primary stage's, or one generation's
 // trace kernels') and adds the light's part of every term whose ray got through.  light_mesh / light_sphere: the unit directions
 // towards the reference's two lights; expected_tiles: how many tiles are expected to hold records (sizes the work items only).
+// soft (may be null: point lights, the hard forms): the lights' radii, RWR_FLAG_SOFT_SHADOWS — the SOFT forms, which key their disk
+// draws by gen (0 behind the primary stage, k behind generation k) and sample_base (the launch group's first global sample).
 hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
                             const WfShadow &shadow, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count, const float light_mesh[3],
-                            const float light_sphere[3]);
+                            const float light_sphere[3], uint32_t gen, uint32_t sample_base, const rwr_shadow_params *soft);
 size_t wf_pool_info_bytes();
 // RWR_WF_STATS=1: trace launches of this process so far {packet kernel, per-lane kernel, its 1 024-thread form}
 void wf_trace_launch_counts(uint64_t out[3]);

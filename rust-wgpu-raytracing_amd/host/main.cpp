@@ -3,7 +3,7 @@
 // input* -> update -> render, with key events taken from a script instead of a window.
 //
 //   rwr_render --res DIR [--scene suzanne_lowpoly.obj] [--size 600x600] [--keys "S*15,D*4"]
-//              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows]
+//              [--frames N] [--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] [--soft-shadows R[,R2]]
 //              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]]
 //              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]...
 //              [--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]]
@@ -61,6 +61,8 @@ int main(int argc, char **argv)
         out = std::strtod(text, &end);
         return end != text && *end == '\0' && out == out && out - out == 0.0;
     };
+    bool soft_shadows = false;
+    rwr_shadow_params shadow_params = RWR_SHADOW_DEFAULTS;   // the library's defaults
     bool sky = false, sky_zenith_set = false, sky_horizon_set = false, show_params = false;
     rwr_sky_params sky_params = RWR_SKY_DEFAULTS;   // the library's defaults
     // "r,g,b": three numbers and nothing else, each finite and in [0, 16] (rwr_sky_set_params' range)
@@ -167,6 +169,21 @@ int main(int argc, char **argv)
         else if (a == "--time") timing = true;
         else if (a == "--accumulate") accumulate = true;
         else if (a == "--shadows") shadows = true;
+        else if (a == "--soft-shadows") {   // "R" (both lights) or "R,R2" (the mesh shader's light, the sphere shader's): numbers in [0, 1]
+            const std::string v = next();
+            const size_t comma = v.find(',');
+            double r0 = 0.0, r1 = 0.0;
+            bool ok = parse_number(v.substr(0, comma).c_str(), r0);
+            r1 = r0;
+            if (ok && comma != std::string::npos) ok = parse_number(v.c_str() + comma + 1, r1);
+            if (!ok || r0 < 0.0 || r0 > (double)RWR_SHADOW_RADIUS_MAX || r1 < 0.0 || r1 > (double)RWR_SHADOW_RADIUS_MAX) {
+                std::fprintf(stderr, "--soft-shadows R[,R2]: one or two numbers in [0, 1]\n");
+                return 2;
+            }
+            shadow_params.mesh_light_radius = (float)r0;
+            shadow_params.sphere_light_radius = (float)r1;
+            shadows = soft_shadows = true;
+        }
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-iterations") { denoise = true; denoise_iterations = std::atoi(next()); }
         else if (a == "--denoise-sigma") { denoise = true; denoise_sigma = (float)std::atof(next()); }
@@ -234,7 +251,7 @@ int main(int argc, char **argv)
             if (std::sscanf(next(), "%ux%u", &w, &h) != 2) { std::fprintf(stderr, "--size WxH\n"); return 2; }
         } else if (a == "--help" || a == "-h") {
             std::printf("usage: rwr_render --res DIR [--scene F.obj] [--size WxH] [--keys \"S*15,D*4\"] [--frames N] "
-                        "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] "
+                        "[--resize WxH@FRAME]... [--spp N] [--bounces B] [--accumulate] [--shadows] [--soft-shadows R[,R2]] "
                         "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
                         "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]... "
                         "[--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... "
@@ -244,6 +261,9 @@ int main(int argc, char **argv)
                         "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n"
                         "  --shadows     every hit casts a shadow ray towards its light (RWR_FLAG_SHADOWS); works with --spp, --bounces "
                         "and --accumulate\n"
+                        "  --soft-shadows R[,R2]  the two lights get an angular size, so that shadows get penumbrae (RWR_FLAG_SOFT_SHADOWS; implies "
+                        "--shadows): R is the tangent of the half-angle a hit sees the light under, in [0, 1] (0.0047: the sun; 0: the point light "
+                        "of --shadows); one value sets both lights, two the mesh shader's and the sphere shader's (rwr_shadow_set_params)\n"
                         "  --denoise     the edge-avoiding a-trous filter over every frame (RWR_FLAG_DENOISE): N iterations (1-5), colour "
                         "sigma S (rwr_denoise_set_params)\n"
                         "  --sky         bounce rays that leave the scene return the sky's radiance (RWR_FLAG_SKY; needs --bounces >= 1): a "
@@ -275,12 +295,14 @@ int main(int argc, char **argv)
     const uint32_t flags = (accumulate ? (uint32_t)RWR_FLAG_ACCUMULATE : 0u) | (bounces > 1u ? (uint32_t)RWR_FLAG_MULTI_BOUNCE : 0u) |   // more than one bounce: the deeper paths
                            (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u) | (denoise ? (uint32_t)RWR_FLAG_DENOISE : 0u) | (sky ? (uint32_t)RWR_FLAG_SKY : 0u) |
                            (mirrors.empty() ? 0u : (uint32_t)RWR_FLAG_MIRRORS) | (glasses.empty() ? 0u : (uint32_t)RWR_FLAG_GLASS) |
-                           (glosses.empty() ? 0u : (uint32_t)RWR_FLAG_GLOSSY) |
+                           (glosses.empty() ? 0u : (uint32_t)RWR_FLAG_GLOSSY) | (soft_shadows ? (uint32_t)RWR_FLAG_SOFT_SHADOWS : 0u) |
                            (reproject ? (uint32_t)RWR_FLAG_REPROJECT : 0u);
     if (show_params) {
         if (reproject)   // (a line of its own, ahead of the line every run prints)
             std::printf("reproject 1 history %u normal %g depth %g\n", reproject_params.max_history, (double)reproject_params.normal_cos_min,
                         (double)reproject_params.depth_rel);
+        if (soft_shadows)   // (likewise)
+            std::printf("soft-shadows 1 radii %g,%g\n", (double)shadow_params.mesh_light_radius, (double)shadow_params.sphere_light_radius);
         std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g gloss %zu", spp, bounces, flags, sky ? 1 : 0,
                     (double)sky_params.zenith[0], (double)sky_params.zenith[1], (double)sky_params.zenith[2],
                     (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2], glosses.size());
@@ -318,6 +340,7 @@ int main(int argc, char **argv)
         if (sky_zenith_set || sky_horizon_set) {
             if (rwr_sky_set_params(state.context(), &sky_params) != RWR_OK) { std::fprintf(stderr, "--sky: %s\n", rwr_last_error_string()); return 2; }
         }
+        if (soft_shadows) state.set_shadow_params(shadow_params);   // (in range already: a failure is the library's, reported below)
         for (const Mirror &m : mirrors) {   // (the scene is loaded: a part the scene does not have is the library's refusal)
             const int rc = m.sphere ? rwr_scene_set_sphere_mirror(state.context(), m.index, m.r) : rwr_scene_set_part_mirror(state.context(), m.index, m.r);
             if (rc != RWR_OK) { std::fprintf(stderr, "%s: %s\n", m.sphere ? "--mirror-sphere" : "--mirror-part", rwr_last_error_string()); return 2; }

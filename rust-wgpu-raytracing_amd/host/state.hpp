@@ -128,6 +128,9 @@ public:
         if (!camera_inv_uniform_.update_view_proj(camera_)) throw RwrFailure(RWR_ERR_INVALID_ARGUMENT, "singular camera");
     }
     void render(const rwr_render_params *params = nullptr) { check(rwr_render(ctx_, &camera_inv_uniform_, params)); }  // lib.rs:1012-1230
+    // extension (RWR_FLAG_SOFT_SHADOWS): the radii of the two lights, as the context holds them
+    void set_shadow_params(const rwr_shadow_params &p) { check(rwr_shadow_set_params(ctx_, &p)); shadow_params_ = p; }
+    const rwr_shadow_params &shadow_params() const { return shadow_params_; }
     // extension (RWR_FLAG_ACCUMULATE): samples per pixel the frame rendered last holds, 0 when it did not accumulate
     uint64_t accumulated_samples()
     {
@@ -183,6 +186,7 @@ private:
     models::Sphere sphere_, sphere_front_;
     models::TriangleList triangle_list_;
     rwr_context *ctx_ = nullptr;
+    rwr_shadow_params shadow_params_ = RWR_SHADOW_DEFAULTS;
 };
 
 }  // namespace rwr
