@@ -762,6 +762,19 @@ RWR_API int rwr_tile_cover_stats(rwr_context *ctx, uint64_t *frames, uint64_t *t
  * A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_lean_rest_stats(rwr_context *ctx, uint64_t *frames);
 
+/* How the last frame of the wavefront integrator walked the BVH per lane, for its trace stage (the bounce rays) and its shadow stage
+ * (RWR_FLAG_SHADOWS) separately: {launches, nodes_in_lds, stack16, wide}.  launches: per-lane kernel launches the stage put on its
+ * streams (the trace stage: one per generation and launch group, beside the packet kernel when the scene has one — which pools
+ * each of the two traces is decided on the device; the shadow stage has no other kernel) — 0 for a stage the frame did not have
+ * (no bounce / no shadow rays), and then the other three are 0 too, not a plan nobody used.  nodes_in_lds, stack16, wide: the form of
+ * the stage's launches (one per frame: it depends on the scene and the context alone) — the nodelets staged in LDS, 16-bit
+ * traversal stack entries (a scene of at most 4 095 world faces and 32 767 nodes), 1 024-thread workgroups around one copy of the
+ * nodelets (the trace stage alone).  RWR_WF_STACK16=0 (read when the context is created) makes every frame keep 32-bit entries —
+ * and so never the wide form, which needs the 16-bit ones; any other value leaves the rule alone: the variable cannot give 16-bit
+ * entries to a scene beyond the limit.  Frames are the same bytes either way.  Recorded on the host when the frame is enqueued: no
+ * wait.  Zeros before the first such frame.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_last_traversal_plan(rwr_context *ctx, uint32_t trace[4], uint32_t shadow[4]);
+
 /* RWR_FLAG_SHADOWS: shadow rays traced by the last render call (= hits shaded: primary hits and the bounce hits of every
  * generation; an accumulating frame: its own samples; 0 without the flag) and how many of them were occluded.  Exact counts.
  * Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */

@@ -122,6 +122,7 @@ def lib() -> C.CDLL:
         "rwr_last_shadow_stats": [vp, vp, vp], "rwr_frame_setup_launches": [vp, vp], "rwr_ray_plane_stats": [vp, vp, vp],
         "rwr_debug_tile_classes": [vp, vp, C.c_size_t, vp, vp],
         "rwr_debug_tile_cover": [vp, vp, C.c_size_t, vp, vp], "rwr_tile_cover_stats": [vp, vp, vp], "rwr_lean_rest_stats": [vp, vp],
+        "rwr_last_traversal_plan": [vp, vp, vp],
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
         "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
@@ -152,7 +153,7 @@ def lib() -> C.CDLL:
         "rwr_dist_loopback_deposit": [vp, u32, u32, i32], "rwr_dist_loopback_finish": [vp, u32, i32],
         "rwr_measure_valu_clock": [vp, u32, vp], "rwr_clock_probe_start": [vp, u32], "rwr_clock_probe_read": [vp, vp],
     }
-    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats", "rwr_debug_tile_classes", "rwr_debug_tile_cover", "rwr_tile_cover_stats", "rwr_lean_rest_stats",
+    _NEWER_ENTRY_POINTS = ("rwr_last_shadow_stats", "rwr_denoise_set_params", "rwr_denoise_get_params", "rwr_frame_setup_launches", "rwr_ray_plane_stats", "rwr_debug_tile_classes", "rwr_debug_tile_cover", "rwr_tile_cover_stats", "rwr_lean_rest_stats", "rwr_last_traversal_plan",
                            "rwr_sky_set_params", "rwr_sky_get_params", "rwr_scene_set_part_mirror", "rwr_scene_set_sphere_mirror",
                            "rwr_scene_get_part_mirror", "rwr_scene_get_sphere_mirror", "rwr_scene_set_part_glass", "rwr_scene_set_sphere_glass",
                            "rwr_scene_get_part_glass", "rwr_scene_get_sphere_glass", "rwr_last_glass_stats",
@@ -776,6 +777,15 @@ class Context:
         a = C.c_uint64()
         _check(lib().rwr_lean_rest_stats(self._h, C.byref(a)))
         return a.value
+
+    def last_traversal_plan(self) -> dict:
+        """How the last wavefront frame walked the BVH per lane (rwr_last_traversal_plan): {"trace": plan, "shadow": plan}, a plan
+        being {"launches", "nodes_in_lds", "stack16", "wide"} - all 0 for a stage the frame did not have.  RWR_WF_STACK16=0 (read
+        when the context is created): 32-bit stack entries whatever the scene's size."""
+        t, s = np.zeros(4, np.uint32), np.zeros(4, np.uint32)
+        _check(lib().rwr_last_traversal_plan(self._h, _p(t), _p(s)))
+        names = ("launches", "nodes_in_lds", "stack16", "wide")
+        return {"trace": dict(zip(names, map(int, t))), "shadow": dict(zip(names, map(int, s)))}
 
     def last_shadow_stats(self) -> tuple[int, int]:
         """(shadow rays traced by the last render call, how many of them were occluded); (0, 0) without FLAG_SHADOWS."""

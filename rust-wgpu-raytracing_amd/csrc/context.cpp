@@ -102,6 +102,11 @@ void read_tunables(rwr_context *ctx)
     env_u32("RWR_WF_ZSPLIT", &ctx->wf_z_split);
     env_u32("RWR_WF_PACKET_RAYS", &ctx->wf_packet_dense_rays);
     if (env_flag("RWR_WF_WIDE_LANE", &wide)) ctx->wf_wide_lane = wide ? 1 : 0;
+    if (const char *e = std::getenv("RWR_WF_STACK16")) {   // a number that is 0 switches the 16-bit entries off; nothing switches them on
+        char *end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (end != e && *end == '\0' && v == 0) ctx->wf_stack16 = false;
+    }
     if (env_u32("RWR_WF_LANE_ITEMS", &ctx->wf_lane_items)) ctx->wf_lane_items = std::max(1u, ctx->wf_lane_items);
     env_u32("RWR_WF_MIN_PACKET_POOLS", &ctx->wf_min_packet_pools);
     env_f32("RWR_WF_PACKET_EXTENT", &ctx->wf_packet_extent);

@@ -99,6 +99,17 @@ int rwr_lean_rest_stats(rwr_context *ctx, uint64_t *frames)
     return RWR_OK;
 }
 
+int rwr_last_traversal_plan(rwr_context *ctx, uint32_t trace[4], uint32_t shadow[4])
+{
+    if (!ctx || !trace || !shadow) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    const LanePlanRecord *from[2] = {&ctx->last_trace_plan, &ctx->last_shadow_plan};
+    uint32_t *to[2] = {trace, shadow};
+    for (int k = 0; k < 2; k++) {
+        to[k][0] = from[k]->launches; to[k][1] = from[k]->nodes_in_lds; to[k][2] = from[k]->stack16; to[k][3] = from[k]->wide;
+    }
+    return RWR_OK;
+}
+
 int rwr_measure_valu_clock(rwr_context *ctx, uint32_t waves_per_simd, double out4[4])
 {
     if (!ctx || !out4) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");

@@ -949,7 +949,8 @@ static std::atomic<uint64_t> g_trace_launches[3];
 
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf, uint32_t n_tiles,
-                            uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list, const WfFeatures &ft)
+                            uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list, const WfFeatures &ft,
+                            LanePlanRecord *plan)
 {
     if (n_tiles == 0 || sample_count == 0) return hipSuccess;
     uint32_t *counters = wf.counters;   // this queue's set, zeroed by the primary stage that filled the queue
@@ -975,6 +976,7 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     const LaneLdsPlan l = lane_lds_plan(bvh, fp, bvh.wide_lane && !nmap);
     const uint32_t form = LaneForms::encode({l.nodes_in_lds, nmap, l.stack16, l.wide, ft.emits, ft.shadows, ft.sky_on, surf});
     if (wf.dbg) g_trace_launches[l.wide ? 2 : 1].fetch_add(1u, std::memory_order_relaxed);
+    if (plan) *plan = LanePlanRecord{plan->launches + 1u, l.nodes_in_lds, l.stack16, l.wide};
     if (l.wide) {   // (at most 146 KiB: beyond the default limit, raised per form)
         static std::atomic<uint64_t> wide_raised_on[LaneForms::kRange];
         const hipError_t e = raise_dynamic_lds_once(wide_raised_on[form], 146 * 1024, {kLaneForms[form]});

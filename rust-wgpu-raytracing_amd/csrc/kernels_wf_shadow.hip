@@ -154,7 +154,8 @@ static_assert(check_forms<ShadowForms>(8), "nodelets in LDS or not, 16-bit stack
 
 hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
                             const WfShadow &shadow, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count, const float light_mesh[3],
-                            const float light_sphere[3], uint32_t gen, uint32_t sample_base, const rwr_shadow_params *soft)
+                            const float light_sphere[3], uint32_t gen, uint32_t sample_base, const rwr_shadow_params *soft,
+                            LanePlanRecord *plan)
 {
     if (n_tiles == 0 || sample_count == 0) return hipSuccess;
     ShadowLights lights;
@@ -187,6 +188,7 @@ hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecor
     const uint32_t n_shares = std::max(1u, std::min(std::min(32u, sample_count * 8u), 4096u / work_tiles));
     const dim3 grid((uint32_t)std::min<uint64_t>(2048u, (uint64_t)n_tiles * n_shares));
     const LaneLdsPlan l = lane_lds_plan(bvh, fp, false);   // (no 1 024-thread form here)
+    if (plan) *plan = LanePlanRecord{plan->launches + 1u, l.nodes_in_lds, l.stack16, l.wide};
     hipLaunchKernelGGL(kShadowForms[ShadowForms::encode({l.nodes_in_lds, l.stack16, soft != nullptr})], grid, dim3(256), l.bytes, s, fp, tris, bvh, wf, shadow,
                        n_tiles, sample_count, n_shares, lights, sf);
     return hipGetLastError();

@@ -30,6 +30,7 @@ struct WfFrame {
     WfBuffers wfq[kWfMaxQueues];
     WfFeatures ft;
     const uint32_t *last_counters = nullptr;   // the last group's live-pool counts, for the next frame's split
+    LanePlanRecord trace_plan, shadow_plan;    // what the frame's two stages launched per lane (rwr_last_traversal_plan)
 
     WfFrame(rwr_context *c, FrameSlot &s, const FrameRequest &r, const FrameParams &p, const Targets &t)
         : ctx(c), sl(s), rq(r), rp(r.rp), fp(p), tg(t), W(c->wf_state[c->n_slots > 1u ? c->cur : 0u]), stream(s.stream), n((size_t)p.width * p.height)
@@ -164,7 +165,7 @@ int WfFrame::schedule()
                         // 16 samples: 0.625 -> 0.607 ms with 4 096 items, but 0.74 -> 0.79 ms one frame at a time; configs[4]'s
                         // frame, 64 samples: 16 384 is best either way)
                         ctx->wf_lane_items ? ctx->wf_lane_items : (wide_lane ? 256u : ctx->n_slots > 1u ? std::min(16384u, 256u * group) : 16384u),
-                        ctx->wf_packet_dense_rays, wide_lane ? 1u : 0u};
+                        ctx->wf_packet_dense_rays, wide_lane ? 1u : 0u, ctx->wf_stack16 ? 0u : 1u};
     return RWR_OK;
 }
 
@@ -244,7 +245,7 @@ int WfFrame::trace_groups(const AccumPlan &ap)
                                         (uint32_t)ap.before + s0, cnt, z_split, ft));
         if (rq.shadows)   // h0's shadow rays
             RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere, 0u,
-                                           (uint32_t)ap.before + s0, soft));
+                                           (uint32_t)ap.before + s0, soft, &shadow_plan));
         // the bounce stage: one generation of rays per bounce (RWR_FLAG_MULTI_BOUNCE: up to RWR_MAX_BOUNCES).  Generation k traces
         // ray k of every path that is still alive — the sort and trace kernels run again over the same fixed slots — and, unless
         // it is the last, writes ray k + 1 back into the slot of every hit, with its bit in the other ballot array.
@@ -260,10 +261,10 @@ int WfFrame::trace_groups(const AccumPlan &ap)
             if (rq.shadows) RWR_HIP_CHECK(hipMemsetAsync(ft.shadow.masks, 0, mask_words * sizeof(unsigned long long), gs));   // the trace kernels set bits
             RWR_HIP_CHECK(launch_wf_bounce(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh, tex0, wg, n_tiles, cnt,
                                            (uint32_t)std::fmax(1.0f, std::ceil(ctx->wf_packet_fill * (float)(cnt * kWfTilePixels))),
-                                           W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles, ft));
+                                           W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles, ft, &trace_plan));
             if (rq.shadows)   // this generation's hits
                 RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere, gen,
-                                               (uint32_t)ap.before + s0, soft));
+                                               (uint32_t)ap.before + s0, soft, &shadow_plan));
             if (emit) std::swap(wg.masks, masks_next);
         }
         if (rp.max_bounces && s0 + group >= rp.spp) last_counters = wfq[q].counters;
@@ -372,6 +373,8 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
     if (rq.reproject && (rc = F.reproject_stage(pp)) != RWR_OK) return rc;
     if (rq.denoise && (rc = F.denoise_stage()) != RWR_OK) return rc;
     ctx->last_segments = F.n_tiles;
+    ctx->last_trace_plan = F.trace_plan;
+    ctx->last_shadow_plan = F.shadow_plan;
     ctx->last_wf_state = ctx->n_slots > 1u ? ctx->cur : 0u;
     return RWR_OK;
 }

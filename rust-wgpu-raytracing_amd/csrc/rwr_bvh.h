@@ -255,7 +255,9 @@ RWR_DEV bool bvh_occluded(NodePtr nodes, const uint32_t *__restrict__ leaf_faces
 }
 
 // Host side: the dynamic LDS of a kernel that walks the BVH per lane (k_wf_trace_lane, k_wf_shadow), [nodelets][traversal stacks].
-//   stack16       node indices and leaf links (first << 3 | count - 1) fit 15 bits: 16-bit stack entries
+//   stack16       node indices and leaf links (first << 3 | count - 1) fit 15 bits: 16-bit stack entries.  bvh.no_stack16
+//                 (RWR_WF_STACK16=0) takes them away from a scene that would have them — never the other way round — and with
+//                 them the wide form, which needs them
 //   nodes_in_lds  nodelets go to LDS when the 256-thread workgroup then still fits a CU at least four times (160 KiB LDS, 12 KiB
 //                 static) — or when the workgroup is wide
 //   wide          (may_widen: the caller has a 1 024-thread form and wants it) a BVH too large for a copy per 256-thread
@@ -265,7 +267,7 @@ struct LaneLdsPlan { bool stack16, nodes_in_lds, wide; size_t bytes; };
 inline LaneLdsPlan lane_lds_plan(const BvhDevice &bvh, const FrameParams &fp, bool may_widen)
 {
     LaneLdsPlan l;
-    l.stack16 = bvh.n_nodes <= 0x7fffu && fp.n_tris <= 4095u;
+    l.stack16 = !bvh.no_stack16 && bvh.n_nodes <= 0x7fffu && fp.n_tris <= 4095u;
     const size_t fixed = (size_t)bvh.stack_depth * 256u * (l.stack16 ? 2u : 4u);
     const size_t node_bytes = (size_t)bvh.n_nodes * sizeof(BvhNode4);
     const size_t wide_bytes = node_bytes + 4u * fixed;

@@ -292,6 +292,9 @@ struct rwr_context {
                                           // and is 5 % faster with them as packets, an eighth share has 50 and is 10 % faster per lane: tools/share_probe.py)
     uint32_t wf_lane_items = 0;           // tunable: RWR_WF_LANE_ITEMS (0: chosen per frame, see the BvhDevice of the wavefront path)
     int32_t wf_wide_lane = -1;            // the per-lane trace kernel as 1 024-thread workgroups: -1 by itself (render_wavefront.cpp wf_schedule), tunable: RWR_WF_WIDE_LANE=0/1
+    bool wf_stack16 = true;               // the per-lane kernels' 16-bit stack entries where the scene allows them (rwr_bvh.h lane_lds_plan); RWR_WF_STACK16=0: 32-bit
+                                          // entries for every scene — and so no wide form, which needs the 16-bit ones.  It can only switch them off
+    rwr::LanePlanRecord last_trace_plan, last_shadow_plan;   // the last wavefront frame's per-lane launches, by stage (rwr_last_traversal_plan)
     uint32_t wf_packet_dense_rays = 16384;   // a pool of at least this many rays (32 samples of a full tile) is traced as packets
                                              // however far apart its rays start; tunable: RWR_WF_PACKET_RAYS (0: never).  Measured
                                              // (tools/packet_rays_sweep.sh): configs[4]'s frame, 64 samples per group, 2.11 -> 1.75

@@ -404,7 +404,11 @@ struct BvhDevice {
     uint32_t lane_items;        // work items the per-lane kernel's launch should have when pools are few (pool_split; tunable)
     uint32_t packet_dense_rays; // a pool of at least this many rays is traced as packets however far apart its rays start (0: never)
     uint32_t wide_lane;         // the per-lane trace kernel may run as 1 024-thread workgroups sharing one LDS copy of the nodelets
+    uint32_t no_stack16;        // the per-lane kernels keep 32-bit stack entries whatever the scene's size (RWR_WF_STACK16=0; host only: lane_lds_plan)
 };
+// What a stage of the last wavefront frame launched per lane, written by the launchers where they encode the form (rwr_last_traversal_plan):
+// launches of the per-lane kernel by that stage, and the LaneLdsPlan (rwr_bvh.h) of the last of them — all zero while launches is.
+struct LanePlanRecord { uint32_t launches = 0, nodes_in_lds = 0, stack16 = 0, wide = 0; };
 
 // A frame slot's kept plane of ray directions (frame_records.cpp ray_plane_step): the normalised directions of the two-pixel frame
 // kernel's pixel pairs, 24 bytes per lane of its grid — xy[i] = {x.x, x.y, y.x, y.y}, z[i] = {z.x, z.y} of the pair whose lane
@@ -442,18 +446,21 @@ hipError_t launch_wf_classify(hipStream_t s, const FrameParams &fp, const FrameT
 // One generation of rays: the sort, then the trace kernels in the forms of ft (WfFeatures) — ft.emits: a generation of a deeper
 // path that is not its last, the EMIT forms write every hit's next ray back into its slot; else the kernels that end the path.
 // ft.shadows: the SHADOW forms; ft.sky_on: the SKY forms, a ray that hits nothing adds the sky's term; ft.trace_surf(): SURF.
+// plan (may be null): receives the per-lane launch and its LaneLdsPlan.
 hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                             const BvhDevice &bvh, const float4 *tex, const WfBuffers &wf,
                             uint32_t n_tiles, uint32_t sample_count, uint32_t packet_min_rays, void *pool_info, uint32_t *pool_list,
-                            const WfFeatures &ft);
+                            const WfFeatures &ft, LanePlanRecord *plan = nullptr);
 // RWR_FLAG_SHADOWS: traces the shadow records the kernels of one stage left in the queue (the primary stage's, or one generation's
 // trace kernels') and adds the light's part of every term whose ray got through.  light_mesh / light_sphere: the unit directions
 // towards the reference's two lights; expected_tiles: how many tiles are expected to hold records (sizes the work items only).
 // soft (may be null: point lights, the hard forms): the lights' radii, RWR_FLAG_SOFT_SHADOWS — the SOFT forms, which key their disk
 // draws by gen (0 behind the primary stage, k behind generation k) and sample_base (the launch group's first global sample).
+// plan (may be null): as launch_wf_bounce's.
 hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
                             const WfShadow &shadow, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count, const float light_mesh[3],
-                            const float light_sphere[3], uint32_t gen, uint32_t sample_base, const rwr_shadow_params *soft);
+                            const float light_sphere[3], uint32_t gen, uint32_t sample_base, const rwr_shadow_params *soft,
+                            LanePlanRecord *plan = nullptr);
 size_t wf_pool_info_bytes();
 // RWR_WF_STATS=1: trace launches of this process so far {packet kernel, per-lane kernel, its 1 024-thread form}
 void wf_trace_launch_counts(uint64_t out[3]);

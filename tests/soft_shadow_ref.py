@@ -107,7 +107,8 @@ def render_path(L, orc, cam_inv, screen, params, spheres, model, instances=None,
     return {"color": color, "depth": depth, "color_f32": color_f, "obj_id": obj_id, "hit_t": hit_t, "rays": int(rays[0]),
             "shadow_rays": int(shadow_rays[0]), "occluded": int(occluded[0]), "occluded0": occl0, "sky_terms": int(sky_terms[0]),
             "gen_rays": gen_rays.astype(np.int64), "gen_gloss": gen_gloss.astype(np.int64), "glossy": int(gen_gloss.sum()),
-            "changed_to_lit": int(changed[0]), "changed_to_dark": int(changed[1]), "primary": primary}
+            "changed_to_lit": int(changed[0]), "changed_to_dark": int(changed[1]), "primary": primary,
+            "events": tuple(int(v) for v in events), "gen_mirror": gen_mirror.astype(np.int64), "gen_glass": gen_glass.astype(np.int64)}
 
 
 def reference(L, orc, sc, cam_inv, w, h, spp, bounces, seed=7, radii=None, shadows=True, rows=None, **kw):
