@@ -435,15 +435,15 @@ int rwr_last_shadow_stats(rwr_context *ctx, uint64_t *shadow_rays, uint64_t *occ
 int rwr_last_glass_stats(rwr_context *ctx, uint64_t *reflected, uint64_t *transmitted, uint64_t *tir)
 {
     if (!ctx || !reflected || !transmitted || !tir) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
-    unsigned long long counts[3] = {0ull, 0ull, 0ull};
-    if (ctx->last_glass && ctx->wf_state[ctx->last_wf_state].d_glass_counts.ptr) {
+    unsigned long long counts[kEventGlossy] = {0ull, 0ull, 0ull};   // the glass events come first
+    if (ctx->last_glass && ctx->wf_state[ctx->last_wf_state].d_surface_events.ptr) {
         DeviceGuard g(ctx->device);
         RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
-        RWR_HIP_CHECK(hipMemcpy(counts, ctx->wf_state[ctx->last_wf_state].d_glass_counts.ptr, sizeof counts, hipMemcpyDeviceToHost));
+        RWR_HIP_CHECK(hipMemcpy(counts, ctx->wf_state[ctx->last_wf_state].d_surface_events.ptr, sizeof counts, hipMemcpyDeviceToHost));
     }
-    *reflected = counts[0];
-    *transmitted = counts[1];
-    *tir = counts[2];
+    *reflected = counts[kEventReflected];
+    *transmitted = counts[kEventTransmitted];
+    *tir = counts[kEventTotalReflection];
     return RWR_OK;
 }
 
@@ -451,10 +451,10 @@ int rwr_last_gloss_stats(rwr_context *ctx, uint64_t *glossy_rays)
 {
     if (!ctx || !glossy_rays) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
     unsigned long long count = 0ull;
-    if (ctx->last_gloss && ctx->wf_state[ctx->last_wf_state].d_glass_counts.ptr) {
+    if (ctx->last_gloss && ctx->wf_state[ctx->last_wf_state].d_surface_events.ptr) {
         DeviceGuard g(ctx->device);
         RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
-        RWR_HIP_CHECK(hipMemcpy(&count, ctx->wf_state[ctx->last_wf_state].d_glass_counts.ptr + 3, sizeof count, hipMemcpyDeviceToHost));
+        RWR_HIP_CHECK(hipMemcpy(&count, ctx->wf_state[ctx->last_wf_state].d_surface_events.ptr + kEventGlossy, sizeof count, hipMemcpyDeviceToHost));
     }
     *glossy_rays = count;
     return RWR_OK;

@@ -274,11 +274,10 @@ k_wf_sort(const WfBuffers wf, PoolInfo *__restrict__ info, uint32_t *__restrict_
 // about n instead (reflect_direction: no random number is read, the generation's RNG dimensions are left unused), thr is T * R.
 // Glass forms (RWR_FLAG_GLASS; SURF == kSurfGlass), a hit on glass (`eta` != 0, its index): direction and side by
 // refract_or_reflect with the generation's first random number, origin P + 1e-4 m, thr is T * C — computed here, where the
-// traversal's registers are dead.  Returns the glass event (0 reflected, 1 transmitted, 2 totally reflected), 3 for no glass hit.
+// traversal's registers are dead.  Returns the hit's SurfaceEvent (rwr_surface.h): refract_or_reflect's, kEventNone for no counted hit.
 // Glossy forms (RWR_FLAG_GLOSSY; SURF == kSurfGloss), a hit on a glossy surface (`rho` != 0, its roughness): the diffuse direction
 // of the same dimensions goes through gloss_direction — computed for every lane that draws a diffuse direction and selected, so
 // that the lanes stay together — thr is T * R.  Returns kEventGlossy for such a hit.
-constexpr uint32_t kEventGlossy = 4u;
 template <int SURF = kSurfNone>
 RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const WfEmit &em, const TriRecord *__restrict__ tris, uint32_t tile,
                                uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr, bool mirror = false, float eta = 0.0f,
@@ -287,7 +286,7 @@ RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const 
     f3 n;
     f3 O1 = hit_exit_point(p, tris, O, D, obj, t, ndotd, n);
     f3 D1;
-    uint32_t event = 3u;
+    uint32_t event = kEventNone;
     // glossy forms: a ray that starts at P + 1e-4 n (every one but a glass hit's) has its origin and the first two channels of its
     // throughput stored ahead of the direction's arithmetic — five registers fewer across the disk loop and the rule, which these
     // forms hold live together
@@ -326,42 +325,17 @@ RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const 
     return event;
 }
 
-// Glass forms: a wave's glass events into the frame's three counters (WfMirror::glass_counts) — ballots and popcounts, added by
-// the wave's first active lane, one atomic per event kind the wave saw.  Call where the wave's lanes have come together again.
-// GLOSS (the glossy forms): the glossy rays too, into the fourth counter behind them.
-template <bool GLOSS = false>
-RWR_DEV void count_glass_events(unsigned long long *__restrict__ counts, uint32_t ev0, uint32_t ev1 = 3u)
+// The surface forms' emit step for the hit (obj, t): the hit's record (rwr_surface.h surface_record), decoded; a surface with a
+// model sends on T * its record's colour, a diffuse one T * albedo; emit_next_ray does the rest.  Returns its event.
+template <int SURF>
+RWR_DEV uint32_t emit_from_surface(const FrameParams &p, const WfBuffers &wf, const WfEmit &em, const WfSurfaces &sf, const TriRecord *__restrict__ tris,
+                                   const ShadeRec *__restrict__ shade, uint32_t tile, uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd,
+                                   f3 thr, f3 albedo)
 {
-    const unsigned long long active = __ballot(true);
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (uint32_t k = 0; k < 3u; k++) {
-        const uint32_t n = (uint32_t)__popcll(__ballot(ev0 == k)) + (uint32_t)__popcll(__ballot(ev1 == k));
-        if (n && lane == (uint32_t)__builtin_ctzll(active)) atomicAdd(&counts[k], (unsigned long long)n);
-    }
-    if (GLOSS) {
-        const uint32_t n = (uint32_t)__popcll(__ballot(ev0 == kEventGlossy)) + (uint32_t)__popcll(__ballot(ev1 == kEventGlossy));
-        if (n && lane == (uint32_t)__builtin_ctzll(active)) atomicAdd(&counts[3], (unsigned long long)n);
-    }
-}
-
-// MIRROR forms: the surface record {r, g, b, on} of the hit `obj` (rwr_internal.h WfMirror).  Part 0's record is read at a constant
-// index through the constant address space: a wave-uniform address, one scalar load into scalar registers, and all a face of a
-// one-part scene needs (it never looks at ShadeRec::material).  Only a sphere hit (by its index) and a face of a scene with
-// several parts (by ShadeRec::material) read their record per lane, under a branch of their own, so that the two reads stay two.
-RWR_DEV float4 mirror_record(const FrameParams &p, const WfMirror &mir, const ShadeRec *__restrict__ shade, int32_t obj)
-{
-    const const_ptr<float> tab = to_const_space(reinterpret_cast<const float *>(mir.table));
-    // part 0; the empty asm pins the four values to scalar registers where they are read, or the compiler folds this read into the
-    // per-lane one below (one vector load at a selected index)
-    float r0 = tab[0], r1 = tab[1], r2 = tab[2], r3 = tab[3];
-    asm volatile("" : "+s"(r0), "+s"(r1), "+s"(r2), "+s"(r3));
-    float4 m = make_float4(r0, r1, r2, r3);
-    if (obj < 0 || p.n_materials > 1u) {
-        const uint32_t i = obj < 0 ? mir.n_parts + (uint32_t)(-2 - obj) : shade[obj].material;
-        m = make_float4(tab[4u * i], tab[4u * i + 1u], tab[4u * i + 2u], tab[4u * i + 3u]);
-    }
-    return m;
+    const float4 m = surface_record(sf.table, sf.n_parts, p.n_materials > 1u, shade, obj);
+    const SurfaceDecode s = decode_surface<SURF>(m.w);
+    const f3 next = (s.mirror || s.glass || s.gloss) ? mk3(m.x, m.y, m.z) : albedo;
+    return emit_next_ray<SURF>(p, wf, em, tris, tile, e, O, D, obj, t, ndotd, mk3(thr.x * next.x, thr.y * next.y, thr.z * next.z), s.mirror, s.eta, s.rho);
 }
 
 // SHADOW forms: the term T * E(h) of the hit (obj, t) of the ray in slot e is a select between clamp(T * ambient part) and
@@ -454,7 +428,7 @@ __global__ void __launch_bounds__(WIDE ? 1024 : 256)
 k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                 const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                 uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
-                const WfSky sky, const WfMirror mir)
+                const WfSky sky, const WfSurfaces sf)
 {
     static_assert(EMIT || SURF == kSurfNone, "only a kernel that emits rays has a MIRROR or a glass form");
     constexpr bool MIRROR = SURF != kSurfNone;
@@ -517,7 +491,7 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                 else bvh_nearest(bvh.nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, D, mh);
                 if (mh.have && (!have || mh.t < best_t)) { have = true; best_t = mh.t; obj = (int32_t)mh.idx; }
             }
-            uint32_t event = 3u;   // glass forms: what a glass hit did
+            uint32_t event = kEventNone;   // glass and glossy forms: what a counted hit did
             if (have) {
                 const Shaded s1 = shade_winner<NMAP>(p, obj, best_t, mh.u, mh.v, mh.ndotd, shade, tex, O, D);
                 const f3 e1 = s1.colour;
@@ -526,20 +500,11 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                 if (EMIT && !MIRROR)
                     emit_next_ray(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd,
                                   mk3(thr.x * s1.albedo.x, thr.y * s1.albedo.y, thr.z * s1.albedo.z));
-                if (EMIT && MIRROR) {
-                    const float4 m = mirror_record(p, mir, shade, obj);
-                    const bool gloss = SURF == kSurfGloss && m.w > 1.0f;   // (w = 1 + roughness, in (1, 2]; the other forms never see one)
-                    const bool mirror = SURF == kSurfNone || SURF == kSurfMirrors ? m.w != 0.0f : m.w > 0.0f && !gloss;
-                    const bool glass = (SURF == kSurfGlass || SURF == kSurfGloss) && m.w < 0.0f;
-                    const f3 next = (mirror || glass || gloss) ? mk3(m.x, m.y, m.z) : s1.albedo;
-                    event = emit_next_ray<SURF>(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd, mk3(thr.x * next.x, thr.y * next.y, thr.z * next.z),
-                                                mirror, glass ? -m.w : 0.0f, gloss ? m.w - 1.0f : 0.0f);
-                }
+                if (EMIT && MIRROR) event = emit_from_surface<SURF>(p, wf, em, sf, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, s1.albedo);
             } else if (SKY) {
                 add_sky(sh, sky, e, D.y, thr);
             }
-            if (SURF == kSurfGlass) count_glass_events(mir.glass_counts, event);
-            if (SURF == kSurfGloss) count_glass_events<true>(mir.glass_counts, event);
+            if (SURF == kSurfGlass || SURF == kSurfGloss) count_surface_events<SURF == kSurfGloss>(sf.events, event);
             if (EMIT) {   // rays written for the next generation (lanes past the pool's end have left the iteration)
                 const unsigned long long em = __ballot(have);
                 if (em && (tid & 63u) == (uint32_t)__builtin_ctzll(em)) atomicAdd(&wf.wave_total[tile * 4u], (uint32_t)__popcll(em));
@@ -639,7 +604,7 @@ __global__ void __launch_bounds__(256, (SURF == kSurfGloss && SKY && !SHADOW) ? 
 k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                   uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
-                  const WfSky sky, const WfMirror mir)
+                  const WfSky sky, const WfSurfaces sf)
 {
     static_assert(EMIT || SURF == kSurfNone, "only a kernel that emits rays has a MIRROR or a glass form");
     constexpr bool MIRROR = SURF != kSurfNone;
@@ -861,23 +826,15 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
                                       k ? best.ndotd.y : best.ndotd.x, k ? mk3(nr.y, ng.y, nb.y) : mk3(nr.x, ng.x, nb.x));
             }
             if (EMIT && MIRROR) {   // the same, but a hit on a mirror sends T * R on, not T * albedo, in the reflected direction
-                uint32_t event[2] = {3u, 3u};   // glass forms: what each ray's glass hit did
+                uint32_t event[2] = {kEventNone, kEventNone};   // glass and glossy forms: what each ray's counted hit did
 #pragma unroll
                 for (int k = 0; k < 2; k++)
-                    if (k ? have.y : have.x) {
-                        const int32_t o = k ? obj.y : obj.x;
-                        const float4 m = mirror_record(p, mir, shade, o);
-                        const bool gloss = SURF == kSurfGloss && m.w > 1.0f;
-                        const bool mirror = SURF == kSurfNone || SURF == kSurfMirrors ? m.w != 0.0f : m.w > 0.0f && !gloss;
-                        const bool glass = (SURF == kSurfGlass || SURF == kSurfGloss) && m.w < 0.0f;
-                        const f3 next = (mirror || glass || gloss) ? mk3(m.x, m.y, m.z) : (k ? mk3(ar.y, ag.y, ab.y) : mk3(ar.x, ag.x, ab.x));
-                        const f3 t = k ? mk3(thr.x.y, thr.y.y, thr.z.y) : mk3(thr.x.x, thr.y.x, thr.z.x);
-                        event[k] = emit_next_ray<SURF>(p, wf, em, tris, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), o, k ? best_t.y : best_t.x,
-                                                       k ? best.ndotd.y : best.ndotd.x, mk3(t.x * next.x, t.y * next.y, t.z * next.z), mirror,
-                                                       glass ? -m.w : 0.0f, gloss ? m.w - 1.0f : 0.0f);
-                    }
-                if (SURF == kSurfGlass) count_glass_events(mir.glass_counts, event[0], event[1]);
-                if (SURF == kSurfGloss) count_glass_events<true>(mir.glass_counts, event[0], event[1]);
+                    if (k ? have.y : have.x)
+                        event[k] = emit_from_surface<SURF>(p, wf, em, sf, tris, shade, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), k ? obj.y : obj.x,
+                                                           k ? best_t.y : best_t.x, k ? best.ndotd.y : best.ndotd.x,
+                                                           k ? mk3(thr.x.y, thr.y.y, thr.z.y) : mk3(thr.x.x, thr.y.x, thr.z.x),
+                                                           k ? mk3(ar.y, ag.y, ab.y) : mk3(ar.x, ag.x, ab.x));
+                if (SURF == kSurfGlass || SURF == kSurfGloss) count_surface_events<SURF == kSurfGloss>(sf.events, event[0], event[1]);
             }
             if (EMIT) {
                 const uint32_t n_emit = (uint32_t)__popcll(__ballot(have.x != 0)) + (uint32_t)__popcll(__ballot(have.y != 0));
@@ -971,7 +928,7 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     if (packets) {
         if (wf.dbg) g_trace_launches[0].fetch_add(1u, std::memory_order_relaxed);
         hipLaunchKernelGGL(kPacketForms[PacketForms::encode({nmap, ft.emits, ft.shadows, ft.sky_on, surf})], dim3(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit)),
-                           dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, ft.emit, ft.shadow, ft.sky, ft.mirror);
+                           dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, ft.emit, ft.shadow, ft.sky, ft.surfaces);
     }
     const LaneLdsPlan l = lane_lds_plan(bvh, fp, bvh.wide_lane && !nmap);
     const uint32_t form = LaneForms::encode({l.nodes_in_lds, nmap, l.stack16, l.wide, ft.emits, ft.shadows, ft.sky_on, surf});
@@ -984,7 +941,7 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     }
     const dim3 grid(std::min(l.wide ? 512u : kWfTraceGroups, n_tiles * kWfMaxSplit));
     hipLaunchKernelGGL(kLaneForms[form], grid, dim3(l.wide ? 1024 : 256), l.bytes, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles,
-                       ft.emit, ft.shadow, ft.sky, ft.mirror);
+                       ft.emit, ft.shadow, ft.sky, ft.surfaces);
     return hipGetLastError();
 }
 

@@ -161,7 +161,7 @@ struct WfPrimaryArgs {
     Targets tg;
     WfBuffers wf;
     WfShadow sw;   // RWR_FLAG_SHADOWS (the SHADOW forms); behind the rest, so that the other forms read their arguments where they always did
-    WfMirror mr;   // RWR_FLAG_MIRRORS (the MIRROR forms); last, for the same reason
+    WfSurfaces surfaces;   // RWR_FLAG_MIRRORS, _GLASS, _GLOSSY (the surface forms); last, for the same reason
 };
 template <typename T> using kernarg = const __attribute__((address_space(4))) T;
 RWR_DEV kernarg<WfPrimaryArgs> *wf_args_again(kernarg<WfPrimaryArgs> *q)
@@ -174,11 +174,11 @@ RWR_DEV f3 ld3(kernarg<float> *q) { return mk3(q[0], q[1], q[2]); }
 // SHADOW (RWR_FLAG_SHADOWS): a hit adds the AMBIENT part of E(h0) to the group's sums and leaves a shadow record — the bounce
 // ray's origin, the light of the shader that shaded it, fix(E) - fix(ambient) — at its queue slot, with its bit in the shadow
 // ballots, for k_wf_shadow (kernels_wf_shadow.hip).  Forms of their own: the others keep their registers.
-// MIRROR (RWR_FLAG_MIRRORS): a hit on a mirror surface (WfMirror's table: per part, per sphere) emits the reflection of its ray
+// MIRROR (RWR_FLAG_MIRRORS): a hit on a mirror surface (WfSurfaces' table: per part, per sphere) emits the reflection of its ray
 // with throughput R instead of the cosine-distributed ray with the albedo, decided per pixel of the lane's pair.  A tile without
 // a mirror hit skips the reflection, a tile whose emitting pixels are all mirror hits skips the RNG and the disk-to-hemisphere
 // arithmetic (wave-uniform branches on ballots), a mixed tile computes both and selects.  Forms of their own again.
-// SURF (rwr_internal.h): kSurfNone, kSurfMirrors — the MIRROR forms — or kSurfGlass (RWR_FLAG_GLASS, with or without mirrors): a hit
+// SURF (rwr_surface.h): kSurfNone, kSurfMirrors — the MIRROR forms — or kSurfGlass (RWR_FLAG_GLASS, with or without mirrors): a hit
 // on glass emits the reflected or the refracted ray of refract_or_reflect from P + 1e-4 m with throughput C, decided per pixel too.
 // A tile without a glass hit skips that arithmetic, a tile whose emitting pixels are all specular skips the RNG disk loop.
 // kSurfGloss (RWR_FLAG_GLOSSY, with or without the other two): a glossy hit draws the diffuse direction like a diffuse one and
@@ -482,35 +482,26 @@ k_wf_primary(const WfPrimaryArgs a)
                 if (bounces) {
                 v3 D1;
                 if (MIRROR) {
-                    // each pixel's surface record.  Part 0's is read at a constant index — a wave-uniform address, one scalar load
-                    // into scalar registers — and is all a face of a one-part scene needs (no look at ShadeRec::material); a sphere
-                    // (by its index) and a face of a scene with several parts read theirs per lane, under a branch of their own
+                    // each pixel's surface record (rwr_surface.h surface_record), decoded
                     kernarg<WfPrimaryArgs> *const qv = wf_args_again(ka);
-                    const const_ptr<float> tab = to_const_space(reinterpret_cast<const float *>(qv->mr.table));
-                    const uint32_t n_parts = qv->mr.n_parts;
+                    const SurfaceRec *const table = qv->surfaces.table;
+                    const uint32_t n_parts = qv->surfaces.n_parts;
                     const bool parts = qv->p.n_materials > 1u;
                     const ShadeRec *const shade = qv->shade;
-                    float r0 = tab[0], r1 = tab[1], r2 = tab[2], r3 = tab[3];
-                    asm volatile("" : "+s"(r0), "+s"(r1), "+s"(r2), "+s"(r3));   // (pinned to scalar registers: not folded into the per-lane read)
-                    const float4 m0 = make_float4(r0, r1, r2, r3);
                     i2 mir = i2{0, 0}, gl = i2{0, 0}, gs = i2{0, 0};
                     f2 eta = splat(0.0f);   // GLASS: the index of a pixel's glass hit
-                    f2 rho = splat(0.0f);   // GLOSS: the roughness of a pixel's glossy hit
+                    f2 rho = splat(0.0f);   // GLOSS: the roughness of a pixel's glossy hit (it draws the diffuse direction too)
 #pragma unroll
                     for (int k = 0; k < 2; k++) {
-                        const int o = k ? obj.y : obj.x;
                         if (k ? emit.y : emit.x) {
-                            float4 m = m0;
-                            if (o < 0 || parts) {
-                                const uint32_t i = o < 0 ? n_parts + (uint32_t)(-2 - o) : shade[o].material;
-                                m = make_float4(tab[4u * i], tab[4u * i + 1u], tab[4u * i + 2u], tab[4u * i + 3u]);
-                            }
-                            if (m.w != 0.0f) {
+                            const float4 m = surface_record(table, n_parts, parts, shade, k ? obj.y : obj.x);
+                            const SurfaceDecode sd = decode_surface<SURF>(m.w);
+                            if (sd.mirror || sd.glass || sd.gloss) {
                                 if (k) { tr.y = m.x; tgc.y = m.y; tb.y = m.z; } else { tr.x = m.x; tgc.x = m.y; tb.x = m.z; }
-                                if (GLASS && m.w < 0.0f) {
-                                    if (k) { gl.y = -1; eta.y = -m.w; } else { gl.x = -1; eta.x = -m.w; }
-                                } else if (GLOSS && m.w > 1.0f) {   // (w = 1 + roughness; it draws the diffuse direction too)
-                                    if (k) { gs.y = -1; rho.y = m.w - 1.0f; } else { gs.x = -1; rho.x = m.w - 1.0f; }
+                                if (sd.glass) {
+                                    if (k) { gl.y = -1; eta.y = sd.eta; } else { gl.x = -1; eta.x = sd.eta; }
+                                } else if (sd.gloss) {
+                                    if (k) { gs.y = -1; rho.y = sd.rho; } else { gs.x = -1; rho.x = sd.rho; }
                                 } else {
                                     if (k) mir.y = -1; else mir.x = -1;
                                 }
@@ -529,16 +520,12 @@ k_wf_primary(const WfPrimaryArgs a)
                         if (__any(any2(gs))) {
                             const v3 S = gloss_direction_pair(n, D, Dd, rho);
                             D1 = v3{gs ? S.x : D1.x, gs ? S.y : D1.y, gs ? S.z : D1.z};
-                            // the wave's glossy rays into the frame's counter behind the glass events: ballots and popcounts, one atomic.
-                            // Lane 0 is the wave's first active lane here, as for the glass counters above: every branch down to
-                            // this one is wave-uniform (m0 | m1, bounces, __any), so all 64 lanes of the pixel-pair wave are live;
-                            // and cnt > 0, since __any(any2(gs)) holds.
-                            const uint32_t cnt = (uint32_t)__popcll(__ballot(gs.x != 0)) + (uint32_t)__popcll(__ballot(gs.y != 0));
-                            if (lane == 0u) atomicAdd(&wf_args_again(ka)->mr.glass_counts[3], (unsigned long long)cnt);
+                            count_surface_events<true, false>(wf_args_again(ka)->surfaces.events, gs.x ? kEventGlossy : kEventNone,
+                                                              gs.y ? kEventGlossy : kEventNone);
                         }
                     }
                     if (GLASS) {
-                        uint32_t ev[2] = {3u, 3u};
+                        uint32_t ev[2] = {kEventNone, kEventNone};
                         if (__any(any2(gl))) {   // (rwr_device.h refract_or_reflect, one pixel of the pair after the other; dimension 2 of the sample)
 #pragma unroll
                             for (int k = 0; k < 2; k++)
@@ -549,13 +536,7 @@ k_wf_primary(const WfPrimaryArgs a)
                                     if (k) { D1.x.y = Dg.x; D1.y.y = Dg.y; D1.z.y = Dg.z; O1.x.y = P.x.y + mg.x * 1e-4f; O1.y.y = P.y.y + mg.y * 1e-4f; O1.z.y = P.z.y + mg.z * 1e-4f; }
                                     else { D1.x.x = Dg.x; D1.y.x = Dg.y; D1.z.x = Dg.z; O1.x.x = P.x.x + mg.x * 1e-4f; O1.y.x = P.y.x + mg.y * 1e-4f; O1.z.x = P.z.x + mg.z * 1e-4f; }
                                 }
-                            // the wave's events into the frame's three counters: ballots and popcounts, one atomic per kind it saw
-                            unsigned long long *const counts = wf_args_again(ka)->mr.glass_counts;
-#pragma unroll
-                            for (uint32_t c = 0; c < 3u; c++) {
-                                const uint32_t cnt = (uint32_t)__popcll(__ballot(ev[0] == c)) + (uint32_t)__popcll(__ballot(ev[1] == c));
-                                if (cnt && lane == 0u) atomicAdd(&counts[c], (unsigned long long)cnt);
-                            }
+                            count_surface_events(wf_args_again(ka)->surfaces.events, ev[0], ev[1]);
                         }
                     }
                 } else {
@@ -628,7 +609,7 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
     if (fp.row_end <= fp.row_begin || fp.width == 0 || sample_count == 0) return hipSuccess;
     z_split = std::max(1u, std::min(z_split, sample_count));
     const WfPrimaryArgs args{ftris, fp.n_tris, fp.row_begin, fp.bins.enabled, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3],
-                             sample_begin, sample_count, z_split, fp, tris, shade, tex, tg, wf, ft.shadow, ft.mirror};
+                             sample_begin, sample_count, z_split, fp, tris, shade, tex, tg, wf, ft.shadow, ft.surfaces};
     PrimaryForms::Form f;
     f.aux = (fp.flags & RWR_FLAG_AUX_OUTPUTS) != 0;
     f.cull = (fp.flags & RWR_FLAG_NO_CULL) == 0;

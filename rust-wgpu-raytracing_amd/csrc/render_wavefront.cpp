@@ -179,33 +179,30 @@ int WfFrame::surface_table()
     const uint32_t modes = (rq.mirrors ? surface_mode(SurfaceModel::kMirror) : 0u) | (rq.glass ? surface_mode(SurfaceModel::kGlass) : 0u) |
                            (rq.gloss ? surface_mode(SurfaceModel::kGloss) : 0u);
     if (!modes) return RWR_OK;
-    const size_t n_parts = ctx->part_mirrors.size(), n_recs = n_parts + RWR_MAX_SPHERES;
-    if (W.mirror_version != ctx->mirror_version || W.mirror_modes != modes || W.d_mirror.count < n_recs) {
-        if (W.mirror_version != 0u) RWR_HIP_CHECK(hipEventSynchronize(W.mirror_copied));   // the image's last copy has been read
-        if (W.h_mirror_count < n_recs) {
-            W.h_mirror = PinnedMirror();
-            RWR_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&W.h_mirror.h), n_recs * sizeof(MirrorRec), hipHostMallocDefault));
-            W.h_mirror_count = n_recs;
+    const size_t n_parts = ctx->part_surfaces.size(), n_recs = n_parts + RWR_MAX_SPHERES;
+    if (W.surface_version != ctx->surface_version || W.surface_modes != modes || W.d_surface.count < n_recs) {
+        if (W.surface_version != 0u) RWR_HIP_CHECK(hipEventSynchronize(W.surface_copied));   // the image's last copy has been read
+        if (W.h_surface_count < n_recs) {
+            W.h_surface = PinnedSurface();
+            RWR_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&W.h_surface.h), n_recs * sizeof(SurfaceRec), hipHostMallocDefault));
+            W.h_surface_count = n_recs;
         }
-        RWR_HIP_CHECK(W.d_mirror.ensure(n_recs));
-        if (!W.mirror_copied) RWR_HIP_CHECK(hipEventCreateWithFlags(&W.mirror_copied.h, hipEventDisableTiming));
-        auto visible = [&](const MirrorRec &m) {   // a surface whose flag the frame lacks is the diffuse surface it was
-            return (modes & surface_mode(surface_model(m))) ? m : kDiffuseRec;
-        };
-        for (size_t i = 0; i < n_parts; i++) W.h_mirror.h[i] = visible(ctx->part_mirrors[i]);
-        for (size_t i = 0; i < RWR_MAX_SPHERES; i++) W.h_mirror.h[n_parts + i] = visible(ctx->sphere_mirrors[i]);
-        RWR_HIP_CHECK(hipMemcpyAsync(W.d_mirror.ptr, W.h_mirror.h, n_recs * sizeof(MirrorRec), hipMemcpyHostToDevice, stream));
-        RWR_HIP_CHECK(hipEventRecord(W.mirror_copied, stream));
-        W.mirror_version = ctx->mirror_version;
-        W.mirror_modes = modes;
+        RWR_HIP_CHECK(W.d_surface.ensure(n_recs));
+        if (!W.surface_copied) RWR_HIP_CHECK(hipEventCreateWithFlags(&W.surface_copied.h, hipEventDisableTiming));
+        for (size_t i = 0; i < n_parts; i++) W.h_surface.h[i] = visible_record(ctx->part_surfaces[i], modes);
+        for (size_t i = 0; i < RWR_MAX_SPHERES; i++) W.h_surface.h[n_parts + i] = visible_record(ctx->sphere_surfaces[i], modes);
+        RWR_HIP_CHECK(hipMemcpyAsync(W.d_surface.ptr, W.h_surface.h, n_recs * sizeof(SurfaceRec), hipMemcpyHostToDevice, stream));
+        RWR_HIP_CHECK(hipEventRecord(W.surface_copied, stream));
+        W.surface_version = ctx->surface_version;
+        W.surface_modes = modes;
     }
-    ft.mirror = WfMirror{W.d_mirror.ptr, (uint32_t)n_parts, 0u, nullptr};
-    // (intended: a frame with RWR_FLAG_GLASS alone also holds and zeroes four counters now, 8 bytes more than its three — one
+    ft.surfaces = WfSurfaces{W.d_surface.ptr, (uint32_t)n_parts, 0u, nullptr};
+    // (intended: a frame with RWR_FLAG_GLASS alone also holds and zeroes the glossy counter, 8 bytes more than its three — one
     // buffer of one size for either flag, so that a context alternating between them never reallocates; no launch is added)
-    if (rq.glass || rq.gloss) {   // the frame's event counters — three of glass, then the glossy rays — start from zero
-        RWR_HIP_CHECK(W.d_glass_counts.ensure(4));
-        RWR_HIP_CHECK(hipMemsetAsync(W.d_glass_counts.ptr, 0, 4 * sizeof(unsigned long long), stream));
-        ft.mirror.glass_counts = W.d_glass_counts.ptr;
+    if (rq.glass || rq.gloss) {   // the frame's event counters (SurfaceEvent) start from zero
+        RWR_HIP_CHECK(W.d_surface_events.ensure(kEventNone));
+        RWR_HIP_CHECK(hipMemsetAsync(W.d_surface_events.ptr, 0, kEventNone * sizeof(unsigned long long), stream));
+        ft.surfaces.events = W.d_surface_events.ptr;
     }
     return RWR_OK;
 }

@@ -63,38 +63,8 @@ using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
 using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
 using OwnedGraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
 using PinnedWords = Owned<uint32_t *, free_pinned_words>;
-// A surface's record, a float4 of WfMirror::table: r, g, b and the surface's model in `on` (SurfaceModel below).
-struct MirrorRec { float r, g, b, on; };
-static_assert(sizeof(MirrorRec) == sizeof(float4), "MirrorRec is a float4");
-inline hipError_t free_pinned_mirror(MirrorRec *p) { return hipHostFree(p); }
-using PinnedMirror = Owned<MirrorRec *, free_pinned_mirror>;
-
-// The one statement of MirrorRec::on.  A surface has one model:
-//   kDiffuse  on = 0               neither of the others (r, g, b are zero)
-//   kMirror   on = 1               reflectance r, g, b (RWR_FLAG_MIRRORS)
-//   kGlass    on = -ior            tint r, g, b; ior in [1, 4] (RWR_FLAG_GLASS)
-//   kGloss    on = 1 + roughness   reflectance r, g, b; roughness in [2^-10, 1], a multiple of 2^-23 once stored (RWR_FLAG_GLOSSY)
-// Invariant: every record a setter can write (scene.cpp, through the makers below) has on in {0} U {1} U [-4, -1] U [1 + 2^-10, 2].
-// So `on == 1` and `on > 0 && !(on > 1)` name the same records, and so do `on > 1` and `on >= 1 + 2^-10`: whichever comparison
-// a reader of the table uses (the kernels decode m.w themselves, rwr_internal.h WfMirror), it agrees with surface_model.
-enum class SurfaceModel { kDiffuse, kMirror, kGlass, kGloss };
-inline SurfaceModel surface_model(const MirrorRec &m)
-{
-    return m.on > 1.0f ? SurfaceModel::kGloss : m.on > 0.0f ? SurfaceModel::kMirror : m.on < 0.0f ? SurfaceModel::kGlass : SurfaceModel::kDiffuse;
-}
-constexpr float kGlassIorMin = 1.0f, kGlassIorMax = 4.0f, kGlossRoughnessMin = 0x1p-10f, kGlossRoughnessMax = 1.0f;
-constexpr MirrorRec kDiffuseRec{0.0f, 0.0f, 0.0f, 0.0f};
-// the record makers: rgb in [0, 1] each, ior and roughness in the ranges above (the setters refuse anything else before they call)
-inline MirrorRec mirror_rec(const float rgb[3]) { return MirrorRec{rgb[0], rgb[1], rgb[2], 1.0f}; }
-inline MirrorRec glass_rec(const float rgb[3], float ior) { return MirrorRec{rgb[0], rgb[1], rgb[2], -ior}; }
-inline MirrorRec gloss_rec(const float rgb[3], float roughness) { return MirrorRec{rgb[0], rgb[1], rgb[2], 1.0f + roughness}; }
-// ... and what a glass record holds of its ior, a glossy one of its roughness (a diffuse record: 0)
-inline float surface_param(const MirrorRec &m) { return m.on < 0.0f ? -m.on : m.on > 1.0f ? m.on - 1.0f : 0.0f; }
-// A model's bit in the words that say which models a table holds (WfState::mirror_modes): 1 mirrors, 2 glass, 4 glossy
-constexpr uint32_t surface_mode(SurfaceModel s)
-{
-    return s == SurfaceModel::kMirror ? 1u : s == SurfaceModel::kGlass ? 2u : s == SurfaceModel::kGloss ? 4u : 0u;
-}
+inline hipError_t free_pinned_surface(SurfaceRec *p) { return hipHostFree(p); }
+using PinnedSurface = Owned<SurfaceRec *, free_pinned_surface>;   // (the record and what it means: rwr_surface.h)
 
 // Everything one frame in flight owns: its stream, its targets and the per-frame records / tables.
 // Frames alternate between slots (rwr_ctx_set_frames_in_flight), so the ramp-up of one frame's kernel
@@ -177,16 +147,16 @@ struct WfState {
     DeviceBuffer<ShadowRec> d_shadow_recs;
     DeviceBuffer<unsigned long long> d_shadow_masks, d_shadow_counts;
     DeviceBuffer<uint32_t> d_tiles;           // frames that show little: live tile list, per-tile live pieces, the count (k_wf_classify)
-    // RWR_FLAG_MIRRORS, allocated by the first frame with mirrors: this slot's copy of the surface table (WfMirror::table), the
-    // pinned image it is copied from on the slot's stream, the event behind that copy (the image is not rewritten before it), and
-    // the context's mirror_version the copy holds (0: none)
-    DeviceBuffer<float4> d_mirror;
-    PinnedMirror h_mirror;
-    size_t h_mirror_count = 0;
-    OwnedEvent mirror_copied;
-    uint64_t mirror_version = 0;
-    uint32_t mirror_modes = 0;                // which surfaces that copy holds: 1 mirrors, 2 glass, 4 glossy (WfMirror, rwr_internal.h)
-    DeviceBuffer<unsigned long long> d_glass_counts;   // RWR_FLAG_GLASS: reflected, transmitted, totally reflected; RWR_FLAG_GLOSSY: then the glossy rays; zeroed per frame
+    // RWR_FLAG_MIRRORS, _GLASS, _GLOSSY, allocated by the first frame with one of them: this slot's copy of the surface table
+    // (WfSurfaces::table), the pinned image it is copied from on the slot's stream, the event behind that copy (the image is not
+    // rewritten before it), and the context's surface_version the copy holds (0: none)
+    DeviceBuffer<SurfaceRec> d_surface;
+    PinnedSurface h_surface;
+    size_t h_surface_count = 0;
+    OwnedEvent surface_copied;
+    uint64_t surface_version = 0;
+    uint32_t surface_modes = 0;                // which surfaces that copy holds: 1 mirrors, 2 glass, 4 glossy (surface_mode, rwr_surface.h)
+    DeviceBuffer<unsigned long long> d_surface_events;   // RWR_FLAG_GLASS, _GLOSSY: the frame's kEventNone counters by SurfaceEvent (WfSurfaces::events); zeroed per frame
 };
 
 // Progressive accumulation (RWR_FLAG_ACCUMULATE): ONE accumulation per context.  Its sums and the first frame's sample-0 planes
@@ -351,10 +321,10 @@ struct rwr_context {
     rwr_sphere_buffer_data spheres[RWR_MAX_SPHERES]{};
     uint32_t n_spheres = 0;
     // RWR_FLAG_MIRRORS (rwr_scene_set_part_mirror / _sphere_mirror): {r, g, b, on} per scene part (one entry per st_materials
-    // entry) and per sphere index; mirror_version counts their changes, a WfState's table is refreshed when it lags behind
-    std::vector<rwr::MirrorRec> part_mirrors;
-    rwr::MirrorRec sphere_mirrors[RWR_MAX_SPHERES]{};
-    uint64_t mirror_version = 1;
+    // entry) and per sphere index; surface_version counts their changes, a WfState's table is refreshed when it lags behind
+    std::vector<rwr::SurfaceRec> part_surfaces;
+    rwr::SurfaceRec sphere_surfaces[RWR_MAX_SPHERES]{};
+    uint64_t surface_version = 1;
     rwr_triangle_buffer_data triangles[RWR_MAX_TRIANGLES]{};
     uint32_t n_triangles = 0;
 
@@ -363,7 +333,7 @@ struct rwr_context {
 
     uint64_t last_primary = 0, last_bounce = 0;
     bool last_shadows = false;      // the last render call traced shadow rays (RWR_FLAG_SHADOWS): their counters are in its WfState
-    bool last_gloss = false;        // the last render call ran the glossy forms (RWR_FLAG_GLOSSY): their counter is the fourth of d_glass_counts
+    bool last_gloss = false;        // the last render call ran the glossy forms (RWR_FLAG_GLOSSY): their counter is d_surface_events[kEventGlossy]
     bool last_glass = false;        // the last render call ran the glass forms (RWR_FLAG_GLASS): their counters are in its WfState
     // optional per-kernel timing (rwr_ctx_set_kernel_timing)
     uint32_t timing_every = 0;
@@ -417,8 +387,8 @@ inline uint64_t instanced_faces(uint64_t n_faces, uint32_t n_instances) { return
 inline uint32_t surface_modes(const rwr_context *ctx)
 {
     uint32_t modes = 0;
-    for (const MirrorRec &m : ctx->part_mirrors) modes |= surface_mode(surface_model(m));
-    for (uint32_t i = 0; i < ctx->n_spheres; i++) modes |= surface_mode(surface_model(ctx->sphere_mirrors[i]));
+    for (const SurfaceRec &m : ctx->part_surfaces) modes |= surface_mode(surface_model(m));
+    for (uint32_t i = 0; i < ctx->n_spheres; i++) modes |= surface_mode(surface_model(ctx->sphere_surfaces[i]));
     return modes;
 }
 

@@ -500,8 +500,8 @@ RWR_DEV f3 reflect_direction(f3 n, f3 D)
 // hit_exit_point builds; D: the direction of the ray that found the hit, of any length; face / ndotd: a face hit decides its side
 // by the winner's stored N.D (n is flipped towards the ray already), a sphere hit by dot3(n, Dh); u: the generation's first
 // random number (unused under total internal reflection).  m: the side the next ray starts on, its origin is P + 1e-4 m.
-// Returns the event: 0 reflected, 1 transmitted, 2 totally reflected.  f32 operations in this order, no contraction; selects, no
-// branches.
+// Returns the event (rwr_surface.h SurfaceEvent): reflected, transmitted or totally reflected.  f32 operations in this order, no
+// contraction; selects, no branches.
 RWR_DEV uint32_t refract_or_reflect(f3 n, f3 D, bool face, float ndotd, float eta, float u, f3 &D1, f3 &m)
 {
     const f3 Dh = normalize3(D);
@@ -521,7 +521,7 @@ RWR_DEV uint32_t refract_or_reflect(f3 n, f3 D, bool face, float ndotd, float et
     const float a = reflect ? 1.0f : e, b = reflect ? 2.0f * c : e * c - ct;
     D1 = mk3(a * Dh.x + b * nf.x, a * Dh.y + b * nf.y, a * Dh.z + b * nf.z);
     m = reflect ? nf : neg3(nf);
-    return tir ? 2u : reflect ? 0u : 1u;
+    return tir ? kEventTotalReflection : reflect ? kEventReflected : kEventTransmitted;
 }
 
 // RWR_FLAG_GLOSSY: the ray that leaves a hit on a glossy surface of roughness rho (rwr_hip.h, RWR_FLAG_GLOSSY items 1-5) — between

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/rwr_hip.h"
+#include "rwr_surface.h"
 
 namespace rwr {
 
@@ -357,26 +358,6 @@ struct WfSky {
     float zr, zg, zb, hr, hg, hb;   // zenith, horizon: rwr_sky_params' six floats in its order (plain members, no arrays: they stay registers)
 };
 static_assert(sizeof(WfSky) == sizeof(rwr_sky_params), "WfSky is rwr_sky_params");
-// Mirror surfaces (RWR_FLAG_MIRRORS; the MIRROR forms of k_wf_primary and of the trace kernels' EMIT forms): the surface table —
-// one record {reflectance r, g, b, on} per scene part, then one per sphere index (RWR_MAX_SPHERES of them); on != 0: the surface
-// is a mirror.  A kernel argument of its own behind the others (cf. WfSky), so that MaterialRec and ShadeRec stay as they are and
-// the kernels without the flag keep their code.  Part 0's record sits at the table's start: the kernels read it at a constant
-// index — a wave-uniform address, scalar registers — and a one-part scene needs no other for its faces and never looks at
-// ShadeRec::material; spheres and the faces of a scene with several parts read their records per lane.
-// Glass surfaces (RWR_FLAG_GLASS; the glass forms of the same kernels, SURF = 2) share the table: on > 0 marks a mirror, on < 0
-// glass of index -on and tint r, g, b.  A slot's copy holds the surfaces of the flags its frame has, the others' records are
-// zero there, so no kernel looks at a flag.  glass_counts: the frame's three event counters (reflected, transmitted, totally
-// reflected), one atomic per wave; null in the mirror forms.
-// Glossy surfaces (RWR_FLAG_GLOSSY; the glossy forms, SURF = 3) share it too: on = 1 + roughness, in (1, 2], marks a glossy surface
-// of reflectance r, g, b — on == 1 stays a mirror.  Their one counter, the glossy rays emitted, is glass_counts[3], behind the
-// three glass counters (four are allocated whenever any is).
-struct WfMirror {
-    const float4 *table;
-    uint32_t n_parts;
-    uint32_t pad;
-    unsigned long long *glass_counts;
-};
-constexpr int kSurfNone = 0, kSurfMirrors = 1, kSurfGlass = 2, kSurfGloss = 3;   // the kernels' SURF argument: no table, mirrors alone, mirrors and glass, those and glossy
 // What the kernels of one launch group know: the four argument structs above — all zero where the frame lacks the flag, and that
 // is what the kernels then get — and the switches the launchers pick the kernels' forms by.  render_wavefront.cpp fills it once per launch
 // group; `emit` and `emits` change per generation (a generation that is not the path's last: the trace kernels' EMIT forms).
@@ -384,7 +365,7 @@ struct WfFeatures {
     WfEmit emit{nullptr, 0u, 0u};
     WfShadow shadow{nullptr, nullptr, nullptr};
     WfSky sky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    WfMirror mirror{nullptr, 0u, 0u, nullptr};
+    WfSurfaces surfaces{nullptr, 0u, 0u, nullptr};   // rwr_surface.h
     bool emits = false, shadows = false, sky_on = false;
     bool soft = false;   // RWR_FLAG_SOFT_SHADOWS: k_wf_shadow's SOFT forms (no other kernel looks)
     int surf = kSurfNone;   // the surface models of the frame's flags (kSurfGlass: the table may hold glass records; kSurfGloss: glossy ones too)
@@ -436,7 +417,7 @@ hipError_t launch_primary_p2(hipStream_t s, const FrameParams &fp, const TriReco
                              bool *lean = nullptr);
 // grid rows the fused form puts in front of the frame's strips for `n_blocks` record-making workgroups
 uint32_t primary_p2_fused_rows(const FrameParams &fp, uint32_t n_blocks);
-// ft (WfFeatures): ft.shadows — the SHADOW forms, which read ft.shadow; ft.primary_surf(fp) — SURF, the forms that read ft.mirror
+// ft (WfFeatures): ft.shadows — the SHADOW forms, which read ft.shadow; ft.primary_surf(fp) — SURF, the forms that read ft.surfaces
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg,
                              const WfBuffers &wf, uint32_t sample_begin, uint32_t sample_count, uint32_t z_split, const WfFeatures &ft);

@@ -1,0 +1,150 @@
+// The surface table of the path tracer (RWR_FLAG_MIRRORS, _GLASS, _GLOSSY): its record, the one statement of what the record's
+// `on` field means, the one decode the kernels read it with, its fetch and the event counters.  Host and device share this header;
+// the host half compiles without HIP (tests/surface_host.cpp).
+#pragma once
+
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define RWR_HD __host__ __device__
+#else
+#define RWR_HD
+#endif
+
+namespace rwr {
+
+// A surface's record, 16 bytes of WfSurfaces::table: r, g, b and the surface's model in `on`.
+struct SurfaceRec { float r, g, b, on; };
+static_assert(sizeof(SurfaceRec) == 16, "SurfaceRec is a float4");
+
+// The one statement of SurfaceRec::on.  A surface has one model:
+//   kDiffuse  on = 0               neither of the others (r, g, b are zero)
+//   kMirror   on = 1               reflectance r, g, b (RWR_FLAG_MIRRORS)
+//   kGlass    on = -ior            tint r, g, b; ior in [1, 4] (RWR_FLAG_GLASS)
+//   kGloss    on = 1 + roughness   reflectance r, g, b; roughness in [2^-10, 1], a multiple of 2^-23 once stored (RWR_FLAG_GLOSSY)
+// Invariant: every record a setter can write (scene.cpp, through the makers below) has on in {0} U {1} U [-4, -1] U [1 + 2^-10, 2].
+// So `on == 1` and `on > 0 && !(on > 1)` name the same records, and so do `on > 1` and `on >= 1 + 2^-10`: whichever comparison
+// decode_surface uses for a kernel's SURF, it agrees with surface_model (the static_asserts below at the ranges' ends,
+// tests/test_surface_decode_host.py on every storable value).
+enum class SurfaceModel { kDiffuse, kMirror, kGlass, kGloss };
+RWR_HD constexpr SurfaceModel surface_model(const SurfaceRec &m)
+{
+    return m.on > 1.0f ? SurfaceModel::kGloss : m.on > 0.0f ? SurfaceModel::kMirror : m.on < 0.0f ? SurfaceModel::kGlass : SurfaceModel::kDiffuse;
+}
+constexpr float kGlassIorMin = 1.0f, kGlassIorMax = 4.0f, kGlossRoughnessMin = 0x1p-10f, kGlossRoughnessMax = 1.0f;
+constexpr SurfaceRec kDiffuseRec{0.0f, 0.0f, 0.0f, 0.0f};
+// the record makers: rgb in [0, 1] each, ior and roughness in the ranges above (the setters refuse anything else before they call)
+inline SurfaceRec mirror_rec(const float rgb[3]) { return SurfaceRec{rgb[0], rgb[1], rgb[2], 1.0f}; }
+inline SurfaceRec glass_rec(const float rgb[3], float ior) { return SurfaceRec{rgb[0], rgb[1], rgb[2], -ior}; }
+inline SurfaceRec gloss_rec(const float rgb[3], float roughness) { return SurfaceRec{rgb[0], rgb[1], rgb[2], 1.0f + roughness}; }
+// ... and what a glass record holds of its ior, a glossy one of its roughness (a diffuse record: 0)
+RWR_HD constexpr float surface_param(const SurfaceRec &m) { return m.on < 0.0f ? -m.on : m.on > 1.0f ? m.on - 1.0f : 0.0f; }
+// A model's bit in the words that say which models a table holds (WfState::surface_modes): 1 mirrors, 2 glass, 4 glossy
+RWR_HD constexpr uint32_t surface_mode(SurfaceModel s)
+{
+    return s == SurfaceModel::kMirror ? 1u : s == SurfaceModel::kGlass ? 2u : s == SurfaceModel::kGloss ? 4u : 0u;
+}
+// What a frame's copy of the table holds of a record: a surface whose flag the frame lacks (`modes`: surface_mode bits) is the
+// diffuse surface it was.  So no kernel looks at a flag.
+RWR_HD constexpr SurfaceRec visible_record(const SurfaceRec &m, uint32_t modes)
+{
+    return (modes & surface_mode(surface_model(m))) ? m : kDiffuseRec;
+}
+
+// The kernels' SURF argument, the surface models of the frame's flags: no table, mirrors alone, mirrors and glass, those and glossy.
+// A form decodes only what visible_record leaves of the models it knows.
+constexpr int kSurfNone = 0, kSurfMirrors = 1, kSurfGlass = 2, kSurfGloss = 3;
+
+// What a kernel reads of a record's `on`: which model the surface has, a glass surface's index, a glossy one's roughness.
+struct SurfaceDecode {
+    bool mirror, glass, gloss;
+    float eta, rho;   // 0 where the surface is not glass / not glossy
+};
+template <int SURF>
+RWR_HD constexpr SurfaceDecode decode_surface(float on)
+{
+    const bool gloss = SURF == kSurfGloss && on > 1.0f;   // (1 + roughness, in (1, 2]; the other forms never see one)
+    const bool mirror = SURF == kSurfNone || SURF == kSurfMirrors ? on != 0.0f : on > 0.0f && !gloss;
+    const bool glass = (SURF == kSurfGlass || SURF == kSurfGloss) && on < 0.0f;
+    return SurfaceDecode{mirror, glass, gloss, glass ? -on : 0.0f, gloss ? on - 1.0f : 0.0f};
+}
+// decode_surface<SURF> names the model and the parameter that surface_model and surface_param do, on a record as a frame of
+// `modes` sees it
+template <int SURF>
+RWR_HD constexpr bool decode_agrees(float on, uint32_t modes)
+{
+    const SurfaceRec v = visible_record(SurfaceRec{0.0f, 0.0f, 0.0f, on}, modes);
+    const SurfaceDecode d = decode_surface<SURF>(v.on);
+    const SurfaceModel s = surface_model(v);
+    return d.mirror == (s == SurfaceModel::kMirror) && d.glass == (s == SurfaceModel::kGlass) && d.gloss == (s == SurfaceModel::kGloss) &&
+           (d.glass ? d.eta : d.gloss ? d.rho : 0.0f) == surface_param(v) && (d.glass || d.eta == 0.0f) && (d.gloss || d.rho == 0.0f);
+}
+template <int SURF>
+RWR_HD constexpr bool decode_agrees_at_ends(uint32_t modes)
+{
+    return decode_agrees<SURF>(0.0f, modes) && decode_agrees<SURF>(1.0f, modes) && decode_agrees<SURF>(-kGlassIorMin, modes) &&
+           decode_agrees<SURF>(-kGlassIorMax, modes) && decode_agrees<SURF>(1.0f + kGlossRoughnessMin, modes) &&
+           decode_agrees<SURF>(1.0f + kGlossRoughnessMax, modes);
+}
+static_assert(decode_agrees_at_ends<kSurfMirrors>(1u), "the mirror forms decode what surface_model states");
+static_assert(decode_agrees_at_ends<kSurfGlass>(2u) && decode_agrees_at_ends<kSurfGlass>(3u), "the glass forms decode what surface_model states");
+static_assert(decode_agrees_at_ends<kSurfGloss>(4u) && decode_agrees_at_ends<kSurfGloss>(5u) && decode_agrees_at_ends<kSurfGloss>(6u) &&
+                  decode_agrees_at_ends<kSurfGloss>(7u),
+              "the glossy forms decode what surface_model states");
+
+// What a ray did at a surface that is counted: a glass hit's three outcomes (rwr_device.h refract_or_reflect returns them) and a
+// glossy hit's one.  A value is the event's index among the frame's counters, WfSurfaces::events; kEventNone is their number.
+enum SurfaceEvent : uint32_t { kEventReflected = 0u, kEventTransmitted = 1u, kEventTotalReflection = 2u, kEventGlossy = 3u, kEventNone = 4u };
+
+// The kernels' argument (the surface forms of k_wf_primary and of the trace kernels' EMIT forms): the table — one record per scene
+// part, then one per sphere index (RWR_MAX_SPHERES of them) — as the frame sees it (visible_record).  A kernel argument of its own
+// behind the others (cf. WfSky), so that MaterialRec and ShadeRec stay as they are and the kernels without a surface flag keep
+// their code.  events: the frame's kEventNone counters, one atomic per wave and event kind; null in the mirror forms, which count
+// nothing (all are allocated whenever one is).
+struct WfSurfaces {
+    const SurfaceRec *table;
+    uint32_t n_parts;
+    uint32_t pad;
+    unsigned long long *events;
+};
+
+#ifdef __HIPCC__
+// The record {r, g, b, on} of the hit `obj` (a face, or -2 - the sphere's index).  Part 0's record sits at the table's start and
+// is read at a constant index through the constant address space: a wave-uniform address, one scalar load into scalar registers,
+// and all a face of a one-part scene needs (it never looks at ShadeRec::material).  Only a sphere hit (by its index) and a face of
+// a scene with several parts (`several_parts`, by ShadeRec::material) read their record per lane, under a branch of their own, so
+// that the two reads stay two.  Shade: ShadeRec (rwr_internal.h, which includes this header).
+template <typename Shade>
+__device__ __forceinline__ float4 surface_record(const SurfaceRec *table, uint32_t n_parts, bool several_parts, const Shade *__restrict__ shade,
+                                                 int32_t obj)
+{
+    const __attribute__((address_space(4))) float *const tab = (const __attribute__((address_space(4))) float *)(table);
+    // part 0; the empty asm pins the four values to scalar registers where they are read, or the compiler folds this read into the
+    // per-lane one below (one vector load at a selected index)
+    float r0 = tab[0], r1 = tab[1], r2 = tab[2], r3 = tab[3];
+    asm volatile("" : "+s"(r0), "+s"(r1), "+s"(r2), "+s"(r3));
+    float4 m = make_float4(r0, r1, r2, r3);
+    if (obj < 0 || several_parts) {
+        const uint32_t i = obj < 0 ? n_parts + (uint32_t)(-2 - obj) : shade[obj].material;
+        m = make_float4(tab[4u * i], tab[4u * i + 1u], tab[4u * i + 2u], tab[4u * i + 3u]);
+    }
+    return m;
+}
+
+// A wave's events (two per lane: a packet's or a pixel pair's rays) into the frame's counters — ballots and popcounts, added by the
+// wave's first active lane, one atomic per event kind the wave saw.  Call where the wave's lanes have come together again.
+// GLASS: the three glass events; GLOSS (the glossy forms): the glossy rays too.
+template <bool GLOSS = false, bool GLASS = true>
+__device__ __forceinline__ void count_surface_events(unsigned long long *__restrict__ events, uint32_t ev0, uint32_t ev1 = kEventNone)
+{
+    const unsigned long long active = __ballot(true);
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (uint32_t k = GLASS ? kEventReflected : kEventGlossy; k < (GLOSS ? kEventNone : kEventGlossy); k++) {
+        const uint32_t n = (uint32_t)__popcll(__ballot(ev0 == k)) + (uint32_t)__popcll(__ballot(ev1 == k));
+        if (n && lane == (uint32_t)__builtin_ctzll(active)) atomicAdd(&events[k], (unsigned long long)n);
+    }
+}
+#endif
+
+}  // namespace rwr

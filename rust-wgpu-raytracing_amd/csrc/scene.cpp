@@ -72,8 +72,8 @@ int rwr_scene_clear(rwr_context *ctx)
     RWR_HIP_CHECK(sync_all(ctx));
     ctx->st_verts.clear(); ctx->st_faces.clear(); ctx->st_face_mat.clear(); ctx->st_materials.clear();
     ctx->d_texs.clear(); ctx->d_quads.clear(); ctx->d_nmaps.clear();
-    ctx->part_mirrors.clear();   // (a new scene: its parts are no mirrors; the sphere attributes are kept per index)
-    ctx->mirror_version++;
+    ctx->part_surfaces.clear();   // (a new scene: its parts are no mirrors; the sphere attributes are kept per index)
+    ctx->surface_version++;
     ctx->have_mesh = false;
     ctx->n_faces = ctx->n_verts = ctx->n_tris = 0;
     return RWR_OK;
@@ -144,8 +144,8 @@ int rwr_scene_add_mesh(rwr_context *ctx, const rwr_model_vertex_small *verts, ui
     M.nmap = nullptr; M.nmap_w = M.nmap_h = 0u;
     ctx->st_materials.push_back(M);
     ctx->d_nmaps.emplace_back();
-    ctx->part_mirrors.push_back(kDiffuseRec);
-    ctx->mirror_version++;
+    ctx->part_surfaces.push_back(kDiffuseRec);
+    ctx->surface_version++;
     if (mid == 0) ctx->material = *material;
     return RWR_OK;
 }
@@ -227,16 +227,16 @@ int rwr_scene_set_normal_map(rwr_context *ctx, uint32_t part, const uint8_t *rgb
 // so the twelve entry points — set and get, part and sphere, three models — are one lookup, one setter and one getter.
 
 // the record of part / sphere `index`; NULL: refused, RWR_ERR_INVALID_ARGUMENT is set
-static MirrorRec *surface_at(rwr_context *ctx, bool sphere, uint32_t index)
+static SurfaceRec *surface_at(rwr_context *ctx, bool sphere, uint32_t index)
 {
     if (!ctx) {
         set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
     } else if (sphere) {
-        if (index < RWR_MAX_SPHERES) return &ctx->sphere_mirrors[index];
+        if (index < RWR_MAX_SPHERES) return &ctx->sphere_surfaces[index];
         set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", index, RWR_MAX_SPHERES);
     } else {
-        if (index < ctx->part_mirrors.size()) return &ctx->part_mirrors[index];
-        set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", index, ctx->part_mirrors.size());
+        if (index < ctx->part_surfaces.size()) return &ctx->part_surfaces[index];
+        set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", index, ctx->part_surfaces.size());
     }
     return nullptr;
 }
@@ -245,10 +245,10 @@ static MirrorRec *surface_at(rwr_context *ctx, bool sphere, uint32_t index)
 // glass's ior, the glossy surface's roughness.  The record replaces whichever attribute the surface had.
 static int set_surface(rwr_context *ctx, bool sphere, uint32_t index, SurfaceModel model, const float *rgb, float param)
 {
-    MirrorRec *at = surface_at(ctx, sphere, index);
+    SurfaceRec *at = surface_at(ctx, sphere, index);
     if (!at) return RWR_ERR_INVALID_ARGUMENT;
     const char *what = sphere ? "sphere" : "part";
-    MirrorRec m = kDiffuseRec;
+    SurfaceRec m = kDiffuseRec;
     if (rgb) {   // (the range tests are false for NaN)
         if (model == SurfaceModel::kGlass && !(param >= kGlassIorMin && param <= kGlassIorMax))
             return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: ior %g: finite, 1 ... 4", what, index, (double)param);
@@ -262,17 +262,17 @@ static int set_surface(rwr_context *ctx, bool sphere, uint32_t index, SurfaceMod
     }
     ctx->scene_generation++;   // (a refused call never gets here: it changes nothing, the scene's generation included)
     *at = m;
-    ctx->mirror_version++;
+    ctx->surface_version++;
     return RWR_OK;
 }
 
 // is the surface of `model`, and if so its r, g, b and its parameter (zeros if not; any of the three pointers may be NULL)
 static int get_surface(rwr_context *ctx, bool sphere, uint32_t index, SurfaceModel model, int *is_model, float rgb[3], float *param)
 {
-    const MirrorRec *at = surface_at(ctx, sphere, index);
+    const SurfaceRec *at = surface_at(ctx, sphere, index);
     if (!at) return RWR_ERR_INVALID_ARGUMENT;
     const bool on = surface_model(*at) == model;
-    const MirrorRec m = on ? *at : kDiffuseRec;
+    const SurfaceRec m = on ? *at : kDiffuseRec;
     if (is_model) *is_model = on ? 1 : 0;
     if (rgb) { rgb[0] = m.r; rgb[1] = m.g; rgb[2] = m.b; }
     if (param) *param = surface_param(m);
