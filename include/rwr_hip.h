@@ -417,7 +417,7 @@ enum {
                                           other flag, instances, parts, frames in flight, row bands, strips and the multi-GPU gather keep
                                           their contracts.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED, whatever max_bounces is and whether or not a surface is glossy. */
-    RWR_FLAG_SOFT_SHADOWS = 1u << 14 /* extension: soft shadows — RWR_FLAG_SHADOWS' two lights get a finite angular size
+    RWR_FLAG_SOFT_SHADOWS = 1u << 14, /* extension: soft shadows — RWR_FLAG_SHADOWS' two lights get a finite angular size
                                        (rwr_shadow_set_params), so that shadow edges become penumbrae: sharp at the contact, wide far
                                        from the occluder.  The radius r of a light is the tangent of the half-angle under which a hit
                                        sees it (0: the point light at infinity; 0.0047: the sun).  Without the flag every frame is what
@@ -451,6 +451,40 @@ enum {
                                           anew.  RNG keys are global pixel and global sample: frames in flight, row bands, strips, the
                                           multi-GPU gather and every schedule give the same bytes; every other flag keeps its contract.
                                           With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
+    RWR_FLAG_EMISSIVE = 1u << 15    /* extension: emissive surfaces — a scene part or a sphere that gives off light of radiance Le
+                                       (rwr_scene_set_part_emission, rwr_scene_set_sphere_emission), so that a scene can hold its own
+                                       lamps.  Emission is an attribute beside the surface model, not a model: a diffuse, mirror, glass
+                                       or glossy surface may also emit, and the setters of one never touch the other.  Without the flag
+                                       every frame is what it was, byte for byte.
+                                       1. With the flag and at least one emitting surface in the scene, the local shading of every hit h
+                                          the integrator shades — h0 and the hit of every bounce ray — becomes E'(h) = E(h) + Le(h): per
+                                          channel one f32 add to the value the shader produced (after the normal map, where that is on).
+                                          With RWR_FLAG_SHADOWS an occluded hit's shading is ambient(h) + Le(h): a surface's own light is
+                                          never shadowed.  Term k is then, as without the flag, T(k-1) * E'(h_k) with T(-1) = 1,
+                                          converted and capped as ever — [0, 16] at h0, [0, 64] later, NaN as 0: the sum first, then the
+                                          product with T, then the conversion, no contraction.  Le goes inside the clamps, so the range of
+                                          every fixed-point sum is what it was.
+                                       2. Both sides of a face emit; a sphere emits inwards as well as outwards.
+                                       3. Nothing else moves.  Primary, bounce and shadow rays, throughputs, RNG dimensions, the
+                                          nearest-hit rule, rwr_last_render_stats, rwr_last_shadow_stats, rwr_last_glass_stats,
+                                          rwr_last_gloss_stats, rwr_last_traversal_plan and the depth, id and t planes are those of the
+                                          frame without the flag, bit for bit.  A shadow record carries fix(T (E + Le)) - fix(T (amb + Le)).
+                                       4. A frame with the flag and an emitter always takes the integrator, also at spp 1 and
+                                          max_bounces 0, as with RWR_FLAG_SHADOWS; samples are placed as without the flag.  Unlike the
+                                          surface flags it is not cleared at max_bounces 0: an emitter shows at h0.
+                                       5. No part of the scene and none of its spheres (indices below the count rwr_scene_set_spheres
+                                          gave) emits: the flag is ignored — cleared before the frame's kernels are chosen — and the frame
+                                          is the frame without it, byte for byte, in the same kernels (the flag alone at spp 1 without a
+                                          bounce: the reference frame).
+                                       6. The bit (after item 5) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
+                                          effective flags; every accepted call of the emission setters changes the scene's generation, a
+                                          refused one changes nothing.  rwr_last_emission_stats counts the shaded hits with Le != 0.
+                                       7. Accumulation, frames in flight, row bands, strips and the multi-GPU gather keep their
+                                          contracts; RWR_FLAG_DENOISE and RWR_FLAG_REPROJECT are stages behind the resolve and do not know.
+                                       8. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED,
+                                          whatever the scene holds.
+                                       No ray is aimed at an emitter (no next-event estimation): a small lamp is found by chance and
+                                       its light is noisy at low sample counts. */
 };
 
 #define RWR_MAX_BOUNCES 8u
@@ -561,6 +595,19 @@ RWR_API int rwr_scene_set_part_gloss(rwr_context *ctx, uint32_t part, const floa
 RWR_API int rwr_scene_set_sphere_gloss(rwr_context *ctx, uint32_t sphere, const float *reflectance, float roughness);
 RWR_API int rwr_scene_get_part_gloss(rwr_context *ctx, uint32_t part, int *is_glossy, float reflectance[3], float *roughness);
 RWR_API int rwr_scene_get_sphere_gloss(rwr_context *ctx, uint32_t sphere, int *is_glossy, float reflectance[3], float *roughness);
+
+/* RWR_FLAG_EMISSIVE: the emission attribute of a scene part or of a sphere index, with the mirror attribute's index and reset rules
+ * (part < rwr_scene_part_count, reset by a new scene; sphere < RWR_MAX_SPHERES, kept per index whatever rwr_scene_set_spheres
+ * holds).  radiance: 3 floats, each finite and in [0, RWR_MAX_EMISSION]; NULL or 0, 0, 0 = does not emit (-0.0 is kept as 0).
+ * Anything else, NaN and inf included: RWR_ERR_INVALID_ARGUMENT and the old state stays.  Emission stands beside the surface's
+ * model: these setters leave the mirror, glass and gloss attributes alone, and those setters leave the emission alone.  Every
+ * accepted call changes the scene's generation, also one that sets the value the surface already has.  The getters return
+ * *emits = 0 / 1 and the radiance (zeros for a surface that does not emit); every output may be NULL. */
+#define RWR_MAX_EMISSION 64.0f
+RWR_API int rwr_scene_set_part_emission(rwr_context *ctx, uint32_t part, const float *radiance);
+RWR_API int rwr_scene_set_sphere_emission(rwr_context *ctx, uint32_t sphere, const float *radiance);
+RWR_API int rwr_scene_get_part_emission(rwr_context *ctx, uint32_t part, int *emits, float radiance[3]);
+RWR_API int rwr_scene_get_sphere_emission(rwr_context *ctx, uint32_t sphere, int *emits, float radiance[3]);
 
 /* Replaces Sphere::new's uniform, one per analytic sphere pass, composited in
  * array order before the mesh (src/lib.rs:532-534, 1106-1173).  n <= RWR_MAX_SPHERES. */
@@ -789,6 +836,11 @@ RWR_API int rwr_last_glass_stats(rwr_context *ctx, uint64_t *reflected, uint64_t
  * frame the flag did nothing to).  An exact count.  Waits for the frame, as rwr_last_render_stats does.  A NULL argument is
  * RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_last_gloss_stats(rwr_context *ctx, uint64_t *glossy_rays);
+
+/* RWR_FLAG_EMISSIVE: the shaded hits of the last render call that lay on a surface with Le != 0 — h0 and every bounce hit, over all
+ * samples the call traced (an accumulating frame: its own samples; zero for a frame the flag did nothing to).  An exact count.
+ * Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_last_emission_stats(rwr_context *ctx, uint64_t *emissive_hits);
 
 /* Progressive accumulation (RWR_FLAG_ACCUMULATE).  One context holds one accumulation.
  * rwr_accum_reset: the next accumulating frame starts over at N = 0 (host-side only, nothing waits).

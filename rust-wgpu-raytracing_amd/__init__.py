@@ -55,6 +55,8 @@ FLAG_GLASS = 1 << 11         # parts and spheres marked as glass reflect by Fres
 FLAG_REPROJECT = 1 << 12     # temporal reprojection of the context's history while the camera moves; implies FLAG_AUX_OUTPUTS (include/rwr_hip.h)
 FLAG_GLOSSY = 1 << 13        # parts and spheres marked as glossy send on a ray between the mirror reflection and the diffuse ray (include/rwr_hip.h)
 FLAG_SOFT_SHADOWS = 1 << 14  # FLAG_SHADOWS' two lights get an angular size: penumbrae (include/rwr_hip.h)
+FLAG_EMISSIVE = 1 << 15      # parts and spheres with an emission (set_part_emission, set_sphere_emission) give off light (include/rwr_hip.h)
+MAX_EMISSION = 64.0          # RWR_MAX_EMISSION: the largest component of a radiance
 SHADOW_PARAMS_DTYPE = np.dtype([("mesh_light_radius", "<f4"), ("sphere_light_radius", "<f4")])
 REPROJECT_PARAMS_DTYPE = np.dtype([("max_history", "<u4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
 MAX_BOUNCES = 8
@@ -137,6 +139,9 @@ def lib() -> C.CDLL:
         "rwr_scene_set_part_gloss": [vp, u32, vp, f32], "rwr_scene_set_sphere_gloss": [vp, u32, vp, f32],
         "rwr_scene_get_part_gloss": [vp, u32, vp, vp, vp], "rwr_scene_get_sphere_gloss": [vp, u32, vp, vp, vp],
         "rwr_last_gloss_stats": [vp, vp],
+        "rwr_scene_set_part_emission": [vp, u32, vp], "rwr_scene_set_sphere_emission": [vp, u32, vp],
+        "rwr_scene_get_part_emission": [vp, u32, vp, vp], "rwr_scene_get_sphere_emission": [vp, u32, vp, vp],
+        "rwr_last_emission_stats": [vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
         "rwr_load_model_compute": [C.c_char_p, C.c_char_p, vp], "rwr_model_free": [vp],
         "rwr_model_info": [vp, vp, vp, vp, vp, vp, vp], "rwr_scene_upload_model": [vp, vp],
@@ -160,7 +165,8 @@ def lib() -> C.CDLL:
                            "rwr_reproject_set_params", "rwr_reproject_get_params", "rwr_reproject_reset", "rwr_reproject_frames",
                            "rwr_last_reproject_stats", "rwr_reproject_readback", "rwr_scene_set_part_gloss", "rwr_scene_set_sphere_gloss",
                            "rwr_scene_get_part_gloss", "rwr_scene_get_sphere_gloss", "rwr_last_gloss_stats",
-                           "rwr_shadow_set_params", "rwr_shadow_get_params")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_shadow_set_params", "rwr_shadow_get_params", "rwr_scene_set_part_emission", "rwr_scene_set_sphere_emission",
+                           "rwr_scene_get_part_emission", "rwr_scene_get_sphere_emission", "rwr_last_emission_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -553,6 +559,45 @@ class Context:
         """The rays the glossy hits of the last render call sent on (rwr_last_gloss_stats)."""
         a = C.c_uint64(0)
         _check(lib().rwr_last_gloss_stats(self._h, C.byref(a)))
+        return int(a.value)
+
+    @staticmethod
+    def _radiance(radiance):
+        if radiance is None:
+            return None
+        r = np.ascontiguousarray(radiance, dtype=np.float32)
+        if r.shape != (3,):
+            raise ValueError("radiance: three floats, or None")
+        return r
+
+    def set_part_emission(self, part: int, radiance=(1.0, 1.0, 1.0)):
+        """FLAG_EMISSIVE: scene part `part` gives off light of this radiance (three floats in [0, MAX_EMISSION]); None or zeros: it
+        does not emit.  Out of range, NaN or inf: RwrError(ERR_INVALID_ARGUMENT), and the old state stays.  The part's mirror,
+        glass or gloss attribute is left alone (rwr_scene_set_part_emission)."""
+        _check(lib().rwr_scene_set_part_emission(self._h, part, _p(self._radiance(radiance))))
+
+    def set_sphere_emission(self, sphere: int, radiance=(1.0, 1.0, 1.0)):
+        """FLAG_EMISSIVE: the sphere of index `sphere` (< 8, kept whatever set_spheres holds) gives off light; None or zeros: it does not."""
+        _check(lib().rwr_scene_set_sphere_emission(self._h, sphere, _p(self._radiance(radiance))))
+
+    def _get_emission(self, fn, index: int):
+        on = C.c_int(0)
+        r = np.zeros(3, np.float32)
+        _check(fn(self._h, index, C.byref(on), _p(r)))
+        return r if on.value else None
+
+    def get_part_emission(self, part: int):
+        """The part's radiance, float32[3], when it emits, else None (rwr_scene_get_part_emission)."""
+        return self._get_emission(lib().rwr_scene_get_part_emission, part)
+
+    def get_sphere_emission(self, sphere: int):
+        """The sphere index's radiance, float32[3], when it emits, else None (rwr_scene_get_sphere_emission)."""
+        return self._get_emission(lib().rwr_scene_get_sphere_emission, sphere)
+
+    def last_emission_stats(self):
+        """The shaded hits of the last render call that lay on an emitting surface (rwr_last_emission_stats)."""
+        a = C.c_uint64(0)
+        _check(lib().rwr_last_emission_stats(self._h, C.byref(a)))
         return int(a.value)
 
     def set_triangles(self, triangles):

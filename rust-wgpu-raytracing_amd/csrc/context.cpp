@@ -460,6 +460,19 @@ int rwr_last_gloss_stats(rwr_context *ctx, uint64_t *glossy_rays)
     return RWR_OK;
 }
 
+int rwr_last_emission_stats(rwr_context *ctx, uint64_t *emissive_hits)
+{
+    if (!ctx || !emissive_hits) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    unsigned long long count = 0ull;
+    if (ctx->last_glow && ctx->wf_state[ctx->last_wf_state].d_glow_hits.ptr) {
+        DeviceGuard g(ctx->device);
+        RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
+        RWR_HIP_CHECK(hipMemcpy(&count, ctx->wf_state[ctx->last_wf_state].d_glow_hits.ptr, sizeof count, hipMemcpyDeviceToHost));
+    }
+    *emissive_hits = count;
+    return RWR_OK;
+}
+
 int rwr_denoise_set_params(rwr_context *ctx, const rwr_denoise_params *params)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");

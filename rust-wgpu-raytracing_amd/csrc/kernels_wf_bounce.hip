@@ -342,10 +342,14 @@ RWR_DEV uint32_t emit_from_surface(const FrameParams &p, const WfBuffers &wf, co
 // clamp(T * E(h)), decided by the hit's shadow ray.  The ambient value goes into the sums here, the record for k_wf_shadow
 // (origin = the next bounce ray's, the light of the shader that shades h, the difference of the two fixed-point values) into
 // the hit's slot, its bit into the shadow ballots (cleared before the generation).
+// GLOW forms: e1 comes with the surface's radiance added, and `le` — that radiance — is added to the ambient part here: ambient(h) + Le(h).
+template <bool GLOW = false>
 RWR_DEV void shadow_hit(TraceShared &sh, const FrameParams &p, const WfBuffers &wf, const WfShadow &sw, const TriRecord *__restrict__ tris,
-                        const ShadeRec *__restrict__ shade, uint32_t tile, uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr, f3 e1)
+                        const ShadeRec *__restrict__ shade, uint32_t tile, uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr, f3 e1,
+                        f3 le = f3{})
 {
-    const f3 amb = hit_ambient(p, shade, obj);
+    f3 amb = hit_ambient(p, shade, obj);
+    if (GLOW) amb = mk3(amb.x + le.x, amb.y + le.y, amb.z + le.z);
     const float cf[3] = {thr.x * e1.x, thr.y * e1.y, thr.z * e1.z}, ca[3] = {thr.x * amb.x, thr.y * amb.y, thr.z * amb.z};
     uint32_t ff[3], fa[3];
 #pragma unroll
@@ -368,6 +372,17 @@ RWR_DEV void add_sky(TraceShared &sh, const WfSky &sky, uint32_t e, float dy, f3
     const float s2 = sky.hb + (sky.zb - sky.hb) * u;
     // (a black sky adds nothing at all: add_fixed skips zeros)
     add_fixed(sh, e, (uint32_t)(thr.x * s0 * kWfFixedScale), (uint32_t)(thr.y * s1 * kWfFixedScale), (uint32_t)(thr.z * s2 * kWfFixedScale));
+}
+
+// GLOW forms (RWR_FLAG_EMISSIVE): the local shading of the hit `obj` becomes E'(h) = E(h) + Le(h), Le the radiance of the hit's
+// surface (rwr_surface.h glow_record) — one f32 add per channel to the shader's value, ahead of the product with the throughput.
+// le: that radiance, for shadow_hit's ambient part.  Returns whether the surface emits (count_glow_hits).
+RWR_DEV bool add_glow(const FrameParams &p, const WfGlow &gl, const ShadeRec *__restrict__ shade, int32_t obj, f3 &e1, f3 &le)
+{
+    const float4 g = glow_record(gl, p.n_materials > 1u, shade, obj);
+    le = mk3(g.x, g.y, g.z);
+    e1 = mk3(e1.x + g.x, e1.y + g.y, e1.z + g.z);
+    return glows(g);
 }
 
 // The trace kernels are PERSISTENT: kWfTraceGroups workgroups pull work items — (pool of the class, share of it)
@@ -421,14 +436,16 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // SURF: which surface models the EMIT form knows — kSurfNone, kSurfMirrors (RWR_FLAG_MIRRORS alone: the MIRROR forms), kSurfGlass
 // (RWR_FLAG_GLASS, with or without mirrors: a hit on glass sends on a reflected or a refracted ray with T * C and is counted) or
 // kSurfGloss (RWR_FLAG_GLOSSY, with or without the other two: a glossy hit sends on gloss_direction's ray with T * R and is counted).
+// GLOW: RWR_FLAG_EMISSIVE — a hit's local shading gets the radiance of its surface added (add_glow) and the emitting hits are
+// counted; of the forms that end a path as of the EMIT forms; separate instantiations for the same reason.
 // Which combinations exist, and how launch_wf_bounce picks one: LaneForms and PacketForms below, behind the kernels.
 template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false, bool SKY = false,
-          int SURF = kSurfNone>
+          int SURF = kSurfNone, bool GLOW = false>
 __global__ void __launch_bounds__(WIDE ? 1024 : 256)
 k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                 const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                 uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
-                const WfSky sky, const WfSurfaces sf)
+                const WfSky sky, const WfSurfaces sf, const WfGlow gl)
 {
     static_assert(EMIT || SURF == kSurfNone, "only a kernel that emits rays has a MIRROR or a glass form");
     constexpr bool MIRROR = SURF != kSurfNone;
@@ -492,10 +509,12 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                 if (mh.have && (!have || mh.t < best_t)) { have = true; best_t = mh.t; obj = (int32_t)mh.idx; }
             }
             uint32_t event = kEventNone;   // glass and glossy forms: what a counted hit did
+            bool lit = false;              // GLOW forms: the hit's surface emits
             if (have) {
                 const Shaded s1 = shade_winner<NMAP>(p, obj, best_t, mh.u, mh.v, mh.ndotd, shade, tex, O, D);
-                const f3 e1 = s1.colour;
-                if (SHADOW) shadow_hit(sh, p, wf, sw, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, e1);
+                f3 e1 = s1.colour, le = f3{};
+                if (GLOW) lit = add_glow(p, gl, shade, obj, e1, le);
+                if (SHADOW) shadow_hit<GLOW>(sh, p, wf, sw, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, e1, le);
                 else add_contribution(sh, e, thr.x * e1.x, thr.y * e1.y, thr.z * e1.z);
                 if (EMIT && !MIRROR)
                     emit_next_ray(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd,
@@ -505,6 +524,7 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                 add_sky(sh, sky, e, D.y, thr);
             }
             if (SURF == kSurfGlass || SURF == kSurfGloss) count_surface_events<SURF == kSurfGloss>(sf.events, event);
+            if (GLOW) count_glow_hits(gl.hits, lit);
             if (EMIT) {   // rays written for the next generation (lanes past the pool's end have left the iteration)
                 const unsigned long long em = __ballot(have);
                 if (em && (tid & 63u) == (uint32_t)__builtin_ctzll(em)) atomicAdd(&wf.wave_total[tile * 4u], (uint32_t)__popcll(em));
@@ -599,12 +619,12 @@ RWR_DEV i2 sphere_pair_intersect_t(f3 center, float radius, v3 O, v3 D, f2 &t_ou
 #ifndef RWR_GLOSS_SKY_PACKET_OCC
 #define RWR_GLOSS_SKY_PACKET_OCC 3
 #endif
-template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false, int SURF = kSurfNone>   // EMIT, SHADOW, SKY, SURF: see k_wf_trace_lane
+template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false, int SURF = kSurfNone, bool GLOW = false>   // EMIT, SHADOW, SKY, SURF, GLOW: see k_wf_trace_lane
 __global__ void __launch_bounds__(256, (SURF == kSurfGloss && SKY && !SHADOW) ? RWR_GLOSS_SKY_PACKET_OCC : RWR_PACKET_OCC)
 k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                   uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
-                  const WfSky sky, const WfSurfaces sf)
+                  const WfSky sky, const WfSurfaces sf, const WfGlow gl)
 {
     static_assert(EMIT || SURF == kSurfNone, "only a kernel that emits rays has a MIRROR or a glass form");
     constexpr bool MIRROR = SURF != kSurfNone;
@@ -805,13 +825,26 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
                     }
                 }
             }
+            f2 lr = splat(0.0f), lg = splat(0.0f), lb = splat(0.0f);   // GLOW: Le of each ray's hit
+            if (GLOW) {   // here, where the wave's lanes are together: each ray's record, the add, the count
+                bool lit[2] = {false, false};
+#pragma unroll
+                for (int k = 0; k < 2; k++)
+                    if (k ? have.y : have.x) {
+                        f3 ek = k ? mk3(er.y, eg.y, eb.y) : mk3(er.x, eg.x, eb.x), le;
+                        lit[k] = add_glow(p, gl, shade, k ? obj.y : obj.x, ek, le);
+                        if (k) { er.y = ek.x; eg.y = ek.y; eb.y = ek.z; lr.y = le.x; lg.y = le.y; lb.y = le.z; }
+                        else { er.x = ek.x; eg.x = ek.y; eb.x = ek.z; lr.x = le.x; lg.x = le.y; lb.x = le.z; }
+                    }
+                count_glow_hits(gl.hits, lit[0], lit[1]);
+            }
             if (SHADOW) {   // one ray of the lane after the other
 #pragma unroll
                 for (int k = 0; k < 2; k++)
                     if (k ? have.y : have.x)
-                        shadow_hit(sh, p, wf, sw, tris, shade, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), k ? obj.y : obj.x, k ? best_t.y : best_t.x,
-                                   k ? best.ndotd.y : best.ndotd.x, k ? mk3(thr.x.y, thr.y.y, thr.z.y) : mk3(thr.x.x, thr.y.x, thr.z.x),
-                                   k ? mk3(er.y, eg.y, eb.y) : mk3(er.x, eg.x, eb.x));
+                        shadow_hit<GLOW>(sh, p, wf, sw, tris, shade, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), k ? obj.y : obj.x, k ? best_t.y : best_t.x,
+                                         k ? best.ndotd.y : best.ndotd.x, k ? mk3(thr.x.y, thr.y.y, thr.z.y) : mk3(thr.x.x, thr.y.x, thr.z.x),
+                                         k ? mk3(er.y, eg.y, eb.y) : mk3(er.x, eg.x, eb.x), k ? mk3(lr.y, lg.y, lb.y) : mk3(lr.x, lg.x, lb.x));
             } else {
             const f2 cr = thr.x * er, cg = thr.y * eg, cb = thr.z * eb;
             if (have.x) add_contribution(sh, e0, cr.x, cg.x, cb.x);
@@ -862,29 +895,34 @@ struct SortForms {
     template <uint32_t I> static constexpr Kernel kernel() { return &k_wf_sort<decode(I).list>; }
 };
 struct PacketForms {
-    struct Form { bool nmap, emit, shadow, sky; int surf; };
-    static constexpr uint32_t kRange = 16u * 4u;
-    static constexpr uint32_t encode(Form f) { return f.nmap + 2u * f.emit + 4u * f.shadow + 8u * f.sky + 16u * (uint32_t)f.surf; }
-    static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (int)(i >> 4)}; }
+    struct Form { bool nmap, emit, shadow, sky; int surf; bool glow; };
+    static constexpr uint32_t kRange = 16u * 4u * 2u;
+    static constexpr uint32_t encode(Form f) { return f.nmap + 2u * f.emit + 4u * f.shadow + 8u * f.sky + 16u * (uint32_t)f.surf + 64u * f.glow; }
+    static constexpr Form decode(uint32_t i)
+    {
+        return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (int)((i >> 4) & 3u), (i & 64u) != 0};
+    }
     static constexpr bool valid(Form f) { return f.emit || f.surf == kSurfNone; }
     using Kernel = decltype(&k_wf_trace_packet<false>);
     template <uint32_t I> static constexpr Kernel kernel()
     {
         constexpr Form f = decode(I);
-        return &k_wf_trace_packet<f.nmap, f.emit, f.shadow, f.sky, f.surf>;
+        return &k_wf_trace_packet<f.nmap, f.emit, f.shadow, f.sky, f.surf, f.glow>;
     }
 };
 // WIDE — 1 024 threads around one copy of the nodelets — only with the nodelets in LDS, 16-bit stacks and no normal map (LaneLdsPlan)
 struct LaneForms {
-    struct Form { bool nodes_in_lds, nmap, stack16, wide, emit, shadow, sky; int surf; };
-    static constexpr uint32_t kRange = 128u * 4u;
+    struct Form { bool nodes_in_lds, nmap, stack16, wide, emit, shadow, sky; int surf; bool glow; };
+    static constexpr uint32_t kRange = 128u * 4u * 2u;
     static constexpr uint32_t encode(Form f)
     {
-        return f.nodes_in_lds + 2u * f.nmap + 4u * f.stack16 + 8u * f.wide + 16u * f.emit + 32u * f.shadow + 64u * f.sky + 128u * (uint32_t)f.surf;
+        return f.nodes_in_lds + 2u * f.nmap + 4u * f.stack16 + 8u * f.wide + 16u * f.emit + 32u * f.shadow + 64u * f.sky + 128u * (uint32_t)f.surf +
+               512u * f.glow;
     }
     static constexpr Form decode(uint32_t i)
     {
-        return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (i & 16u) != 0, (i & 32u) != 0, (i & 64u) != 0, (int)(i >> 7)};
+        return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (i & 16u) != 0, (i & 32u) != 0, (i & 64u) != 0, (int)((i >> 7) & 3u),
+                    (i & 512u) != 0};
     }
     static constexpr bool valid(Form f) { return (f.emit || f.surf == kSurfNone) && (!f.wide || (f.nodes_in_lds && !f.nmap && f.stack16)); }
     static constexpr bool is_wide(Form f) { return f.wide; }
@@ -892,14 +930,16 @@ struct LaneForms {
     template <uint32_t I> static constexpr Kernel kernel()
     {
         constexpr Form f = decode(I);
-        return &k_wf_trace_lane<f.nodes_in_lds, f.nmap, f.stack16, f.wide, f.emit, f.shadow, f.sky, f.surf>;
+        return &k_wf_trace_lane<f.nodes_in_lds, f.nmap, f.stack16, f.wide, f.emit, f.shadow, f.sky, f.surf, f.glow>;
     }
 };
 static constexpr auto kSortForms = form_table<SortForms>();
 static constexpr auto kPacketForms = form_table<PacketForms>();
 static constexpr auto kLaneForms = form_table<LaneForms>();
-static_assert(check_forms<SortForms>(2) && check_forms<PacketForms>(40), "packets: NMAP x (4 path-ending + 16 EMIT forms)");
-static_assert(check_forms<LaneForms>(180) && count_forms<LaneForms>(LaneForms::is_wide) == 20, "per lane: 8 x 20 with 256 threads, 20 wide");
+// (GLOW goes with every form and adds no condition to valid(): the rule is stated beside PrimaryForms, kernels_wf_primary.hip)
+static_assert(check_forms<SortForms>(2) && check_forms<PacketForms>(80), "packets: NMAP x (4 path-ending + 16 EMIT forms), with and without GLOW");
+static_assert(check_forms<LaneForms>(360) && count_forms<LaneForms>(LaneForms::is_wide) == 40,
+              "per lane: 8 x 20 with 256 threads, 20 wide, with and without GLOW");
 
 // RWR_WF_STATS=1 (wf.dbg set): launches of the packet kernel, the per-lane kernel and its WIDE form, by this process
 static std::atomic<uint64_t> g_trace_launches[3];
@@ -927,11 +967,11 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     const int surf = ft.trace_surf();
     if (packets) {
         if (wf.dbg) g_trace_launches[0].fetch_add(1u, std::memory_order_relaxed);
-        hipLaunchKernelGGL(kPacketForms[PacketForms::encode({nmap, ft.emits, ft.shadows, ft.sky_on, surf})], dim3(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit)),
-                           dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, ft.emit, ft.shadow, ft.sky, ft.surfaces);
+        hipLaunchKernelGGL(kPacketForms[PacketForms::encode({nmap, ft.emits, ft.shadows, ft.sky_on, surf, ft.glows})], dim3(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit)),
+                           dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, ft.emit, ft.shadow, ft.sky, ft.surfaces, ft.glow);
     }
     const LaneLdsPlan l = lane_lds_plan(bvh, fp, bvh.wide_lane && !nmap);
-    const uint32_t form = LaneForms::encode({l.nodes_in_lds, nmap, l.stack16, l.wide, ft.emits, ft.shadows, ft.sky_on, surf});
+    const uint32_t form = LaneForms::encode({l.nodes_in_lds, nmap, l.stack16, l.wide, ft.emits, ft.shadows, ft.sky_on, surf, ft.glows});
     if (wf.dbg) g_trace_launches[l.wide ? 2 : 1].fetch_add(1u, std::memory_order_relaxed);
     if (plan) *plan = LanePlanRecord{plan->launches + 1u, l.nodes_in_lds, l.stack16, l.wide};
     if (l.wide) {   // (at most 146 KiB: beyond the default limit, raised per form)
@@ -941,7 +981,7 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     }
     const dim3 grid(std::min(l.wide ? 512u : kWfTraceGroups, n_tiles * kWfMaxSplit));
     hipLaunchKernelGGL(kLaneForms[form], grid, dim3(l.wide ? 1024 : 256), l.bytes, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles,
-                       ft.emit, ft.shadow, ft.sky, ft.surfaces);
+                       ft.emit, ft.shadow, ft.sky, ft.surfaces, ft.glow);
     return hipGetLastError();
 }
 

@@ -161,7 +161,8 @@ struct WfPrimaryArgs {
     Targets tg;
     WfBuffers wf;
     WfShadow sw;   // RWR_FLAG_SHADOWS (the SHADOW forms); behind the rest, so that the other forms read their arguments where they always did
-    WfSurfaces surfaces;   // RWR_FLAG_MIRRORS, _GLASS, _GLOSSY (the surface forms); last, for the same reason
+    WfSurfaces surfaces;   // RWR_FLAG_MIRRORS, _GLASS, _GLOSSY (the surface forms); behind the rest, for the same reason
+    WfGlow glow;           // RWR_FLAG_EMISSIVE (the GLOW forms); last, for the same reason
 };
 template <typename T> using kernarg = const __attribute__((address_space(4))) T;
 RWR_DEV kernarg<WfPrimaryArgs> *wf_args_again(kernarg<WfPrimaryArgs> *q)
@@ -183,7 +184,10 @@ RWR_DEV f3 ld3(kernarg<float> *q) { return mk3(q[0], q[1], q[2]); }
 // A tile without a glass hit skips that arithmetic, a tile whose emitting pixels are all specular skips the RNG disk loop.
 // kSurfGloss (RWR_FLAG_GLOSSY, with or without the other two): a glossy hit draws the diffuse direction like a diffuse one and
 // sends gloss_direction_pair's ray on with throughput R; a tile without a glossy hit skips that arithmetic.
-template <bool AUX, bool CULL, bool NMAP, bool LIST = false, bool SHADOW = false, int SURF = kSurfNone>
+// GLOW (RWR_FLAG_EMISSIVE): the radiance Le of the hit's surface (WfGlow's table, rwr_surface.h glow_record) is added to the shader's
+// E(h0) — and, under SHADOW, to its ambient part: a surface's own light is not shadowed — ahead of the conversion, one f32 add per
+// channel; the hits with Le != 0 are counted.  Rays, planes and counts are the twin's.  Forms of their own again.
+template <bool AUX, bool CULL, bool NMAP, bool LIST = false, bool SHADOW = false, int SURF = kSurfNone, bool GLOW = false>
 // (LIST — frames that show little — keeps an item loop's state on top of everything else and needs 142 registers: three waves
 // per SIMD like the AUX / NMAP forms; such a frame does not fill the chip anyway.  MIRROR does not loosen the bound: the plain
 // mirror forms hold RWR_WF_OCC waves like their twins, profiles/mirror_kernel_resources.txt)
@@ -394,6 +398,25 @@ k_wf_primary(const WfPrimaryArgs a)
             }
         }
         const i2 hit = obj != -1;
+        f2 lr = splat(0.0f), lg = splat(0.0f), lb = splat(0.0f);   // GLOW: Le(h0) of each pixel's hit
+        if (GLOW) {
+            kernarg<WfPrimaryArgs> *const qg = wf_args_again(ka);   // the emission table, the shading records
+            const WfGlow gl = {qg->glow.table, qg->glow.n_parts, 0u, qg->glow.hits};
+            const bool parts = qg->p.n_materials > 1u;
+            const ShadeRec *const shade = qg->shade;
+            const i2 seen = hit & i2{in0 ? -1 : 0, in1 ? -1 : 0};   // (a pixel off the frame is no hit anyone counts)
+            bool lit[2] = {false, false};
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                if (k ? seen.y : seen.x) {
+                    const float4 g = glow_record(gl, parts, shade, k ? obj.y : obj.x);
+                    if (k) { lr.y = g.x; lg.y = g.y; lb.y = g.z; } else { lr.x = g.x; lg.x = g.y; lb.x = g.z; }
+                    lit[k] = glows(g);
+                }
+            }
+            cr = cr + lr; cg = cg + lg; cb = cb + lb;   // E'(h0) = E(h0) + Le(h0)
+            count_glow_hits(gl.hits, lit[0], lit[1]);
+        }
         int32_t dr0 = 0, dg0 = 0, db0 = 0, dr1 = 0, dg1 = 0, db1 = 0;   // SHADOW: fix(E) - fix(ambient part) in the planes' units
         if (SHADOW) {
             // the term is a select between its ambient part and E(h0), decided by the hit's shadow ray: the ambient part is summed
@@ -411,6 +434,7 @@ k_wf_primary(const WfPrimaryArgs a)
                 if (o == -1) am = mk3(0.0f, 0.0f, 0.0f);
                 if (k) { ar.y = am.x; ag.y = am.y; ab.y = am.z; } else { ar.x = am.x; ag.x = am.y; ab.x = am.z; }
             }
+            if (GLOW) { ar = ar + lr; ag = ag + lg; ab = ab + lb; }   // the occluded hit's shading: ambient(h0) + Le(h0)
             const f2 sr = cr * kScale22, sg = cg * kScale22, sb = cb * kScale22;
             const f2 qr = ar * kScale22, qg = ag * kScale22, qb2 = ab * kScale22;
             const uint32_t F[6] = {min((uint32_t)sr.x, kCap), min((uint32_t)sg.x, kCap), min((uint32_t)sb.x, kCap),
@@ -587,20 +611,28 @@ k_wf_primary(const WfPrimaryArgs a)
 // k_wf_primary's forms (rwr_wf_forms.h).  LIST walks the list of the tiles the culling found live: only with CULL.  SHADOW goes
 // with every such (CULL, LIST) — (1, 1), (1, 0), (0, 0) — so it adds no condition of its own.
 struct PrimaryForms {
-    struct Form { bool aux, cull, nmap, list, shadow; int surf; };
-    static constexpr uint32_t kRange = 32u * 4u;
-    static constexpr uint32_t encode(Form f) { return f.aux + 2u * f.cull + 4u * f.nmap + 8u * f.list + 16u * f.shadow + 32u * (uint32_t)f.surf; }
-    static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (i & 16u) != 0, (int)(i >> 5)}; }
+    struct Form { bool aux, cull, nmap, list, shadow; int surf; bool glow; };
+    static constexpr uint32_t kRange = 32u * 4u * 2u;
+    static constexpr uint32_t encode(Form f)
+    {
+        return f.aux + 2u * f.cull + 4u * f.nmap + 8u * f.list + 16u * f.shadow + 32u * (uint32_t)f.surf + 128u * f.glow;
+    }
+    static constexpr Form decode(uint32_t i)
+    {
+        return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (i & 16u) != 0, (int)((i >> 5) & 3u), (i & 128u) != 0};
+    }
     static constexpr bool valid(Form f) { return !f.list || f.cull; }
     using Kernel = decltype(&k_wf_primary<false, false, false>);
     template <uint32_t I> static constexpr Kernel kernel()
     {
         constexpr Form f = decode(I);
-        return &k_wf_primary<f.aux, f.cull, f.nmap, f.list, f.shadow, f.surf>;
+        return &k_wf_primary<f.aux, f.cull, f.nmap, f.list, f.shadow, f.surf, f.glow>;
     }
 };
 static constexpr auto kPrimaryForms = form_table<PrimaryForms>();
-static_assert(check_forms<PrimaryForms>(96), "8 plain + 4 LIST + 12 SHADOW forms, times four surface models");
+// GLOW (rwr_surface.h WfGlow) goes with every form of all three templates — a hit is shaded by the kernels that end a path as by
+// those that send a ray on — so it adds no condition to any valid(): each table's count is twice what it was.
+static_assert(check_forms<PrimaryForms>(192), "8 plain + 4 LIST + 12 SHADOW forms, times four surface models, with and without GLOW");
 
 hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const ShadeRec *shade,
                              const FrameTri *ftris, const float4 *tex, const Targets &tg, const WfBuffers &wf,
@@ -609,7 +641,7 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
     if (fp.row_end <= fp.row_begin || fp.width == 0 || sample_count == 0) return hipSuccess;
     z_split = std::max(1u, std::min(z_split, sample_count));
     const WfPrimaryArgs args{ftris, fp.n_tris, fp.row_begin, fp.bins.enabled, fp.mesh_px[0], fp.mesh_px[1], fp.mesh_px[2], fp.mesh_px[3],
-                             sample_begin, sample_count, z_split, fp, tris, shade, tex, tg, wf, ft.shadow, ft.surfaces};
+                             sample_begin, sample_count, z_split, fp, tris, shade, tex, tg, wf, ft.shadow, ft.surfaces, ft.glow};
     PrimaryForms::Form f;
     f.aux = (fp.flags & RWR_FLAG_AUX_OUTPUTS) != 0;
     f.cull = (fp.flags & RWR_FLAG_NO_CULL) == 0;
@@ -617,6 +649,7 @@ hipError_t launch_wf_primary(hipStream_t s, const FrameParams &fp, const TriReco
     f.list = wf.live_list && f.cull;   // item after item of (live tile) x (share of its samples)
     f.shadow = ft.shadows;
     f.surf = ft.primary_surf(fp);
+    f.glow = ft.glows;
     const dim3 tiles((fp.width + kWfTileW - 1u) / kWfTileW, band_strips(fp), z_split);
     const dim3 grid = f.list ? dim3(std::min(tiles.x * tiles.y * z_split, 4096u)) : tiles;
     hipLaunchKernelGGL(kPrimaryForms[PrimaryForms::encode(f)], grid, dim3(256), 0, s, args);

@@ -46,6 +46,7 @@ struct WfFrame {
     int reserve();
     int schedule();
     int surface_table();
+    int glow_table();
     int trace_groups(const AccumPlan &ap);
     int resolve(AccumPlan &ap);
     int reproject_stage(ReprojectPlan &pp);
@@ -207,6 +208,35 @@ int WfFrame::surface_table()
     return RWR_OK;
 }
 
+// RWR_FLAG_EMISSIVE: this slot's copy of the emission table — the radiance of every part, then of every sphere index — kept as
+// the surface table's copy is (refreshed on the frame's stream when the context's attributes have changed since), and the frame's
+// count of emitting hits, from zero.
+int WfFrame::glow_table()
+{
+    ft.glows = rq.glow;
+    if (!rq.glow) return RWR_OK;
+    const size_t n_parts = ctx->part_glow.size(), n_recs = n_parts + RWR_MAX_SPHERES;
+    if (W.glow_version != ctx->glow_version || W.d_glow.count < n_recs) {
+        if (W.glow_version != 0u) RWR_HIP_CHECK(hipEventSynchronize(W.glow_copied));   // the image's last copy has been read
+        if (W.h_glow_count < n_recs) {
+            W.h_glow = PinnedSurface();
+            RWR_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&W.h_glow.h), n_recs * sizeof(SurfaceRec), hipHostMallocDefault));
+            W.h_glow_count = n_recs;
+        }
+        RWR_HIP_CHECK(W.d_glow.ensure(n_recs));
+        if (!W.glow_copied) RWR_HIP_CHECK(hipEventCreateWithFlags(&W.glow_copied.h, hipEventDisableTiming));
+        for (size_t i = 0; i < n_parts; i++) W.h_glow.h[i] = ctx->part_glow[i];
+        for (size_t i = 0; i < RWR_MAX_SPHERES; i++) W.h_glow.h[n_parts + i] = ctx->sphere_glow[i];
+        RWR_HIP_CHECK(hipMemcpyAsync(W.d_glow.ptr, W.h_glow.h, n_recs * sizeof(SurfaceRec), hipMemcpyHostToDevice, stream));
+        RWR_HIP_CHECK(hipEventRecord(W.glow_copied, stream));
+        W.glow_version = ctx->glow_version;
+    }
+    RWR_HIP_CHECK(W.d_glow_hits.ensure(1));
+    RWR_HIP_CHECK(hipMemsetAsync(W.d_glow_hits.ptr, 0, sizeof(unsigned long long), stream));
+    ft.glow = WfGlow{W.d_glow.ptr, (uint32_t)n_parts, 0u, W.d_glow_hits.ptr};
+    return RWR_OK;
+}
+
 // The samples, in launch groups that alternate between the queues: per group the primary stage, then per bounce one generation
 // of the bounce stage; the other queues' streams fork off the slot's ahead of the first group and join it behind the last.
 // ft: what the frame's kernels know (WfFeatures) — the surfaces come filled in, the sky here, a queue's shadow records per launch
@@ -365,7 +395,7 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
     so.zero_a = F.W.d_wave_total.ptr; so.n_zero_a = F.n_tiles * 4u;
     so.zero_b = F.W.d_tiles.ptr + 2u * (size_t)F.n_tiles; so.n_zero_b = 1u;   // live_count (WfFrame::schedule)
     if ((rc = enqueue_records(ctx, sl, FrameKernel::kWavefront, fc, so, timing)) != RWR_OK) return rc;
-    if ((rc = F.reserve()) != RWR_OK || (rc = F.schedule()) != RWR_OK || (rc = F.surface_table()) != RWR_OK) return rc;
+    if ((rc = F.reserve()) != RWR_OK || (rc = F.schedule()) != RWR_OK || (rc = F.surface_table()) != RWR_OK || (rc = F.glow_table()) != RWR_OK) return rc;
     if ((rc = F.trace_groups(ap)) != RWR_OK || (rc = F.resolve(ap)) != RWR_OK) return rc;
     if (rq.reproject && (rc = F.reproject_stage(pp)) != RWR_OK) return rc;
     if (rq.denoise && (rc = F.denoise_stage()) != RWR_OK) return rc;

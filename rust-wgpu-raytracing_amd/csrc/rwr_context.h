@@ -157,6 +157,15 @@ struct WfState {
     uint64_t surface_version = 0;
     uint32_t surface_modes = 0;                // which surfaces that copy holds: 1 mirrors, 2 glass, 4 glossy (surface_mode, rwr_surface.h)
     DeviceBuffer<unsigned long long> d_surface_events;   // RWR_FLAG_GLASS, _GLOSSY: the frame's kEventNone counters by SurfaceEvent (WfSurfaces::events); zeroed per frame
+    // RWR_FLAG_EMISSIVE, allocated by the first frame with an emitter: this slot's copy of the emission table (WfGlow::table), kept
+    // as the surface table's copy is — pinned image, event behind the copy, the context's glow_version it holds (0: none) — and the
+    // frame's count of emitting hits (WfGlow::hits), zeroed per frame
+    DeviceBuffer<SurfaceRec> d_glow;
+    PinnedSurface h_glow;
+    size_t h_glow_count = 0;
+    OwnedEvent glow_copied;
+    uint64_t glow_version = 0;
+    DeviceBuffer<unsigned long long> d_glow_hits;
 };
 
 // Progressive accumulation (RWR_FLAG_ACCUMULATE): ONE accumulation per context.  Its sums and the first frame's sample-0 planes
@@ -325,6 +334,11 @@ struct rwr_context {
     std::vector<rwr::SurfaceRec> part_surfaces;
     rwr::SurfaceRec sphere_surfaces[RWR_MAX_SPHERES]{};
     uint64_t surface_version = 1;
+    // RWR_FLAG_EMISSIVE (rwr_scene_set_part_emission / _sphere_emission): the radiance {r, g, b, 0} per scene part and per sphere
+    // index, beside the surface records and with their reset rules; glow_version counts their changes (a WfState's table lags behind)
+    std::vector<rwr::SurfaceRec> part_glow;
+    rwr::SurfaceRec sphere_glow[RWR_MAX_SPHERES]{};
+    uint64_t glow_version = 1;
     rwr_triangle_buffer_data triangles[RWR_MAX_TRIANGLES]{};
     uint32_t n_triangles = 0;
 
@@ -335,6 +349,7 @@ struct rwr_context {
     bool last_shadows = false;      // the last render call traced shadow rays (RWR_FLAG_SHADOWS): their counters are in its WfState
     bool last_gloss = false;        // the last render call ran the glossy forms (RWR_FLAG_GLOSSY): their counter is d_surface_events[kEventGlossy]
     bool last_glass = false;        // the last render call ran the glass forms (RWR_FLAG_GLASS): their counters are in its WfState
+    bool last_glow = false;         // the last render call ran the GLOW forms (RWR_FLAG_EMISSIVE): their counter is its WfState's d_glow_hits
     // optional per-kernel timing (rwr_ctx_set_kernel_timing)
     uint32_t timing_every = 0;
     uint64_t timing_calls = 0;
@@ -390,6 +405,15 @@ inline uint32_t surface_modes(const rwr_context *ctx)
     for (const SurfaceRec &m : ctx->part_surfaces) modes |= surface_mode(surface_model(m));
     for (uint32_t i = 0; i < ctx->n_spheres; i++) modes |= surface_mode(surface_model(ctx->sphere_surfaces[i]));
     return modes;
+}
+// does a part of the context's scene or one of its spheres in use emit (RWR_FLAG_EMISSIVE)?
+inline bool scene_glows(const rwr_context *ctx)
+{
+    for (const SurfaceRec &g : ctx->part_glow)
+        if (glows(g)) return true;
+    for (uint32_t i = 0; i < ctx->n_spheres; i++)
+        if (glows(ctx->sphere_glow[i])) return true;
+    return false;
 }
 
 // context.cpp: per-frame buffers of every active slot for the current scene and screen

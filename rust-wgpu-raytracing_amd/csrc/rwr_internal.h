@@ -366,7 +366,9 @@ struct WfFeatures {
     WfShadow shadow{nullptr, nullptr, nullptr};
     WfSky sky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     WfSurfaces surfaces{nullptr, 0u, 0u, nullptr};   // rwr_surface.h
+    WfGlow glow{nullptr, 0u, 0u, nullptr};           // rwr_surface.h
     bool emits = false, shadows = false, sky_on = false;
+    bool glows = false;   // RWR_FLAG_EMISSIVE with an emitter in the scene: the GLOW forms of all three kernels, which read `glow`
     bool soft = false;   // RWR_FLAG_SOFT_SHADOWS: k_wf_shadow's SOFT forms (no other kernel looks)
     int surf = kSurfNone;   // the surface models of the frame's flags (kSurfGlass: the table may hold glass records; kSurfGloss: glossy ones too)
     // The two rules for SURF.  The surface forms differ where a ray is emitted and nowhere else: the primary stage has one only

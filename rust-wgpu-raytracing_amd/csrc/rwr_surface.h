@@ -108,6 +108,24 @@ struct WfSurfaces {
     unsigned long long *events;
 };
 
+// Emissive surfaces (RWR_FLAG_EMISSIVE; the GLOW forms of k_wf_primary and of the trace kernels — "glow", since EMIT, emit_next_ray
+// and WfEmit already mean "sends a ray on").  A second table of the surface table's shape and order — one record {r, g, b, 0} per
+// scene part, then one per sphere index: the radiance Le the surface gives off, zeros where it gives off none — fetched like
+// WfSurfaces::table (surface_record below).  Emission stands beside a surface's model: a record here says nothing about `on` there.
+// hits: the frame's count of shaded hits with Le != 0, one atomic per wave (count_glow_hits).  A kernel argument of its own behind
+// the others (cf. WfSurfaces), so that the forms without GLOW read their arguments where they did.
+struct WfGlow {
+    const SurfaceRec *table;
+    uint32_t n_parts;
+    uint32_t pad;
+    unsigned long long *hits;
+};
+constexpr float kMaxEmission = 64.0f;   // RWR_MAX_EMISSION
+// the record of a surface of radiance rgb (each in [0, kMaxEmission]: the setters refuse anything else; -0.0 is stored as +0.0, so
+// that "emits" is "a component is not zero" on the bits as well)
+inline SurfaceRec glow_rec(const float rgb[3]) { return SurfaceRec{rgb[0] + 0.0f, rgb[1] + 0.0f, rgb[2] + 0.0f, 0.0f}; }
+RWR_HD constexpr bool glows(const SurfaceRec &g) { return g.r != 0.0f || g.g != 0.0f || g.b != 0.0f; }
+
 #ifdef __HIPCC__
 // The record {r, g, b, on} of the hit `obj` (a face, or -2 - the sphere's index).  Part 0's record sits at the table's start and
 // is read at a constant index through the constant address space: a wave-uniform address, one scalar load into scalar registers,
@@ -144,6 +162,24 @@ __device__ __forceinline__ void count_surface_events(unsigned long long *__restr
         const uint32_t n = (uint32_t)__popcll(__ballot(ev0 == k)) + (uint32_t)__popcll(__ballot(ev1 == k));
         if (n && lane == (uint32_t)__builtin_ctzll(active)) atomicAdd(&events[k], (unsigned long long)n);
     }
+}
+
+// GLOW forms: the radiance {r, g, b, 0} of the hit `obj` — surface_record on the emission table: part 0's record by the one scalar
+// load, a sphere's or another part's per lane under the same branch.
+template <typename Shade>
+__device__ __forceinline__ float4 glow_record(const WfGlow &gl, bool several_parts, const Shade *__restrict__ shade, int32_t obj)
+{
+    return surface_record(gl.table, gl.n_parts, several_parts, shade, obj);
+}
+__device__ __forceinline__ bool glows(const float4 &g) { return g.x != 0.0f || g.y != 0.0f || g.z != 0.0f; }
+// A wave's shaded hits on emitting surfaces (two per lane: a packet's or a pixel pair's) into the frame's counter, as
+// count_surface_events counts: ballots and popcounts, one atomic from the wave's first active lane.  Call where the wave's lanes
+// have come together again.
+__device__ __forceinline__ void count_glow_hits(unsigned long long *__restrict__ hits, bool lit0, bool lit1 = false)
+{
+    const unsigned long long active = __ballot(true);
+    const uint32_t n = (uint32_t)__popcll(__ballot(lit0)) + (uint32_t)__popcll(__ballot(lit1));
+    if (n && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(active)) atomicAdd(hits, (unsigned long long)n);
 }
 #endif
 

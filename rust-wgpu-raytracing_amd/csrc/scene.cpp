@@ -74,6 +74,8 @@ int rwr_scene_clear(rwr_context *ctx)
     ctx->d_texs.clear(); ctx->d_quads.clear(); ctx->d_nmaps.clear();
     ctx->part_surfaces.clear();   // (a new scene: its parts are no mirrors; the sphere attributes are kept per index)
     ctx->surface_version++;
+    ctx->part_glow.clear();       // (... and give off no light)
+    ctx->glow_version++;
     ctx->have_mesh = false;
     ctx->n_faces = ctx->n_verts = ctx->n_tris = 0;
     return RWR_OK;
@@ -146,6 +148,8 @@ int rwr_scene_add_mesh(rwr_context *ctx, const rwr_model_vertex_small *verts, ui
     ctx->d_nmaps.emplace_back();
     ctx->part_surfaces.push_back(kDiffuseRec);
     ctx->surface_version++;
+    ctx->part_glow.push_back(kDiffuseRec);
+    ctx->glow_version++;
     if (mid == 0) ctx->material = *material;
     return RWR_OK;
 }
@@ -292,6 +296,57 @@ int rwr_scene_set_part_gloss(rwr_context *ctx, uint32_t part, const float *refle
 int rwr_scene_set_sphere_gloss(rwr_context *ctx, uint32_t sphere, const float *reflectance, float roughness) { return set_surface(ctx, true, sphere, SurfaceModel::kGloss, reflectance, roughness); }
 int rwr_scene_get_part_gloss(rwr_context *ctx, uint32_t part, int *is_glossy, float reflectance[3], float *roughness) { return get_surface(ctx, false, part, SurfaceModel::kGloss, is_glossy, reflectance, roughness); }
 int rwr_scene_get_sphere_gloss(rwr_context *ctx, uint32_t sphere, int *is_glossy, float reflectance[3], float *roughness) { return get_surface(ctx, true, sphere, SurfaceModel::kGloss, is_glossy, reflectance, roughness); }
+
+// Emission (RWR_FLAG_EMISSIVE): an attribute beside the surface's model, with the same index rules — a record of its own per part
+// and per sphere index, so that neither kind of setter touches the other's.
+
+// the emission record of part / sphere `index`; NULL: refused, RWR_ERR_INVALID_ARGUMENT is set
+static SurfaceRec *glow_at(rwr_context *ctx, bool sphere, uint32_t index)
+{
+    if (!ctx) {
+        set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    } else if (sphere) {
+        if (index < RWR_MAX_SPHERES) return &ctx->sphere_glow[index];
+        set_error(RWR_ERR_INVALID_ARGUMENT, "sphere %u: at most %d spheres", index, RWR_MAX_SPHERES);
+    } else {
+        if (index < ctx->part_glow.size()) return &ctx->part_glow[index];
+        set_error(RWR_ERR_INVALID_ARGUMENT, "part %u: the scene has %zu parts", index, ctx->part_glow.size());
+    }
+    return nullptr;
+}
+
+static int set_glow(rwr_context *ctx, bool sphere, uint32_t index, const float *radiance)
+{
+    SurfaceRec *at = glow_at(ctx, sphere, index);
+    if (!at) return RWR_ERR_INVALID_ARGUMENT;
+    static_assert(kMaxEmission == RWR_MAX_EMISSION, "kMaxEmission is RWR_MAX_EMISSION");
+    SurfaceRec g = kDiffuseRec;
+    if (radiance) {
+        for (int c = 0; c < 3; c++)   // (false for NaN)
+            if (!(radiance[c] >= 0.0f && radiance[c] <= kMaxEmission))
+                return set_error(RWR_ERR_INVALID_ARGUMENT, "%s %u: radiance[%d] %g: finite, 0 ... %g", sphere ? "sphere" : "part", index, c,
+                                 (double)radiance[c], (double)kMaxEmission);
+        g = glow_rec(radiance);
+    }
+    ctx->scene_generation++;   // (a refused call never gets here)
+    *at = g;
+    ctx->glow_version++;
+    return RWR_OK;
+}
+
+static int get_glow(rwr_context *ctx, bool sphere, uint32_t index, int *emits, float radiance[3])
+{
+    const SurfaceRec *at = glow_at(ctx, sphere, index);
+    if (!at) return RWR_ERR_INVALID_ARGUMENT;
+    if (emits) *emits = glows(*at) ? 1 : 0;
+    if (radiance) { radiance[0] = at->r; radiance[1] = at->g; radiance[2] = at->b; }
+    return RWR_OK;
+}
+
+int rwr_scene_set_part_emission(rwr_context *ctx, uint32_t part, const float *radiance) { return set_glow(ctx, false, part, radiance); }
+int rwr_scene_set_sphere_emission(rwr_context *ctx, uint32_t sphere, const float *radiance) { return set_glow(ctx, true, sphere, radiance); }
+int rwr_scene_get_part_emission(rwr_context *ctx, uint32_t part, int *emits, float radiance[3]) { return get_glow(ctx, false, part, emits, radiance); }
+int rwr_scene_get_sphere_emission(rwr_context *ctx, uint32_t sphere, int *emits, float radiance[3]) { return get_glow(ctx, true, sphere, emits, radiance); }
 
 int rwr_scene_upload_mesh(rwr_context *ctx, const rwr_model_vertex_small *verts, uint32_t n_verts,
                           const rwr_model_face_small *faces, uint32_t n_faces, const rwr_material_data *material,

@@ -7,6 +7,7 @@
 //              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]]
 //              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]...
 //              [--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]]
+//              [--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]...
 //              [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
@@ -151,6 +152,23 @@ int main(int argc, char **argv)
         for (int c = 0; c < 3; c++) g.r[c] = v[c];
         return true;
     };
+    // --emissive-part / --emissive-sphere "N:r,g,b": an index and a radiance in [0, RWR_MAX_EMISSION]^3
+    struct Emitter { bool sphere; uint32_t index; float le[3]; };
+    std::vector<Emitter> emitters;
+    auto parse_emitter = [](const char *text, Emitter &e) {
+        char *end = nullptr;
+        if (*text < '0' || *text > '9') return false;
+        const unsigned long idx = std::strtoul(text, &end, 10);
+        if (end == text || idx > 0xfffffffful || *end != ':') return false;
+        e.index = (uint32_t)idx;
+        float v[3];
+        char tail = 0;
+        if (std::sscanf(end + 1, "%f,%f,%f%c", &v[0], &v[1], &v[2], &tail) != 3) return false;
+        for (int c = 0; c < 3; c++)   // (false for NaN)
+            if (!(v[c] >= 0.0f && v[c] <= RWR_MAX_EMISSION)) return false;
+        for (int c = 0; c < 3; c++) e.le[c] = v[c];
+        return true;
+    };
     struct Resize { uint64_t frame; uint32_t w, h; };
     std::vector<Resize> resizes;
     for (int i = 1; i < argc; i++) {
@@ -239,6 +257,14 @@ int main(int argc, char **argv)
             }
             glosses.push_back(g);
         }
+        else if (a == "--emissive-part" || a == "--emissive-sphere") {
+            Emitter e{a == "--emissive-sphere", 0u, {0.0f, 0.0f, 0.0f}};
+            if (!parse_emitter(next(), e) || (e.sphere && e.index >= RWR_MAX_SPHERES)) {
+                std::fprintf(stderr, "%s N:r,g,b: an index%s and three numbers in [0, %g]\n", a.c_str(), e.sphere ? " below 8" : "", (double)RWR_MAX_EMISSION);
+                return 2;
+            }
+            emitters.push_back(e);
+        }
         else if (a == "--show-params") show_params = true;
         else if (a == "--resize") {
             Resize r{0, 0, 0};
@@ -255,6 +281,7 @@ int main(int argc, char **argv)
                         "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
                         "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]... "
                         "[--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... "
+                        "[--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... "
                         "[--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]] "
                         "[--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
@@ -281,6 +308,10 @@ int main(int argc, char **argv)
                         "the mirror reflection and the diffuse ray (RWR_FLAG_GLOSSY, implied; needs --bounces >= 1; rwr_scene_set_part_gloss / "
                         "rwr_scene_set_sphere_gloss); repeatable; prints `glossy rays N` for the final frame.  Mirror, glass and gloss options "
                         "are applied in that order: of several for one surface the last of these wins\n"
+                        "  --emissive-part N:r,g,b, --emissive-sphere N:r,g,b  part N of the scene / sphere N gives off light of radiance r,g,b in "
+                        "[0, 64], whatever its surface model (RWR_FLAG_EMISSIVE, implied; rwr_scene_set_part_emission / "
+                        "rwr_scene_set_sphere_emission); repeatable; prints `emissive hits N` for the final frame.  No ray is aimed at an emitter: "
+                        "a small lamp wants many samples\n"
                         "  --reproject   every frame is blended with the history of the frames before it, fetched where its points were seen "
                         "last frame, while the camera moves (RWR_FLAG_REPROJECT; with --keys every key step's frame feeds the next one's history): "
                         "at most N frames of history per pixel (1-1024), taps of faces whose normals' cosine is at least C and whose distance "
@@ -296,13 +327,19 @@ int main(int argc, char **argv)
                            (shadows ? (uint32_t)RWR_FLAG_SHADOWS : 0u) | (denoise ? (uint32_t)RWR_FLAG_DENOISE : 0u) | (sky ? (uint32_t)RWR_FLAG_SKY : 0u) |
                            (mirrors.empty() ? 0u : (uint32_t)RWR_FLAG_MIRRORS) | (glasses.empty() ? 0u : (uint32_t)RWR_FLAG_GLASS) |
                            (glosses.empty() ? 0u : (uint32_t)RWR_FLAG_GLOSSY) | (soft_shadows ? (uint32_t)RWR_FLAG_SOFT_SHADOWS : 0u) |
-                           (reproject ? (uint32_t)RWR_FLAG_REPROJECT : 0u);
+                           (reproject ? (uint32_t)RWR_FLAG_REPROJECT : 0u) | (emitters.empty() ? 0u : (uint32_t)RWR_FLAG_EMISSIVE);
     if (show_params) {
         if (reproject)   // (a line of its own, ahead of the line every run prints)
             std::printf("reproject 1 history %u normal %g depth %g\n", reproject_params.max_history, (double)reproject_params.normal_cos_min,
                         (double)reproject_params.depth_rel);
         if (soft_shadows)   // (likewise)
             std::printf("soft-shadows 1 radii %g,%g\n", (double)shadow_params.mesh_light_radius, (double)shadow_params.sphere_light_radius);
+        if (!emitters.empty()) {   // (likewise)
+            std::printf("emissive %zu", emitters.size());
+            for (const Emitter &e : emitters)
+                std::printf(" %s %u:%g,%g,%g", e.sphere ? "sphere" : "part", e.index, (double)e.le[0], (double)e.le[1], (double)e.le[2]);
+            std::printf("\n");
+        }
         std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g gloss %zu", spp, bounces, flags, sky ? 1 : 0,
                     (double)sky_params.zenith[0], (double)sky_params.zenith[1], (double)sky_params.zenith[2],
                     (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2], glosses.size());
@@ -353,6 +390,10 @@ int main(int argc, char **argv)
             const int rc = g.sphere ? rwr_scene_set_sphere_gloss(state.context(), g.index, g.r, g.rough) : rwr_scene_set_part_gloss(state.context(), g.index, g.r, g.rough);
             if (rc != RWR_OK) { std::fprintf(stderr, "%s: %s\n", g.sphere ? "--gloss-sphere" : "--gloss-part", rwr_last_error_string()); return 2; }
         }
+        for (const Emitter &e : emitters) {   // (beside the surface's model: no order among these and the three above)
+            const int rc = e.sphere ? rwr_scene_set_sphere_emission(state.context(), e.index, e.le) : rwr_scene_set_part_emission(state.context(), e.index, e.le);
+            if (rc != RWR_OK) { std::fprintf(stderr, "%s: %s\n", e.sphere ? "--emissive-sphere" : "--emissive-part", rwr_last_error_string()); return 2; }
+        }
         if (denoise_iterations != 0 || denoise_sigma != 0.0f) {
             rwr_denoise_params dp;
             int rc = rwr_denoise_get_params(state.context(), &dp);
@@ -387,6 +428,7 @@ int main(int argc, char **argv)
         if (accumulate) std::printf("samples %llu\n", (unsigned long long)state.accumulated_samples());
         if (reproject) std::printf("history %llu\n", (unsigned long long)state.reprojected_frames());
         if (!glosses.empty()) std::printf("glossy rays %llu\n", (unsigned long long)state.glossy_rays());
+        if (!emitters.empty()) std::printf("emissive hits %llu\n", (unsigned long long)state.emissive_hits());
         if (timing) std::printf("%.3f ms/frame over %llu frames (update + render, host wall clock)\n", sec * 1e3 / (double)rendered,
                                 (unsigned long long)rendered);
         if (!out.empty()) {

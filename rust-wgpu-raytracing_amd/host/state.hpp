@@ -147,6 +147,13 @@ public:
         return n;
     }
 
+    // extension (RWR_FLAG_EMISSIVE): the shaded hits of the frame rendered last that lay on an emitting surface
+    uint64_t emissive_hits()
+    {
+        uint64_t n = 0;
+        check(rwr_last_emission_stats(ctx_, &n));
+        return n;
+    }
     // extension (RWR_FLAG_GLOSSY): the rays the glossy hits of the frame rendered last sent on
     uint64_t glossy_rays()
     {

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the device code of two builds of one kernel file, kernel by kernel, as text.
 
-usage: tools/asm_identity.py PARENT.s CHANGE.s [--rename OLD=NEW ...] [--cxxfilt PATH]   (ROCm's llvm-cxxfilt, else c++filt)
+usage: tools/asm_identity.py PARENT.s CHANGE.s [--rename OLD=NEW ...] [--diff-summary] [--cxxfilt PATH]   (ROCm's llvm-cxxfilt, else c++filt)
 
 The inputs are listings of `hipcc --offload-arch=gfx950 --cuda-device-only -S` with the Makefile's HIPFLAGS (tools/isa_stats.sh).
 A kernel is every function with an .amdhsa_kernel block; its text runs from its .type line to the end of its `; Kernel info`
@@ -85,6 +85,7 @@ def main():
     ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     llvm = "/opt/rocm/llvm/bin/llvm-cxxfilt"
     ap.add_argument("--cxxfilt", default=llvm if os.path.exists(llvm) else shutil.which("c++filt"))
+    ap.add_argument("--diff-summary", action="store_true", help="print which lines the differing kernels differ in, as a histogram; kernels only in change by template, differing kernels by name only where a figure moved")
     a = ap.parse_args()
     renames = [r.split("=", 1) for r in a.rename]
     sides = []
@@ -109,8 +110,39 @@ def main():
           f"only in parent {len(only_parent)}, only in change {len(only_change)}, identical {len(both) - len(differing)}, differing {len(differing)}")
     for n in only_parent:
         print("  only in parent: " + n)
-    for n in only_change:
-        print("  only in change: " + n)
+    if a.diff_summary and only_change:   # (by template: a summary names no kernel that has no counterpart to differ from)
+        by_template = {}
+        for n in only_change:
+            t = n.split("<")[0]
+            by_template[t] = by_template.get(t, 0) + 1
+        print("  only in change: " + ", ".join(f"{k} {t}" for t, k in sorted(by_template.items())))
+    else:
+        for n in only_change:
+            print("  only in change: " + n)
+    if a.diff_summary and differing:
+        # what the differing kernels differ in, line by line: every (parent line -> change line) pair with the scalar register
+        # numbers taken out, and in how many kernels it occurs; a kernel whose texts do not pair up line by line is named
+        pairs, unpaired = {}, []
+        for n in differing:
+            pl, cl = parent[n][0].split("\n"), change[n][0].split("\n")
+            if len(pl) != len(cl):
+                unpaired.append(n)
+                continue
+            seen = set()
+            for x, y in zip(pl, cl):
+                if x != y:
+                    seen.add((re.sub(r"\bs\d+\b", "sN", x.strip()), re.sub(r"\bs\d+\b", "sN", y.strip())))
+            for k in seen:
+                pairs[k] = pairs.get(k, 0) + 1
+        print(f"  line pairs the {len(differing) - len(unpaired)} differing kernels of equal length differ in (kernels: parent line -> change line):")
+        for (x, y), k in sorted(pairs.items(), key=lambda kv: (-kv[1], kv[0])):
+            print(f"    {k:4d}: {x}  ->  {y}")
+        for n in unpaired:
+            print("  differs in length: " + n)
+    same_figures = [n for n in differing if parent[n][1:] == change[n][1:]]
+    if a.diff_summary and same_figures:   # (... and only the differing kernels whose figures moved, below)
+        print(f"  {len(same_figures)} of the {len(differing)} differing kernels: instructions, vgpr, sgpr, scratch, occupancy and spill counts unchanged")
+        differing = [n for n in differing if n not in set(same_figures)]
     for n in differing:
         p, c = parent[n], change[n]
         cols = "  ".join(f"{k} {p[1][k]}->{c[1][k]}" for k in ("instructions", "vgpr", "sgpr", "scratch", "occupancy"))
