@@ -451,7 +451,7 @@ enum {
                                           anew.  RNG keys are global pixel and global sample: frames in flight, row bands, strips, the
                                           multi-GPU gather and every schedule give the same bytes; every other flag keeps its contract.
                                           With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
-    RWR_FLAG_EMISSIVE = 1u << 15    /* extension: emissive surfaces — a scene part or a sphere that gives off light of radiance Le
+    RWR_FLAG_EMISSIVE = 1u << 15,   /* extension: emissive surfaces — a scene part or a sphere that gives off light of radiance Le
                                        (rwr_scene_set_part_emission, rwr_scene_set_sphere_emission), so that a scene can hold its own
                                        lamps.  Emission is an attribute beside the surface model, not a model: a diffuse, mirror, glass
                                        or glossy surface may also emit, and the setters of one never touch the other.  Without the flag
@@ -483,8 +483,55 @@ enum {
                                           contracts; RWR_FLAG_DENOISE and RWR_FLAG_REPROJECT are stages behind the resolve and do not know.
                                        8. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED,
                                           whatever the scene holds.
-                                       No ray is aimed at an emitter (no next-event estimation): a small lamp is found by chance and
-                                       its light is noisy at low sample counts. */
+                                       A ray is aimed at an emitting sphere only under RWR_FLAG_LIGHT_SAMPLING; an emitting part is
+                                       found by chance, and its light is noisy at low sample counts. */
+    RWR_FLAG_LIGHT_SAMPLING = 1u << 16 /* extension: light sampling (next-event estimation) towards emitting SPHERES — every diffuse hit
+                                       that sends a ray on also sends one ray towards an emitting sphere, so that a small lamp lights a
+                                       room at few samples.  Emitting mesh parts are out of scope (they would need a per-part area
+                                       distribution): they are found by chance as before and their Le is never suppressed.  There is
+                                       no multiple importance sampling, and mirror, glass and glossy hits send no light ray.  Without
+                                       the flag every frame is what it was, byte for byte.  All arithmetic f32, no contraction.
+                                       1. The flag is effective only while RWR_FLAG_EMISSIVE is effective, max_bounces >= 1 and at
+                                          least one sphere in use (index below the count rwr_scene_set_spheres gave) emits; otherwise it
+                                          is cleared before the frame's kernels are chosen and the frame is the frame without it, in the
+                                          same kernels.  s_0 < ... < s_{M-1}: the indices of the emitting spheres in use.
+                                       2. A hit h_k (k = 0 ... max_bounces - 1) is eligible when its surface's model, as the frame sees
+                                          it, is diffuse, so that ray k + 1 is the cosine-distributed bounce ray (a "diffuse ray"; its
+                                          queue record carries a mark).  Mirror, glass and glossy hits — roughness 1 included — are not.
+                                       3. The light sample of an eligible hit.  O: the origin of ray k + 1 (P + 1e-4 n); T: its
+                                          throughput as the queue holds it (after the unorm16 rounding); n: the hit record's normal.
+                                          RNG block d = 274 + 17 k on (global pixel, global sample, seed), behind soft shadows' last
+                                          dimension (273): no existing random number moves.
+                                          u = rng(d); i = min((uint32)(u * (float)M), M - 1); s = s_i, centre C, radius R.
+                                          w = C - O; d2 = dot3(w, w); !(d2 > R*R): no sample.  dl = sqrtf(d2); w = w / dl per component.
+                                          s2 = R*R / d2; cmax = sqrtf(fmaxf(0, 1 - s2)); kc = s2 / (1 + cmax)   (1 - cmax, no cancellation).
+                                          (a, b): the bounce direction's rejection loop over the unit disk, 8 tries on dimensions
+                                          d + 1 + 2j, d + 2 + 2j; a = b = 0 when all are refused.
+                                          q = a*a + b*b; c = 1 - q*kc; r = q > 0 ? sqrtf(fmaxf(0, 1 - c*c) / q) : 0; (b1, b2): the
+                                          bounce direction's basis about w; omega = r*(a*b1 + b*b2) + c*w per component, not
+                                          re-normalised: uniform over the solid angle the sphere subtends.
+                                          ndw = dot3(n, omega); !(ndw > 0): no ray is traced.
+                                          The ray (O, omega) REACHES s when the nearest hit along it under the integrator's own rule —
+                                          spheres in order, strict '<', then the mesh if closer — is sphere s: the sample counts exactly
+                                          when a bounce ray in that direction would have found the lamp; a ray that rounding lets graze
+                                          past the rim does not reach it.
+                                          g = 2 * (float)M * kc * ndw; per channel the term is T.c * (Le_s.c * g), converted and capped
+                                          to [0, 64] like a bounce term (NaN as 0) and added to the same fixed-point sums.
+                                       4. No double counting: a diffuse ray from origin O that hits an emitting sphere s in use with
+                                          dot3(C - O, C - O) > R*R takes Le(hit) as 0 everywhere in RWR_FLAG_EMISSIVE's rule — shading,
+                                          ambient part, rwr_last_emission_stats.  Every other hit keeps Le: h0, the hits of mirror, glass
+                                          and glossy rays, hits from inside the sphere, emitting parts.
+                                       5. Everything else is the frame's with RWR_FLAG_EMISSIVE alone, bit for bit: primary, bounce and
+                                          shadow rays, throughputs, existing RNG dimensions, rwr_last_render_stats, the shadow, glass and
+                                          gloss stats, rwr_last_traversal_plan, the depth, id and t planes.  The light ray needs no
+                                          RWR_FLAG_SHADOWS and does not know it.  A path adds up to 1 + 2 max_bounces terms: 17 terms
+                                          below 2^32 at 2^24 accumulated samples stay below 2^61 in the 64-bit sums.
+                                       6. The bit (after item 1) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
+                                          effective flags; the emitting spheres are part of the scene's generation.
+                                          rwr_last_light_stats counts the rays traced, those that reached, and the hits item 4 silenced.
+                                          RNG keys are global pixel and global sample: frames in flight, row bands, strips, the multi-GPU
+                                          gather, accumulation and every schedule give the same bytes.
+                                       7. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
 };
 
 #define RWR_MAX_BOUNCES 8u
@@ -841,6 +888,11 @@ RWR_API int rwr_last_gloss_stats(rwr_context *ctx, uint64_t *glossy_rays);
  * samples the call traced (an accumulating frame: its own samples; zero for a frame the flag did nothing to).  An exact count.
  * Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_last_emission_stats(rwr_context *ctx, uint64_t *emissive_hits);
+
+/* RWR_FLAG_LIGHT_SAMPLING: of the last render call, over all samples it traced — the light rays traced (item 3: a sample with
+ * d2 > R*R and ndw > 0), those that reached their sphere, and the hits whose Le item 4 took as 0.  Zeros for a frame the flag did
+ * nothing to.  Exact counts.  Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_last_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits);
 
 /* Progressive accumulation (RWR_FLAG_ACCUMULATE).  One context holds one accumulation.
  * rwr_accum_reset: the next accumulating frame starts over at N = 0 (host-side only, nothing waits).

@@ -56,11 +56,12 @@ FLAG_REPROJECT = 1 << 12     # temporal reprojection of the context's history wh
 FLAG_GLOSSY = 1 << 13        # parts and spheres marked as glossy send on a ray between the mirror reflection and the diffuse ray (include/rwr_hip.h)
 FLAG_SOFT_SHADOWS = 1 << 14  # FLAG_SHADOWS' two lights get an angular size: penumbrae (include/rwr_hip.h)
 FLAG_EMISSIVE = 1 << 15      # parts and spheres with an emission (set_part_emission, set_sphere_emission) give off light (include/rwr_hip.h)
+FLAG_LIGHT_SAMPLING = 1 << 16  # every diffuse hit also sends a ray towards an emitting sphere: next-event estimation (include/rwr_hip.h)
 MAX_EMISSION = 64.0          # RWR_MAX_EMISSION: the largest component of a radiance
 SHADOW_PARAMS_DTYPE = np.dtype([("mesh_light_radius", "<f4"), ("sphere_light_radius", "<f4")])
 REPROJECT_PARAMS_DTYPE = np.dtype([("max_history", "<u4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
 MAX_BOUNCES = 8
-FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 16, 1 << 17
+FLAG_DEBUG_COUNTS, FLAG_ONE_PIXEL_PER_LANE = 1 << 20, 1 << 17
 KEY_FORWARD, KEY_BACKWARD, KEY_LEFT, KEY_RIGHT, KEY_UP, KEY_DOWN = 1, 2, 4, 8, 16, 32
 OK, ERR_INVALID_ARGUMENT, ERR_HIP, ERR_NOT_READY, ERR_IO, ERR_PARSE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 
@@ -141,7 +142,7 @@ def lib() -> C.CDLL:
         "rwr_last_gloss_stats": [vp, vp],
         "rwr_scene_set_part_emission": [vp, u32, vp], "rwr_scene_set_sphere_emission": [vp, u32, vp],
         "rwr_scene_get_part_emission": [vp, u32, vp, vp], "rwr_scene_get_sphere_emission": [vp, u32, vp, vp],
-        "rwr_last_emission_stats": [vp, vp],
+        "rwr_last_emission_stats": [vp, vp], "rwr_last_light_stats": [vp, vp, vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
         "rwr_load_model_compute": [C.c_char_p, C.c_char_p, vp], "rwr_model_free": [vp],
         "rwr_model_info": [vp, vp, vp, vp, vp, vp, vp], "rwr_scene_upload_model": [vp, vp],
@@ -166,7 +167,7 @@ def lib() -> C.CDLL:
                            "rwr_last_reproject_stats", "rwr_reproject_readback", "rwr_scene_set_part_gloss", "rwr_scene_set_sphere_gloss",
                            "rwr_scene_get_part_gloss", "rwr_scene_get_sphere_gloss", "rwr_last_gloss_stats",
                            "rwr_shadow_set_params", "rwr_shadow_get_params", "rwr_scene_set_part_emission", "rwr_scene_set_sphere_emission",
-                           "rwr_scene_get_part_emission", "rwr_scene_get_sphere_emission", "rwr_last_emission_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_scene_get_part_emission", "rwr_scene_get_sphere_emission", "rwr_last_emission_stats", "rwr_last_light_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -599,6 +600,13 @@ class Context:
         a = C.c_uint64(0)
         _check(lib().rwr_last_emission_stats(self._h, C.byref(a)))
         return int(a.value)
+
+    def last_light_stats(self):
+        """FLAG_LIGHT_SAMPLING: (light rays traced, those that reached their sphere, hits whose Le was suppressed) of the last
+        render call (rwr_last_light_stats)."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rwr_last_light_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
 
     def set_triangles(self, triangles):
         """Single-triangle passes (the reference's dormant models/triangle), after the spheres."""

@@ -473,6 +473,19 @@ int rwr_last_emission_stats(rwr_context *ctx, uint64_t *emissive_hits)
     return RWR_OK;
 }
 
+int rwr_last_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits)
+{
+    if (!ctx || !light_rays || !reached || !suppressed_hits) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    unsigned long long counts[3] = {0ull, 0ull, 0ull};
+    if (ctx->last_light && ctx->wf_state[ctx->last_wf_state].d_light_counts.ptr) {
+        DeviceGuard g(ctx->device);
+        RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
+        RWR_HIP_CHECK(hipMemcpy(counts, ctx->wf_state[ctx->last_wf_state].d_light_counts.ptr, sizeof counts, hipMemcpyDeviceToHost));
+    }
+    *light_rays = counts[0]; *reached = counts[1]; *suppressed_hits = counts[2];
+    return RWR_OK;
+}
+
 int rwr_denoise_set_params(rwr_context *ctx, const rwr_denoise_params *params)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");

@@ -356,6 +356,7 @@ hipError_t preload_kernels()
     if (e == hipSuccess) e = preload_kernels_wf_primary();
     if (e == hipSuccess) e = preload_kernels_wf_bounce();
     if (e == hipSuccess) e = preload_kernels_wf_shadow();
+    if (e == hipSuccess) e = preload_kernels_wf_light();
     if (e == hipSuccess) e = preload_kernels_dist();
     return e;
 }

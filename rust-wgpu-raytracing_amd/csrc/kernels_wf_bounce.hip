@@ -266,6 +266,12 @@ k_wf_sort(const WfBuffers wf, PoolInfo *__restrict__ info, uint32_t *__restrict_
     }
 }
 
+// emit_next_ray's view of its WfGlow argument: the mark of the ray a hit sends on — 1 (0xffff as unorm16) for a diffuse ray of a frame
+// that samples its lights, else the 0 the records always held
+RWR_DEV float light_mark(const WfGlow &gl, bool mirror, float eta, float rho) { return (gl.light && !mirror && eta == 0.0f && rho == 0.0f) ? 1.0f : 0.0f; }
+RWR_DEV LightRec *light_recs_of(const WfGlow &gl) { return gl.light_recs; }
+RWR_DEV unsigned long long *light_masks_of(const WfGlow &gl) { return gl.light_masks; }
+
 // EMIT forms: the next ray of the path whose ray hit (obj, t) — from P + 1e-4 n (P = O + t D, n = the face's normal flipped
 // towards the ray or the sphere's outward normal, as the first stage builds the first bounce ray), in the cosine-distributed
 // direction of RNG dimensions em.next_dim ... keyed by the slot's global pixel and sample, throughput thr — goes back into slot
@@ -278,15 +284,25 @@ k_wf_sort(const WfBuffers wf, PoolInfo *__restrict__ info, uint32_t *__restrict_
 // Glossy forms (RWR_FLAG_GLOSSY; SURF == kSurfGloss), a hit on a glossy surface (`rho` != 0, its roughness): the diffuse direction
 // of the same dimensions goes through gloss_direction — computed for every lane that draws a diffuse direction and selected, so
 // that the lanes stay together — thr is T * R.  Returns kEventGlossy for such a hit.
-template <int SURF = kSurfNone>
+// GLOW forms pass their WfGlow behind the other arguments (gl: one argument or none — the other forms' calls, arguments and code are
+// what they were).  With light sampling on (WfGlow::light; rwr_surface.h) a hit that sends on a DIFFUSE ray — no mirror, glass or
+// glossy one — marks the ray's record, leaves its normal at the slot and sets the slot's bit in the light ballots, for k_wf_light.
+template <int SURF = kSurfNone, typename... Glow>
 RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const WfEmit &em, const TriRecord *__restrict__ tris, uint32_t tile,
                                uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd, f3 thr, bool mirror = false, float eta = 0.0f,
-                               float rho = 0.0f)
+                               float rho = 0.0f, const Glow &...gl)
 {
+    static_assert(sizeof...(Glow) <= 1u, "the kernel's WfGlow, or nothing");
     f3 n;
     f3 O1 = hit_exit_point(p, tris, O, D, obj, t, ndotd, n);
     f3 D1;
     uint32_t event = kEventNone;
+    if constexpr (sizeof...(Glow) != 0u) {   // (here, while n is live anyway)
+        if (light_mark(gl..., SURF != kSurfNone && mirror, eta, rho) != 0.0f) {
+            *reinterpret_cast<float4 *>(light_recs_of(gl...) + (size_t)tile * wf.group * kWfTilePixels + e) = make_float4(n.x, n.y, n.z, 0.0f);
+            atomicOr(&light_masks_of(gl...)[(size_t)tile * wf.group * 8u + (e >> 6)], 1ull << (e & 63u));
+        }
+    }
     // glossy forms: a ray that starts at P + 1e-4 n (every one but a glass hit's) has its origin and the first two channels of its
     // throughput stored ahead of the direction's arithmetic — five registers fewer across the disk loop and the rule, which these
     // forms hold live together
@@ -319,6 +335,9 @@ RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const 
     }
     const size_t slot = (size_t)tile * wf.group * kWfTilePixels + e;
     if (SURF != kSurfGloss || eta != 0.0f) wf.rays[2u * slot] = make_float4(O1.x, O1.y, O1.z, wf_pack_unorm16x2(thr.x, thr.y));
+    if constexpr (sizeof...(Glow) != 0u)   // (the record's spare half: 0xffff on a diffuse ray of a frame that samples its lights)
+        wf.rays[2u * slot + 1u] = make_float4(D1.x, D1.y, D1.z, wf_pack_unorm16x2(thr.z, light_mark(gl..., SURF != kSurfNone && mirror, eta, rho)));
+    else
     wf.rays[2u * slot + 1u] = make_float4(D1.x, D1.y, D1.z, wf_pack_unorm16x2(thr.z, 0.0f));
     wf.bins[slot] = (uint16_t)wf_direction_bin(D1);
     atomicOr(&em.masks_out[(size_t)tile * wf.group * 8u + (e >> 6)], 1ull << (e & 63u));
@@ -327,15 +346,15 @@ RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const 
 
 // The surface forms' emit step for the hit (obj, t): the hit's record (rwr_surface.h surface_record), decoded; a surface with a
 // model sends on T * its record's colour, a diffuse one T * albedo; emit_next_ray does the rest.  Returns its event.
-template <int SURF>
+template <int SURF, typename... Glow>
 RWR_DEV uint32_t emit_from_surface(const FrameParams &p, const WfBuffers &wf, const WfEmit &em, const WfSurfaces &sf, const TriRecord *__restrict__ tris,
                                    const ShadeRec *__restrict__ shade, uint32_t tile, uint32_t e, f3 O, f3 D, int32_t obj, float t, float ndotd,
-                                   f3 thr, f3 albedo)
+                                   f3 thr, f3 albedo, const Glow &...gl)
 {
     const float4 m = surface_record(sf.table, sf.n_parts, p.n_materials > 1u, shade, obj);
     const SurfaceDecode s = decode_surface<SURF>(m.w);
     const f3 next = (s.mirror || s.glass || s.gloss) ? mk3(m.x, m.y, m.z) : albedo;
-    return emit_next_ray<SURF>(p, wf, em, tris, tile, e, O, D, obj, t, ndotd, mk3(thr.x * next.x, thr.y * next.y, thr.z * next.z), s.mirror, s.eta, s.rho);
+    return emit_next_ray<SURF>(p, wf, em, tris, tile, e, O, D, obj, t, ndotd, mk3(thr.x * next.x, thr.y * next.y, thr.z * next.z), s.mirror, s.eta, s.rho, gl...);
 }
 
 // SHADOW forms: the term T * E(h) of the hit (obj, t) of the ray in slot e is a select between clamp(T * ambient part) and
@@ -377,13 +396,28 @@ RWR_DEV void add_sky(TraceShared &sh, const WfSky &sky, uint32_t e, float dy, f3
 // GLOW forms (RWR_FLAG_EMISSIVE): the local shading of the hit `obj` becomes E'(h) = E(h) + Le(h), Le the radiance of the hit's
 // surface (rwr_surface.h glow_record) — one f32 add per channel to the shader's value, ahead of the product with the throughput.
 // le: that radiance, for shadow_hit's ambient part.  Returns whether the surface emits (count_glow_hits).
-RWR_DEV bool add_glow(const FrameParams &p, const WfGlow &gl, const ShadeRec *__restrict__ shade, int32_t obj, f3 &e1, f3 &le)
+// Light sampling on (gl.light, RWR_FLAG_LIGHT_SAMPLING item 4): O is the origin of the ray that found the hit and `marked` whether
+// its record says a diffuse hit sent it.  Such a ray's hit on an emitting sphere that O lies outside of — dot3(C - O, C - O) > R R,
+// the light stage's own test on the same origin — takes Le as 0: O's light sample has that light already; such hits are counted.
+RWR_DEV bool add_glow(const FrameParams &p, const WfGlow &gl, const ShadeRec *__restrict__ shade, int32_t obj, f3 &e1, f3 &le, f3 O, bool marked)
 {
-    const float4 g = glow_record(gl, p.n_materials > 1u, shade, obj);
+    float4 g = glow_record(gl, p.n_materials > 1u, shade, obj);
+    bool silenced = false;
+    if (gl.light) {   // (uniform)
+        if (marked && obj < -1 && glows(g)) {
+            const f3 w = sub3(ld3(p.spheres[-2 - obj].center), O);
+            const float R = p.spheres[-2 - obj].radius;
+            silenced = dot3(w, w) > R * R;
+        }
+        if (silenced) g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        count_glow_hits(gl.light_counts + 2, silenced);   // (the lanes that shade a hit here: the ballots take whoever is active)
+    }
     le = mk3(g.x, g.y, g.z);
     e1 = mk3(e1.x + g.x, e1.y + g.y, e1.z + g.z);
     return glows(g);
 }
+// whether a ray record's last word carries emit_next_ray's mark
+RWR_DEV bool wf_ray_marked(float w) { return (__float_as_uint(w) >> 16) != 0u; }
 
 // The trace kernels are PERSISTENT: kWfTraceGroups workgroups pull work items — (pool of the class, share of it)
 // — from a device counter until the class's live x split items are handed out.  Returns false when none are left.
@@ -513,13 +547,20 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
             if (have) {
                 const Shaded s1 = shade_winner<NMAP>(p, obj, best_t, mh.u, mh.v, mh.ndotd, shade, tex, O, D);
                 f3 e1 = s1.colour, le = f3{};
-                if (GLOW) lit = add_glow(p, gl, shade, obj, e1, le);
+                if (GLOW) lit = add_glow(p, gl, shade, obj, e1, le, O, wf_ray_marked(b.w));
                 if (SHADOW) shadow_hit<GLOW>(sh, p, wf, sw, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, e1, le);
                 else add_contribution(sh, e, thr.x * e1.x, thr.y * e1.y, thr.z * e1.z);
+                if constexpr (GLOW) {   // (the same calls, with the kernel's WfGlow behind the other arguments)
+                    if (EMIT && !MIRROR)
+                        emit_next_ray(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd,
+                                      mk3(thr.x * s1.albedo.x, thr.y * s1.albedo.y, thr.z * s1.albedo.z), false, 0.0f, 0.0f, gl);
+                    if (EMIT && MIRROR) event = emit_from_surface<SURF>(p, wf, em, sf, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, s1.albedo, gl);
+                } else {
                 if (EMIT && !MIRROR)
                     emit_next_ray(p, wf, em, tris, tile, e, O, D, obj, best_t, mh.ndotd,
                                   mk3(thr.x * s1.albedo.x, thr.y * s1.albedo.y, thr.z * s1.albedo.z));
                 if (EMIT && MIRROR) event = emit_from_surface<SURF>(p, wf, em, sf, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, s1.albedo);
+                }
             } else if (SKY) {
                 add_sky(sh, sky, e, D.y, thr);
             }
@@ -832,7 +873,7 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
                 for (int k = 0; k < 2; k++)
                     if (k ? have.y : have.x) {
                         f3 ek = k ? mk3(er.y, eg.y, eb.y) : mk3(er.x, eg.x, eb.x), le;
-                        lit[k] = add_glow(p, gl, shade, k ? obj.y : obj.x, ek, le);
+                        lit[k] = add_glow(p, gl, shade, k ? obj.y : obj.x, ek, le, lane3(R.O, k), wf_ray_marked(k ? b1.w : b0.w));
                         if (k) { er.y = ek.x; eg.y = ek.y; eb.y = ek.z; lr.y = le.x; lg.y = le.y; lb.y = le.z; }
                         else { er.x = ek.x; eg.x = ek.y; eb.x = ek.z; lr.x = le.x; lg.x = le.y; lb.x = le.z; }
                     }
@@ -854,19 +895,31 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
                 const f2 nr = thr.x * ar, ng = thr.y * ag, nb = thr.z * ab;
 #pragma unroll
                 for (int k = 0; k < 2; k++)
-                    if (k ? have.y : have.x)
+                    if (k ? have.y : have.x) {
+                        if constexpr (GLOW)
+                            emit_next_ray(p, wf, em, tris, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), k ? obj.y : obj.x, k ? best_t.y : best_t.x,
+                                          k ? best.ndotd.y : best.ndotd.x, k ? mk3(nr.y, ng.y, nb.y) : mk3(nr.x, ng.x, nb.x), false, 0.0f, 0.0f, gl);
+                        else
                         emit_next_ray(p, wf, em, tris, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), k ? obj.y : obj.x, k ? best_t.y : best_t.x,
                                       k ? best.ndotd.y : best.ndotd.x, k ? mk3(nr.y, ng.y, nb.y) : mk3(nr.x, ng.x, nb.x));
+                    }
             }
             if (EMIT && MIRROR) {   // the same, but a hit on a mirror sends T * R on, not T * albedo, in the reflected direction
                 uint32_t event[2] = {kEventNone, kEventNone};   // glass and glossy forms: what each ray's counted hit did
 #pragma unroll
                 for (int k = 0; k < 2; k++)
-                    if (k ? have.y : have.x)
+                    if (k ? have.y : have.x) {
+                        if constexpr (GLOW)
+                            event[k] = emit_from_surface<SURF>(p, wf, em, sf, tris, shade, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), k ? obj.y : obj.x,
+                                                               k ? best_t.y : best_t.x, k ? best.ndotd.y : best.ndotd.x,
+                                                               k ? mk3(thr.x.y, thr.y.y, thr.z.y) : mk3(thr.x.x, thr.y.x, thr.z.x),
+                                                               k ? mk3(ar.y, ag.y, ab.y) : mk3(ar.x, ag.x, ab.x), gl);
+                        else
                         event[k] = emit_from_surface<SURF>(p, wf, em, sf, tris, shade, tile, k ? e1 : e0, lane3(R.O, k), lane3(R.D, k), k ? obj.y : obj.x,
                                                            k ? best_t.y : best_t.x, k ? best.ndotd.y : best.ndotd.x,
                                                            k ? mk3(thr.x.y, thr.y.y, thr.z.y) : mk3(thr.x.x, thr.y.x, thr.z.x),
                                                            k ? mk3(ar.y, ag.y, ab.y) : mk3(ar.x, ag.x, ab.x));
+                    }
                 if (SURF == kSurfGlass || SURF == kSurfGloss) count_surface_events<SURF == kSurfGloss>(sf.events, event[0], event[1]);
             }
             if (EMIT) {

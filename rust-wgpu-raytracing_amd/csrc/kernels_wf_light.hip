@@ -1,0 +1,192 @@
+// Wavefront integrator, light stage (RWR_FLAG_LIGHT_SAMPLING; definition: include/rwr_hip.h).
+//
+// Every hit that sends on a DIFFUSE ray — the primary stage's h0, a trace kernel's h_k in a generation that emits — has left its
+// normal at its fixed queue slot (rwr_surface.h LightRec) and its bit in the light ballots; the ray it sent on sits in the same
+// slot of the ray queue, marked, with the origin O and the throughput T the light sample shares with it.
+//   k_wf_light   runs once behind the primary stage and once behind every generation's trace kernels but the last, on the launch
+//                group's stream, ahead of the next generation's sort: per record it chooses one emitting sphere, draws a direction
+//                uniformly over the solid angle the sphere subtends from O, and — when the ray reaches that sphere — adds
+//                clamp(T * Le * g) to the tile's sums (LDS, then the frame's planes: rwr_wf_pool.h), g = 2 M kc (n . w).
+// Work item = (tile, share of its ballot words); a wave takes one ballot word — 64 slots, one record per lane — at a time and
+// skips empty words, as k_wf_shadow does.  Every lane has its own direction, so it builds its own slab constants (make_slab_ray).
+// "Reaches" is the integrator's nearest-hit rule decided without a nearest-hit walk: the ray must hit its sphere s at t_s; a sphere
+// before s in the order occludes at t <= t_s, one behind it at t < t_s (strict '<' keeps the earlier candidate), a face at
+// t < t_s (rwr_bvh.h bvh_occluded_before).  The emitting spheres' indices and radiances arrive as a kernel argument (WfLights:
+// scalar registers), centre and radius are the frame's (FrameParams::spheres); with one emitter nothing is selected per lane.
+// Arithmetic: f32, operation for operation the header's rule and tests/light_ref.c; no contraction.
+#include <algorithm>
+#include <type_traits>
+
+#include "rwr_bvh.h"
+#include "rwr_wf_forms.h"
+#include "rwr_wf_pool.h"
+
+namespace rwr {
+
+template <bool NODES_IN_LDS, bool STACK16>
+__global__ void __launch_bounds__(256)
+k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDevice bvh, const WfBuffers wf, const WfGlow gl,
+           uint32_t n_tiles, uint32_t sample_count, uint32_t n_shares, uint32_t dim0, uint32_t sample_base, const WfLights lights)
+{
+    __shared__ TraceShared sh;
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    BvhNode4 *s_nodes = reinterpret_cast<BvhNode4 *>(s_dyn);
+    const uint32_t node_bytes = NODES_IN_LDS ? bvh.n_nodes * (uint32_t)sizeof(BvhNode4) : 0u;
+    typedef typename std::conditional<STACK16, uint16_t, uint32_t>::type StackT;
+    StackT *s_stack = reinterpret_cast<StackT *>(s_dyn + node_bytes);
+    // the tiles anything can be seen through, when the frame listed them (the others hold no record: their ballots are cleared)
+    const uint32_t n_live = wf.live_list ? (uint32_t)__builtin_amdgcn_readfirstlane((int)*wf.live_count) : n_tiles;
+    const uint32_t n_items = n_live * n_shares, n_words = sample_count * 8u;
+    const uint32_t M = lights.m;
+    const float Mf = (float)M;
+    uint32_t n_rays = 0, n_reached = 0;   // this wave's (wave-uniform)
+    bool staged = false;
+    for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const uint32_t t = item / n_shares, share = item - t * n_shares;
+        const uint32_t tile = wf.live_list ? (uint32_t)__builtin_amdgcn_readfirstlane((int)wf.live_list[t]) : t;
+        __syncthreads();   // everybody is done with the previous item's sums
+        if (NODES_IN_LDS && !staged) {
+            const float4 *src = reinterpret_cast<const float4 *>(bvh.nodes);
+            float4 *dst = reinterpret_cast<float4 *>(s_nodes);
+            for (uint32_t i = tid; i < bvh.n_nodes * 8u; i += 256u) dst[i] = src[i];
+            staged = true;
+        }
+        for (uint32_t i = tid; i < kWfTilePixels * 3u; i += 256u) sh.acc[i] = 0ull;
+        if (tid == 0u) sh.next_packet = 0u;
+        __syncthreads();
+        const size_t pool_base = (size_t)tile * wf.group * kWfTilePixels;
+        const unsigned long long *__restrict__ masks = gl.light_masks + (size_t)tile * wf.group * 8u;
+        for (;;) {   // the item's ballot words share, share + n_shares, ...: whichever wave is free takes the next
+            uint32_t j = 0u;
+            if (lane == 0u) j = atomicAdd(&sh.next_packet, 1u);
+            j = (uint32_t)__builtin_amdgcn_readfirstlane((int)j);
+            const uint32_t w = share + j * n_shares;
+            if (w >= n_words) break;
+            const unsigned long long m = masks[w];   // wave-uniform
+            if (m == 0ull) continue;
+            const bool live = (m >> lane) & 1ull;
+            const uint32_t e = w * 64u + lane;
+            float4 ra = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rb = ra, rn = ra;
+            if (live) {
+                ra = wf.rays[2u * (pool_base + e)];
+                rb = wf.rays[2u * (pool_base + e) + 1u];
+                rn = *reinterpret_cast<const float4 *>(gl.light_recs + pool_base + e);
+            }
+            const f3 O = mk3(ra.x, ra.y, ra.z), n = mk3(rn.x, rn.y, rn.z);
+            const f3 thr = mk3(wf_unorm16_lo(ra.w), wf_unorm16_hi(ra.w), wf_unorm16_lo(rb.w));
+            // the slot's pixel (as add_contribution maps it) and sample, as emit_next_ray finds them
+            const uint32_t r = e & (kWfTilePixels - 1u), wv = r >> 7, k = (r >> 6) & 1u, l = r & 63u;
+            const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (wv & 1u) * 32u + 2u * (l & 15u) + k;
+            const uint32_t py = p.row_begin + (tile / wf.tiles_x) * p.row_pitch + (wv >> 1) * 4u + (l >> 4);
+            const uint32_t pixel = py * p.width + px, sample = sample_base + e / kWfTilePixels;
+            // which sphere: one emitter needs no random number's value and no select
+            uint32_t s = lights.index[0];
+            f3 Le = mk3(lights.le[0][0], lights.le[0][1], lights.le[0][2]);
+            if (M > 1u) {   // uniform
+                const float u = rng_uniform(pixel, sample, dim0, p.seed);
+                const uint32_t i = min((uint32_t)(u * Mf), M - 1u);
+#pragma unroll
+                for (uint32_t q = 1; q < RWR_MAX_SPHERES; q++)
+                    if (q < M && i == q) { s = lights.index[q]; Le = mk3(lights.le[q][0], lights.le[q][1], lights.le[q][2]); }
+            }
+            f3 C = ld3(p.spheres[0].center);
+            float R = p.spheres[0].radius;
+            if (M > 1u || s != 0u) {   // uniform
+#pragma unroll
+                for (uint32_t q = 1; q < RWR_MAX_SPHERES; q++)
+                    if (q < p.n_spheres && s == q) { C = ld3(p.spheres[q].center); R = p.spheres[q].radius; }
+            }
+            // the cone towards the sphere
+            f3 wd = sub3(C, O);
+            const float d2 = dot3(wd, wd);
+            bool go = live && d2 > R * R;   // (an origin inside or on the sphere takes no sample)
+            const float dl = sqrtf(d2);
+            wd = mk3(wd.x / dl, wd.y / dl, wd.z / dl);
+            const float s2 = R * R / d2;
+            const float cmax = sqrtf(fmaxf(0.0f, 1.0f - s2));
+            const float kc = s2 / (1.0f + cmax);
+            float da = 0.0f, db = 0.0f;
+            for (uint32_t q = 0; q < 8u; q++) {   // bounce_direction's rejection loop, operation for operation
+                const float ua = 2.0f * rng_uniform(pixel, sample, dim0 + 1u + 2u * q, p.seed) - 1.0f;
+                const float ub = 2.0f * rng_uniform(pixel, sample, dim0 + 2u + 2u * q, p.seed) - 1.0f;
+                if (ua * ua + ub * ub <= 1.0f) { da = ua; db = ub; break; }
+            }
+            const float qq = da * da + db * db;
+            const float c = 1.0f - qq * kc;
+            const float rr = qq > 0.0f ? sqrtf(fmaxf(0.0f, 1.0f - c * c) / qq) : 0.0f;
+            // bounce_direction's basis about wd
+            const float sign = copysignf(1.0f, wd.z);
+            const float aa = -1.0f / (sign + wd.z);
+            const float bb = wd.x * wd.y * aa;
+            const f3 b1 = mk3(1.0f + sign * wd.x * wd.x * aa, sign * bb, -sign * wd.x);
+            const f3 b2 = mk3(bb, sign + wd.y * wd.y * aa, -wd.y);
+            const f3 L = mk3(rr * (da * b1.x + db * b2.x) + c * wd.x, rr * (da * b1.y + db * b2.y) + c * wd.y, rr * (da * b1.z + db * b2.z) + c * wd.z);
+            const float ndw = dot3(n, L);
+            go = go && ndw > 0.0f;
+            // visibility: the ray's own sphere, then the others by the nearest-hit rule's ties, then the mesh
+            float ts = 0.0f;
+            bool reach = go && sphere_ray_intersect_t(C, R, O, L, ts);
+            for (uint32_t q = 0; q < p.n_spheres; q++) {
+                float tq;
+                if (reach && q != s && sphere_ray_intersect_t(ld3(p.spheres[q].center), p.spheres[q].radius, O, L, tq))
+                    if (q < s ? tq <= ts : tq < ts) reach = false;
+            }
+            if (p.n_tris) {
+                const SlabRay sr = make_slab_ray(O, L);
+                bool occ;
+                if (NODES_IN_LDS) occ = bvh_occluded_before(s_nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, L, sr, ts, reach);
+                else occ = bvh_occluded_before(bvh.nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, L, sr, ts, reach);
+                reach = reach && !occ;
+            }
+            if (reach) {
+                const float g = 2.0f * Mf * kc * ndw;
+                add_contribution(sh, e, thr.x * (Le.x * g), thr.y * (Le.y * g), thr.z * (Le.z * g));
+            }
+            n_rays += (uint32_t)__popcll(__ballot(go));
+            n_reached += (uint32_t)__popcll(__ballot(reach));
+        }
+        __syncthreads();
+        flush_pool(sh, p, wf, tile);
+    }
+    if (lane == 0u && n_rays) {
+        atomicAdd(&gl.light_counts[0], (unsigned long long)n_rays);
+        if (n_reached) atomicAdd(&gl.light_counts[1], (unsigned long long)n_reached);
+    }
+}
+
+struct LightForms {   // rwr_wf_forms.h
+    struct Form { bool nodes_in_lds, stack16; };
+    static constexpr uint32_t kRange = 4u;
+    static constexpr uint32_t encode(Form f) { return f.nodes_in_lds + 2u * f.stack16; }
+    static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0}; }
+    static constexpr bool valid(Form) { return true; }
+    using Kernel = decltype(&k_wf_light<false, false>);
+    template <uint32_t I> static constexpr Kernel kernel() { return &k_wf_light<decode(I).nodes_in_lds, decode(I).stack16>; }
+};
+static constexpr auto kLightForms = form_table<LightForms>();
+static_assert(check_forms<LightForms>(4), "nodelets in LDS or not, 16-bit stacks or not");
+
+// gen: the generation whose hits' light samples these are (0: h0's, behind the primary stage) — RNG block 274 + 17 gen, behind
+// soft shadows' last (130 + 16 * 8 + 15 = 273).  expected_tiles: as launch_wf_shadow.
+hipError_t launch_wf_light(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
+                           const WfGlow &glow, const WfLights &lights, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count,
+                           uint32_t gen, uint32_t sample_base)
+{
+    if (n_tiles == 0 || sample_count == 0 || lights.m == 0) return hipSuccess;
+    const uint32_t work_tiles = std::max(1u, std::min(expected_tiles, n_tiles));
+    const uint32_t n_shares = std::max(1u, std::min(std::min(32u, sample_count * 8u), 4096u / work_tiles));
+    const dim3 grid((uint32_t)std::min<uint64_t>(2048u, (uint64_t)n_tiles * n_shares));
+    const LaneLdsPlan l = lane_lds_plan(bvh, fp, false);   // (no 1 024-thread form here)
+    hipLaunchKernelGGL(kLightForms[LightForms::encode({l.nodes_in_lds, l.stack16})], grid, dim3(256), l.bytes, s, fp, tris, bvh, wf, glow, n_tiles,
+                       sample_count, n_shares, 274u + 17u * gen, sample_base, lights);
+    return hipGetLastError();
+}
+
+hipError_t preload_kernels_wf_light()
+{
+    hipFuncAttributes attr;
+    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>((&k_wf_light<true, true>)));
+}
+
+}  // namespace rwr

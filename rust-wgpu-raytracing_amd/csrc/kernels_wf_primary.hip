@@ -401,7 +401,7 @@ k_wf_primary(const WfPrimaryArgs a)
         f2 lr = splat(0.0f), lg = splat(0.0f), lb = splat(0.0f);   // GLOW: Le(h0) of each pixel's hit
         if (GLOW) {
             kernarg<WfPrimaryArgs> *const qg = wf_args_again(ka);   // the emission table, the shading records
-            const WfGlow gl = {qg->glow.table, qg->glow.n_parts, 0u, qg->glow.hits};
+            const WfGlow gl = {qg->glow.table, qg->glow.n_parts, 0u, qg->glow.hits, nullptr, nullptr, nullptr};
             const bool parts = qg->p.n_materials > 1u;
             const ShadeRec *const shade = qg->shade;
             const i2 seen = hit & i2{in0 ? -1 : 0, in1 ? -1 : 0};   // (a pixel off the frame is no hit anyone counts)
@@ -505,6 +505,7 @@ k_wf_primary(const WfPrimaryArgs a)
                 }
                 if (bounces) {
                 v3 D1;
+                i2 lit_from = emit;   // GLOW with light sampling on: the pixels whose ray 1 is a diffuse ray
                 if (MIRROR) {
                     // each pixel's surface record (rwr_surface.h surface_record), decoded
                     kernarg<WfPrimaryArgs> *const qv = wf_args_again(ka);
@@ -533,6 +534,7 @@ k_wf_primary(const WfPrimaryArgs a)
                         }
                     }
                     const i2 diffuse = emit & ~mir & ~gl;
+                    lit_from = diffuse & ~gs;
                     v3 Dd = D, Dm = D;
                     if (__any(any2(diffuse))) Dd = bounce_direction_pair(n, base, diffuse);
                     if (__any(any2(mir))) {   // D' = D - (2 d) n, d = dot3(n, D) (rwr_device.h reflect_direction, for the pair)
@@ -569,17 +571,38 @@ k_wf_primary(const WfPrimaryArgs a)
                 kernarg<WfPrimaryArgs> *const qq = wf_args_again(ka);   // where the rays go
                 float4 *const rays = qq->wf.rays;
                 uint16_t *const bins = qq->wf.bins;
+                f2 mark = splat(0.0f);   // the records' spare half: 0xffff on a diffuse ray of a frame that samples its lights
+                if (GLOW) {
+                    const bool light_on = qq->glow.light != 0u;   // (scalar)
+                    mark = f2{(light_on && lit_from.x) ? 1.0f : 0.0f, (light_on && lit_from.y) ? 1.0f : 0.0f};
+                }
                 if (emit.x) {
                     const uint32_t slot = slot_base + lane;
                     rays[2u * slot] = make_float4(O1.x.x, O1.y.x, O1.z.x, wf_pack_unorm16x2(tr.x, tgc.x));
-                    rays[2u * slot + 1u] = make_float4(D1.x.x, D1.y.x, D1.z.x, wf_pack_unorm16x2(tb.x, 0.0f));
+                    rays[2u * slot + 1u] = make_float4(D1.x.x, D1.y.x, D1.z.x, wf_pack_unorm16x2(tb.x, mark.x));
                     bins[slot] = (uint16_t)wf_direction_bin(lane3(D1, 0));
                 }
                 if (emit.y) {
                     const uint32_t slot = slot_base + 64u + lane;
                     rays[2u * slot] = make_float4(O1.x.y, O1.y.y, O1.z.y, wf_pack_unorm16x2(tr.y, tgc.y));
-                    rays[2u * slot + 1u] = make_float4(D1.x.y, D1.y.y, D1.z.y, wf_pack_unorm16x2(tb.y, 0.0f));
+                    rays[2u * slot + 1u] = make_float4(D1.x.y, D1.y.y, D1.z.y, wf_pack_unorm16x2(tb.y, mark.y));
                     bins[slot] = (uint16_t)wf_direction_bin(lane3(D1, 1));
+                }
+                if (GLOW) {
+                    // light sampling (rwr_surface.h WfGlow::light, a scalar branch), for k_wf_light: the hit's normal goes to the slot of
+                    // every marked ray and the slot's bit into the light ballots (cleared ahead of this kernel) - behind the ray
+                    // stores, where the directions and origins are dead
+                    kernarg<WfPrimaryArgs> *const ql = wf_args_again(ka);
+                    if (ql->glow.light) {
+                        LightRec *const lrecs = ql->glow.light_recs;
+                        const unsigned long long l0 = __ballot(lit_from.x != 0), l1 = __ballot(lit_from.y != 0);
+                        if (lane == 0u) {
+                            unsigned long long *mk = ql->glow.light_masks + (size_t)(tile * wf_group + sidx) * 8u + wave * 2u;
+                            mk[0] = l0; mk[1] = l1;
+                        }
+                        if (lit_from.x) *reinterpret_cast<float4 *>(lrecs + slot_base + lane) = make_float4(n.x.x, n.y.x, n.z.x, 0.0f);
+                        if (lit_from.y) *reinterpret_cast<float4 *>(lrecs + slot_base + 64u + lane) = make_float4(n.x.y, n.y.y, n.z.y, 0.0f);
+                    }
                 }
                 }
             }

@@ -233,7 +233,19 @@ int WfFrame::glow_table()
     }
     RWR_HIP_CHECK(W.d_glow_hits.ensure(1));
     RWR_HIP_CHECK(hipMemsetAsync(W.d_glow_hits.ptr, 0, sizeof(unsigned long long), stream));
-    ft.glow = WfGlow{W.d_glow.ptr, (uint32_t)n_parts, 0u, W.d_glow_hits.ptr};
+    ft.glow = WfGlow{W.d_glow.ptr, (uint32_t)n_parts, 0u, W.d_glow_hits.ptr, nullptr, nullptr, nullptr};
+    // RWR_FLAG_LIGHT_SAMPLING: a normal per queue slot and the light ballots, per queue like the rays and kept like them (allocated by
+    // the first frame that needs them); the frame's three counts start from zero.  trace_groups points ft.glow at a queue's share.
+    ft.lights_on = rq.light;
+    if (rq.light) {
+        ft.lights = scene_lights(ctx);
+        RWR_HIP_CHECK(W.d_light_recs.ensure(n_queues * slots));
+        RWR_HIP_CHECK(W.d_light_masks.ensure(n_queues * n_tiles * group * 8u));
+        RWR_HIP_CHECK(W.d_light_counts.ensure(3));
+        RWR_HIP_CHECK(hipMemsetAsync(W.d_light_counts.ptr, 0, 3 * sizeof(unsigned long long), stream));
+        ft.glow.light = 1u;
+        ft.glow.light_counts = W.d_light_counts.ptr;
+    }
     return RWR_OK;
 }
 
@@ -268,11 +280,18 @@ int WfFrame::trace_groups(const AccumPlan &ap)
         hipStream_t gs = q ? W.streams[q].h : stream;
         if (rq.shadows) ft.shadow = WfShadow{W.d_shadow_recs.ptr + q * slots, W.d_shadow_masks.ptr + q * mask_words, W.d_shadow_counts.ptr};
         ft.shadows = ft.shadow.recs != nullptr;
+        if (ft.lights_on) {   // this queue's light records; the primary stage stores whole ballot words where it emits, the rest stay clear
+            ft.glow.light_recs = W.d_light_recs.ptr + q * slots;
+            ft.glow.light_masks = W.d_light_masks.ptr + q * mask_words;
+            RWR_HIP_CHECK(hipMemsetAsync(ft.glow.light_masks, 0, mask_words * sizeof(unsigned long long), gs));
+        }
         RWR_HIP_CHECK(launch_wf_primary(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, sl.d_ftris.ptr, tex0, tg, wfq[q],
                                         (uint32_t)ap.before + s0, cnt, z_split, ft));
         if (rq.shadows)   // h0's shadow rays
             RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere, 0u,
                                            (uint32_t)ap.before + s0, soft, &shadow_plan));
+        if (ft.lights_on)   // h0's light samples: ray 1 sits in the queue, the first sort has not run
+            RWR_HIP_CHECK(launch_wf_light(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.glow, ft.lights, n_tiles, shadow_tiles, cnt, 0u, (uint32_t)ap.before + s0));
         // the bounce stage: one generation of rays per bounce (RWR_FLAG_MULTI_BOUNCE: up to RWR_MAX_BOUNCES).  Generation k traces
         // ray k of every path that is still alive — the sort and trace kernels run again over the same fixed slots — and, unless
         // it is the last, writes ray k + 1 back into the slot of every hit, with its bit in the other ballot array.
@@ -286,12 +305,15 @@ int WfFrame::trace_groups(const AccumPlan &ap)
             ft.emit = emit ? WfEmit{masks_next, 2u + 16u * gen, (uint32_t)ap.before + s0} : WfEmit{nullptr, 0u, 0u};
             if (emit) RWR_HIP_CHECK(hipMemsetAsync(masks_next, 0, mask_words * sizeof(unsigned long long), gs));
             if (rq.shadows) RWR_HIP_CHECK(hipMemsetAsync(ft.shadow.masks, 0, mask_words * sizeof(unsigned long long), gs));   // the trace kernels set bits
+            if (ft.lights_on && emit) RWR_HIP_CHECK(hipMemsetAsync(ft.glow.light_masks, 0, mask_words * sizeof(unsigned long long), gs));   // likewise
             RWR_HIP_CHECK(launch_wf_bounce(gs, fp, ctx->d_tris.ptr, ctx->d_shade.ptr, bvh, tex0, wg, n_tiles, cnt,
                                            (uint32_t)std::fmax(1.0f, std::ceil(ctx->wf_packet_fill * (float)(cnt * kWfTilePixels))),
                                            W.d_pool_info.ptr + q * n_tiles * wf_pool_info_bytes(), W.d_pool_list.ptr + q * 2u * (size_t)n_tiles, ft, &trace_plan));
             if (rq.shadows)   // this generation's hits
                 RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere, gen,
                                                (uint32_t)ap.before + s0, soft, &shadow_plan));
+            if (ft.lights_on && emit)   // the light samples of this generation's hits, from the rays it just wrote, ahead of the next sort
+                RWR_HIP_CHECK(launch_wf_light(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.glow, ft.lights, n_tiles, shadow_tiles, cnt, gen, (uint32_t)ap.before + s0));
             if (emit) std::swap(wg.masks, masks_next);
         }
         if (rp.max_bounces && s0 + group >= rp.spp) last_counters = wfq[q].counters;

@@ -254,6 +254,62 @@ RWR_DEV bool bvh_occluded(NodePtr nodes, const uint32_t *__restrict__ leaf_faces
     return bvh_occluded(nodes, leaf_faces, tris, n_faces, stack, O, D, slab_ray_from(sd, O), active);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Any-hit traversal with a distance limit (light rays, RWR_FLAG_LIGHT_SAMPLING): is any face hit at t < tmax?  tmax is per lane —
+// the distance at which the lane's ray meets the sphere it is aimed at.  A face is an occluder exactly when the nearest-hit rule
+// would prefer it to that sphere (the mesh wins with strict '<'): the same t, by the same operations, as intersect_and_select's.
+// The bound also prunes: bvh_inner_step drops a box whose entry distance, slack taken off, lies beyond tmax — conservative, since
+// a face inside such a box has t >= the entry distance.  An OR over faces again: any visiting order gives the brute-force answer.
+
+// occludes_any_order with the limit: triangleRayIntersect's verdict and t < tmax
+RWR_DEV bool occludes_before_any_order(const TriRecord &T, f3 O, f3 D, float tmax)
+{
+    const f3 N = ld3(T.N);
+    const float ndotd = dot3(N, D);
+    bool hit = !(fabsf(ndotd) < kEpsilon);              // :94
+    const float t = -(dot3(N, O) + T.d) / ndotd;        // :99-102
+    hit &= !(t < 0.0f);                                 // :105
+    hit &= t < tmax;
+    if (!__any(hit)) return false;
+    const f3 P = along(O, t, D);                        // :110
+    f3 C = cross3(ld3(T.e0), sub3(P, ld3(T.p0)));       // :115-117
+    hit &= !(dot3(N, C) < 0.0f);                        // :118
+    if (!__any(hit)) return false;
+    C = cross3(ld3(T.e1), sub3(P, ld3(T.p1)));          // :123-125
+    hit &= !(dot3(N, C) < 0.0f);                        // :127
+    if (!__any(hit)) return false;
+    C = cross3(ld3(T.e2), sub3(P, ld3(T.p2)));          // :132-134
+    hit &= !(dot3(N, C) < 0.0f);                        // :136
+    return hit;
+}
+
+// One ray per lane with its slab constants sr and its limit tmax; lanes with `active` unset only keep the wave company.
+template <typename NodePtr, typename StackT>
+RWR_DEV bool bvh_occluded_before(NodePtr nodes, const uint32_t *__restrict__ leaf_faces, const TriRecord *__restrict__ tris,
+                                 uint32_t n_faces, StackT *stack, f3 O, f3 D, const SlabRay &sr, float tmax, bool active)
+{
+    const uint32_t stride = blockDim.x;
+    StackT *sp = stack + threadIdx.x;
+    StackT *const sp0 = sp;
+    uint32_t cur = 0;  // the root is always an inner node
+    bool have_cur = active, occluded = false;
+    while (__any(have_cur)) {
+        while (have_cur && !(cur & kBvhLeafBit))
+            have_cur = bvh_inner_step(nodes, sr, tmax, cur, sp, sp0, stride);
+        if (have_cur) {
+            const uint32_t first = (cur & ~kBvhLeafBit) >> 3, count = (cur & 7u) + 1u;
+            for (uint32_t k = 0; k < count; k++) {
+                if (first + k >= n_faces) break;  // (as bvh_leaf_step)
+                const uint32_t idx = leaf_faces[first + k];
+                if (idx < n_faces && occludes_before_any_order(tris[idx], O, D, tmax)) occluded = true;
+            }
+            if (occluded || sp == sp0) have_cur = false;
+            else { sp -= stride; cur = bvh_stack_dec(*sp); }
+        }
+    }
+    return occluded;
+}
+
 // Host side: the dynamic LDS of a kernel that walks the BVH per lane (k_wf_trace_lane, k_wf_shadow), [nodelets][traversal stacks].
 //   stack16       node indices and leaf links (first << 3 | count - 1) fit 15 bits: 16-bit stack entries.  bvh.no_stack16
 //                 (RWR_WF_STACK16=0) takes them away from a scene that would have them — never the other way round — and with

@@ -166,6 +166,12 @@ struct WfState {
     OwnedEvent glow_copied;
     uint64_t glow_version = 0;
     DeviceBuffer<unsigned long long> d_glow_hits;
+    // RWR_FLAG_LIGHT_SAMPLING, allocated by the first frame that samples its lights: per ray queue a 16-byte record per slot (the
+    // hit's normal, WfGlow::light_recs) and the light ballots (layout of d_masks), kept like the queues; the frame's three counts
+    // {light rays, reached, silenced hits} (WfGlow::light_counts), zeroed per frame
+    DeviceBuffer<LightRec> d_light_recs;
+    DeviceBuffer<unsigned long long> d_light_masks;
+    DeviceBuffer<unsigned long long> d_light_counts;
 };
 
 // Progressive accumulation (RWR_FLAG_ACCUMULATE): ONE accumulation per context.  Its sums and the first frame's sample-0 planes
@@ -339,6 +345,7 @@ struct rwr_context {
     std::vector<rwr::SurfaceRec> part_glow;
     rwr::SurfaceRec sphere_glow[RWR_MAX_SPHERES]{};
     uint64_t glow_version = 1;
+    rwr::WfLights lights{};   // RWR_FLAG_LIGHT_SAMPLING: the emitting spheres in use (scene.cpp rebuild_lights: after the emission setters and rwr_scene_set_spheres)
     rwr_triangle_buffer_data triangles[RWR_MAX_TRIANGLES]{};
     uint32_t n_triangles = 0;
 
@@ -349,6 +356,7 @@ struct rwr_context {
     bool last_shadows = false;      // the last render call traced shadow rays (RWR_FLAG_SHADOWS): their counters are in its WfState
     bool last_gloss = false;        // the last render call ran the glossy forms (RWR_FLAG_GLOSSY): their counter is d_surface_events[kEventGlossy]
     bool last_glass = false;        // the last render call ran the glass forms (RWR_FLAG_GLASS): their counters are in its WfState
+    bool last_light = false;        // the last render call sampled its lights (RWR_FLAG_LIGHT_SAMPLING): the counts are its WfState's d_light_counts
     bool last_glow = false;         // the last render call ran the GLOW forms (RWR_FLAG_EMISSIVE): their counter is its WfState's d_glow_hits
     // optional per-kernel timing (rwr_ctx_set_kernel_timing)
     uint32_t timing_every = 0;
@@ -415,6 +423,8 @@ inline bool scene_glows(const rwr_context *ctx)
         if (glows(ctx->sphere_glow[i])) return true;
     return false;
 }
+// the emitting spheres in use, in index order (RWR_FLAG_LIGHT_SAMPLING: s_0 < ... < s_{M-1}); scene.cpp keeps ctx->lights equal to it
+inline WfLights scene_lights(const rwr_context *ctx) { return ctx->lights; }
 
 // context.cpp: per-frame buffers of every active slot for the current scene and screen
 hipError_t ensure_frame_buffers(rwr_context *ctx);

@@ -19,6 +19,7 @@ struct FrameRequest {
     bool sky;         // RWR_FLAG_SKY with at least one bounce: the trace kernels' SKY forms (without a bounce the bit is cleared from rp.flags)
     bool soft;        // RWR_FLAG_SOFT_SHADOWS with RWR_FLAG_SHADOWS and a radius that is not 0: k_wf_shadow's SOFT forms (else the bit is cleared from rp.flags)
     bool glow;        // RWR_FLAG_EMISSIVE with an emitting surface in the scene: the GLOW forms (else the bit is cleared from rp.flags)
+    bool light;       // RWR_FLAG_LIGHT_SAMPLING with RWR_FLAG_EMISSIVE effective, a bounce and an emitting sphere in use: k_wf_light (else the bit is cleared from rp.flags)
     bool wavefront;   // the wavefront integrator renders it (several samples, a bounce, or an accumulation)
     bool dormant;     // the reference's dormant parts (single-triangle passes, orthographic rays) have their own plain kernel
 };

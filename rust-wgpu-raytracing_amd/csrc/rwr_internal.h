@@ -12,8 +12,10 @@ namespace rwr {
 
 // Internal debug flag (not in the public header): with RWR_FLAG_AUX_OUTPUTS, the
 // obj_id plane receives the number of block-level candidate faces and the hit_t
-// plane the number of faces the pixel's wave ran the exact test on.
-constexpr uint32_t RWR_FLAG_DEBUG_COUNTS = 1u << 16;
+// plane the number of faces the pixel's wave ran the exact test on.  (Bit 20: bit 16, which it had, is the public header's
+// RWR_FLAG_LIGHT_SAMPLING now; the internal bits lie above the public ones.)
+constexpr uint32_t RWR_FLAG_DEBUG_COUNTS = 1u << 20;
+
 // Internal: render frames with the one-pixel-per-lane kernel (k_primary) instead of the
 // two-pixels-per-lane one (k_primary_p2); both must give identical results.
 constexpr uint32_t RWR_FLAG_ONE_PIXEL_PER_LANE = 1u << 17;
@@ -24,6 +26,8 @@ constexpr uint32_t RWR_FLAG_TILE_CLASS = 1u << 18;
 // slot's records made (launch_records: a key hit): the kernel reads the tiles' cover words (kTileCovered below) and writes the ones
 // it learns.  Clear (a key miss, RWR_TILE_COVER=0, any other form): the kernel neither reads nor writes them.
 constexpr uint32_t RWR_FLAG_TILE_COVER = 1u << 19;
+constexpr uint32_t kInternalFlags = RWR_FLAG_DEBUG_COUNTS | RWR_FLAG_ONE_PIXEL_PER_LANE | RWR_FLAG_TILE_CLASS | RWR_FLAG_TILE_COVER;
+static_assert((kInternalFlags & (2u * (uint32_t)RWR_FLAG_LIGHT_SAMPLING - 1u)) == 0u, "an internal bit is no public flag: they lie above the header's last");
 
 // ---------------------------------------------------------------------------
 // Device-side scene records (data layout in HBM, see DESIGN.md §"Data layout").
@@ -366,10 +370,12 @@ struct WfFeatures {
     WfShadow shadow{nullptr, nullptr, nullptr};
     WfSky sky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     WfSurfaces surfaces{nullptr, 0u, 0u, nullptr};   // rwr_surface.h
-    WfGlow glow{nullptr, 0u, 0u, nullptr};           // rwr_surface.h
+    WfGlow glow{nullptr, 0u, 0u, nullptr, nullptr, nullptr, nullptr};   // rwr_surface.h
     bool emits = false, shadows = false, sky_on = false;
     bool glows = false;   // RWR_FLAG_EMISSIVE with an emitter in the scene: the GLOW forms of all three kernels, which read `glow`
     bool soft = false;   // RWR_FLAG_SOFT_SHADOWS: k_wf_shadow's SOFT forms (no other kernel looks)
+    bool lights_on = false;   // RWR_FLAG_LIGHT_SAMPLING: glow.light is set, k_wf_light runs (kernels_wf_light.hip) with `lights`
+    WfLights lights{};        // rwr_surface.h
     int surf = kSurfNone;   // the surface models of the frame's flags (kSurfGlass: the table may hold glass records; kSurfGloss: glossy ones too)
     // The two rules for SURF.  The surface forms differ where a ray is emitted and nowhere else: the primary stage has one only
     // when the frame bounces at all, a trace kernel only in a generation that emits (a kernel that ends a path has none).
@@ -444,6 +450,11 @@ hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecor
                             const WfShadow &shadow, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count, const float light_mesh[3],
                             const float light_sphere[3], uint32_t gen, uint32_t sample_base, const rwr_shadow_params *soft,
                             LanePlanRecord *plan = nullptr);
+// kernels_wf_light.hip (RWR_FLAG_LIGHT_SAMPLING): the light samples of the hits whose diffuse rays generation `gen` emitted (0: the
+// primary stage), from glow's records and ballots, added to wf's sums; the rays traced and reached into glow.light_counts
+hipError_t launch_wf_light(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
+                           const WfGlow &glow, const WfLights &lights, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count,
+                           uint32_t gen, uint32_t sample_base);
 size_t wf_pool_info_bytes();
 // RWR_WF_STATS=1: trace launches of this process so far {packet kernel, per-lane kernel, its 1 024-thread form}
 void wf_trace_launch_counts(uint64_t out[3]);
@@ -549,6 +560,7 @@ hipError_t preload_kernels_wavefront();
 hipError_t preload_kernels_wf_primary();
 hipError_t preload_kernels_wf_bounce();
 hipError_t preload_kernels_wf_shadow();
+hipError_t preload_kernels_wf_light();
 hipError_t preload_kernels_dist();
 
 // kernels_dist.hip: the interleaved partition's gather (layout: rwr_strips.h) — every rank packs its strips into one message,

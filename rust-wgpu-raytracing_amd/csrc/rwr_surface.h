@@ -114,11 +114,30 @@ struct WfSurfaces {
 // WfSurfaces::table (surface_record below).  Emission stands beside a surface's model: a record here says nothing about `on` there.
 // hits: the frame's count of shaded hits with Le != 0, one atomic per wave (count_glow_hits).  A kernel argument of its own behind
 // the others (cf. WfSurfaces), so that the forms without GLOW read their arguments where they did.
+// Light sampling (RWR_FLAG_LIGHT_SAMPLING; kernels_wf_light.hip) rides on the GLOW forms behind a run-time switch, `light` (wave-
+// uniform: a scalar branch; 0 in every frame without the flag, whose GLOW forms then do what they did).  With it on, the kernel
+// that sends on a DIFFUSE ray from a hit — the primary stage, emit_next_ray — marks the ray's record (upper 16 bits of its last
+// word), leaves the hit's normal at the slot (light_recs, 16 B per queue slot) and sets the slot's bit in the light ballots
+// (light_masks: layout of WfBuffers::masks, cleared per generation); and add_glow takes Le as 0 for the hit of a marked ray on an
+// emitting sphere seen from outside (the light sample of the ray's origin has that light already) and counts it in
+// light_counts[2] ([0], [1]: k_wf_light's rays traced and rays that reached their sphere).
+struct LightRec { float n[3]; uint32_t pad; };
+static_assert(sizeof(LightRec) == 16, "LightRec is 16 B");
 struct WfGlow {
     const SurfaceRec *table;
     uint32_t n_parts;
-    uint32_t pad;
+    uint32_t light;
     unsigned long long *hits;
+    LightRec *light_recs;
+    unsigned long long *light_masks;
+    unsigned long long *light_counts;
+};
+// The emitting spheres in use, s_0 < ... < s_{M-1} (rwr_hip.h RWR_FLAG_LIGHT_SAMPLING): index and radiance; centre and radius are
+// FrameParams::spheres[index]'s.  A kernel argument of k_wf_light: scalar registers.
+struct WfLights {
+    uint32_t m;
+    uint32_t index[8];
+    float le[8][3];
 };
 constexpr float kMaxEmission = 64.0f;   // RWR_MAX_EMISSION
 // the record of a surface of radiance rgb (each in [0, kMaxEmission]: the setters refuse anything else; -0.0 is stored as +0.0, so

@@ -300,6 +300,20 @@ int rwr_scene_get_sphere_gloss(rwr_context *ctx, uint32_t sphere, int *is_glossy
 // Emission (RWR_FLAG_EMISSIVE): an attribute beside the surface's model, with the same index rules — a record of its own per part
 // and per sphere index, so that neither kind of setter touches the other's.
 
+// RWR_FLAG_LIGHT_SAMPLING: the list of the emitting spheres in use — index below the count rwr_scene_set_spheres gave, radiance not
+// zero — in index order.  Rebuilt by whatever changes it: the sphere emission setter and rwr_scene_set_spheres.
+static void rebuild_lights(rwr_context *ctx)
+{
+    WfLights l{};
+    for (uint32_t i = 0; i < ctx->n_spheres; i++)
+        if (glows(ctx->sphere_glow[i])) {
+            l.index[l.m] = i;
+            l.le[l.m][0] = ctx->sphere_glow[i].r; l.le[l.m][1] = ctx->sphere_glow[i].g; l.le[l.m][2] = ctx->sphere_glow[i].b;
+            l.m++;
+        }
+    ctx->lights = l;
+}
+
 // the emission record of part / sphere `index`; NULL: refused, RWR_ERR_INVALID_ARGUMENT is set
 static SurfaceRec *glow_at(rwr_context *ctx, bool sphere, uint32_t index)
 {
@@ -331,6 +345,7 @@ static int set_glow(rwr_context *ctx, bool sphere, uint32_t index, const float *
     ctx->scene_generation++;   // (a refused call never gets here)
     *at = g;
     ctx->glow_version++;
+    if (sphere) rebuild_lights(ctx);
     return RWR_OK;
 }
 
@@ -366,6 +381,7 @@ int rwr_scene_set_spheres(rwr_context *ctx, const rwr_sphere_buffer_data *sphere
     if (n && !spheres) return set_error(RWR_ERR_INVALID_ARGUMENT, "spheres is NULL");
     for (uint32_t i = 0; i < n; i++) ctx->spheres[i] = spheres[i];
     ctx->n_spheres = n;
+    rebuild_lights(ctx);
     return RWR_OK;
 }
 

@@ -154,6 +154,13 @@ public:
         check(rwr_last_emission_stats(ctx_, &n));
         return n;
     }
+    // extension (RWR_FLAG_LIGHT_SAMPLING): the light rays of the frame rendered last and those that reached their sphere
+    void light_rays(uint64_t &rays, uint64_t &reached)
+    {
+        uint64_t silenced = 0;
+        rays = reached = 0;
+        check(rwr_last_light_stats(ctx_, &rays, &reached, &silenced));
+    }
     // extension (RWR_FLAG_GLOSSY): the rays the glossy hits of the frame rendered last sent on
     uint64_t glossy_rays()
     {

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Compare the device code of two builds of one kernel file, kernel by kernel, as text.
 
-usage: tools/asm_identity.py PARENT.s CHANGE.s [--rename OLD=NEW ...] [--diff-summary] [--cxxfilt PATH]   (ROCm's llvm-cxxfilt, else c++filt)
+usage: tools/asm_identity.py PARENT.s CHANGE.s [--rename OLD=NEW ...] [--skip REGEX] [--diff-summary] [--cxxfilt PATH]   (ROCm's llvm-cxxfilt, else c++filt)
 
 The inputs are listings of `hipcc --offload-arch=gfx950 --cuda-device-only -S` with the Makefile's HIPFLAGS (tools/isa_stats.sh).
 A kernel is every function with an .amdhsa_kernel block; its text runs from its .type line to the end of its `; Kernel info`
 comments: instructions, the kernel descriptor and the resource comments.  Kernels are paired by demangled name, after --rename has
-replaced OLD by NEW in the parent's names (a type of the signature that the change renamed).  Normalised before the comparison, since
+replaced OLD by NEW in the parent's names (a type of the signature that the change renamed); kernels whose demangled name matches --skip
+are left out on both sides and counted (forms that are meant to change, such as the GLOW forms: ", true>\(").  Normalised before the comparison, since
 another function earlier in the file shifts them: the kernel's own symbol, the block labels (.LBB<n>_, BB<n>_ in loop comments),
 the .Lfunc_begin / .Lfunc_end ordinals and the column at which a trailing comment starts.  Nothing else is touched.
 
@@ -85,16 +86,20 @@ def main():
     ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     llvm = "/opt/rocm/llvm/bin/llvm-cxxfilt"
     ap.add_argument("--cxxfilt", default=llvm if os.path.exists(llvm) else shutil.which("c++filt"))
+    ap.add_argument("--skip", metavar="REGEX", help="leave out the kernels whose demangled name matches, on both sides")
     ap.add_argument("--diff-summary", action="store_true", help="print which lines the differing kernels differ in, as a histogram; kernels only in change by template, differing kernels by name only where a figure moved")
     a = ap.parse_args()
     renames = [r.split("=", 1) for r in a.rename]
-    sides = []
+    sides, skipped = [], [0, 0]
     for path, is_parent in ((a.parent, True), (a.change, False)):
         ks, spills = kernels(path)
         names = demangle(sorted(ks), a.cxxfilt)
         by_name = {}
         for sym, body in ks.items():
             name = names[sym]
+            if a.skip and re.search(a.skip, name):
+                skipped[0 if is_parent else 1] += 1
+                continue
             if is_parent:
                 for old, new in renames:
                     name = name.replace(old, new)
@@ -108,6 +113,8 @@ def main():
     lines = sum(parent[n][1]["instructions"] for n in both)
     print(f"{a.parent} -> {a.change}: parent {len(parent)} kernels, change {len(change)} kernels, {lines} instruction lines compared; "
           f"only in parent {len(only_parent)}, only in change {len(only_change)}, identical {len(both) - len(differing)}, differing {len(differing)}")
+    if a.skip:
+        print(f"  left out by --skip '{a.skip}': {skipped[0]} of the parent's kernels, {skipped[1]} of the change's")
     for n in only_parent:
         print("  only in parent: " + n)
     if a.diff_summary and only_change:   # (by template: a summary names no kernel that has no counterpart to differ from)

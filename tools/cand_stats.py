@@ -3,7 +3,7 @@ import sys, os, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as g
 r = g.load_package()
-DEBUG_COUNTS = 1 << 16
+DEBUG_COUNTS = 1 << 20
 for scene, eye, (w, h) in [("suzanne_lowpoly.obj", (0, 0, 0), (1920, 1080)), ("suzanne_lowpoly.obj", (0, 0, 3), (1920, 1080)),
                            ("cube.obj", (0, 0, 0), (256, 256))]:
     m = r.load_model_compute(scene)
