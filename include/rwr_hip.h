@@ -483,13 +483,14 @@ enum {
                                           contracts; RWR_FLAG_DENOISE and RWR_FLAG_REPROJECT are stages behind the resolve and do not know.
                                        8. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED,
                                           whatever the scene holds.
-                                       A ray is aimed at an emitting sphere only under RWR_FLAG_LIGHT_SAMPLING; an emitting part is
-                                       found by chance, and its light is noisy at low sample counts. */
-    RWR_FLAG_LIGHT_SAMPLING = 1u << 16 /* extension: light sampling (next-event estimation) towards emitting SPHERES — every diffuse hit
+                                       A ray is aimed at an emitting sphere only under RWR_FLAG_LIGHT_SAMPLING and at an emitting part
+                                       only under RWR_FLAG_LIGHT_PARTS; without them a lamp is found by chance, and its light is noisy
+                                       at low sample counts. */
+    RWR_FLAG_LIGHT_SAMPLING = 1u << 16, /* extension: light sampling (next-event estimation) towards emitting SPHERES — every diffuse hit
                                        that sends a ray on also sends one ray towards an emitting sphere, so that a small lamp lights a
-                                       room at few samples.  Emitting mesh parts are out of scope (they would need a per-part area
-                                       distribution): they are found by chance as before and their Le is never suppressed.  There is
-                                       no multiple importance sampling, and mirror, glass and glossy hits send no light ray.  Without
+                                       room at few samples.  Emitting mesh parts are RWR_FLAG_LIGHT_PARTS' (an area distribution over
+                                       their faces): under this flag alone they are found by chance as before and their Le is never
+                                       suppressed.  There is no multiple importance sampling, and mirror, glass and glossy hits send no light ray.  Without
                                        the flag every frame is what it was, byte for byte.  All arithmetic f32, no contraction.
                                        1. The flag is effective only while RWR_FLAG_EMISSIVE is effective, max_bounces >= 1 and at
                                           least one sphere in use (index below the count rwr_scene_set_spheres gave) emits; otherwise it
@@ -520,7 +521,7 @@ enum {
                                        4. No double counting: a diffuse ray from origin O that hits an emitting sphere s in use with
                                           dot3(C - O, C - O) > R*R takes Le(hit) as 0 everywhere in RWR_FLAG_EMISSIVE's rule — shading,
                                           ambient part, rwr_last_emission_stats.  Every other hit keeps Le: h0, the hits of mirror, glass
-                                          and glossy rays, hits from inside the sphere, emitting parts.
+                                          and glossy rays, hits from inside the sphere, emitting parts (those until RWR_FLAG_LIGHT_PARTS' item 8 silences them).
                                        5. Everything else is the frame's with RWR_FLAG_EMISSIVE alone, bit for bit: primary, bounce and
                                           shadow rays, throughputs, existing RNG dimensions, rwr_last_render_stats, the shadow, glass and
                                           gloss stats, rwr_last_traversal_plan, the depth, id and t planes.  The light ray needs no
@@ -532,7 +533,60 @@ enum {
                                           RNG keys are global pixel and global sample: frames in flight, row bands, strips, the multi-GPU
                                           gather, accumulation and every schedule give the same bytes.
                                        7. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
+    /* bits 17-20 are reserved: the library's internal flags (RWR_FLAGS_RESERVED below) */
+    RWR_FLAG_LIGHT_PARTS = 1u << 21    /* extension: light sampling towards emitting mesh PARTS — the light sample of an eligible hit may
+                                       aim at a point of a face of an emitting part (the "mesh light"), so that a room lit by a ceiling
+                                       panel converges at few samples.  Independent of RWR_FLAG_LIGHT_SAMPLING: either, both or neither.
+                                       Without this flag every frame is what it was, byte for byte — frames with RWR_FLAG_LIGHT_SAMPLING
+                                       and emitting parts included.  There is no multiple importance sampling; emitters emit from both
+                                       sides; mirror, glass and glossy hits send no light ray.  All arithmetic f32, no contraction,
+                                       except the host table of item 2.
+                                       1. The mesh light is the list of the world faces (after instancing) whose part emits and whose
+                                          area is greater than 0, in face-index order.  It changes with the scene and the part emission
+                                          setter, so it is part of the scene's generation.
+                                       2. The host table, one 16-byte record {float cdf; uint32 face; float inv_pdf; uint32 pad} per
+                                          listed face; all sums in double, rounded to f32 once, on storing.  A_f = 0.5 |(p1 - p0) x
+                                          (p2 - p0)| from the world-space vertices; w_f = A_f (Le_r + Le_g + Le_b) of the face's part;
+                                          W the running sum of the w_f in list order; cdf_f that running sum over W, the last entry
+                                          forced to 1.0f; inv_pdf_f = W / (Le_r + Le_g + Le_b): the reciprocal of the area density of a
+                                          point of the face (choice w_f / W times 1 / A_f).
+                                       3. The flag is effective only while RWR_FLAG_EMISSIVE is effective, max_bounces >= 1 and the list
+                                          is not empty; otherwise it is cleared before the frame's kernels are chosen and the frame is
+                                          the frame without it.  RWR_FLAG_LIGHT_SAMPLING keeps its own item 1.  M: the emitting spheres
+                                          in use when that flag is effective, else 0; Q: 1 when this flag is effective, else 0; L = M + Q.
+                                       4. Eligible hits, O, T, n and the RNG block d = 274 + 17 k are RWR_FLAG_LIGHT_SAMPLING's items 2
+                                          and 3, unchanged: one light ray per eligible hit, no random number moves and none is added.
+                                       5. Choosing the light: u = rng(d); i = min((uint32)(u * (float)L), L - 1) (with L = 1, i = 0 and
+                                          no random number picks).  i < M: sphere s_i by RWR_FLAG_LIGHT_SAMPLING's item 3, with M
+                                          replaced by L in g.  i == M: the mesh light, item 6.
+                                       6. The face sample.  uf = rng(d + 1); the face f is that of the first list entry j with
+                                          uf < cdf_j (binary search).  u1 = rng(d + 2), u2 = rng(d + 3); if u1 + u2 > 1 then u1 = 1 - u1,
+                                          u2 = 1 - u2.  P = (p0 + u1*(p1 - p0)) + u2*(p2 - p0) per component, from the face's world-space
+                                          vertices as the kernels hold them.  v = P - O; d2 = dot3(v, v); !(d2 > 0): no sample.
+                                          dl = sqrtf(d2); omega = v / dl per component.  ndw = dot3(n, omega); !(ndw > 0): no ray is traced.
+                                          N_f = normalize(cross(p1 - p0, p2 - p0)), the face's unit normal as the kernels hold it (v / sqrtf(
+                                          dot3(v, v)) per component); cf = fabsf(dot3(N_f, omega)): both sides emit.
+                                          g = (((((float)L * inv_pdf_f) * ndw) * cf) * 0.318309886f) / d2, in that order; per channel the
+                                          term is T.c * (Le.c * g), Le the radiance of f's part, converted and capped to [0, 64] like a
+                                          bounce term (NaN as 0) and added to the same fixed-point sums.  A path adds no more terms than
+                                          under RWR_FLAG_LIGHT_SAMPLING.
+                                       7. The ray (O, omega) REACHES f when the nearest hit along it under the integrator's own rule —
+                                          spheres in order, strict '<', then the mesh if closer, the lowest face index winning ties — is
+                                          face f: the ray hits f at t_f, no sphere at t <= t_f, no face g at t_g < t_f or at t_g == t_f
+                                          with g < f.  A sample whose ray rounding lets miss f does not reach.
+                                       8. No double counting: a diffuse ray (marked, item 4) whose hit is a face of an emitting part
+                                          takes Le(hit) as 0 everywhere in RWR_FLAG_EMISSIVE's rule — shading, ambient part,
+                                          rwr_last_emission_stats — while this flag is effective, and is counted as suppressed.  h0 and
+                                          the hits of mirror, glass and glossy rays keep Le; so does an emitting sphere unless
+                                          RWR_FLAG_LIGHT_SAMPLING's item 4 silences it.
+                                       9. Everything else as RWR_FLAG_LIGHT_SAMPLING's items 5 and 6: the bit (after item 3) is part of
+                                          RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's effective flags; rwr_last_light_stats
+                                          counts the light stage's totals, rwr_last_part_light_stats the mesh light's share of each.
+                                       10. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
 };
+/* every flag above, and the bits between them that the library keeps for itself: a caller sets none of the latter */
+#define RWR_FLAGS_RESERVED (0xfu << 17)
+#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21))
 
 #define RWR_MAX_BOUNCES 8u
 
@@ -893,6 +947,12 @@ RWR_API int rwr_last_emission_stats(rwr_context *ctx, uint64_t *emissive_hits);
  * d2 > R*R and ndw > 0), those that reached their sphere, and the hits whose Le item 4 took as 0.  Zeros for a frame the flag did
  * nothing to.  Exact counts.  Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_last_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits);
+
+/* RWR_FLAG_LIGHT_PARTS: the mesh light's share of each of rwr_last_light_stats' counts (which stay the light stage's totals) — the
+ * light rays aimed at a face (item 6: d2 > 0 and ndw > 0), those that reached it, and the hits on faces of emitting parts whose
+ * Le item 8 took as 0.  Zeros for a frame the flag did nothing to.  Exact counts.  Waits for the frame.  A NULL argument is
+ * RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_last_part_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits);
 
 /* Progressive accumulation (RWR_FLAG_ACCUMULATE).  One context holds one accumulation.
  * rwr_accum_reset: the next accumulating frame starts over at N = 0 (host-side only, nothing waits).

@@ -57,6 +57,7 @@ FLAG_GLOSSY = 1 << 13        # parts and spheres marked as glossy send on a ray 
 FLAG_SOFT_SHADOWS = 1 << 14  # FLAG_SHADOWS' two lights get an angular size: penumbrae (include/rwr_hip.h)
 FLAG_EMISSIVE = 1 << 15      # parts and spheres with an emission (set_part_emission, set_sphere_emission) give off light (include/rwr_hip.h)
 FLAG_LIGHT_SAMPLING = 1 << 16  # every diffuse hit also sends a ray towards an emitting sphere: next-event estimation (include/rwr_hip.h)
+FLAG_LIGHT_PARTS = 1 << 21     # ... or towards a point on a face of an emitting part, the mesh light (include/rwr_hip.h; bits 17-20 are reserved)
 MAX_EMISSION = 64.0          # RWR_MAX_EMISSION: the largest component of a radiance
 SHADOW_PARAMS_DTYPE = np.dtype([("mesh_light_radius", "<f4"), ("sphere_light_radius", "<f4")])
 REPROJECT_PARAMS_DTYPE = np.dtype([("max_history", "<u4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
@@ -142,7 +143,7 @@ def lib() -> C.CDLL:
         "rwr_last_gloss_stats": [vp, vp],
         "rwr_scene_set_part_emission": [vp, u32, vp], "rwr_scene_set_sphere_emission": [vp, u32, vp],
         "rwr_scene_get_part_emission": [vp, u32, vp, vp], "rwr_scene_get_sphere_emission": [vp, u32, vp, vp],
-        "rwr_last_emission_stats": [vp, vp], "rwr_last_light_stats": [vp, vp, vp, vp],
+        "rwr_last_emission_stats": [vp, vp], "rwr_last_light_stats": [vp, vp, vp, vp], "rwr_last_part_light_stats": [vp, vp, vp, vp],
         "rwr_camera_build_inv_uniform": [vp, vp], "rwr_circle_controller_update": [f32, u32, vp],
         "rwr_load_model_compute": [C.c_char_p, C.c_char_p, vp], "rwr_model_free": [vp],
         "rwr_model_info": [vp, vp, vp, vp, vp, vp, vp], "rwr_scene_upload_model": [vp, vp],
@@ -167,7 +168,7 @@ def lib() -> C.CDLL:
                            "rwr_last_reproject_stats", "rwr_reproject_readback", "rwr_scene_set_part_gloss", "rwr_scene_set_sphere_gloss",
                            "rwr_scene_get_part_gloss", "rwr_scene_get_sphere_gloss", "rwr_last_gloss_stats",
                            "rwr_shadow_set_params", "rwr_shadow_get_params", "rwr_scene_set_part_emission", "rwr_scene_set_sphere_emission",
-                           "rwr_scene_get_part_emission", "rwr_scene_get_sphere_emission", "rwr_last_emission_stats", "rwr_last_light_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_scene_get_part_emission", "rwr_scene_get_sphere_emission", "rwr_last_emission_stats", "rwr_last_light_stats", "rwr_last_part_light_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -606,6 +607,12 @@ class Context:
         render call (rwr_last_light_stats)."""
         a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(lib().rwr_last_light_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def last_part_light_stats(self):
+        """FLAG_LIGHT_PARTS: the mesh light's share of last_light_stats' three counts (rwr_last_part_light_stats)."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rwr_last_part_light_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
 
     def set_triangles(self, triangles):

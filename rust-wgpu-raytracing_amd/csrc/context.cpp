@@ -473,16 +473,35 @@ int rwr_last_emission_stats(rwr_context *ctx, uint64_t *emissive_hits)
     return RWR_OK;
 }
 
-int rwr_last_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits)
+// the last frame's six light counts (WfGlow::light_counts): the stage's totals, then the mesh light's share; zeros for a frame without the stage
+static int last_light_counts(rwr_context *ctx, unsigned long long counts[6])
 {
-    if (!ctx || !light_rays || !reached || !suppressed_hits) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
-    unsigned long long counts[3] = {0ull, 0ull, 0ull};
+    for (int i = 0; i < 6; i++) counts[i] = 0ull;
     if (ctx->last_light && ctx->wf_state[ctx->last_wf_state].d_light_counts.ptr) {
         DeviceGuard g(ctx->device);
         RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
-        RWR_HIP_CHECK(hipMemcpy(counts, ctx->wf_state[ctx->last_wf_state].d_light_counts.ptr, sizeof counts, hipMemcpyDeviceToHost));
+        RWR_HIP_CHECK(hipMemcpy(counts, ctx->wf_state[ctx->last_wf_state].d_light_counts.ptr, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     }
+    return RWR_OK;
+}
+
+int rwr_last_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits)
+{
+    if (!ctx || !light_rays || !reached || !suppressed_hits) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    unsigned long long counts[6];
+    const int rc = last_light_counts(ctx, counts);
+    if (rc != RWR_OK) return rc;
     *light_rays = counts[0]; *reached = counts[1]; *suppressed_hits = counts[2];
+    return RWR_OK;
+}
+
+int rwr_last_part_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits)
+{
+    if (!ctx || !light_rays || !reached || !suppressed_hits) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    unsigned long long counts[6];
+    const int rc = last_light_counts(ctx, counts);
+    if (rc != RWR_OK) return rc;
+    *light_rays = counts[3]; *reached = counts[4]; *suppressed_hits = counts[5];
     return RWR_OK;
 }
 

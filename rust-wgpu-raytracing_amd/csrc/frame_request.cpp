@@ -13,7 +13,7 @@ namespace {
 // id / t planes, so RWR_FLAG_AUX_OUTPUTS is implied, and its own bit is not part of rp.flags from there on (nor of a history's key).
 // mode: a surface flag switches on the surfaces of its model (surface_mode's bit).
 struct FlagRule { uint32_t flag; const char *name, *stage, *why; uint32_t mode; };
-constexpr FlagRule kFlagRules[11] = {
+constexpr FlagRule kFlagRules[12] = {
     {RWR_FLAG_ACCUMULATE, "RWR_FLAG_ACCUMULATE", nullptr, nullptr, 0u},
     {RWR_FLAG_SHADOWS, "RWR_FLAG_SHADOWS", nullptr, nullptr, 0u},
     {RWR_FLAG_DENOISE, "RWR_FLAG_DENOISE", "filter", "its taps reach 62 pixels", 0u},
@@ -24,7 +24,8 @@ constexpr FlagRule kFlagRules[11] = {
     {RWR_FLAG_GLOSSY, "RWR_FLAG_GLOSSY", nullptr, nullptr, surface_mode(SurfaceModel::kGloss)},
     {RWR_FLAG_SOFT_SHADOWS, "RWR_FLAG_SOFT_SHADOWS", nullptr, nullptr, 0u},
     {RWR_FLAG_EMISSIVE, "RWR_FLAG_EMISSIVE", nullptr, nullptr, 0u},
-    {RWR_FLAG_LIGHT_SAMPLING, "RWR_FLAG_LIGHT_SAMPLING", nullptr, nullptr, 0u}};
+    {RWR_FLAG_LIGHT_SAMPLING, "RWR_FLAG_LIGHT_SAMPLING", nullptr, nullptr, 0u},
+    {RWR_FLAG_LIGHT_PARTS, "RWR_FLAG_LIGHT_PARTS", nullptr, nullptr, 0u}};
 constexpr uint32_t kSurfaceFlags = RWR_FLAG_MIRRORS | RWR_FLAG_GLASS | RWR_FLAG_GLOSSY;
 
 // What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
@@ -114,12 +115,22 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
     // sends a ray on) or without an emitting sphere in use there is nothing to aim at
     if ((rp.flags & RWR_FLAG_LIGHT_SAMPLING) && (!(rp.flags & RWR_FLAG_EMISSIVE) || rp.max_bounces == 0u || scene_lights(ctx).m == 0u))
         rp.flags &= ~(uint32_t)RWR_FLAG_LIGHT_SAMPLING;
+    // ... and the mesh light likewise, by its own rule: the list of the emitting parts' faces must not be empty (looked at, and rebuilt
+    // if the scene changed it, only when the flag is set and everything else holds)
+    if (rp.flags & RWR_FLAG_LIGHT_PARTS) {
+        uint32_t n_listed = 0;
+        if ((rp.flags & RWR_FLAG_EMISSIVE) && rp.max_bounces != 0u) {
+            const int rc = scene_part_lights(ctx, n_listed);
+            if (rc != RWR_OK) return rc;
+        }
+        if (n_listed == 0u) rp.flags &= ~(uint32_t)RWR_FLAG_LIGHT_PARTS;
+    }
     // Soft shadows change the direction of shadow rays and nothing else: without shadow rays, or with two point lights, there is nothing to change
     if (!(asked & RWR_FLAG_SHADOWS) || (ctx->shadow.mesh_light_radius == 0.0f && ctx->shadow.sphere_light_radius == 0.0f)) rp.flags &= ~(uint32_t)RWR_FLAG_SOFT_SHADOWS;
     auto has = [](uint32_t flags, uint32_t flag) { return (flags & flag) != 0; };
     rq = FrameRequest{rp, row_begin, row_end, row_pitch, has(rp.flags, RWR_FLAG_AUX_OUTPUTS), has(asked, RWR_FLAG_ACCUMULATE), has(asked, RWR_FLAG_SHADOWS),
                       has(asked, RWR_FLAG_DENOISE), has(asked, RWR_FLAG_REPROJECT), has(rp.flags, RWR_FLAG_MIRRORS), has(rp.flags, RWR_FLAG_GLASS),
-                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), has(rp.flags, RWR_FLAG_EMISSIVE), has(rp.flags, RWR_FLAG_LIGHT_SAMPLING), false, false};
+                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), has(rp.flags, RWR_FLAG_EMISSIVE), has(rp.flags, RWR_FLAG_LIGHT_SAMPLING), has(rp.flags, RWR_FLAG_LIGHT_PARTS), false, false};
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
     // with shadow rays (the integrator's stages trace them), one the filter follows (it runs behind the integrator's resolve) or one
     // with an emitter (the integrator's kernels add its light)

@@ -404,13 +404,17 @@ RWR_DEV bool add_glow(const FrameParams &p, const WfGlow &gl, const ShadeRec *__
     float4 g = glow_record(gl, p.n_materials > 1u, shade, obj);
     bool silenced = false;
     if (gl.light) {   // (uniform)
-        if (marked && obj < -1 && glows(g)) {
+        if ((gl.light & 1u) && marked && obj < -1 && glows(g)) {
             const f3 w = sub3(ld3(p.spheres[-2 - obj].center), O);
             const float R = p.spheres[-2 - obj].radius;
             silenced = dot3(w, w) > R * R;
         }
+        // bit 2 (RWR_FLAG_LIGHT_PARTS item 8): such a ray's hit on a face of an emitting part — O's light sample may have aimed there
+        const bool face = (gl.light & 2u) && marked && obj >= 0 && glows(g);
+        silenced = silenced || face;
         if (silenced) g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         count_glow_hits(gl.light_counts + 2, silenced);   // (the lanes that shade a hit here: the ballots take whoever is active)
+        if (gl.light & 2u) count_glow_hits(gl.light_counts + 5, face);   // (uniform) the mesh light's share
     }
     le = mk3(g.x, g.y, g.z);
     e1 = mk3(e1.x + g.x, e1.y + g.y, e1.z + g.z);

@@ -14,6 +14,13 @@
 // t < t_s (rwr_bvh.h bvh_occluded_before).  The emitting spheres' indices and radiances arrive as a kernel argument (WfLights:
 // scalar registers), centre and radius are the frame's (FrameParams::spheres); with one emitter nothing is selected per lane.
 // Arithmetic: f32, operation for operation the header's rule and tests/light_ref.c; no contraction.
+// PARTS forms (RWR_FLAG_LIGHT_PARTS; rwr_part_lights.h): the lights are the M emitting spheres and, last, the mesh light — the list
+// of the faces of emitting parts (WfPartLights, a kernel argument behind WfLights).  The choice is per lane; a lane that takes the
+// mesh light finds its face by binary search over the list's cdf (global memory, 16-byte records, at most ceil(log2 n) + 1 dependent
+// loads), gathers the face's TriRecord, draws a point on it and aims there.  It reaches when it hits its face at t_f, no sphere at
+// t <= t_f and no face g at t_g < t_f or at t_g == t_f with g < f (bvh_occluded_before<true>).  Lanes of either kind share the
+// sphere tests and the one walk: a sphere lane passes self = 0, a face lane compares every sphere with '<='.  The forms without
+// PARTS hold the instructions they held before there were any.  tests/part_light_ref.c is the rule's literal evaluation.
 #include <algorithm>
 #include <type_traits>
 
@@ -23,10 +30,11 @@
 
 namespace rwr {
 
-template <bool NODES_IN_LDS, bool STACK16>
+template <bool NODES_IN_LDS, bool STACK16, bool PARTS>
 __global__ void __launch_bounds__(256)
 k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDevice bvh, const WfBuffers wf, const WfGlow gl,
-           uint32_t n_tiles, uint32_t sample_count, uint32_t n_shares, uint32_t dim0, uint32_t sample_base, const WfLights lights)
+           uint32_t n_tiles, uint32_t sample_count, uint32_t n_shares, uint32_t dim0, uint32_t sample_base, const WfLights lights,
+           const WfPartLights parts)
 {
     __shared__ TraceShared sh;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
@@ -39,8 +47,9 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
     const uint32_t n_live = wf.live_list ? (uint32_t)__builtin_amdgcn_readfirstlane((int)*wf.live_count) : n_tiles;
     const uint32_t n_items = n_live * n_shares, n_words = sample_count * 8u;
     const uint32_t M = lights.m;
-    const float Mf = (float)M;
+    const float Mf = (float)(PARTS ? parts.l : M);   // (PARTS: L = M + 1 takes M's place in the choice and in g)
     uint32_t n_rays = 0, n_reached = 0;   // this wave's (wave-uniform)
+    uint32_t n_part_rays = 0, n_part_reached = 0;   // PARTS: the mesh light's share of them
     bool staged = false;
     for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
         const uint32_t t = item / n_shares, share = item - t * n_shares;
@@ -83,12 +92,14 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
             // which sphere: one emitter needs no random number's value and no select
             uint32_t s = lights.index[0];
             f3 Le = mk3(lights.le[0][0], lights.le[0][1], lights.le[0][2]);
-            if (M > 1u) {   // uniform
+            bool mesh = PARTS && live && M == 0u;   // PARTS: this lane's light is the mesh light (the only one there is when M is 0)
+            if ((PARTS ? parts.l : M) > 1u) {   // uniform
                 const float u = rng_uniform(pixel, sample, dim0, p.seed);
-                const uint32_t i = min((uint32_t)(u * Mf), M - 1u);
+                const uint32_t i = min((uint32_t)(u * Mf), (PARTS ? parts.l : M) - 1u);
 #pragma unroll
                 for (uint32_t q = 1; q < RWR_MAX_SPHERES; q++)
                     if (q < M && i == q) { s = lights.index[q]; Le = mk3(lights.le[q][0], lights.le[q][1], lights.le[q][2]); }
+                if (PARTS) mesh = live && i == M;
             }
             f3 C = ld3(p.spheres[0].center);
             float R = p.spheres[0].radius;
@@ -122,6 +133,7 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
             const f3 b1 = mk3(1.0f + sign * wd.x * wd.x * aa, sign * bb, -sign * wd.x);
             const f3 b2 = mk3(bb, sign + wd.y * wd.y * aa, -wd.y);
             const f3 L = mk3(rr * (da * b1.x + db * b2.x) + c * wd.x, rr * (da * b1.y + db * b2.y) + c * wd.y, rr * (da * b1.z + db * b2.z) + c * wd.z);
+            if constexpr (!PARTS) {
             const float ndw = dot3(n, L);
             go = go && ndw > 0.0f;
             // visibility: the ray's own sphere, then the others by the nearest-hit rule's ties, then the mesh
@@ -145,6 +157,76 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
             }
             n_rays += (uint32_t)__popcll(__ballot(go));
             n_reached += (uint32_t)__popcll(__ballot(reach));
+            } else {
+            // a sphere lane's sample, as above (garbage in a mesh lane, which replaces every value below)
+            float ndw = dot3(n, L);
+            go = go && !mesh && ndw > 0.0f;
+            float g = 2.0f * Mf * kc * ndw;
+            f3 Ld = L;             // the light ray's direction: the cone's, or towards the face's point
+            uint32_t self = 0u;    // a mesh lane's face
+            bool face_ok = false;  // the mesh lane's ray hits its face, at ts
+            float ts = 0.0f;
+            if (__any(mesh)) {
+                // the face: the first list entry j with uf < cdf_j (the last cdf is 1 > uf: the search ends inside the list)
+                const float uf = rng_uniform(pixel, sample, dim0 + 1u, p.seed);
+                uint32_t lo = 0u, hi = mesh ? parts.n - 1u : 0u;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (uf < parts.list[mid].cdf) hi = mid; else lo = mid + 1u;
+                }
+                float4 rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (mesh) rec = *reinterpret_cast<const float4 *>(parts.list + lo);
+                const uint32_t f = __float_as_uint(rec.y);
+                const bool listed = mesh && f < p.n_tris;   // (a well-formed list names faces of the scene: nothing is read past them)
+                const float inv_pdf = rec.z;
+                float u1 = rng_uniform(pixel, sample, dim0 + 2u, p.seed), u2 = rng_uniform(pixel, sample, dim0 + 3u, p.seed);
+                if (u1 + u2 > 1.0f) { u1 = 1.0f - u1; u2 = 1.0f - u2; }
+                const TriRecord &T = tris[listed ? f : 0u];
+                f3 p0 = mk3(0.0f, 0.0f, 0.0f), p1 = p0, p2 = p0, nh = p0, Lf = p0;
+                if (listed) {
+                    p0 = ld3(T.p0); p1 = ld3(T.p1); p2 = ld3(T.p2); nh = ld3(T.nhat);
+                    const float4 lr = glow_record(gl, true, parts.shade, (int32_t)f);
+                    Lf = mk3(lr.x, lr.y, lr.z);
+                }
+                const f3 P = mk3((p0.x + u1 * (p1.x - p0.x)) + u2 * (p2.x - p0.x), (p0.y + u1 * (p1.y - p0.y)) + u2 * (p2.y - p0.y),
+                                 (p0.z + u1 * (p1.z - p0.z)) + u2 * (p2.z - p0.z));
+                const f3 v = sub3(P, O);
+                const float v2 = dot3(v, v);
+                const float vl = sqrtf(v2);
+                const f3 w = mk3(v.x / vl, v.y / vl, v.z / vl);
+                const float nw = dot3(n, w);
+                const float cf = fabsf(dot3(nh, w));
+                if (mesh) {
+                    Ld = w; ndw = nw; Le = Lf; self = f;
+                    go = listed && v2 > 0.0f && nw > 0.0f;
+                    g = Mf * inv_pdf * nw * cf * 0.318309886f / v2;
+                    s = p.n_spheres;   // (every sphere is ahead of the mesh in the order: each occludes at t <= t_f)
+                }
+                face_ok = face_hit_t(T, O, Ld, mesh && go, ts);
+            }
+            // visibility: the ray's own sphere or face, then the others by the nearest-hit rule's ties, then the mesh
+            float tsph = 0.0f;
+            const bool sph_ok = !mesh && go && sphere_ray_intersect_t(C, R, O, Ld, tsph);
+            if (!mesh) ts = tsph;
+            bool reach = mesh ? face_ok : sph_ok;
+            for (uint32_t q = 0; q < p.n_spheres; q++) {
+                float tq;
+                if (reach && q != s && sphere_ray_intersect_t(ld3(p.spheres[q].center), p.spheres[q].radius, O, Ld, tq))
+                    if (q < s ? tq <= ts : tq < ts) reach = false;
+            }
+            if (p.n_tris) {
+                const SlabRay sr = make_slab_ray(O, Ld);
+                bool occ;
+                if (NODES_IN_LDS) occ = bvh_occluded_before<true>(s_nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, Ld, sr, ts, reach, self);
+                else occ = bvh_occluded_before<true>(bvh.nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, Ld, sr, ts, reach, self);
+                reach = reach && !occ;
+            }
+            if (reach) add_contribution(sh, e, thr.x * (Le.x * g), thr.y * (Le.y * g), thr.z * (Le.z * g));
+            n_rays += (uint32_t)__popcll(__ballot(go));
+            n_reached += (uint32_t)__popcll(__ballot(reach));
+            n_part_rays += (uint32_t)__popcll(__ballot(mesh && go));
+            n_part_reached += (uint32_t)__popcll(__ballot(mesh && reach));
+            }
         }
         __syncthreads();
         flush_pool(sh, p, wf, tile);
@@ -152,41 +234,43 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
     if (lane == 0u && n_rays) {
         atomicAdd(&gl.light_counts[0], (unsigned long long)n_rays);
         if (n_reached) atomicAdd(&gl.light_counts[1], (unsigned long long)n_reached);
+        if (PARTS && n_part_rays) atomicAdd(&gl.light_counts[3], (unsigned long long)n_part_rays);
+        if (PARTS && n_part_reached) atomicAdd(&gl.light_counts[4], (unsigned long long)n_part_reached);
     }
 }
 
 struct LightForms {   // rwr_wf_forms.h
-    struct Form { bool nodes_in_lds, stack16; };
-    static constexpr uint32_t kRange = 4u;
-    static constexpr uint32_t encode(Form f) { return f.nodes_in_lds + 2u * f.stack16; }
-    static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0}; }
+    struct Form { bool nodes_in_lds, stack16, parts; };
+    static constexpr uint32_t kRange = 8u;
+    static constexpr uint32_t encode(Form f) { return f.nodes_in_lds + 2u * f.stack16 + 4u * f.parts; }
+    static constexpr Form decode(uint32_t i) { return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0}; }
     static constexpr bool valid(Form) { return true; }
-    using Kernel = decltype(&k_wf_light<false, false>);
-    template <uint32_t I> static constexpr Kernel kernel() { return &k_wf_light<decode(I).nodes_in_lds, decode(I).stack16>; }
+    using Kernel = decltype(&k_wf_light<false, false, false>);
+    template <uint32_t I> static constexpr Kernel kernel() { return &k_wf_light<decode(I).nodes_in_lds, decode(I).stack16, decode(I).parts>; }
 };
 static constexpr auto kLightForms = form_table<LightForms>();
-static_assert(check_forms<LightForms>(4), "nodelets in LDS or not, 16-bit stacks or not");
+static_assert(check_forms<LightForms>(8), "nodelets in LDS or not, 16-bit stacks or not, the mesh light or not");
 
 // gen: the generation whose hits' light samples these are (0: h0's, behind the primary stage) — RNG block 274 + 17 gen, behind
 // soft shadows' last (130 + 16 * 8 + 15 = 273).  expected_tiles: as launch_wf_shadow.
 hipError_t launch_wf_light(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
-                           const WfGlow &glow, const WfLights &lights, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count,
-                           uint32_t gen, uint32_t sample_base)
+                           const WfGlow &glow, const WfLights &lights, const WfPartLights &parts, uint32_t n_tiles, uint32_t expected_tiles,
+                           uint32_t sample_count, uint32_t gen, uint32_t sample_base)
 {
-    if (n_tiles == 0 || sample_count == 0 || lights.m == 0) return hipSuccess;
+    if (n_tiles == 0 || sample_count == 0 || (lights.m == 0 && parts.n == 0)) return hipSuccess;
     const uint32_t work_tiles = std::max(1u, std::min(expected_tiles, n_tiles));
     const uint32_t n_shares = std::max(1u, std::min(std::min(32u, sample_count * 8u), 4096u / work_tiles));
     const dim3 grid((uint32_t)std::min<uint64_t>(2048u, (uint64_t)n_tiles * n_shares));
     const LaneLdsPlan l = lane_lds_plan(bvh, fp, false);   // (no 1 024-thread form here)
-    hipLaunchKernelGGL(kLightForms[LightForms::encode({l.nodes_in_lds, l.stack16})], grid, dim3(256), l.bytes, s, fp, tris, bvh, wf, glow, n_tiles,
-                       sample_count, n_shares, 274u + 17u * gen, sample_base, lights);
+    hipLaunchKernelGGL(kLightForms[LightForms::encode({l.nodes_in_lds, l.stack16, parts.n != 0u})], grid, dim3(256), l.bytes, s, fp, tris, bvh, wf, glow,
+                       n_tiles, sample_count, n_shares, 274u + 17u * gen, sample_base, lights, parts);
     return hipGetLastError();
 }
 
 hipError_t preload_kernels_wf_light()
 {
     hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>((&k_wf_light<true, true>)));
+    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>((&k_wf_light<true, true, false>)));
 }
 
 }  // namespace rwr

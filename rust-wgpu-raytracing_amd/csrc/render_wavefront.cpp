@@ -234,16 +234,19 @@ int WfFrame::glow_table()
     RWR_HIP_CHECK(W.d_glow_hits.ensure(1));
     RWR_HIP_CHECK(hipMemsetAsync(W.d_glow_hits.ptr, 0, sizeof(unsigned long long), stream));
     ft.glow = WfGlow{W.d_glow.ptr, (uint32_t)n_parts, 0u, W.d_glow_hits.ptr, nullptr, nullptr, nullptr};
-    // RWR_FLAG_LIGHT_SAMPLING: a normal per queue slot and the light ballots, per queue like the rays and kept like them (allocated by
-    // the first frame that needs them); the frame's three counts start from zero.  trace_groups points ft.glow at a queue's share.
-    ft.lights_on = rq.light;
-    if (rq.light) {
-        ft.lights = scene_lights(ctx);
+    // RWR_FLAG_LIGHT_SAMPLING, RWR_FLAG_LIGHT_PARTS: a normal per queue slot and the light ballots, per queue like the rays and kept like
+    // them (allocated by the first frame that needs them); the frame's six counts start from zero.  trace_groups points ft.glow at a
+    // queue's share.  glow.light: bit 1 the spheres, bit 2 the mesh light (validate made its list and device copy current).
+    ft.lights_on = rq.light || rq.light_parts;
+    if (ft.lights_on) {
+        if (rq.light) ft.lights = scene_lights(ctx);
+        if (rq.light_parts)
+            ft.part_lights = WfPartLights{ctx->d_part_lights.ptr, ctx->d_shade.ptr, (uint32_t)ctx->part_lights.size(), ft.lights.m + 1u};
         RWR_HIP_CHECK(W.d_light_recs.ensure(n_queues * slots));
         RWR_HIP_CHECK(W.d_light_masks.ensure(n_queues * n_tiles * group * 8u));
-        RWR_HIP_CHECK(W.d_light_counts.ensure(3));
-        RWR_HIP_CHECK(hipMemsetAsync(W.d_light_counts.ptr, 0, 3 * sizeof(unsigned long long), stream));
-        ft.glow.light = 1u;
+        RWR_HIP_CHECK(W.d_light_counts.ensure(6));
+        RWR_HIP_CHECK(hipMemsetAsync(W.d_light_counts.ptr, 0, 6 * sizeof(unsigned long long), stream));
+        ft.glow.light = (rq.light ? 1u : 0u) | (rq.light_parts ? 2u : 0u);
         ft.glow.light_counts = W.d_light_counts.ptr;
     }
     return RWR_OK;
@@ -291,7 +294,7 @@ int WfFrame::trace_groups(const AccumPlan &ap)
             RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere, 0u,
                                            (uint32_t)ap.before + s0, soft, &shadow_plan));
         if (ft.lights_on)   // h0's light samples: ray 1 sits in the queue, the first sort has not run
-            RWR_HIP_CHECK(launch_wf_light(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.glow, ft.lights, n_tiles, shadow_tiles, cnt, 0u, (uint32_t)ap.before + s0));
+            RWR_HIP_CHECK(launch_wf_light(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.glow, ft.lights, ft.part_lights, n_tiles, shadow_tiles, cnt, 0u, (uint32_t)ap.before + s0));
         // the bounce stage: one generation of rays per bounce (RWR_FLAG_MULTI_BOUNCE: up to RWR_MAX_BOUNCES).  Generation k traces
         // ray k of every path that is still alive — the sort and trace kernels run again over the same fixed slots — and, unless
         // it is the last, writes ray k + 1 back into the slot of every hit, with its bit in the other ballot array.
@@ -313,7 +316,7 @@ int WfFrame::trace_groups(const AccumPlan &ap)
                 RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere, gen,
                                                (uint32_t)ap.before + s0, soft, &shadow_plan));
             if (ft.lights_on && emit)   // the light samples of this generation's hits, from the rays it just wrote, ahead of the next sort
-                RWR_HIP_CHECK(launch_wf_light(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.glow, ft.lights, n_tiles, shadow_tiles, cnt, gen, (uint32_t)ap.before + s0));
+                RWR_HIP_CHECK(launch_wf_light(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.glow, ft.lights, ft.part_lights, n_tiles, shadow_tiles, cnt, gen, (uint32_t)ap.before + s0));
             if (emit) std::swap(wg.masks, masks_next);
         }
         if (rp.max_bounces && s0 + group >= rp.spp) last_counters = wfq[q].counters;

@@ -283,10 +283,59 @@ RWR_DEV bool occludes_before_any_order(const TriRecord &T, f3 O, f3 D, float tma
     return hit;
 }
 
+// ... for a ray aimed at a FACE (RWR_FLAG_LIGHT_PARTS): the limit is the distance t_f at which the ray meets its own face `self`, and
+// the nearest-hit rule gives a tie to the lowest index (intersect_and_select_any_order above), so a face idx occludes at t < tmax or at
+// t == tmax with idx < self.  `self` itself never does: its t is tmax, by the same operations.  A lane aimed at a sphere passes
+// self = 0 and gets occludes_before_any_order's verdict.  bvh_inner_step keeps a box whose entry distance equals the limit ('<=').
+RWR_DEV bool occludes_before_or_tie_any_order(const TriRecord &T, uint32_t idx, f3 O, f3 D, float tmax, uint32_t self)
+{
+    const f3 N = ld3(T.N);
+    const float ndotd = dot3(N, D);
+    bool hit = !(fabsf(ndotd) < kEpsilon);              // :94
+    const float t = -(dot3(N, O) + T.d) / ndotd;        // :99-102
+    hit &= !(t < 0.0f);                                 // :105
+    hit &= t < tmax || (t == tmax && idx < self);
+    if (!__any(hit)) return false;
+    const f3 P = along(O, t, D);                        // :110
+    f3 C = cross3(ld3(T.e0), sub3(P, ld3(T.p0)));       // :115-117
+    hit &= !(dot3(N, C) < 0.0f);                        // :118
+    if (!__any(hit)) return false;
+    C = cross3(ld3(T.e1), sub3(P, ld3(T.p1)));          // :123-125
+    hit &= !(dot3(N, C) < 0.0f);                        // :127
+    if (!__any(hit)) return false;
+    C = cross3(ld3(T.e2), sub3(P, ld3(T.p2)));          // :132-134
+    hit &= !(dot3(N, C) < 0.0f);                        // :136
+    return hit;
+}
+
+// triangleRayIntersect's verdict and its t for one face per lane (the face a light ray is aimed at), staged like
+// occludes_any_order: the t of intersect_and_select's operations, which every traversal above computes for that face too.
+RWR_DEV bool face_hit_t(const TriRecord &T, f3 O, f3 D, bool active, float &t_out)
+{
+    const f3 N = ld3(T.N);
+    const float ndotd = dot3(N, D);
+    bool hit = active && !(fabsf(ndotd) < kEpsilon);    // :94
+    const float t = -(dot3(N, O) + T.d) / ndotd;        // :99-102
+    hit &= !(t < 0.0f);                                 // :105
+    t_out = t;
+    if (!__any(hit)) return false;
+    const f3 P = along(O, t, D);                        // :110
+    f3 C = cross3(ld3(T.e0), sub3(P, ld3(T.p0)));       // :115-117
+    hit &= !(dot3(N, C) < 0.0f);                        // :118
+    if (!__any(hit)) return false;
+    C = cross3(ld3(T.e1), sub3(P, ld3(T.p1)));          // :123-125
+    hit &= !(dot3(N, C) < 0.0f);                        // :127
+    if (!__any(hit)) return false;
+    C = cross3(ld3(T.e2), sub3(P, ld3(T.p2)));          // :132-134
+    hit &= !(dot3(N, C) < 0.0f);                        // :136
+    return hit;
+}
+
 // One ray per lane with its slab constants sr and its limit tmax; lanes with `active` unset only keep the wave company.
-template <typename NodePtr, typename StackT>
+// TIE (the light stage's PARTS forms): the per-lane face `self` and the tie rule above; the other form's callers pass neither.
+template <bool TIE = false, typename NodePtr, typename StackT>
 RWR_DEV bool bvh_occluded_before(NodePtr nodes, const uint32_t *__restrict__ leaf_faces, const TriRecord *__restrict__ tris,
-                                 uint32_t n_faces, StackT *stack, f3 O, f3 D, const SlabRay &sr, float tmax, bool active)
+                                 uint32_t n_faces, StackT *stack, f3 O, f3 D, const SlabRay &sr, float tmax, bool active, uint32_t self = 0u)
 {
     const uint32_t stride = blockDim.x;
     StackT *sp = stack + threadIdx.x;
@@ -301,7 +350,11 @@ RWR_DEV bool bvh_occluded_before(NodePtr nodes, const uint32_t *__restrict__ lea
             for (uint32_t k = 0; k < count; k++) {
                 if (first + k >= n_faces) break;  // (as bvh_leaf_step)
                 const uint32_t idx = leaf_faces[first + k];
+                if constexpr (TIE) {
+                    if (idx < n_faces && occludes_before_or_tie_any_order(tris[idx], idx, O, D, tmax, self)) occluded = true;
+                } else {
                 if (idx < n_faces && occludes_before_any_order(tris[idx], O, D, tmax)) occluded = true;
+                }
             }
             if (occluded || sp == sp0) have_cur = false;
             else { sp -= stride; cur = bvh_stack_dec(*sp); }

@@ -167,8 +167,8 @@ struct WfState {
     uint64_t glow_version = 0;
     DeviceBuffer<unsigned long long> d_glow_hits;
     // RWR_FLAG_LIGHT_SAMPLING, allocated by the first frame that samples its lights: per ray queue a 16-byte record per slot (the
-    // hit's normal, WfGlow::light_recs) and the light ballots (layout of d_masks), kept like the queues; the frame's three counts
-    // {light rays, reached, silenced hits} (WfGlow::light_counts), zeroed per frame
+    // hit's normal, WfGlow::light_recs) and the light ballots (layout of d_masks), kept like the queues; the frame's six counts
+    // {light rays, reached, silenced hits} and the mesh light's share of each (WfGlow::light_counts), zeroed per frame
     DeviceBuffer<LightRec> d_light_recs;
     DeviceBuffer<unsigned long long> d_light_masks;
     DeviceBuffer<unsigned long long> d_light_counts;
@@ -345,6 +345,13 @@ struct rwr_context {
     std::vector<rwr::SurfaceRec> part_glow;
     rwr::SurfaceRec sphere_glow[RWR_MAX_SPHERES]{};
     uint64_t glow_version = 1;
+    // RWR_FLAG_LIGHT_PARTS: the mesh light (rwr_part_lights.h) — the world-space corners rebuild_tris read back (9 floats per world
+    // face), the list built from them and the parts' radiances, and its device copy.  part_lights_dirty: the scene's faces or a part's
+    // emission changed since the list was built; scene_part_lights (scene.cpp) rebuilds and uploads it for the next frame that asks.
+    std::vector<float> world_corners;
+    std::vector<rwr::PartLightRec> part_lights;
+    rwr::DeviceBuffer<rwr::PartLightRec> d_part_lights;
+    bool part_lights_dirty = true;
     rwr::WfLights lights{};   // RWR_FLAG_LIGHT_SAMPLING: the emitting spheres in use (scene.cpp rebuild_lights: after the emission setters and rwr_scene_set_spheres)
     rwr_triangle_buffer_data triangles[RWR_MAX_TRIANGLES]{};
     uint32_t n_triangles = 0;
@@ -356,7 +363,7 @@ struct rwr_context {
     bool last_shadows = false;      // the last render call traced shadow rays (RWR_FLAG_SHADOWS): their counters are in its WfState
     bool last_gloss = false;        // the last render call ran the glossy forms (RWR_FLAG_GLOSSY): their counter is d_surface_events[kEventGlossy]
     bool last_glass = false;        // the last render call ran the glass forms (RWR_FLAG_GLASS): their counters are in its WfState
-    bool last_light = false;        // the last render call sampled its lights (RWR_FLAG_LIGHT_SAMPLING): the counts are its WfState's d_light_counts
+    bool last_light = false;        // the last render call sampled its lights (RWR_FLAG_LIGHT_SAMPLING, RWR_FLAG_LIGHT_PARTS): the counts are its WfState's d_light_counts
     bool last_glow = false;         // the last render call ran the GLOW forms (RWR_FLAG_EMISSIVE): their counter is its WfState's d_glow_hits
     // optional per-kernel timing (rwr_ctx_set_kernel_timing)
     uint32_t timing_every = 0;
@@ -425,6 +432,9 @@ inline bool scene_glows(const rwr_context *ctx)
 }
 // the emitting spheres in use, in index order (RWR_FLAG_LIGHT_SAMPLING: s_0 < ... < s_{M-1}); scene.cpp keeps ctx->lights equal to it
 inline WfLights scene_lights(const rwr_context *ctx) { return ctx->lights; }
+// scene.cpp: the mesh light's length, after rebuilding and uploading the list if the scene changed it (RWR_FLAG_LIGHT_PARTS item 1);
+// waits for the frames in flight only when it has to upload.  Called for frames that ask for the flag, so no other frame pays.
+int scene_part_lights(rwr_context *ctx, uint32_t &n);
 
 // context.cpp: per-frame buffers of every active slot for the current scene and screen
 hipError_t ensure_frame_buffers(rwr_context *ctx);

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/rwr_hip.h"
+#include "rwr_part_lights.h"
 #include "rwr_surface.h"
 
 namespace rwr {
@@ -13,7 +14,7 @@ namespace rwr {
 // Internal debug flag (not in the public header): with RWR_FLAG_AUX_OUTPUTS, the
 // obj_id plane receives the number of block-level candidate faces and the hit_t
 // plane the number of faces the pixel's wave ran the exact test on.  (Bit 20: bit 16, which it had, is the public header's
-// RWR_FLAG_LIGHT_SAMPLING now; the internal bits lie above the public ones.)
+// RWR_FLAG_LIGHT_SAMPLING now.  Bits 17-20 are the internal ones; the header reserves them and goes on at bit 21.)
 constexpr uint32_t RWR_FLAG_DEBUG_COUNTS = 1u << 20;
 
 // Internal: render frames with the one-pixel-per-lane kernel (k_primary) instead of the
@@ -27,7 +28,7 @@ constexpr uint32_t RWR_FLAG_TILE_CLASS = 1u << 18;
 // it learns.  Clear (a key miss, RWR_TILE_COVER=0, any other form): the kernel neither reads nor writes them.
 constexpr uint32_t RWR_FLAG_TILE_COVER = 1u << 19;
 constexpr uint32_t kInternalFlags = RWR_FLAG_DEBUG_COUNTS | RWR_FLAG_ONE_PIXEL_PER_LANE | RWR_FLAG_TILE_CLASS | RWR_FLAG_TILE_COVER;
-static_assert((kInternalFlags & (2u * (uint32_t)RWR_FLAG_LIGHT_SAMPLING - 1u)) == 0u, "an internal bit is no public flag: they lie above the header's last");
+static_assert(kInternalFlags == RWR_FLAGS_RESERVED && (kInternalFlags & RWR_FLAGS_PUBLIC) == 0u, "no internal bit equals a public one: the internal bits are the ones the header reserves");
 
 // ---------------------------------------------------------------------------
 // Device-side scene records (data layout in HBM, see DESIGN.md §"Data layout").
@@ -362,6 +363,15 @@ struct WfSky {
     float zr, zg, zb, hr, hg, hb;   // zenith, horizon: rwr_sky_params' six floats in its order (plain members, no arrays: they stay registers)
 };
 static_assert(sizeof(WfSky) == sizeof(rwr_sky_params), "WfSky is rwr_sky_params");
+// The mesh light (RWR_FLAG_LIGHT_PARTS; rwr_part_lights.h): the face list, its length, the frame's shading records (a listed face's
+// part is ShadeRec::material, its radiance that part's record of WfGlow::table) and L = M + 1, the lights the stage chooses among.
+// A kernel argument of k_wf_light behind WfLights: scalar registers.
+struct WfPartLights {
+    const PartLightRec *list;
+    const ShadeRec *shade;
+    uint32_t n;
+    uint32_t l;
+};
 // What the kernels of one launch group know: the four argument structs above — all zero where the frame lacks the flag, and that
 // is what the kernels then get — and the switches the launchers pick the kernels' forms by.  render_wavefront.cpp fills it once per launch
 // group; `emit` and `emits` change per generation (a generation that is not the path's last: the trace kernels' EMIT forms).
@@ -374,8 +384,9 @@ struct WfFeatures {
     bool emits = false, shadows = false, sky_on = false;
     bool glows = false;   // RWR_FLAG_EMISSIVE with an emitter in the scene: the GLOW forms of all three kernels, which read `glow`
     bool soft = false;   // RWR_FLAG_SOFT_SHADOWS: k_wf_shadow's SOFT forms (no other kernel looks)
-    bool lights_on = false;   // RWR_FLAG_LIGHT_SAMPLING: glow.light is set, k_wf_light runs (kernels_wf_light.hip) with `lights`
-    WfLights lights{};        // rwr_surface.h
+    bool lights_on = false;   // RWR_FLAG_LIGHT_SAMPLING or RWR_FLAG_LIGHT_PARTS: glow.light is set, k_wf_light runs (kernels_wf_light.hip) with `lights`
+    WfLights lights{};        // rwr_surface.h (m = 0 while RWR_FLAG_LIGHT_SAMPLING is not effective)
+    WfPartLights part_lights{nullptr, nullptr, 0u, 0u};   // RWR_FLAG_LIGHT_PARTS: the mesh light (n = 0 while the flag is not effective: the forms without PARTS)
     int surf = kSurfNone;   // the surface models of the frame's flags (kSurfGlass: the table may hold glass records; kSurfGloss: glossy ones too)
     // The two rules for SURF.  The surface forms differ where a ray is emitted and nowhere else: the primary stage has one only
     // when the frame bounces at all, a trace kernel only in a generation that emits (a kernel that ends a path has none).
@@ -450,11 +461,12 @@ hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecor
                             const WfShadow &shadow, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count, const float light_mesh[3],
                             const float light_sphere[3], uint32_t gen, uint32_t sample_base, const rwr_shadow_params *soft,
                             LanePlanRecord *plan = nullptr);
-// kernels_wf_light.hip (RWR_FLAG_LIGHT_SAMPLING): the light samples of the hits whose diffuse rays generation `gen` emitted (0: the
-// primary stage), from glow's records and ballots, added to wf's sums; the rays traced and reached into glow.light_counts
+// kernels_wf_light.hip (RWR_FLAG_LIGHT_SAMPLING, RWR_FLAG_LIGHT_PARTS): the light samples of the hits whose diffuse rays generation
+// `gen` emitted (0: the primary stage), from glow's records and ballots, added to wf's sums; the rays traced and reached into
+// glow.light_counts.  parts.n != 0: the PARTS forms, which aim at the mesh light too.
 hipError_t launch_wf_light(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
-                           const WfGlow &glow, const WfLights &lights, uint32_t n_tiles, uint32_t expected_tiles, uint32_t sample_count,
-                           uint32_t gen, uint32_t sample_base);
+                           const WfGlow &glow, const WfLights &lights, const WfPartLights &parts, uint32_t n_tiles, uint32_t expected_tiles,
+                           uint32_t sample_count, uint32_t gen, uint32_t sample_base);
 size_t wf_pool_info_bytes();
 // RWR_WF_STATS=1: trace launches of this process so far {packet kernel, per-lane kernel, its 1 024-thread form}
 void wf_trace_launch_counts(uint64_t out[3]);

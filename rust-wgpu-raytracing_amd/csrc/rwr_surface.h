@@ -121,6 +121,10 @@ struct WfSurfaces {
 // (light_masks: layout of WfBuffers::masks, cleared per generation); and add_glow takes Le as 0 for the hit of a marked ray on an
 // emitting sphere seen from outside (the light sample of the ray's origin has that light already) and counts it in
 // light_counts[2] ([0], [1]: k_wf_light's rays traced and rays that reached their sphere).
+// `light` is two bits: 1 — RWR_FLAG_LIGHT_SAMPLING is effective, the spheres above; 2 — RWR_FLAG_LIGHT_PARTS is effective: the light
+// stage aims at the mesh light too (rwr_part_lights.h), and add_glow takes Le as 0 for the hit of a marked ray on a face of an
+// emitting part and counts it in light_counts[2] and [5].  Either bit marks rays and stores normals.  light_counts holds six:
+// [3], [4], [5] are the mesh light's share of [0], [1], [2].
 struct LightRec { float n[3]; uint32_t pad; };
 static_assert(sizeof(LightRec) == 16, "LightRec is 16 B");
 struct WfGlow {

@@ -55,6 +55,30 @@ int rebuild_tris(rwr_context *ctx)
     ctx->bvh_leaf_extent = bvh.mean_leaf_extent;
     ctx->n_tris = total;
     ctx->tris_dirty = false;
+    ctx->world_corners = std::move(corners);   // (the mesh light's areas: scene_part_lights)
+    ctx->part_lights_dirty = true;
+    return RWR_OK;
+}
+
+// RWR_FLAG_LIGHT_PARTS item 1: the mesh light changes with the world faces (rebuild_tris) and with a part's emission (set_glow); the
+// frame that next asks for the flag rebuilds the list from the corners the device made and uploads it, behind the frames in flight.
+int scene_part_lights(rwr_context *ctx, uint32_t &n)
+{
+    if (ctx->part_lights_dirty) {
+        if (ctx->n_tris != 0u && ctx->world_corners.size() == (size_t)ctx->n_tris * 9u && ctx->n_faces != 0u)
+            ctx->part_lights = build_part_lights(ctx->world_corners.data(), ctx->n_tris, ctx->st_face_mat.data(), ctx->n_faces,
+                                                 &ctx->part_glow.data()->r, (uint32_t)ctx->part_glow.size());
+        else
+            ctx->part_lights.clear();
+        if (!ctx->part_lights.empty()) {
+            DeviceGuard g(ctx->device);
+            RWR_HIP_CHECK(sync_all(ctx));
+            RWR_HIP_CHECK(ctx->d_part_lights.ensure(ctx->part_lights.size()));
+            RWR_HIP_CHECK(hipMemcpy(ctx->d_part_lights.ptr, ctx->part_lights.data(), ctx->part_lights.size() * sizeof(PartLightRec), hipMemcpyHostToDevice));
+        }
+        ctx->part_lights_dirty = false;
+    }
+    n = (uint32_t)ctx->part_lights.size();
     return RWR_OK;
 }
 
@@ -76,6 +100,8 @@ int rwr_scene_clear(rwr_context *ctx)
     ctx->surface_version++;
     ctx->part_glow.clear();       // (... and give off no light)
     ctx->glow_version++;
+    ctx->world_corners.clear();
+    ctx->part_lights_dirty = true;
     ctx->have_mesh = false;
     ctx->n_faces = ctx->n_verts = ctx->n_tris = 0;
     return RWR_OK;
@@ -346,6 +372,7 @@ static int set_glow(rwr_context *ctx, bool sphere, uint32_t index, const float *
     *at = g;
     ctx->glow_version++;
     if (sphere) rebuild_lights(ctx);
+    else ctx->part_lights_dirty = true;
     return RWR_OK;
 }
 
