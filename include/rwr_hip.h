@@ -490,7 +490,8 @@ enum {
                                        that sends a ray on also sends one ray towards an emitting sphere, so that a small lamp lights a
                                        room at few samples.  Emitting mesh parts are RWR_FLAG_LIGHT_PARTS' (an area distribution over
                                        their faces): under this flag alone they are found by chance as before and their Le is never
-                                       suppressed.  There is no multiple importance sampling, and mirror, glass and glossy hits send no light ray.  Without
+                                       suppressed.  The light sample stands alone unless RWR_FLAG_LIGHT_MIS combines it with the bounce ray (multiple importance
+                                       sampling), and mirror, glass and glossy hits send no light ray.  Without
                                        the flag every frame is what it was, byte for byte.  All arithmetic f32, no contraction.
                                        1. The flag is effective only while RWR_FLAG_EMISSIVE is effective, max_bounces >= 1 and at
                                           least one sphere in use (index below the count rwr_scene_set_spheres gave) emits; otherwise it
@@ -534,11 +535,11 @@ enum {
                                           gather, accumulation and every schedule give the same bytes.
                                        7. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
     /* bits 17-20 are reserved: the library's internal flags (RWR_FLAGS_RESERVED below) */
-    RWR_FLAG_LIGHT_PARTS = 1u << 21    /* extension: light sampling towards emitting mesh PARTS — the light sample of an eligible hit may
+    RWR_FLAG_LIGHT_PARTS = 1u << 21,   /* extension: light sampling towards emitting mesh PARTS — the light sample of an eligible hit may
                                        aim at a point of a face of an emitting part (the "mesh light"), so that a room lit by a ceiling
                                        panel converges at few samples.  Independent of RWR_FLAG_LIGHT_SAMPLING: either, both or neither.
                                        Without this flag every frame is what it was, byte for byte — frames with RWR_FLAG_LIGHT_SAMPLING
-                                       and emitting parts included.  There is no multiple importance sampling; emitters emit from both
+                                       and emitting parts included.  Multiple importance sampling is RWR_FLAG_LIGHT_MIS'; emitters emit from both
                                        sides; mirror, glass and glossy hits send no light ray.  All arithmetic f32, no contraction,
                                        except the host table of item 2.
                                        1. The mesh light is the list of the world faces (after instancing) whose part emits and whose
@@ -583,10 +584,60 @@ enum {
                                           RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's effective flags; rwr_last_light_stats
                                           counts the light stage's totals, rwr_last_part_light_stats the mesh light's share of each.
                                        10. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
+    RWR_FLAG_LIGHT_MIS = 1u << 22      /* extension: multiple importance sampling (balance heuristic, Veach 1995) of the light ray and
+                                       the diffuse bounce ray.  Under the two flags above the light sample stands alone and the bounce
+                                       ray that finds the same emitter is silenced; under this flag both count, each weighted by its
+                                       share of the two densities, so that every light term is bounded by T * Le, the cap no longer
+                                       darkens receivers that touch an emitter, and both flags may stay on in any scene.  Without this
+                                       flag every frame is what it was, byte for byte.  All arithmetic f32, no contraction.
+                                       1. The flag is effective only while RWR_FLAG_LIGHT_SAMPLING or RWR_FLAG_LIGHT_PARTS is effective,
+                                          each by its own rule; otherwise it is cleared before the frame's kernels are chosen and the
+                                          frame is the frame without it, in the same kernels.  L: the lights the stage chooses among
+                                          (RWR_FLAG_LIGHT_PARTS' item 3; M under RWR_FLAG_LIGHT_SAMPLING alone).
+                                       2. No ray changes.  Eligible hits, the choice of the light, the sample's direction, the reach
+                                          tests, RNG dimensions, bounce rays and throughputs, rwr_last_render_stats, the shadow, glass
+                                          and gloss stats, rwr_last_traversal_plan, the depth, id and t planes and all six counts of
+                                          rwr_last_light_stats and rwr_last_part_light_stats are those of the frame without the flag,
+                                          bit for bit.  Only the values of items 4 and 5 change.
+                                       3. The weight.  The diffuse bounce ray has density p_b = (n . omega) / pi; the g of
+                                          RWR_FLAG_LIGHT_SAMPLING's item 3 and of RWR_FLAG_LIGHT_PARTS' item 6 is exactly p_b / p_l, p_l
+                                          the light sampler's density of omega with the 1 / L choice.  One function serves both sides:
+                                          m(g) = p_b / (p_b + p_l) = g / (1 + g), evaluated as
+                                            m(g) = g > 0 ? 1.0f / (1.0f + 1.0f / g) : 0.0f
+                                          two f32 divisions and one add: 0 for g <= 0 and for NaN, 0 for a g so small that 1 / g is
+                                          infinite, exactly 1 for g = infinity (d2 -> 0), with no special case.
+                                       4. The light term of a sample that reaches becomes T.c * (Le.c * m(g)) per channel, g computed as
+                                          under the two flags; converted and capped as before, but m <= 1, T <= 1 and Le <= 64 keep it
+                                          from ever reaching the cap.
+                                       5. The bounce side.  The hit of a diffuse (marked) ray that RWR_FLAG_LIGHT_SAMPLING's item 4 or
+                                          RWR_FLAG_LIGHT_PARTS' item 8 silences takes Le.c * m(g') per channel in place of 0, everywhere
+                                          in RWR_FLAG_EMISSIVE's rule: shading, the ambient part, and the hit's count in
+                                          rwr_last_emission_stats when a weighted channel is not zero.  g' is g for the direction the ray
+                                          did take.  O: the ray's origin; D: its direction as its queue record holds it; n: the normal
+                                          of the hit that sent it (item 3 of RWR_FLAG_LIGHT_SAMPLING); t: the hit's distance.
+                                          nd = dot3(n, D).
+                                          Sphere s (centre C, radius R): w = C - O; d2 = dot3(w, w) (> R*R, or the hit is not silenced);
+                                          s2 = R*R / d2; cmax = sqrtf(fmaxf(0, 1 - s2)); kc = s2 / (1 + cmax);
+                                          g' = ((2 * (float)L) * kc) * nd.
+                                          Face f: N_f its unit normal as the kernels hold it; cf = fabsf(dot3(N_f, D)); d2 = t * t;
+                                          inv_pdf that of f's part (every listed face of a part stores the same f32, item 2 of
+                                          RWR_FLAG_LIGHT_PARTS); g' = (((((float)L * inv_pdf) * nd) * cf) * 0.318309886f) / d2.
+                                          These hits still count in suppressed_hits (silenced or weighted).  Every hit the two flags
+                                          leave its Le keeps all of it: h0, the hits of mirror, glass and glossy rays, a sphere hit from
+                                          inside (!(d2 > R*R)), a sphere while only RWR_FLAG_LIGHT_PARTS is effective, a face while only
+                                          RWR_FLAG_LIGHT_SAMPLING is.  (A face whose cdf interval is empty in f32 is never drawn; its
+                                          bounce hits are weighted as if it were: the f32 limit RWR_FLAG_LIGHT_PARTS documents.)
+                                       6. The sum is the same integral: at every direction omega towards an emitter the light sample
+                                          contributes with weight p_l / (p_l + p_b) = 1 - m and the bounce ray with p_b / (p_l + p_b) = m.
+                                          The balance heuristic only; no power heuristic, no power-proportional light choice, no light
+                                          rays from glossy hits, no weighting of the sky.
+                                       7. The bit (after item 1) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
+                                          effective flags.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
+                                          RWR_ERR_UNSUPPORTED. */
 };
 /* every flag above, and the bits between them that the library keeps for itself: a caller sets none of the latter */
 #define RWR_FLAGS_RESERVED (0xfu << 17)
-#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21))
+#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21) | (1u << 22))
 
 #define RWR_MAX_BOUNCES 8u
 
@@ -944,13 +995,13 @@ RWR_API int rwr_last_gloss_stats(rwr_context *ctx, uint64_t *glossy_rays);
 RWR_API int rwr_last_emission_stats(rwr_context *ctx, uint64_t *emissive_hits);
 
 /* RWR_FLAG_LIGHT_SAMPLING: of the last render call, over all samples it traced — the light rays traced (item 3: a sample with
- * d2 > R*R and ndw > 0), those that reached their sphere, and the hits whose Le item 4 took as 0.  Zeros for a frame the flag did
- * nothing to.  Exact counts.  Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
+ * d2 > R*R and ndw > 0), those that reached their sphere, and the hits item 4 silenced (Le taken as 0) or, under
+ * RWR_FLAG_LIGHT_MIS, weighted (Le m(g') in its place: the count is the same).  Zeros for a frame the flag did nothing to.  Exact counts.  Waits for the frame, as rwr_last_render_stats does.  A NULL argument is RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_last_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits);
 
 /* RWR_FLAG_LIGHT_PARTS: the mesh light's share of each of rwr_last_light_stats' counts (which stay the light stage's totals) — the
- * light rays aimed at a face (item 6: d2 > 0 and ndw > 0), those that reached it, and the hits on faces of emitting parts whose
- * Le item 8 took as 0.  Zeros for a frame the flag did nothing to.  Exact counts.  Waits for the frame.  A NULL argument is
+ * light rays aimed at a face (item 6: d2 > 0 and ndw > 0), those that reached it, and the hits on faces of emitting parts that
+ * item 8 silenced or RWR_FLAG_LIGHT_MIS weighted.  Zeros for a frame the flag did nothing to.  Exact counts.  Waits for the frame.  A NULL argument is
  * RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_last_part_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits);
 

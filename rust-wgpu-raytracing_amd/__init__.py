@@ -58,6 +58,7 @@ FLAG_SOFT_SHADOWS = 1 << 14  # FLAG_SHADOWS' two lights get an angular size: pen
 FLAG_EMISSIVE = 1 << 15      # parts and spheres with an emission (set_part_emission, set_sphere_emission) give off light (include/rwr_hip.h)
 FLAG_LIGHT_SAMPLING = 1 << 16  # every diffuse hit also sends a ray towards an emitting sphere: next-event estimation (include/rwr_hip.h)
 FLAG_LIGHT_PARTS = 1 << 21     # ... or towards a point on a face of an emitting part, the mesh light (include/rwr_hip.h; bits 17-20 are reserved)
+FLAG_LIGHT_MIS = 1 << 22       # the light ray and the diffuse bounce ray are combined by the balance heuristic: multiple importance sampling (include/rwr_hip.h)
 MAX_EMISSION = 64.0          # RWR_MAX_EMISSION: the largest component of a radiance
 SHADOW_PARAMS_DTYPE = np.dtype([("mesh_light_radius", "<f4"), ("sphere_light_radius", "<f4")])
 REPROJECT_PARAMS_DTYPE = np.dtype([("max_history", "<u4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
@@ -603,8 +604,8 @@ class Context:
         return int(a.value)
 
     def last_light_stats(self):
-        """FLAG_LIGHT_SAMPLING: (light rays traced, those that reached their sphere, hits whose Le was suppressed) of the last
-        render call (rwr_last_light_stats)."""
+        """FLAG_LIGHT_SAMPLING: (light rays traced, those that reached their sphere, hits whose Le was suppressed or, under
+        FLAG_LIGHT_MIS, weighted) of the last render call (rwr_last_light_stats)."""
         a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(lib().rwr_last_light_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)

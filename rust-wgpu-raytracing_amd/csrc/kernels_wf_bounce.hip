@@ -399,7 +399,10 @@ RWR_DEV void add_sky(TraceShared &sh, const WfSky &sky, uint32_t e, float dy, f3
 // Light sampling on (gl.light, RWR_FLAG_LIGHT_SAMPLING item 4): O is the origin of the ray that found the hit and `marked` whether
 // its record says a diffuse hit sent it.  Such a ray's hit on an emitting sphere that O lies outside of — dot3(C - O, C - O) > R R,
 // the light stage's own test on the same origin — takes Le as 0: O's light sample has that light already; such hits are counted.
-RWR_DEV bool add_glow(const FrameParams &p, const WfGlow &gl, const ShadeRec *__restrict__ shade, int32_t obj, f3 &e1, f3 &le, f3 O, bool marked)
+// gl.light & 4 (RWR_FLAG_LIGHT_MIS item 5; uniform, a scalar branch): a silenced hit takes Le m(gp) instead, gp the g' that
+// mis_bounce_g made of the ray and its hit before the hit was shaded.
+RWR_DEV bool add_glow(const FrameParams &p, const WfGlow &gl, const ShadeRec *__restrict__ shade, int32_t obj, f3 &e1, f3 &le, f3 O, bool marked,
+                      float gp)
 {
     float4 g = glow_record(gl, p.n_materials > 1u, shade, obj);
     bool silenced = false;
@@ -412,13 +415,47 @@ RWR_DEV bool add_glow(const FrameParams &p, const WfGlow &gl, const ShadeRec *__
         // bit 2 (RWR_FLAG_LIGHT_PARTS item 8): such a ray's hit on a face of an emitting part — O's light sample may have aimed there
         const bool face = (gl.light & 2u) && marked && obj >= 0 && glows(g);
         silenced = silenced || face;
-        if (silenced) g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (silenced) {
+            const float m = (gl.light & 4u) ? mis_weight(gp) : 0.0f;   // (0 * Le: Le is finite and not negative, the product +0)
+            g = make_float4(g.x * m, g.y * m, g.z * m, 0.0f);
+        }
         count_glow_hits(gl.light_counts + 2, silenced);   // (the lanes that shade a hit here: the ballots take whoever is active)
         if (gl.light & 2u) count_glow_hits(gl.light_counts + 5, face);   // (uniform) the mesh light's share
     }
     le = mk3(g.x, g.y, g.z);
     e1 = mk3(e1.x + g.x, e1.y + g.y, e1.z + g.z);
     return glows(g);
+}
+// RWR_FLAG_LIGHT_MIS item 5: g' — the light sampler's g for the direction the ray (O, D) did take — of the hit (obj, t) of a marked
+// ray, in the rule's operations: one float, made where the ray and its hit are at hand anyway, ahead of the shading (the registers of
+// D, t and the normals are free again by then).  n is the normal the ray's origin left at its queue slot (pool_base + e): read here, ahead of
+// the emit step of the hit, which overwrites it.  The value means something only for a hit add_glow silences (a face whose part
+// is not listed has inv_pdf 0, a sphere seen from inside a kc without meaning: neither is silenced).
+RWR_DEV float mis_bounce_g(const FrameParams &p, const WfGlow &gl, const ShadeRec *__restrict__ shade, const TriRecord *__restrict__ tris, int32_t obj,
+                           f3 O, f3 D, float t, size_t pool_base, uint32_t e)
+{
+    // (the slot's address is made here, from a copy of e the compiler cannot tie to the ray record's address of long before: that
+    // one would stay in registers across the whole traversal)
+    asm volatile("" : "+v"(e));
+    const float4 rn = *reinterpret_cast<const float4 *>(gl.light_recs + pool_base + e);
+    const float nd = dot3(mk3(rn.x, rn.y, rn.z), D);
+    // (L and 1 / pi are made here, per call: as loop invariants they would be converted and moved into vector registers ahead of the
+    // kernel's item loop and stay there across the traversal, three to four registers that cost the per-lane forms a wave per SIMD)
+    uint32_t l = gl.light >> 8;
+    float inv_pi = 0.318309886f;
+    asm volatile("" : "+s"(l), "+v"(inv_pi));
+    const float Lf = (float)l;
+    if (obj >= 0) {
+        const float inv_pdf = glow_record(gl, p.n_materials > 1u, shade, obj).w;
+        const float cf = fabsf(dot3(ld3(tris[obj].nhat), D));
+        return Lf * inv_pdf * nd * cf * inv_pi / (t * t);
+    }
+    const f3 w = sub3(ld3(p.spheres[-2 - obj].center), O);
+    const float R = p.spheres[-2 - obj].radius;
+    const float s2 = R * R / dot3(w, w);
+    const float cmax = sqrtf(fmaxf(0.0f, 1.0f - s2));
+    const float kc = s2 / (1.0f + cmax);
+    return 2.0f * Lf * kc * nd;
 }
 // whether a ray record's last word carries emit_next_ray's mark
 RWR_DEV bool wf_ray_marked(float w) { return (__float_as_uint(w) >> 16) != 0u; }
@@ -549,9 +586,12 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
             uint32_t event = kEventNone;   // glass and glossy forms: what a counted hit did
             bool lit = false;              // GLOW forms: the hit's surface emits
             if (have) {
+                float gp = 0.0f;   // GLOW forms under RWR_FLAG_LIGHT_MIS: a marked ray's g'
+                if constexpr (GLOW)
+                    if ((gl.light & 4u) && wf_ray_marked(b.w)) gp = mis_bounce_g(p, gl, shade, tris, obj, O, D, best_t, pool_base, e);
                 const Shaded s1 = shade_winner<NMAP>(p, obj, best_t, mh.u, mh.v, mh.ndotd, shade, tex, O, D);
                 f3 e1 = s1.colour, le = f3{};
-                if (GLOW) lit = add_glow(p, gl, shade, obj, e1, le, O, wf_ray_marked(b.w));
+                if (GLOW) lit = add_glow(p, gl, shade, obj, e1, le, O, wf_ray_marked(b.w), gp);
                 if (SHADOW) shadow_hit<GLOW>(sh, p, wf, sw, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, e1, le);
                 else add_contribution(sh, e, thr.x * e1.x, thr.y * e1.y, thr.z * e1.z);
                 if constexpr (GLOW) {   // (the same calls, with the kernel's WfGlow behind the other arguments)
@@ -877,7 +917,13 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
                 for (int k = 0; k < 2; k++)
                     if (k ? have.y : have.x) {
                         f3 ek = k ? mk3(er.y, eg.y, eb.y) : mk3(er.x, eg.x, eb.x), le;
-                        lit[k] = add_glow(p, gl, shade, k ? obj.y : obj.x, ek, le, lane3(R.O, k), wf_ray_marked(k ? b1.w : b0.w));
+                        // (RWR_FLAG_LIGHT_MIS: g' is made here, behind the shading — the packet forms sit at their register bound, and a value
+                        // carried across the shading is a spilled one; the ray, its hit and the slot's normal are still at hand)
+                        float gpk = 0.0f;
+                        if ((gl.light & 4u) && wf_ray_marked(k ? b1.w : b0.w))
+                            gpk = mis_bounce_g(p, gl, shade, tris, k ? obj.y : obj.x, lane3(R.O, k), lane3(R.D, k), k ? best_t.y : best_t.x,
+                                               (size_t)tile * wf.group * kWfTilePixels, k ? e1 : e0);
+                        lit[k] = add_glow(p, gl, shade, k ? obj.y : obj.x, ek, le, lane3(R.O, k), wf_ray_marked(k ? b1.w : b0.w), gpk);
                         if (k) { er.y = ek.x; eg.y = ek.y; eb.y = ek.z; lr.y = le.x; lg.y = le.y; lb.y = le.z; }
                         else { er.x = ek.x; eg.x = ek.y; eb.x = ek.z; lr.x = le.x; lg.x = le.y; lb.x = le.z; }
                     }

@@ -21,6 +21,9 @@
 // t <= t_f and no face g at t_g < t_f or at t_g == t_f with g < f (bvh_occluded_before<true>).  Lanes of either kind share the
 // sphere tests and the one walk: a sphere lane passes self = 0, a face lane compares every sphere with '<='.  The forms without
 // PARTS hold the instructions they held before there were any.  tests/part_light_ref.c is the rule's literal evaluation.
+// RWR_FLAG_LIGHT_MIS (WfGlow::light & 4): the term is T Le m(g), m = mis_weight (rwr_surface.h), behind a wave-uniform switch at
+// both add sites — a scalar branch around two divisions in each of the eight forms, not eight forms more (resources:
+// profiles/mis_kernel_resources.txt).  tests/mis_ref.c is that rule's literal evaluation.
 #include <algorithm>
 #include <type_traits>
 
@@ -152,7 +155,8 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
                 reach = reach && !occ;
             }
             if (reach) {
-                const float g = 2.0f * Mf * kc * ndw;
+                float g = 2.0f * Mf * kc * ndw;
+                if (gl.light & 4u) g = mis_weight(g);   // (uniform) RWR_FLAG_LIGHT_MIS item 4
                 add_contribution(sh, e, thr.x * (Le.x * g), thr.y * (Le.y * g), thr.z * (Le.z * g));
             }
             n_rays += (uint32_t)__popcll(__ballot(go));
@@ -221,6 +225,7 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
                 else occ = bvh_occluded_before<true>(bvh.nodes, bvh.leaf_faces, tris, p.n_tris, s_stack, O, Ld, sr, ts, reach, self);
                 reach = reach && !occ;
             }
+            if (gl.light & 4u) g = mis_weight(g);   // (uniform) RWR_FLAG_LIGHT_MIS item 4
             if (reach) add_contribution(sh, e, thr.x * (Le.x * g), thr.y * (Le.y * g), thr.z * (Le.z * g));
             n_rays += (uint32_t)__popcll(__ballot(go));
             n_reached += (uint32_t)__popcll(__ballot(reach));

@@ -225,7 +225,12 @@ int WfFrame::glow_table()
         }
         RWR_HIP_CHECK(W.d_glow.ensure(n_recs));
         if (!W.glow_copied) RWR_HIP_CHECK(hipEventCreateWithFlags(&W.glow_copied.h, hipEventDisableTiming));
-        for (size_t i = 0; i < n_parts; i++) W.h_glow.h[i] = ctx->part_glow[i];
+        for (size_t i = 0; i < n_parts; i++) {
+            W.h_glow.h[i] = ctx->part_glow[i];
+            // (the spare component: the part's inv_pdf in the mesh light built last — read by mis_bounce_g under RWR_FLAG_LIGHT_MIS
+            // alone, in frames whose validation made that list current; a rebuild that changes one changes glow_version)
+            if (i < ctx->part_inv_pdf.size()) W.h_glow.h[i].on = ctx->part_inv_pdf[i];
+        }
         for (size_t i = 0; i < RWR_MAX_SPHERES; i++) W.h_glow.h[n_parts + i] = ctx->sphere_glow[i];
         RWR_HIP_CHECK(hipMemcpyAsync(W.d_glow.ptr, W.h_glow.h, n_recs * sizeof(SurfaceRec), hipMemcpyHostToDevice, stream));
         RWR_HIP_CHECK(hipEventRecord(W.glow_copied, stream));
@@ -236,7 +241,8 @@ int WfFrame::glow_table()
     ft.glow = WfGlow{W.d_glow.ptr, (uint32_t)n_parts, 0u, W.d_glow_hits.ptr, nullptr, nullptr, nullptr};
     // RWR_FLAG_LIGHT_SAMPLING, RWR_FLAG_LIGHT_PARTS: a normal per queue slot and the light ballots, per queue like the rays and kept like
     // them (allocated by the first frame that needs them); the frame's six counts start from zero.  trace_groups points ft.glow at a
-    // queue's share.  glow.light: bit 1 the spheres, bit 2 the mesh light (validate made its list and device copy current).
+    // queue's share.  glow.light: 1 the spheres, 2 the mesh light (validate made its list and device copy current), 4
+    // RWR_FLAG_LIGHT_MIS (mask values, as rwr_surface.h states them), bits 8-15 L, the lights the stage chooses among.
     ft.lights_on = rq.light || rq.light_parts;
     if (ft.lights_on) {
         if (rq.light) ft.lights = scene_lights(ctx);
@@ -246,7 +252,7 @@ int WfFrame::glow_table()
         RWR_HIP_CHECK(W.d_light_masks.ensure(n_queues * n_tiles * group * 8u));
         RWR_HIP_CHECK(W.d_light_counts.ensure(6));
         RWR_HIP_CHECK(hipMemsetAsync(W.d_light_counts.ptr, 0, 6 * sizeof(unsigned long long), stream));
-        ft.glow.light = (rq.light ? 1u : 0u) | (rq.light_parts ? 2u : 0u);
+        ft.glow.light = (rq.light ? 1u : 0u) | (rq.light_parts ? 2u : 0u) | (rq.light_mis ? 4u : 0u) | ((ft.lights.m + (rq.light_parts ? 1u : 0u)) << 8);
         ft.glow.light_counts = W.d_light_counts.ptr;
     }
     return RWR_OK;

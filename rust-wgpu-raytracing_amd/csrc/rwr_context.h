@@ -352,6 +352,7 @@ struct rwr_context {
     std::vector<rwr::PartLightRec> part_lights;
     rwr::DeviceBuffer<rwr::PartLightRec> d_part_lights;
     bool part_lights_dirty = true;
+    std::vector<float> part_inv_pdf;   // RWR_FLAG_LIGHT_MIS: per part, the inv_pdf of its listed faces (0: none listed), as the list built last holds it
     rwr::WfLights lights{};   // RWR_FLAG_LIGHT_SAMPLING: the emitting spheres in use (scene.cpp rebuild_lights: after the emission setters and rwr_scene_set_spheres)
     rwr_triangle_buffer_data triangles[RWR_MAX_TRIANGLES]{};
     uint32_t n_triangles = 0;

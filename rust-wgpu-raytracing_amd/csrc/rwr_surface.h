@@ -125,6 +125,10 @@ struct WfSurfaces {
 // stage aims at the mesh light too (rwr_part_lights.h), and add_glow takes Le as 0 for the hit of a marked ray on a face of an
 // emitting part and counts it in light_counts[2] and [5].  Either bit marks rays and stores normals.  light_counts holds six:
 // [3], [4], [5] are the mesh light's share of [0], [1], [2].
+// A third bit, mask value 4 — RWR_FLAG_LIGHT_MIS is effective (with bit 1 or 2): k_wf_light adds T Le m(g) in place of T Le g, and add_glow gives
+// the hits it silenced Le m(g') in place of 0 (mis_weight below; g' from the ray, the hit and the slot's LightRec, which the hit's own
+// emit_next_ray has not overwritten yet).  Bits 8-15 hold L, the lights the stage chooses among (M + 1 with the mesh light, else M),
+// which g' needs; a part's record of `table` carries the inv_pdf of the part's listed faces in its fourth component (0: none listed).
 struct LightRec { float n[3]; uint32_t pad; };
 static_assert(sizeof(LightRec) == 16, "LightRec is 16 B");
 struct WfGlow {
@@ -195,6 +199,9 @@ __device__ __forceinline__ float4 glow_record(const WfGlow &gl, bool several_par
     return surface_record(gl.table, gl.n_parts, several_parts, shade, obj);
 }
 __device__ __forceinline__ bool glows(const float4 &g) { return g.x != 0.0f || g.y != 0.0f || g.z != 0.0f; }
+// RWR_FLAG_LIGHT_MIS item 3: the balance heuristic's weight of the bounce side, m(g) = g / (1 + g) for g = p_b / p_l, in the form that
+// is exact at both ends with no special case — 1 / g is +inf for a denormal g (m = 0) and 0 for g = +inf (m = 1); 0 for g <= 0 and NaN.
+__device__ __forceinline__ float mis_weight(float g) { return g > 0.0f ? 1.0f / (1.0f + 1.0f / g) : 0.0f; }
 // A wave's shaded hits on emitting surfaces (two per lane: a packet's or a pixel pair's) into the frame's counter, as
 // count_surface_events counts: ballots and popcounts, one atomic from the wave's first active lane.  Call where the wave's lanes
 // have come together again.

@@ -76,6 +76,18 @@ int scene_part_lights(rwr_context *ctx, uint32_t &n)
             RWR_HIP_CHECK(ctx->d_part_lights.ensure(ctx->part_lights.size()));
             RWR_HIP_CHECK(hipMemcpy(ctx->d_part_lights.ptr, ctx->part_lights.data(), ctx->part_lights.size() * sizeof(PartLightRec), hipMemcpyHostToDevice));
         }
+        // RWR_FLAG_LIGHT_MIS item 5: a part's inv_pdf (every listed face of a part stores the same f32) rides in the spare component of
+        // its record of the emission table; when one changed, a WfState's copy is refreshed like any other change of that table (a
+        // rebuild that leaves them all as they were — the common one under RWR_FLAG_LIGHT_PARTS alone is not: W moves — costs nothing)
+        std::vector<float> inv_pdf(ctx->part_glow.size(), 0.0f);
+        for (const PartLightRec &r : ctx->part_lights) {
+            const uint32_t part = ctx->st_face_mat[r.face % ctx->n_faces];
+            if (part < inv_pdf.size()) inv_pdf[part] = r.inv_pdf;
+        }
+        if (inv_pdf != ctx->part_inv_pdf) {
+            ctx->part_inv_pdf = std::move(inv_pdf);
+            ctx->glow_version++;
+        }
         ctx->part_lights_dirty = false;
     }
     n = (uint32_t)ctx->part_lights.size();

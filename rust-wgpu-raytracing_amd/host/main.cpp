@@ -7,7 +7,7 @@
 //              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]]
 //              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]...
 //              [--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]]
-//              [--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts]
+//              [--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis]
 //              [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
@@ -157,6 +157,7 @@ int main(int argc, char **argv)
     std::vector<Emitter> emitters;
     bool light_sampling = false;   // --light-sampling
     bool light_parts = false;      // --light-parts
+    bool light_mis = false;        // --light-mis
     auto parse_emitter = [](const char *text, Emitter &e) {
         char *end = nullptr;
         if (*text < '0' || *text > '9') return false;
@@ -269,6 +270,7 @@ int main(int argc, char **argv)
         }
         else if (a == "--light-sampling") light_sampling = true;
         else if (a == "--light-parts") light_parts = true;
+        else if (a == "--light-mis") light_mis = true;
         else if (a == "--show-params") show_params = true;
         else if (a == "--resize") {
             Resize r{0, 0, 0};
@@ -285,7 +287,7 @@ int main(int argc, char **argv)
                         "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
                         "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]... "
                         "[--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... "
-                        "[--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] "
+                        "[--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] "
                         "[--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]] "
                         "[--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
@@ -321,6 +323,9 @@ int main(int argc, char **argv)
                         "  --light-parts  every diffuse hit's light ray may aim at a point on a face of an emitting part (RWR_FLAG_LIGHT_PARTS; implies "
                         "nothing: it needs --emissive-part and --bounces >= 1 to do anything; with --light-sampling one ray per hit chooses among "
                         "the spheres and the parts); prints `part light rays N, reached M` for the final frame\n"
+                        "  --light-mis  the light ray and the diffuse bounce ray that finds the same emitter are combined by the balance heuristic "
+                        "(RWR_FLAG_LIGHT_MIS, multiple importance sampling; implies nothing: it needs --light-sampling or --light-parts in effect to do "
+                        "anything); with it both may stay on in a scene that glows all over; prints `weighted hits N` for the final frame\n"
                         "  --reproject   every frame is blended with the history of the frames before it, fetched where its points were seen "
                         "last frame, while the camera moves (RWR_FLAG_REPROJECT; with --keys every key step's frame feeds the next one's history): "
                         "at most N frames of history per pixel (1-1024), taps of faces whose normals' cosine is at least C and whose distance "
@@ -337,7 +342,8 @@ int main(int argc, char **argv)
                            (mirrors.empty() ? 0u : (uint32_t)RWR_FLAG_MIRRORS) | (glasses.empty() ? 0u : (uint32_t)RWR_FLAG_GLASS) |
                            (glosses.empty() ? 0u : (uint32_t)RWR_FLAG_GLOSSY) | (soft_shadows ? (uint32_t)RWR_FLAG_SOFT_SHADOWS : 0u) |
                            (reproject ? (uint32_t)RWR_FLAG_REPROJECT : 0u) | (emitters.empty() ? 0u : (uint32_t)RWR_FLAG_EMISSIVE) |
-                           (light_sampling ? (uint32_t)RWR_FLAG_LIGHT_SAMPLING : 0u) | (light_parts ? (uint32_t)RWR_FLAG_LIGHT_PARTS : 0u);
+                           (light_sampling ? (uint32_t)RWR_FLAG_LIGHT_SAMPLING : 0u) | (light_parts ? (uint32_t)RWR_FLAG_LIGHT_PARTS : 0u) |
+                           (light_mis ? (uint32_t)RWR_FLAG_LIGHT_MIS : 0u);
     if (show_params) {
         if (reproject)   // (a line of its own, ahead of the line every run prints)
             std::printf("reproject 1 history %u normal %g depth %g\n", reproject_params.max_history, (double)reproject_params.normal_cos_min,
@@ -449,6 +455,7 @@ int main(int argc, char **argv)
             state.part_light_rays(rays, reached);
             std::printf("part light rays %llu, reached %llu\n", (unsigned long long)rays, (unsigned long long)reached);
         }
+        if (light_mis) std::printf("weighted hits %llu\n", (unsigned long long)state.light_weighted_hits());
         if (timing) std::printf("%.3f ms/frame over %llu frames (update + render, host wall clock)\n", sec * 1e3 / (double)rendered,
                                 (unsigned long long)rendered);
         if (!out.empty()) {

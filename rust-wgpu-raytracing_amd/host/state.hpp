@@ -161,6 +161,14 @@ public:
         rays = reached = 0;
         check(rwr_last_light_stats(ctx_, &rays, &reached, &silenced));
     }
+    // extension (RWR_FLAG_LIGHT_MIS): the diffuse rays' hits on a sampled emitter in the frame rendered last — weighted under the
+    // flag, silenced without it
+    uint64_t light_weighted_hits()
+    {
+        uint64_t rays = 0, reached = 0, hits = 0;
+        check(rwr_last_light_stats(ctx_, &rays, &reached, &hits));
+        return hits;
+    }
     // extension (RWR_FLAG_LIGHT_PARTS): the mesh light's share of them
     void part_light_rays(uint64_t &rays, uint64_t &reached)
     {
