@@ -584,7 +584,7 @@ enum {
                                           RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's effective flags; rwr_last_light_stats
                                           counts the light stage's totals, rwr_last_part_light_stats the mesh light's share of each.
                                        10. With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
-    RWR_FLAG_LIGHT_MIS = 1u << 22      /* extension: multiple importance sampling (balance heuristic, Veach 1995) of the light ray and
+    RWR_FLAG_LIGHT_MIS = 1u << 22,     /* extension: multiple importance sampling (balance heuristic, Veach 1995) of the light ray and
                                        the diffuse bounce ray.  Under the two flags above the light sample stands alone and the bounce
                                        ray that finds the same emitter is silenced; under this flag both count, each weighted by its
                                        share of the two densities, so that every light term is bounded by T * Le, the cap no longer
@@ -634,10 +634,44 @@ enum {
                                        7. The bit (after item 1) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
                                           effective flags.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED. */
+    RWR_FLAG_SOBOL = 1u << 23          /* extension: an Owen-scrambled Sobol sample sequence (Burley 2020, "Practical Hash-based Owen
+                                       Scrambling") in place of the independent hash.  Every random number the integrator draws — the
+                                       pixel jitter, the disk points of the bounce rays, the glass and gloss choices, the soft-shadow
+                                       disk points, the light stage's numbers — is (h >> 8) * 2^-24 of a 32-bit word h; without the
+                                       flag h = rng_hash(pixel, sample, dim, seed), with it h = rng_sobol(pixel, sample, dim, seed).
+                                       Dimension numbers, the order of draws, the conversion and everything downstream stay; only the
+                                       word changes.  A pixel's samples are then stratified against each other and the error falls
+                                       faster than 1 / spp.  Off by default; without the flag every frame is what it was, byte for byte.
+                                       1. The word.  u32 wrapping arithmetic only; rev(x): the 32 bits of x reversed; rng_mix:
+                                          rng_hash's mixer (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16).
+                                            lk(x, s)   : x += s; x ^= x * 0x6c50b47c; x ^= x * 0xb82f1e52; x ^= x * 0xc7afe638;
+                                                         x ^= x * 0x8d22f6e6
+                                            owen(x, s) = rev(lk(rev(x), s))
+                                            sobol1(i)  : r = 0; v = 1u << 31; while (i) { if (i & 1) r ^= v; i >>= 1; v ^= v >> 1; } -> r
+                                            h0  = rng_mix((seed ^ 0x9E3779B9) ^ pixel)
+                                            s   = rng_mix(h0 ^ ((dim >> 1) * 0xC2B2AE35))
+                                            idx = owen(sample, s)
+                                            x   = (dim & 1) ? sobol1(idx) : rev(idx)
+                                            rng_sobol = owen(x, rng_mix(s ^ (0x85EBCA6B + (dim & 1))))
+                                          pixel = y * width + x of the whole frame, sample the GLOBAL sample index (an accumulation's
+                                          base included), as for rng_hash: K accumulated frames of s samples are one frame of K * s.
+                                       2. Dimensions 2g and 2g + 1 are the two coordinates of one scrambled, shuffled (0,2)-sequence
+                                          with a stream of its own per pixel, seed and g: the jitter pair, every disk try of a bounce
+                                          ray and every soft-shadow point are such pairs.  The light stage's disk pairs start at an
+                                          odd dimension behind generations 1, 3, 5, 7: those are stratified per coordinate only.
+                                       3. The flag is effective only in a frame the wavefront integrator renders (several samples, a
+                                          bounce, an accumulation, shadow rays, a stage behind the resolve, an emitter); it sends no
+                                          frame there.  Otherwise it is cleared and the frame is the frame without it.
+                                       4. Rays, counts and planes follow from the numbers: every rwr_last_*_stats count is that of the
+                                          CPU reference drawing the same words.  Bands, strips, the gather, frames in flight,
+                                          accumulation and every schedule give the same bytes.
+                                       5. The bit (after item 3) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
+                                          effective flags.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
+                                          RWR_ERR_UNSUPPORTED. */
 };
 /* every flag above, and the bits between them that the library keeps for itself: a caller sets none of the latter */
 #define RWR_FLAGS_RESERVED (0xfu << 17)
-#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21) | (1u << 22))
+#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21) | (1u << 22) | (1u << 23))
 
 #define RWR_MAX_BOUNCES 8u
 
@@ -1089,6 +1123,11 @@ RWR_API int rwr_selftest_exact_math(rwr_context *ctx, uint32_t normalize_count, 
  * takes (|ndotd| >= kEpsilon or NaN) compared through the kernel's choice of short form or IEEE division, mismatches}.
  * A non-zero mismatch count is a bug. */
 RWR_API int rwr_selftest_exact_div(rwr_context *ctx, uint32_t count, uint32_t seed, uint64_t out4[4]);
+
+/* Self-test of RWR_FLAG_SOBOL's word: out[i] = rng_sobol(pixel[i], sample[i], dim[i], seed[i]) (the flag's item 1) as the kernels'
+ * device function evaluates it, for n tuples (at most 2^24 a call).  A word that differs from the definition's is a bug. */
+RWR_API int rwr_selftest_sobol(rwr_context *ctx, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, const uint32_t *seed,
+                               size_t n, uint32_t *out);
 
 /* Measurement aid for roofline accounting (bench.py): runs a short f32 VALU loop with `waves_per_simd` (1..8)
  * waves on every SIMD and stamps the shader cycle counter against the constant 100 MHz counter.

@@ -59,7 +59,8 @@ FLAG_EMISSIVE = 1 << 15      # parts and spheres with an emission (set_part_emis
 FLAG_LIGHT_SAMPLING = 1 << 16  # every diffuse hit also sends a ray towards an emitting sphere: next-event estimation (include/rwr_hip.h)
 FLAG_LIGHT_PARTS = 1 << 21     # ... or towards a point on a face of an emitting part, the mesh light (include/rwr_hip.h; bits 17-20 are reserved)
 FLAG_LIGHT_MIS = 1 << 22       # the light ray and the diffuse bounce ray are combined by the balance heuristic: multiple importance sampling (include/rwr_hip.h)
-MAX_EMISSION = 64.0          # RWR_MAX_EMISSION: the largest component of a radiance
+FLAG_SOBOL = 1 << 23           # every random number of the path tracer comes from an Owen-scrambled Sobol sequence instead of the hash (include/rwr_hip.h)
+MAX_EMISSION = 64.0         # RWR_MAX_EMISSION: the largest component of a radiance
 SHADOW_PARAMS_DTYPE = np.dtype([("mesh_light_radius", "<f4"), ("sphere_light_radius", "<f4")])
 REPROJECT_PARAMS_DTYPE = np.dtype([("max_history", "<u4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
 MAX_BOUNCES = 8
@@ -153,6 +154,7 @@ def lib() -> C.CDLL:
         "rwr_write_png_rgba8": [C.c_char_p, vp, u32, u32, i32, i32],
         "rwr_ctx_set_kernel_timing": [vp, u32], "rwr_kernel_timing_stats": [vp, vp, vp],
         "rwr_selftest_exact_math": [vp, u32, u32, vp], "rwr_selftest_exact_div": [vp, u32, u32, vp], "rwr_ctx_set_frames_in_flight": [vp, u32],
+        "rwr_selftest_sobol": [vp, vp, vp, vp, vp, C.c_size_t, vp],
         "rwr_dist_get_unique_id": [vp], "rwr_dist_init": [vp, i32, i32, vp], "rwr_dist_band": [u32, u32, u32, vp, vp],
         "rwr_dist_gather_rgba8": [vp, i32], "rwr_dist_gather_strips_rgba8": [vp, i32], "rwr_dist_frame": [vp, vp], "rwr_dist_readback": [vp, vp],
         "rwr_dist_barrier": [vp], "rwr_dist_destroy": [vp],
@@ -169,7 +171,8 @@ def lib() -> C.CDLL:
                            "rwr_last_reproject_stats", "rwr_reproject_readback", "rwr_scene_set_part_gloss", "rwr_scene_set_sphere_gloss",
                            "rwr_scene_get_part_gloss", "rwr_scene_get_sphere_gloss", "rwr_last_gloss_stats",
                            "rwr_shadow_set_params", "rwr_shadow_get_params", "rwr_scene_set_part_emission", "rwr_scene_set_sphere_emission",
-                           "rwr_scene_get_part_emission", "rwr_scene_get_sphere_emission", "rwr_last_emission_stats", "rwr_last_light_stats", "rwr_last_part_light_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_scene_get_part_emission", "rwr_scene_get_sphere_emission", "rwr_last_emission_stats", "rwr_last_light_stats", "rwr_last_part_light_stats",
+                           "rwr_selftest_sobol")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -733,6 +736,17 @@ class Context:
         out = (C.c_uint64 * 4)()
         _check(lib().rwr_selftest_exact_div(self._h, count, seed, out))
         return tuple(int(v) for v in out)
+
+    def selftest_sobol(self, pixel, sample, dim, seed) -> np.ndarray:
+        """FLAG_SOBOL's 32-bit word for every tuple (pixel[i], sample[i], dim[i], seed[i]), evaluated by the kernels' device
+        function (rwr_selftest_sobol)."""
+        cols = [np.ascontiguousarray(a, dtype=np.uint32).ravel() for a in (pixel, sample, dim, seed)]
+        n = len(cols[0])
+        if any(len(c) != n for c in cols):
+            raise ValueError("the four columns must have one length")
+        out = np.zeros(n, np.uint32)
+        _check(lib().rwr_selftest_sobol(self._h, *[c.ctypes.data_as(C.c_void_p) for c in cols], n, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def measure_valu_clock(self, waves_per_simd: int = 8) -> dict:
         """Shader clock (MHz) and cycles a SIMD spends per wave64 v_fma_f32 / v_pk_fma_f32, measured under load."""

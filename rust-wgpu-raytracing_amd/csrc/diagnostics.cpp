@@ -37,6 +37,24 @@ int rwr_selftest_exact_div(rwr_context *ctx, uint32_t count, uint32_t seed, uint
     return run_selftest(ctx, out4, [&](unsigned long long *d) { return launch_selftest_exact_div(ctx->stream, d, count, seed); });
 }
 
+int rwr_selftest_sobol(rwr_context *ctx, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, const uint32_t *seed, size_t n,
+                       uint32_t *out)
+{
+    if (!ctx || !pixel || !sample || !dim || !seed || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n > (size_t)1 << 24) return set_error(RWR_ERR_INVALID_ARGUMENT, "at most 2^24 tuples a call, not %zu", n);
+    if (n == 0) return RWR_OK;
+    DeviceGuard g(ctx->device);
+    DeviceBuffer<uint32_t> d;   // the four columns, then the words
+    RWR_HIP_CHECK(d.ensure(5 * n));
+    const uint32_t *cols[4] = {pixel, sample, dim, seed};
+    for (size_t k = 0; k < 4; k++)
+        RWR_HIP_CHECK(hipMemcpyAsync(d.ptr + k * n, cols[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    RWR_HIP_CHECK(launch_selftest_sobol(ctx->stream, d.ptr, (uint32_t)n, d.ptr + 4 * n));
+    RWR_HIP_CHECK(hipMemcpyAsync(out, d.ptr + 4 * n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    RWR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return RWR_OK;
+}
+
 int rwr_debug_tile_classes(rwr_context *ctx, uint32_t *classes, size_t capacity, uint32_t *grid_x, uint32_t *grid_y)
 {
     if (!ctx || !grid_x || !grid_y) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");

@@ -13,7 +13,7 @@ namespace {
 // id / t planes, so RWR_FLAG_AUX_OUTPUTS is implied, and its own bit is not part of rp.flags from there on (nor of a history's key).
 // mode: a surface flag switches on the surfaces of its model (surface_mode's bit).
 struct FlagRule { uint32_t flag; const char *name, *stage, *why; uint32_t mode; };
-constexpr FlagRule kFlagRules[13] = {
+constexpr FlagRule kFlagRules[14] = {
     {RWR_FLAG_ACCUMULATE, "RWR_FLAG_ACCUMULATE", nullptr, nullptr, 0u},
     {RWR_FLAG_SHADOWS, "RWR_FLAG_SHADOWS", nullptr, nullptr, 0u},
     {RWR_FLAG_DENOISE, "RWR_FLAG_DENOISE", "filter", "its taps reach 62 pixels", 0u},
@@ -26,7 +26,8 @@ constexpr FlagRule kFlagRules[13] = {
     {RWR_FLAG_EMISSIVE, "RWR_FLAG_EMISSIVE", nullptr, nullptr, 0u},
     {RWR_FLAG_LIGHT_SAMPLING, "RWR_FLAG_LIGHT_SAMPLING", nullptr, nullptr, 0u},
     {RWR_FLAG_LIGHT_PARTS, "RWR_FLAG_LIGHT_PARTS", nullptr, nullptr, 0u},
-    {RWR_FLAG_LIGHT_MIS, "RWR_FLAG_LIGHT_MIS", nullptr, nullptr, 0u}};
+    {RWR_FLAG_LIGHT_MIS, "RWR_FLAG_LIGHT_MIS", nullptr, nullptr, 0u},
+    {RWR_FLAG_SOBOL, "RWR_FLAG_SOBOL", nullptr, nullptr, 0u}};
 constexpr uint32_t kSurfaceFlags = RWR_FLAG_MIRRORS | RWR_FLAG_GLASS | RWR_FLAG_GLOSSY;
 
 // What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
@@ -133,11 +134,15 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
     auto has = [](uint32_t flags, uint32_t flag) { return (flags & flag) != 0; };
     rq = FrameRequest{rp, row_begin, row_end, row_pitch, has(rp.flags, RWR_FLAG_AUX_OUTPUTS), has(asked, RWR_FLAG_ACCUMULATE), has(asked, RWR_FLAG_SHADOWS),
                       has(asked, RWR_FLAG_DENOISE), has(asked, RWR_FLAG_REPROJECT), has(rp.flags, RWR_FLAG_MIRRORS), has(rp.flags, RWR_FLAG_GLASS),
-                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), has(rp.flags, RWR_FLAG_EMISSIVE), has(rp.flags, RWR_FLAG_LIGHT_SAMPLING), has(rp.flags, RWR_FLAG_LIGHT_PARTS), has(rp.flags, RWR_FLAG_LIGHT_MIS), false, false};
+                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), has(rp.flags, RWR_FLAG_EMISSIVE), has(rp.flags, RWR_FLAG_LIGHT_SAMPLING), has(rp.flags, RWR_FLAG_LIGHT_PARTS), has(rp.flags, RWR_FLAG_LIGHT_MIS), false, false, false};
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
     // with shadow rays (the integrator's stages trace them), one the filter follows (it runs behind the integrator's resolve) or one
     // with an emitter (the integrator's kernels add its light)
     rq.wavefront = rp.spp != 1 || rp.max_bounces != 0 || rq.accumulate || rq.shadows || rq.denoise || rq.reproject || rq.glow;
+    // The sample sequence changes the integrator's random numbers and nothing else: it sends no frame there, and a frame of the
+    // reference's kernels draws none (rq.rp.flags is what the histories' keys and the kernels see)
+    rq.sobol = rq.wavefront && has(rp.flags, RWR_FLAG_SOBOL);
+    if (!rq.sobol) rq.rp.flags &= ~(uint32_t)RWR_FLAG_SOBOL;
     rq.dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;
     if (rq.dormant && (rq.wavefront || (rp.flags & RWR_FLAG_USE_BVH)))
         return set_error(RWR_ERR_UNSUPPORTED, "single-triangle passes and RWR_FLAG_ORTHO_RAYS apply to the reference frame (spp 1, no bounce, no RWR_FLAG_USE_BVH)");

@@ -196,6 +196,22 @@ k_clock_probe(ulonglong2 *out, uint32_t ticks)
     if (threadIdx.x == 0) out[0] = make_ulonglong2(c1 - c0, r1 - r0);
 }
 
+// RWR_FLAG_SOBOL: out[i] = rng_sobol of tuple i (rwr_device.h), for rwr_selftest_sobol and tests/test_gpu_sobol.py.
+// in: the four columns one after the other, n words each (pixel, sample, dim, seed).
+__global__ void __launch_bounds__(256)
+k_selftest_sobol(const uint32_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) out[i] = rng_sobol(in[i], in[n + i], in[2u * n + i], in[3u * n + i]);
+}
+
+hipError_t launch_selftest_sobol(hipStream_t s, const uint32_t *d_in, uint32_t n, uint32_t *d_out)
+{
+    if (n == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_selftest_sobol, dim3((n + 255u) / 256u), dim3(256), 0, s, d_in, n, d_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_selftest_exact_div(hipStream_t s, unsigned long long *d_out4, uint32_t count, uint32_t seed)
 {
     hipLaunchKernelGGL(k_selftest_div, dim3(8192), dim3(256), 0, s, d_out4, count, seed);

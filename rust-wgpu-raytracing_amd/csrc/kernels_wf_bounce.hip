@@ -315,8 +315,9 @@ RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const 
         const uint32_t r = e & (kWfTilePixels - 1u), w = r >> 7, k = (r >> 6) & 1u, l = r & 63u;
         const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (w & 1u) * 32u + 2u * (l & 15u) + k;
         const uint32_t py = p.row_begin + (tile / wf.tiles_x) * p.row_pitch + (w >> 1) * 4u + (l >> 4);
+        const bool sob = (p.flags & RWR_FLAG_SOBOL) != 0u;   // (uniform) RWR_FLAG_SOBOL: the sequence's numbers in place of the hash's
         if ((SURF == kSurfGlass || SURF == kSurfGloss) && eta != 0.0f) {
-            const float u = rng_uniform(py * p.width + px, em.sample_base + e / kWfTilePixels, em.next_dim, p.seed);
+            const float u = rng_uniform(py * p.width + px, em.sample_base + e / kWfTilePixels, em.next_dim, p.seed, sob);
             f3 m;
             event = refract_or_reflect(n, D, obj >= 0, ndotd, eta, u, D1, m);
             const f3 P = along(O, t, D);
@@ -324,7 +325,7 @@ RWR_DEV uint32_t emit_next_ray(const FrameParams &p, const WfBuffers &wf, const 
         } else {
             f3 Rf = D;
             if (SURF == kSurfGloss) Rf = gloss_reflection(n, D);   // (gloss_direction's first half, ahead of the disk loop: fewer registers across it)
-            D1 = bounce_direction(n, py * p.width + px, em.sample_base + e / kWfTilePixels, p.seed, em.next_dim);
+            D1 = bounce_direction(n, py * p.width + px, em.sample_base + e / kWfTilePixels, p.seed, sob, em.next_dim);
             if (SURF == kSurfGloss) {
                 const bool glossy = rho != 0.0f;
                 const f3 S = gloss_blend(Rf, D1, rho);

@@ -92,12 +92,13 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
             const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (wv & 1u) * 32u + 2u * (l & 15u) + k;
             const uint32_t py = p.row_begin + (tile / wf.tiles_x) * p.row_pitch + (wv >> 1) * 4u + (l >> 4);
             const uint32_t pixel = py * p.width + px, sample = sample_base + e / kWfTilePixels;
+            const bool sob = (p.flags & RWR_FLAG_SOBOL) != 0u;   // (uniform) the light stage's numbers are the sequence's: RWR_FLAG_SOBOL
             // which sphere: one emitter needs no random number's value and no select
             uint32_t s = lights.index[0];
             f3 Le = mk3(lights.le[0][0], lights.le[0][1], lights.le[0][2]);
             bool mesh = PARTS && live && M == 0u;   // PARTS: this lane's light is the mesh light (the only one there is when M is 0)
             if ((PARTS ? parts.l : M) > 1u) {   // uniform
-                const float u = rng_uniform(pixel, sample, dim0, p.seed);
+                const float u = rng_uniform(pixel, sample, dim0, p.seed, sob);
                 const uint32_t i = min((uint32_t)(u * Mf), (PARTS ? parts.l : M) - 1u);
 #pragma unroll
                 for (uint32_t q = 1; q < RWR_MAX_SPHERES; q++)
@@ -121,11 +122,7 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
             const float cmax = sqrtf(fmaxf(0.0f, 1.0f - s2));
             const float kc = s2 / (1.0f + cmax);
             float da = 0.0f, db = 0.0f;
-            for (uint32_t q = 0; q < 8u; q++) {   // bounce_direction's rejection loop, operation for operation
-                const float ua = 2.0f * rng_uniform(pixel, sample, dim0 + 1u + 2u * q, p.seed) - 1.0f;
-                const float ub = 2.0f * rng_uniform(pixel, sample, dim0 + 2u + 2u * q, p.seed) - 1.0f;
-                if (ua * ua + ub * ub <= 1.0f) { da = ua; db = ub; break; }
-            }
+            rng_disk_point(pixel, sample, dim0 + 1u, p.seed, sob, da, db);   // bounce_direction's rejection loop, operation for operation
             const float qq = da * da + db * db;
             const float c = 1.0f - qq * kc;
             const float rr = qq > 0.0f ? sqrtf(fmaxf(0.0f, 1.0f - c * c) / qq) : 0.0f;
@@ -172,7 +169,7 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
             float ts = 0.0f;
             if (__any(mesh)) {
                 // the face: the first list entry j with uf < cdf_j (the last cdf is 1 > uf: the search ends inside the list)
-                const float uf = rng_uniform(pixel, sample, dim0 + 1u, p.seed);
+                const float uf = rng_uniform(pixel, sample, dim0 + 1u, p.seed, sob);
                 uint32_t lo = 0u, hi = mesh ? parts.n - 1u : 0u;
                 while (lo < hi) {
                     const uint32_t mid = (lo + hi) >> 1;
@@ -183,7 +180,7 @@ k_wf_light(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDev
                 const uint32_t f = __float_as_uint(rec.y);
                 const bool listed = mesh && f < p.n_tris;   // (a well-formed list names faces of the scene: nothing is read past them)
                 const float inv_pdf = rec.z;
-                float u1 = rng_uniform(pixel, sample, dim0 + 2u, p.seed), u2 = rng_uniform(pixel, sample, dim0 + 3u, p.seed);
+                float u1 = rng_uniform(pixel, sample, dim0 + 2u, p.seed, sob), u2 = rng_uniform(pixel, sample, dim0 + 3u, p.seed, sob);
                 if (u1 + u2 > 1.0f) { u1 = 1.0f - u1; u2 = 1.0f - u2; }
                 const TriRecord &T = tris[listed ? f : 0u];
                 f3 p0 = mk3(0.0f, 0.0f, 0.0f), p1 = p0, p2 = p0, nh = p0, Lf = p0;

@@ -43,6 +43,27 @@ RWR_DEV float rng_dim(uint32_t base, uint32_t dim)
 {
     return (float)(rng_mix(base ^ (dim * 0xC2B2AE35u)) >> 8) * (1.0f / 16777216.0f);
 }
+// RWR_FLAG_SOBOL (sobol: wave-uniform): `base` is sobol_pixel of the pixel instead, which the sample does not enter — the
+// sequence's steps take it.  rng_draw2: the uniforms of dimensions dim and dim + 1, dim even, one pair of the sequence.
+RWR_DEV uint32_t rng_base(uint32_t pixel, uint32_t sample, uint32_t seed, bool sobol)
+{
+    return sobol ? sobol_pixel(pixel, seed) : rng_base(pixel, sample, seed);
+}
+RWR_DEV float rng_draw(uint32_t base, uint32_t sample, uint32_t dim, bool sobol)
+{
+    return sobol ? rng_to_unit(sobol_coord(sobol_pair(base, sample, dim), dim & 1u)) : rng_dim(base, dim);
+}
+RWR_DEV void rng_draw2(uint32_t base, uint32_t sample, uint32_t dim, bool sobol, float &u0, float &u1)
+{
+    if (sobol) {
+        const SobolPair q = sobol_pair(base, sample, dim);
+        u0 = rng_to_unit(sobol_coord(q, 0u));
+        u1 = rng_to_unit(sobol_coord(q, 1u));
+    } else {
+        u0 = rng_dim(base, dim);
+        u1 = rng_dim(base, dim + 1u);
+    }
+}
 
 // n / d for a wave-uniform positive integer-valued d (the frame's width or height) and 0 <= n < 2^16: the
 // compiler's IEEE expansion of the quotient with the reciprocal refined once per wave and the instructions that
@@ -75,7 +96,7 @@ RWR_DEV v3 pixel_pair_ray_dir_at(const Cam &cam, f2 fx, f2 fy, float width, floa
 
 // bounce_direction (rwr_device.h) for a pixel pair; lanes / elements whose `want` is 0 still compute (cheaply
 // wrong values are never stored).  base: rng_base of each pixel for this sample.
-RWR_DEV v3 bounce_direction_pair(v3 n, u2 base, i2 want)
+RWR_DEV v3 bounce_direction_pair(v3 n, u2 base, i2 want, uint32_t sample, bool sobol)
 {
     // Rejection-sample the unit disk (up to 8 tries per pixel, a = b = 0 when all fail).  78.5 % of the tries
     // succeed: the first try runs for both pixels at once; for the rest a lane takes ONE try of ONE pixel per
@@ -84,8 +105,11 @@ RWR_DEV v3 bounce_direction_pair(v3 n, u2 base, i2 want)
     f2 a = splat(0.0f), b = splat(0.0f);
     i2 need = want;
     {
-        const f2 ua = 2.0f * f2{rng_dim(base.x, 2u), rng_dim(base.y, 2u)} - 1.0f;
-        const f2 ub = 2.0f * f2{rng_dim(base.x, 3u), rng_dim(base.y, 3u)} - 1.0f;
+        float x0, x1, y0, y1;
+        rng_draw2(base.x, sample, 2u, sobol, x0, x1);
+        rng_draw2(base.y, sample, 2u, sobol, y0, y1);
+        const f2 ua = 2.0f * f2{x0, y0} - 1.0f;
+        const f2 ub = 2.0f * f2{x1, y1} - 1.0f;
         const i2 ok = need & ((ua * ua + ub * ub) <= 1.0f);
         a = ok ? ua : a;
         b = ok ? ub : b;
@@ -96,8 +120,10 @@ RWR_DEV v3 bounce_direction_pair(v3 n, u2 base, i2 want)
     while (__any(busy)) {
         if (busy) {
             const uint32_t bs = sel ? base.y : base.x;
-            const float ua = 2.0f * rng_dim(bs, 2u + 2u * k) - 1.0f;
-            const float ub = 2.0f * rng_dim(bs, 3u + 2u * k) - 1.0f;
+            float u0, u1;
+            rng_draw2(bs, sample, 2u + 2u * k, sobol, u0, u1);
+            const float ua = 2.0f * u0 - 1.0f;
+            const float ub = 2.0f * u1 - 1.0f;
             const bool ok = (ua * ua + ub * ub) <= 1.0f;
             if (ok) {
                 if (sel) { a.y = ua; b.y = ub; } else { a.x = ua; b.x = ub; }
@@ -274,11 +300,15 @@ k_wf_primary(const WfPrimaryArgs a)
         const uint32_t sample = sample_begin + sidx;
         // -- the sample's ray: pixel centre at spp = 1, else (and in every accumulating frame) two uniforms of the counter-based RNG
         kernarg<WfPrimaryArgs> *const qr = wf_args_again(ka);   // this phase's kernel arguments: seed, jitter rule, the camera
-        const u2 base = u2{rng_base(pix0, sample, qr->p.seed), rng_base(pix0 + 1u, sample, qr->p.seed)};
+        const bool sobol = (qr->p.flags & RWR_FLAG_SOBOL) != 0u;   // (scalar) the sequence's numbers in place of the hash's
+        const u2 base = u2{rng_base(pix0, sample, qr->p.seed, sobol), rng_base(pix0 + 1u, sample, qr->p.seed, sobol)};
         f2 jx = splat(0.5f), jy = splat(0.5f);
         if (qr->p.jitter_spp > 1u) {
-            jx = f2{rng_dim(base.x, 0u), rng_dim(base.y, 0u)};
-            jy = f2{rng_dim(base.x, 1u), rng_dim(base.y, 1u)};
+            float x0, x1, y0, y1;
+            rng_draw2(base.x, sample, 0u, sobol, x0, x1);
+            rng_draw2(base.y, sample, 0u, sobol, y0, y1);
+            jx = f2{x0, y0};
+            jy = f2{x1, y1};
         }
         const f2 fx = f2{(float)px0, (float)(px0 + 1u)} + jx;
         const f2 fy = splat((float)py) + jy;
@@ -536,7 +566,7 @@ k_wf_primary(const WfPrimaryArgs a)
                     const i2 diffuse = emit & ~mir & ~gl;
                     lit_from = diffuse & ~gs;
                     v3 Dd = D, Dm = D;
-                    if (__any(any2(diffuse))) Dd = bounce_direction_pair(n, base, diffuse);
+                    if (__any(any2(diffuse))) Dd = bounce_direction_pair(n, base, diffuse, sample, (wf_args_again(ka)->p.flags & RWR_FLAG_SOBOL) != 0u);
                     if (__any(any2(mir))) {   // D' = D - (2 d) n, d = dot3(n, D) (rwr_device.h reflect_direction, for the pair)
                         const f2 two_d = 2.0f * dot3(n, D);
                         Dm = v3{D.x - two_d * n.x, D.y - two_d * n.y, D.z - two_d * n.z};
@@ -558,7 +588,7 @@ k_wf_primary(const WfPrimaryArgs a)
                                 if (k ? gl.y : gl.x) {
                                     f3 Dg, mg;
                                     ev[k] = refract_or_reflect(lane3(n, k), lane3(D, k), (k ? obj.y : obj.x) >= 0, k ? best.ndotd.y : best.ndotd.x,
-                                                               k ? eta.y : eta.x, rng_dim(k ? base.y : base.x, 2u), Dg, mg);
+                                                               k ? eta.y : eta.x, rng_draw(k ? base.y : base.x, sample, 2u, (wf_args_again(ka)->p.flags & RWR_FLAG_SOBOL) != 0u), Dg, mg);
                                     if (k) { D1.x.y = Dg.x; D1.y.y = Dg.y; D1.z.y = Dg.z; O1.x.y = P.x.y + mg.x * 1e-4f; O1.y.y = P.y.y + mg.y * 1e-4f; O1.z.y = P.z.y + mg.z * 1e-4f; }
                                     else { D1.x.x = Dg.x; D1.y.x = Dg.y; D1.z.x = Dg.z; O1.x.x = P.x.x + mg.x * 1e-4f; O1.y.x = P.y.x + mg.y * 1e-4f; O1.z.x = P.z.x + mg.z * 1e-4f; }
                                 }
@@ -566,7 +596,7 @@ k_wf_primary(const WfPrimaryArgs a)
                         }
                     }
                 } else {
-                    D1 = bounce_direction_pair(n, base, emit);
+                    D1 = bounce_direction_pair(n, base, emit, sample, (wf_args_again(ka)->p.flags & RWR_FLAG_SOBOL) != 0u);
                 }
                 kernarg<WfPrimaryArgs> *const qq = wf_args_again(ka);   // where the rays go
                 float4 *const rays = qq->wf.rays;

@@ -88,11 +88,8 @@ k_wf_shadow(const FrameParams p, const TriRecord *__restrict__ tris, const BvhDe
                 const uint32_t px = (tile % wf.tiles_x) * kWfTileW + (wv & 1u) * 32u + 2u * (l & 15u) + k;
                 const uint32_t py = p.row_begin + (tile / wf.tiles_x) * p.row_pitch + (wv >> 1) * 4u + (l >> 4);
                 const uint32_t pixel = py * p.width + px, sample = soft.sample_base + e / kWfTilePixels;
-                for (uint32_t j = 0; j < 8u; j++) {   // bounce_direction's rejection loop, operation for operation
-                    const float ua = 2.0f * rng_uniform(pixel, sample, soft.dim0 + 2u * j, p.seed) - 1.0f;
-                    const float ub = 2.0f * rng_uniform(pixel, sample, soft.dim0 + 1u + 2u * j, p.seed) - 1.0f;
-                    if (ua * ua + ub * ub <= 1.0f) { da = ua; db = ub; break; }
-                }
+                // bounce_direction's rejection loop, operation for operation (dim0 is even: a try is one pair of RWR_FLAG_SOBOL's sequence)
+                rng_disk_point(pixel, sample, soft.dim0, p.seed, (p.flags & RWR_FLAG_SOBOL) != 0u, da, db);
             }
             bool occluded = false;
 #pragma unroll

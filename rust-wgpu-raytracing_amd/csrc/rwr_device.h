@@ -462,21 +462,87 @@ RWR_DEV uint32_t rng_hash(uint32_t pixel, uint32_t sample, uint32_t dim, uint32_
     h = rng_mix(h ^ (dim * 0xC2B2AE35u));
     return h;
 }
-RWR_DEV float rng_uniform(uint32_t pixel, uint32_t sample, uint32_t dim, uint32_t seed)
+RWR_DEV float rng_to_unit(uint32_t h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }
+
+// RWR_FLAG_SOBOL (rwr_hip.h): the 32-bit word of an Owen-scrambled Sobol sequence in place of rng_hash's — Burley 2020,
+// "Practical Hash-based Owen Scrambling".  Dimensions 2g and 2g+1 are the two coordinates of one (0,2)-sequence, shuffled and
+// scrambled per pixel, seed and g.  In three steps, as rng_hash is in two in kernels_wf_primary.hip: sobol_pixel per pixel,
+// sobol_pair once per pair of dimensions, sobol_coord per number.
+//   rng_sobol(pixel, sample, dim, seed) == sobol_coord(sobol_pair(sobol_pixel(pixel, seed), sample, dim), dim & 1)
+// owen(x, s) = rev(lk(rev(x), s)), rev the bit reversal: the reversals of the definition that meet cancel here.
+RWR_DEV uint32_t sobol_lk(uint32_t x, uint32_t s)   // Laine-Karras permutation, Burley's constants
 {
-    return (float)(rng_hash(pixel, sample, dim, seed) >> 8) * (1.0f / 16777216.0f);
+    x += s;
+    x ^= x * 0x6c50b47cu; x ^= x * 0xb82f1e52u; x ^= x * 0xc7afe638u; x ^= x * 0x8d22f6e6u;
+    return x;
+}
+RWR_DEV uint32_t sobol_pixel(uint32_t pixel, uint32_t seed) { return rng_mix((seed ^ 0x9E3779B9u) ^ pixel); }   // rng_hash's first step
+struct SobolPair { uint32_t s, idx; };   // the pair's stream, and the sample's shuffled index in it
+RWR_DEV SobolPair sobol_pair(uint32_t h0, uint32_t sample, uint32_t dim)
+{
+    const uint32_t s = rng_mix(h0 ^ ((dim >> 1) * 0xC2B2AE35u));
+    return SobolPair{s, __builtin_bitreverse32(sobol_lk(__builtin_bitreverse32(sample), s))};
+}
+RWR_DEV uint32_t sobol_coord(SobolPair q, uint32_t odd)
+{
+    // rev(x) of the definition.  Even: x = rev(idx).  Odd: x = sobol1(idx), whose matrix, read from idx to rev(x), is Pascal's
+    // triangle mod 2 — (1 + t)^k = the product of (1 + t^(2^j)) over the set bits j of k, so five masked shift-xor steps
+    uint32_t x = q.idx;
+    if (odd) {
+        x ^= x >> 16;
+        x ^= (x & 0xff00ff00u) >> 8;
+        x ^= (x & 0xf0f0f0f0u) >> 4;
+        x ^= (x & 0xccccccccu) >> 2;
+        x ^= (x & 0xaaaaaaaau) >> 1;
+    }
+    return __builtin_bitreverse32(sobol_lk(x, rng_mix(q.s ^ (0x85EBCA6Bu + odd))));
+}
+RWR_DEV uint32_t rng_sobol(uint32_t pixel, uint32_t sample, uint32_t dim, uint32_t seed)
+{
+    return sobol_coord(sobol_pair(sobol_pixel(pixel, seed), sample, dim), dim & 1u);
+}
+
+// sobol: RWR_FLAG_SOBOL is effective in this frame (wave-uniform: a bit of FrameParams::flags)
+RWR_DEV float rng_uniform(uint32_t pixel, uint32_t sample, uint32_t dim, uint32_t seed, bool sobol)
+{
+    return rng_to_unit(sobol ? rng_sobol(pixel, sample, dim, seed) : rng_hash(pixel, sample, dim, seed));
+}
+// The point of the unit disk that eight tries of rejection sampling give (0, 0 when all fail): try k reads dimensions
+// dim0 + 2 k and dim0 + 1 + 2 k.  bounce_direction's loop, and the soft shadows' and the light stage's, operation for operation.
+// Two loops, not one loop with the switch inside: what either keeps across its tries is live in its own branch alone, and the
+// hash's loop is what it was.  Under RWR_FLAG_SOBOL with dim0 EVEN a try is one (0,2)-pair, its stream and index made once.
+RWR_DEV void rng_disk_point(uint32_t pixel, uint32_t sample, uint32_t dim0, uint32_t seed, bool sobol, float &a, float &b)
+{
+    a = 0.0f; b = 0.0f;
+    if (sobol) {
+        const uint32_t h0 = sobol_pixel(pixel, seed);
+        for (uint32_t k = 0; k < 8u; k++) {
+            float ua, ub;
+            if (dim0 & 1u) {   // (uniform) the light stage behind an odd generation: the two coordinates come from two pairs
+                ua = 2.0f * rng_to_unit(sobol_coord(sobol_pair(h0, sample, dim0 + 2u * k), 1u)) - 1.0f;
+                ub = 2.0f * rng_to_unit(sobol_coord(sobol_pair(h0, sample, dim0 + 1u + 2u * k), 0u)) - 1.0f;
+            } else {
+                const SobolPair q = sobol_pair(h0, sample, dim0 + 2u * k);
+                ua = 2.0f * rng_to_unit(sobol_coord(q, 0u)) - 1.0f;
+                ub = 2.0f * rng_to_unit(sobol_coord(q, 1u)) - 1.0f;
+            }
+            if (ua * ua + ub * ub <= 1.0f) { a = ua; b = ub; break; }
+        }
+    } else {
+        for (uint32_t k = 0; k < 8u; k++) {
+            const float ua = 2.0f * rng_to_unit(rng_hash(pixel, sample, dim0 + 2u * k, seed)) - 1.0f;
+            const float ub = 2.0f * rng_to_unit(rng_hash(pixel, sample, dim0 + 1u + 2u * k, seed)) - 1.0f;
+            if (ua * ua + ub * ub <= 1.0f) { a = ua; b = ub; break; }
+        }
+    }
 }
 
 // dim0: the first of the 16 RNG dimensions the direction reads (2 for the first bounce; ray k of a deeper path,
-// RWR_FLAG_MULTI_BOUNCE: 2 + 16 (k - 1))
-RWR_DEV f3 bounce_direction(f3 n, uint32_t pixel, uint32_t sample, uint32_t seed, uint32_t dim0 = 2u)
+// RWR_FLAG_MULTI_BOUNCE: 2 + 16 (k - 1)), always even
+RWR_DEV f3 bounce_direction(f3 n, uint32_t pixel, uint32_t sample, uint32_t seed, bool sobol, uint32_t dim0 = 2u)
 {
-    float a = 0.0f, b = 0.0f;
-    for (uint32_t k = 0; k < 8u; k++) {  // rejection-sample the unit disk
-        const float ua = 2.0f * rng_uniform(pixel, sample, dim0 + 2u * k, seed) - 1.0f;
-        const float ub = 2.0f * rng_uniform(pixel, sample, dim0 + 1u + 2u * k, seed) - 1.0f;
-        if (ua * ua + ub * ub <= 1.0f) { a = ua; b = ub; break; }
-    }
+    float a, b;
+    rng_disk_point(pixel, sample, dim0, seed, sobol, a, b);   // rejection-sample the unit disk
     const float dz = sqrtf(fmaxf(0.0f, 1.0f - a * a - b * b));
     const float sign = copysignf(1.0f, n.z);
     const float aa = -1.0f / (sign + n.z);

@@ -586,6 +586,8 @@ void strips_deal_host(const StripLayout &L, size_t row_bytes, const uint8_t *rec
 // kernels_selftest.hip: out[0..3] += depth inputs compared, mismatches, normalize inputs compared, mismatches
 hipError_t launch_selftest_exact_math(hipStream_t s, unsigned long long *d_out4, uint32_t normalize_count, uint32_t seed);
 hipError_t launch_selftest_exact_div(hipStream_t s, unsigned long long *d_out4, uint32_t count, uint32_t seed);
+// kernels_selftest.hip: d_out[i] = rng_sobol(d_in[i], d_in[n + i], d_in[2 n + i], d_in[3 n + i]) (RWR_FLAG_SOBOL's word)
+hipError_t launch_selftest_sobol(hipStream_t s, const uint32_t *d_in, uint32_t n, uint32_t *d_out);
 
 // kernels_selftest.hip: d_out[wave] = {shader cycles, 100 MHz ticks} around iters * 8 v_fma_f32 (mode 0) / v_pk_fma_f32 (mode 1)
 hipError_t launch_clock_probe(hipStream_t s, ulonglong2 *d_out, uint32_t ticks_100mhz);

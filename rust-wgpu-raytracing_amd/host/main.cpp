@@ -7,7 +7,7 @@
 //              [--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]]
 //              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]...
 //              [--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]]
-//              [--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis]
+//              [--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] [--sobol]
 //              [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
@@ -158,6 +158,7 @@ int main(int argc, char **argv)
     bool light_sampling = false;   // --light-sampling
     bool light_parts = false;      // --light-parts
     bool light_mis = false;        // --light-mis
+    bool sobol = false;            // --sobol
     auto parse_emitter = [](const char *text, Emitter &e) {
         char *end = nullptr;
         if (*text < '0' || *text > '9') return false;
@@ -271,6 +272,7 @@ int main(int argc, char **argv)
         else if (a == "--light-sampling") light_sampling = true;
         else if (a == "--light-parts") light_parts = true;
         else if (a == "--light-mis") light_mis = true;
+        else if (a == "--sobol") sobol = true;
         else if (a == "--show-params") show_params = true;
         else if (a == "--resize") {
             Resize r{0, 0, 0};
@@ -287,7 +289,7 @@ int main(int argc, char **argv)
                         "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
                         "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]... "
                         "[--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... "
-                        "[--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] "
+                        "[--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] [--sobol] "
                         "[--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]] "
                         "[--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
@@ -326,6 +328,10 @@ int main(int argc, char **argv)
                         "  --light-mis  the light ray and the diffuse bounce ray that finds the same emitter are combined by the balance heuristic "
                         "(RWR_FLAG_LIGHT_MIS, multiple importance sampling; implies nothing: it needs --light-sampling or --light-parts in effect to do "
                         "anything); with it both may stay on in a scene that glows all over; prints `weighted hits N` for the final frame\n"
+                        "  --sobol       every random number of the path tracer comes from an Owen-scrambled Sobol sequence instead of the "
+                        "independent hash (RWR_FLAG_SOBOL; implies nothing: it does something in frames with --spp > 1, --bounces >= 1, "
+                        "--accumulate or --soft-shadows): a pixel's samples are stratified against each other, so that 16 samples "
+                        "give about the error of 64\n"
                         "  --reproject   every frame is blended with the history of the frames before it, fetched where its points were seen "
                         "last frame, while the camera moves (RWR_FLAG_REPROJECT; with --keys every key step's frame feeds the next one's history): "
                         "at most N frames of history per pixel (1-1024), taps of faces whose normals' cosine is at least C and whose distance "
@@ -343,7 +349,7 @@ int main(int argc, char **argv)
                            (glosses.empty() ? 0u : (uint32_t)RWR_FLAG_GLOSSY) | (soft_shadows ? (uint32_t)RWR_FLAG_SOFT_SHADOWS : 0u) |
                            (reproject ? (uint32_t)RWR_FLAG_REPROJECT : 0u) | (emitters.empty() ? 0u : (uint32_t)RWR_FLAG_EMISSIVE) |
                            (light_sampling ? (uint32_t)RWR_FLAG_LIGHT_SAMPLING : 0u) | (light_parts ? (uint32_t)RWR_FLAG_LIGHT_PARTS : 0u) |
-                           (light_mis ? (uint32_t)RWR_FLAG_LIGHT_MIS : 0u);
+                           (light_mis ? (uint32_t)RWR_FLAG_LIGHT_MIS : 0u) | (sobol ? (uint32_t)RWR_FLAG_SOBOL : 0u);
     if (show_params) {
         if (reproject)   // (a line of its own, ahead of the line every run prints)
             std::printf("reproject 1 history %u normal %g depth %g\n", reproject_params.max_history, (double)reproject_params.normal_cos_min,
