@@ -634,7 +634,7 @@ enum {
                                        7. The bit (after item 1) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
                                           effective flags.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED. */
-    RWR_FLAG_SOBOL = 1u << 23          /* extension: an Owen-scrambled Sobol sample sequence (Burley 2020, "Practical Hash-based Owen
+    RWR_FLAG_SOBOL = 1u << 23,         /* extension: an Owen-scrambled Sobol sample sequence (Burley 2020, "Practical Hash-based Owen
                                        Scrambling") in place of the independent hash.  Every random number the integrator draws — the
                                        pixel jitter, the disk points of the bounce rays, the glass and gloss choices, the soft-shadow
                                        disk points, the light stage's numbers — is (h >> 8) * 2^-24 of a 32-bit word h; without the
@@ -668,10 +668,42 @@ enum {
                                        5. The bit (after item 3) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
                                           effective flags.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED. */
+    RWR_FLAG_SKY_IMAGE = 1u << 24      /* extension: sky light from an image — RWR_FLAG_SKY's radiance S(D) comes from an octahedral
+                                       environment map (rwr_sky_set_image) instead of the two-colour gradient.  The flag implies
+                                       nothing.  Off by default; without the flag every frame is what it was, byte for byte.
+                                       1. With the flag in effect the S(D) of RWR_FLAG_SKY item 1 is S_img(D), f32 operations in
+                                          exactly this order, no contraction, `/` the IEEE division:
+                                            a  = (|D.x| + |D.y|) + |D.z|
+                                            px = D.x / a;  pz = D.z / a
+                                            if (D.y < 0) { qx = (1 - |pz|) * copysignf(1, px);  qz = (1 - |px|) * copysignf(1, pz);
+                                                           px = qx;  pz = qz; }
+                                            u  = px * 0.5 + 0.5;  v = pz * 0.5 + 0.5
+                                            S_img = the bilinear fetch of the mesh textures (four taps, ClampToEdge, the blend
+                                                    fma(t11, w11, fma(t01, w01, fma(t10, w10, t00 * w00))) per channel) of the
+                                                    n x n image at texel-space position (u * n - 0.5, v * n - 0.5)
+                                          Column i of the image is u, row j is v.  The upper hemisphere (+y, the reference's
+                                          Camera.up) is the inner diamond |2u - 1| + |2v - 1| <= 1 with the zenith at the map's
+                                          centre; the lower hemisphere is folded into the four corners, the nadir at all four.
+                                       2. RWR_FLAG_SKY's items 2-7 hold as written: bounce rays only, the term is
+                                          clamp(T * S_img(D), 0, 64), NaN counts as 0, primary misses are unchanged.  No random
+                                          number is used and no ray or count changes: every rwr_last_*_stats count is that of the
+                                          frame under the gradient.
+                                       3. ClampToEdge at the map's outer border is not the octahedral wrap: within half a texel of
+                                          the border — directions below the horizon only, and at most half a texel off — the fetch
+                                          repeats the border texel where the true wrap would blend with the texel mirrored across
+                                          the border's midpoint.  No mip levels: a map much finer than a glossy lobe is noisy.
+                                       4. The flag is effective only while RWR_FLAG_SKY is in effect (max_bounces >= 1) and the
+                                          context holds an image.  Otherwise it is cleared and the frame is the frame without it,
+                                          byte for byte, in the same kernels.
+                                       5. While the bit is effective, the image's generation (rwr_sky_get_image_info) is part of
+                                          RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's, next to rwr_sky_params, which stay
+                                          in both: a new image starts a new history.  Without the bit, rwr_sky_set_image disturbs
+                                          neither.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
+                                          RWR_ERR_UNSUPPORTED. */
 };
 /* every flag above, and the bits between them that the library keeps for itself: a caller sets none of the latter */
 #define RWR_FLAGS_RESERVED (0xfu << 17)
-#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21) | (1u << 22) | (1u << 23))
+#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21) | (1u << 22) | (1u << 23) | (1u << 24))
 
 #define RWR_MAX_BOUNCES 8u
 
@@ -1072,6 +1104,27 @@ typedef struct rwr_sky_params {
 RWR_API int rwr_sky_set_params(rwr_context *ctx, const rwr_sky_params *params);
 RWR_API int rwr_sky_get_params(rwr_context *ctx, rwr_sky_params *out);
 
+/* RWR_FLAG_SKY_IMAGE: the sky's image, per context — an octahedral map of n x n texels (the flag's item 1), n * n * 3 floats
+ * (r, g, b), row-major, row j <-> v, column i <-> u.  2 <= n <= RWR_SKY_IMAGE_SIZE_MAX; every component finite and in
+ * [0, RWR_SKY_IMAGE_COMPONENT_MAX] (the integrator's per-term clamp, the range of Le); anything else, NaN included:
+ * RWR_ERR_INVALID_ARGUMENT naming the first offending index and value, and the image stays as it was.  rgb = NULL or n = 0 removes
+ * the image.  The image is kept on the device as one float4 per texel (w = 0).  Every successful call, a removal included, advances
+ * the 64-bit image generation, also with equal contents.  A frame already enqueued keeps the image it was enqueued with (its frame
+ * slot holds on to that buffer); the call itself may wait for the device: the upload is synchronous, and so is the release of a buffer
+ * that no frame slot holds any more.
+ * rwr_sky_get_image_info: n (0 when no image is held) and the generation; either pointer may be NULL. */
+#define RWR_SKY_IMAGE_SIZE_MAX 2048u
+#define RWR_SKY_IMAGE_COMPONENT_MAX 64.0f
+RWR_API int rwr_sky_set_image(rwr_context *ctx, const float *rgb, uint32_t n);
+RWR_API int rwr_sky_get_image_info(rwr_context *ctx, uint32_t *n, uint64_t *generation);
+/* Host only, no context and no device: turns a latitude-longitude picture (w x h x 3 floats, row 0 = straight up, the centre column
+ * = direction (0, 0, -1), columns increasing towards +x) into the n x n x 3 octahedral map `out` that rwr_sky_set_image takes.  Per
+ * output texel the mean of 4 x 4 sub-positions; each is mapped to a direction by the inverse of the flag's mapping, the direction to
+ * source coordinates with atan2 / acos in double, the source fetched bilinearly (wrapping in longitude, clamping in latitude); the
+ * mean times `scale`, clamped to [0, 64], as float.  w, h >= 1, w * h <= 2^28, 2 <= n <= RWR_SKY_IMAGE_SIZE_MAX, scale finite and
+ * >= 0, every source component finite: else RWR_ERR_INVALID_ARGUMENT. */
+RWR_API int rwr_sky_image_from_equirect(const float *rgb, uint32_t w, uint32_t h, float scale, uint32_t n, float *out);
+
 /* RWR_FLAG_SOFT_SHADOWS: the angular size of the two lights, per context.  A radius is the tangent of the half-angle under which a
  * hit sees the light: mesh_light_radius for the mesh shader's light (face hits), sphere_light_radius for the sphere shader's.
  * Defaults 0.05 and 0.05; params = NULL restores them.  Each radius must be finite and in [0, 1]; anything else, NaN included:
@@ -1128,6 +1181,11 @@ RWR_API int rwr_selftest_exact_div(rwr_context *ctx, uint32_t count, uint32_t se
  * device function evaluates it, for n tuples (at most 2^24 a call).  A word that differs from the definition's is a bug. */
 RWR_API int rwr_selftest_sobol(rwr_context *ctx, const uint32_t *pixel, const uint32_t *sample, const uint32_t *dim, const uint32_t *seed,
                                size_t n, uint32_t *out);
+
+/* Self-test of RWR_FLAG_SKY_IMAGE's S_img: out_rgb[3 i ...] = S_img(dirs[3 i ...]) of the context's image as the kernels' device
+ * function evaluates it, for `count` directions (at most 2^24 a call).  RWR_ERR_NOT_READY while the context holds no image.  A
+ * value that differs from the definition's bits is a bug. */
+RWR_API int rwr_selftest_sky_image(rwr_context *ctx, const float *dirs, size_t count, float *out_rgb);
 
 /* Measurement aid for roofline accounting (bench.py): runs a short f32 VALU loop with `waves_per_simd` (1..8)
  * waves on every SIMD and stamps the shader cycle counter against the constant 100 MHz counter.

@@ -60,6 +60,8 @@ FLAG_LIGHT_SAMPLING = 1 << 16  # every diffuse hit also sends a ray towards an e
 FLAG_LIGHT_PARTS = 1 << 21     # ... or towards a point on a face of an emitting part, the mesh light (include/rwr_hip.h; bits 17-20 are reserved)
 FLAG_LIGHT_MIS = 1 << 22       # the light ray and the diffuse bounce ray are combined by the balance heuristic: multiple importance sampling (include/rwr_hip.h)
 FLAG_SOBOL = 1 << 23           # every random number of the path tracer comes from an Owen-scrambled Sobol sequence instead of the hash (include/rwr_hip.h)
+FLAG_SKY_IMAGE = 1 << 24       # FLAG_SKY's radiance comes from the context's octahedral environment map (sky_set_image) instead of the gradient (include/rwr_hip.h)
+SKY_IMAGE_SIZE_MAX, SKY_IMAGE_COMPONENT_MAX = 2048, 64.0   # RWR_SKY_IMAGE_SIZE_MAX, RWR_SKY_IMAGE_COMPONENT_MAX
 MAX_EMISSION = 64.0         # RWR_MAX_EMISSION: the largest component of a radiance
 SHADOW_PARAMS_DTYPE = np.dtype([("mesh_light_radius", "<f4"), ("sphere_light_radius", "<f4")])
 REPROJECT_PARAMS_DTYPE = np.dtype([("max_history", "<u4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
@@ -132,6 +134,8 @@ def lib() -> C.CDLL:
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
         "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
+        "rwr_sky_set_image": [vp, vp, u32], "rwr_sky_get_image_info": [vp, vp, vp],
+        "rwr_sky_image_from_equirect": [vp, u32, u32, f32, u32, vp], "rwr_selftest_sky_image": [vp, vp, C.c_size_t, vp],
         "rwr_shadow_set_params": [vp, vp], "rwr_shadow_get_params": [vp, vp],
         "rwr_reproject_set_params": [vp, vp], "rwr_reproject_get_params": [vp, vp], "rwr_reproject_reset": [vp],
         "rwr_reproject_frames": [vp, vp], "rwr_last_reproject_stats": [vp, vp, vp, vp], "rwr_reproject_readback": [vp, vp],
@@ -172,7 +176,7 @@ def lib() -> C.CDLL:
                            "rwr_scene_get_part_gloss", "rwr_scene_get_sphere_gloss", "rwr_last_gloss_stats",
                            "rwr_shadow_set_params", "rwr_shadow_get_params", "rwr_scene_set_part_emission", "rwr_scene_set_sphere_emission",
                            "rwr_scene_get_part_emission", "rwr_scene_get_sphere_emission", "rwr_last_emission_stats", "rwr_last_light_stats", "rwr_last_part_light_stats",
-                           "rwr_selftest_sobol")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_selftest_sobol", "rwr_sky_set_image", "rwr_sky_get_image_info", "rwr_sky_image_from_equirect", "rwr_selftest_sky_image")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -748,6 +752,14 @@ class Context:
         _check(lib().rwr_selftest_sobol(self._h, *[c.ctypes.data_as(C.c_void_p) for c in cols], n, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def selftest_sky_image(self, dirs) -> np.ndarray:
+        """FLAG_SKY_IMAGE's S_img(D) of the context's image for every row of `dirs` (float32 (N, 3)), evaluated by the kernels' device
+        function (rwr_selftest_sky_image): float32 (N, 3).  RwrError(ERR_NOT_READY) while no image is held."""
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros_like(d)
+        _check(lib().rwr_selftest_sky_image(self._h, _p(d), len(d), _p(out)))
+        return out
+
     def measure_valu_clock(self, waves_per_simd: int = 8) -> dict:
         """Shader clock (MHz) and cycles a SIMD spends per wave64 v_fma_f32 / v_pk_fma_f32, measured under load."""
         out = (C.c_double * 4)()
@@ -954,6 +966,24 @@ class Context:
         _check(lib().rwr_sky_get_params(self._h, _p(p)))
         return {"zenith": p["zenith"][0].copy(), "horizon": p["horizon"][0].copy()}
 
+    def sky_set_image(self, img):
+        """The FLAG_SKY_IMAGE sky's octahedral map (rwr_sky_set_image): float32 (n, n, 3), row j <-> v, column i <-> u, 2 <= n <= 2048,
+        every component finite and in [0, 64]; None removes the image.  Anything else: RwrError(ERR_INVALID_ARGUMENT), and the image
+        stays.  Every accepted call advances the image's generation (sky_get_image_info)."""
+        if img is None:
+            _check(lib().rwr_sky_set_image(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(img, dtype=np.float32)
+        if a.ndim != 3 or a.shape[0] != a.shape[1] or a.shape[2] != 3:
+            raise ValueError(f"a sky image is (n, n, 3), not {a.shape}")
+        _check(lib().rwr_sky_set_image(self._h, _p(a), a.shape[0]))
+
+    def sky_get_image_info(self) -> dict:
+        """{"n": side of the image held (0: none), "generation": how many accepted sky_set_image calls} (rwr_sky_get_image_info)."""
+        n, gen = C.c_uint32(0), C.c_uint64(0)
+        _check(lib().rwr_sky_get_image_info(self._h, C.byref(n), C.byref(gen)))
+        return {"n": int(n.value), "generation": int(gen.value)}
+
     def shadow_set_params(self, mesh=None, sphere=None):
         """The FLAG_SOFT_SHADOWS radii of the two lights (rwr_shadow_set_params): `mesh` the mesh shader's light, `sphere` the sphere
         shader's, each the tangent of the half-angle a hit sees the light under, in [0, 1]; an argument left out keeps its value, no
@@ -990,6 +1020,21 @@ def csrc_tree() -> str:
         with open(f, "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
+
+
+def sky_image_from_equirect(arr, n: int, scale: float = 1.0) -> np.ndarray:
+    """A latitude-longitude picture, float32 (h, w, 3) — row 0 straight up, the centre column direction (0, 0, -1), columns
+    increasing towards +x — as the (n, n, 3) octahedral map Context.sky_set_image takes, times `scale`, clamped to [0, 64]
+    (rwr_sky_image_from_equirect; host only, needs no device)."""
+    a = np.ascontiguousarray(arr, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"a picture is (h, w, 3), not {a.shape}")
+    n = int(n)
+    if not 2 <= n <= SKY_IMAGE_SIZE_MAX:   # (ahead of the output's allocation; the library's own refusal, in its words)
+        raise RwrError(ERR_INVALID_ARGUMENT, f"sky image size {n}: 2 ... {SKY_IMAGE_SIZE_MAX}")
+    out = np.zeros((n, n, 3), np.float32)
+    _check(lib().rwr_sky_image_from_equirect(_p(a), a.shape[1], a.shape[0], float(scale), n, _p(out)))
+    return out
 
 
 def exported_symbols_declared_in_header() -> list[str]:

@@ -623,6 +623,44 @@ int rwr_sky_get_params(rwr_context *ctx, rwr_sky_params *out)
     return RWR_OK;
 }
 
+// The image goes into a buffer of its own, filled before anything can read it; the context then points at it.  The buffer before
+// stays with the frame slots whose frames read it (WfState::sky_image) and goes when the last of them lets go (hipFree waits for the device).
+int rwr_sky_set_image(rwr_context *ctx, const float *rgb, uint32_t n)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (!rgb || n == 0u) {
+        ctx->sky_image.reset();
+        ctx->sky_image_n = 0u;
+        ctx->sky_image_generation++;
+        return RWR_OK;
+    }
+    if (n < 2u || n > RWR_SKY_IMAGE_SIZE_MAX)
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "sky image size %u: 2 ... %u", n, RWR_SKY_IMAGE_SIZE_MAX);
+    const size_t texels = (size_t)n * n;
+    std::vector<float4> host(texels);
+    for (size_t i = 0; i < texels * 3u; i++) {
+        if (!(rgb[i] >= 0.0f && rgb[i] <= RWR_SKY_IMAGE_COMPONENT_MAX))   // (false for NaN)
+            return set_error(RWR_ERR_INVALID_ARGUMENT, "sky image component [%zu] %g: finite, 0 ... 64", i, (double)rgb[i]);
+    }
+    for (size_t i = 0; i < texels; i++) host[i] = make_float4(rgb[3u * i], rgb[3u * i + 1u], rgb[3u * i + 2u], 0.0f);
+    DeviceGuard g(ctx->device);
+    auto buf = std::make_shared<DeviceBuffer<float4>>();
+    RWR_HIP_CHECK(buf->ensure(texels));
+    RWR_HIP_CHECK(hipMemcpy(buf->ptr, host.data(), texels * sizeof(float4), hipMemcpyHostToDevice));
+    ctx->sky_image = std::move(buf);
+    ctx->sky_image_n = n;
+    ctx->sky_image_generation++;
+    return RWR_OK;
+}
+
+int rwr_sky_get_image_info(rwr_context *ctx, uint32_t *n, uint64_t *generation)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (n) *n = ctx->sky_image ? ctx->sky_image_n : 0u;
+    if (generation) *generation = ctx->sky_image_generation;
+    return RWR_OK;
+}
+
 int rwr_shadow_set_params(rwr_context *ctx, const rwr_shadow_params *params)
 {
     if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");

@@ -55,6 +55,23 @@ int rwr_selftest_sobol(rwr_context *ctx, const uint32_t *pixel, const uint32_t *
     return RWR_OK;
 }
 
+int rwr_selftest_sky_image(rwr_context *ctx, const float *dirs, size_t count, float *out_rgb)
+{
+    if (!ctx || !dirs || !out_rgb) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (count > (size_t)1 << 24) return set_error(RWR_ERR_INVALID_ARGUMENT, "at most 2^24 directions a call, not %zu", count);
+    if (!ctx->sky_image) return set_error(RWR_ERR_NOT_READY, "the context holds no sky image (rwr_sky_set_image)");
+    if (count == 0) return RWR_OK;
+    DeviceGuard g(ctx->device);
+    const std::shared_ptr<DeviceBuffer<float4>> image = ctx->sky_image;
+    DeviceBuffer<float> d;   // the directions, then the values
+    RWR_HIP_CHECK(d.ensure(6 * count));
+    RWR_HIP_CHECK(hipMemcpyAsync(d.ptr, dirs, 3 * count * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    RWR_HIP_CHECK(launch_selftest_sky_image(ctx->stream, WfSkyImage{image->ptr, ctx->sky_image_n, 0u}, d.ptr, (uint32_t)count, d.ptr + 3 * count));
+    RWR_HIP_CHECK(hipMemcpyAsync(out_rgb, d.ptr + 3 * count, 3 * count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    RWR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return RWR_OK;
+}
+
 int rwr_debug_tile_classes(rwr_context *ctx, uint32_t *classes, size_t capacity, uint32_t *grid_x, uint32_t *grid_y)
 {
     if (!ctx || !grid_x || !grid_y) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");

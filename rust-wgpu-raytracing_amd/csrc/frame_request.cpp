@@ -13,7 +13,7 @@ namespace {
 // id / t planes, so RWR_FLAG_AUX_OUTPUTS is implied, and its own bit is not part of rp.flags from there on (nor of a history's key).
 // mode: a surface flag switches on the surfaces of its model (surface_mode's bit).
 struct FlagRule { uint32_t flag; const char *name, *stage, *why; uint32_t mode; };
-constexpr FlagRule kFlagRules[14] = {
+constexpr FlagRule kFlagRules[15] = {
     {RWR_FLAG_ACCUMULATE, "RWR_FLAG_ACCUMULATE", nullptr, nullptr, 0u},
     {RWR_FLAG_SHADOWS, "RWR_FLAG_SHADOWS", nullptr, nullptr, 0u},
     {RWR_FLAG_DENOISE, "RWR_FLAG_DENOISE", "filter", "its taps reach 62 pixels", 0u},
@@ -27,7 +27,8 @@ constexpr FlagRule kFlagRules[14] = {
     {RWR_FLAG_LIGHT_SAMPLING, "RWR_FLAG_LIGHT_SAMPLING", nullptr, nullptr, 0u},
     {RWR_FLAG_LIGHT_PARTS, "RWR_FLAG_LIGHT_PARTS", nullptr, nullptr, 0u},
     {RWR_FLAG_LIGHT_MIS, "RWR_FLAG_LIGHT_MIS", nullptr, nullptr, 0u},
-    {RWR_FLAG_SOBOL, "RWR_FLAG_SOBOL", nullptr, nullptr, 0u}};
+    {RWR_FLAG_SOBOL, "RWR_FLAG_SOBOL", nullptr, nullptr, 0u},
+    {RWR_FLAG_SKY_IMAGE, "RWR_FLAG_SKY_IMAGE", nullptr, nullptr, 0u}};
 constexpr uint32_t kSurfaceFlags = RWR_FLAG_MIRRORS | RWR_FLAG_GLASS | RWR_FLAG_GLOSSY;
 
 // What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
@@ -39,12 +40,13 @@ std::vector<unsigned char> accum_key_of(const rwr_context *ctx, const rwr_camera
 {
     const uint32_t words[9] = {ctx->screen.width, ctx->screen.height, rq.row_begin, rq.row_end, rq.row_pitch, rq.rp.max_bounces, rq.rp.seed,
                                rq.rp.flags & ~(uint32_t)RWR_FLAG_ACCUMULATE, ctx->n_slots};
-    std::vector<unsigned char> key(sizeof cam + sizeof words + sizeof ctx->scene_generation + (rq.sky ? sizeof ctx->sky : 0u) + (rq.soft ? sizeof ctx->shadow : 0u));
+    std::vector<unsigned char> key(sizeof cam + sizeof words + sizeof ctx->scene_generation + (rq.sky ? sizeof ctx->sky : 0u) + (rq.sky_image ? sizeof ctx->sky_image_generation : 0u) + (rq.soft ? sizeof ctx->shadow : 0u));
     unsigned char *at = key.data();
     std::memcpy(at, &cam, sizeof cam); at += sizeof cam;
     std::memcpy(at, words, sizeof words); at += sizeof words;
     std::memcpy(at, &ctx->scene_generation, sizeof ctx->scene_generation); at += sizeof ctx->scene_generation;
     if (rq.sky) { std::memcpy(at, &ctx->sky, sizeof ctx->sky); at += sizeof ctx->sky; }
+    if (rq.sky_image) { std::memcpy(at, &ctx->sky_image_generation, sizeof ctx->sky_image_generation); at += sizeof ctx->sky_image_generation; }   // (RWR_FLAG_SKY_IMAGE: the image's generation next to the sky's parameters)
     if (rq.soft) std::memcpy(at, &ctx->shadow, sizeof ctx->shadow);   // (the flag's bit is among the words: the two optional tails cannot be taken for each other)
     return key;
 }
@@ -55,12 +57,13 @@ std::vector<unsigned char> accum_key_of(const rwr_context *ctx, const rwr_camera
 std::vector<unsigned char> reproject_key_of(const rwr_context *ctx, const FrameRequest &rq)
 {
     const uint32_t words[7] = {ctx->screen.width, ctx->screen.height, rq.rp.spp, rq.rp.max_bounces, rq.rp.seed, rq.rp.flags, ctx->n_slots};
-    std::vector<unsigned char> key(sizeof words + sizeof ctx->scene_generation + sizeof ctx->reproject + (rq.sky ? sizeof ctx->sky : 0u) + (rq.soft ? sizeof ctx->shadow : 0u));
+    std::vector<unsigned char> key(sizeof words + sizeof ctx->scene_generation + sizeof ctx->reproject + (rq.sky ? sizeof ctx->sky : 0u) + (rq.sky_image ? sizeof ctx->sky_image_generation : 0u) + (rq.soft ? sizeof ctx->shadow : 0u));
     unsigned char *at = key.data();
     std::memcpy(at, words, sizeof words); at += sizeof words;
     std::memcpy(at, &ctx->scene_generation, sizeof ctx->scene_generation); at += sizeof ctx->scene_generation;
     std::memcpy(at, &ctx->reproject, sizeof ctx->reproject); at += sizeof ctx->reproject;
     if (rq.sky) { std::memcpy(at, &ctx->sky, sizeof ctx->sky); at += sizeof ctx->sky; }
+    if (rq.sky_image) { std::memcpy(at, &ctx->sky_image_generation, sizeof ctx->sky_image_generation); at += sizeof ctx->sky_image_generation; }   // (RWR_FLAG_SKY_IMAGE: the image's generation next to the sky's parameters)
     if (rq.soft) std::memcpy(at, &ctx->shadow, sizeof ctx->shadow);
     return key;
 }
@@ -111,6 +114,8 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
         for (const FlagRule &f : kFlagRules)
             if (f.mode && !(modes & f.mode)) rp.flags &= ~f.flag;
     }
+    // The sky's image replaces the gradient's S(D) and nothing else: without the sky in effect, or without an image, there is nothing to replace
+    if (!(rp.flags & RWR_FLAG_SKY) || !ctx->sky_image) rp.flags &= ~(uint32_t)RWR_FLAG_SKY_IMAGE;
     // An emitter shows at h0 already, so RWR_FLAG_EMISSIVE stays at max_bounces 0; without an emitting surface it has nothing to add
     if ((rp.flags & RWR_FLAG_EMISSIVE) && !scene_glows(ctx)) rp.flags &= ~(uint32_t)RWR_FLAG_EMISSIVE;
     // Light sampling aims rays from diffuse hits at the emitting spheres: without RWR_FLAG_EMISSIVE in effect, without a bounce (no hit
@@ -134,13 +139,14 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
     auto has = [](uint32_t flags, uint32_t flag) { return (flags & flag) != 0; };
     rq = FrameRequest{rp, row_begin, row_end, row_pitch, has(rp.flags, RWR_FLAG_AUX_OUTPUTS), has(asked, RWR_FLAG_ACCUMULATE), has(asked, RWR_FLAG_SHADOWS),
                       has(asked, RWR_FLAG_DENOISE), has(asked, RWR_FLAG_REPROJECT), has(rp.flags, RWR_FLAG_MIRRORS), has(rp.flags, RWR_FLAG_GLASS),
-                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), has(rp.flags, RWR_FLAG_EMISSIVE), has(rp.flags, RWR_FLAG_LIGHT_SAMPLING), has(rp.flags, RWR_FLAG_LIGHT_PARTS), has(rp.flags, RWR_FLAG_LIGHT_MIS), false, false, false};
+                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), has(rp.flags, RWR_FLAG_EMISSIVE), has(rp.flags, RWR_FLAG_LIGHT_SAMPLING), has(rp.flags, RWR_FLAG_LIGHT_PARTS), has(rp.flags, RWR_FLAG_LIGHT_MIS), false, false, false, false};
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
     // with shadow rays (the integrator's stages trace them), one the filter follows (it runs behind the integrator's resolve) or one
     // with an emitter (the integrator's kernels add its light)
     rq.wavefront = rp.spp != 1 || rp.max_bounces != 0 || rq.accumulate || rq.shadows || rq.denoise || rq.reproject || rq.glow;
     // The sample sequence changes the integrator's random numbers and nothing else: it sends no frame there, and a frame of the
     // reference's kernels draws none (rq.rp.flags is what the histories' keys and the kernels see)
+    rq.sky_image = has(rp.flags, RWR_FLAG_SKY_IMAGE);
     rq.sobol = rq.wavefront && has(rp.flags, RWR_FLAG_SOBOL);
     if (!rq.sobol) rq.rp.flags &= ~(uint32_t)RWR_FLAG_SOBOL;
     rq.dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;

@@ -31,6 +31,52 @@ int rwr_camera_build_inv_uniform(const rwr_camera *camera, rwr_camera_inv_unifor
     return RWR_OK;
 }
 
+// RWR_FLAG_SKY_IMAGE: a latitude-longitude picture as the octahedral map rwr_sky_set_image takes.  All in double.  Texel (i, j)
+// covers u in [i, i + 1) / n, v in [j, j + 1) / n; its value is the mean over 4 x 4 sub-positions of the source at the direction
+// the inverse mapping gives: p = 2 (u, v) - 1, y = 1 - |p.x| - |p.z|, below the horizon (y < 0) the fold undone, normalised.
+int rwr_sky_image_from_equirect(const float *rgb, uint32_t w, uint32_t h, float scale, uint32_t n, float *out)
+{
+    if (!rgb || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (w == 0u || h == 0u || (uint64_t)w * h > (1ull << 28))
+        return set_error(RWR_ERR_INVALID_ARGUMENT, "picture of %u x %u: each at least 1, at most 2^28 pixels", w, h);
+    if (n < 2u || n > RWR_SKY_IMAGE_SIZE_MAX) return set_error(RWR_ERR_INVALID_ARGUMENT, "sky image size %u: 2 ... %u", n, RWR_SKY_IMAGE_SIZE_MAX);
+    if (!(scale >= 0.0f && scale <= 3.0e38f)) return set_error(RWR_ERR_INVALID_ARGUMENT, "scale %g: finite, >= 0", (double)scale);
+    for (size_t i = 0; i < (size_t)w * h * 3u; i++)
+        if (!std::isfinite(rgb[i])) return set_error(RWR_ERR_INVALID_ARGUMENT, "picture component [%zu] %g is not finite", i, (double)rgb[i]);
+    const double kPi = 3.14159265358979323846;
+    constexpr int kSub = 4;
+    auto texel = [&](int64_t x, int64_t y, int c) {
+        x %= (int64_t)w;
+        if (x < 0) x += w;                                            // longitude wraps
+        y = y < 0 ? 0 : y >= (int64_t)h ? (int64_t)h - 1 : y;         // latitude clamps
+        return (double)rgb[((size_t)y * w + (size_t)x) * 3u + (size_t)c];
+    };
+    for (uint32_t j = 0; j < n; j++)
+        for (uint32_t i = 0; i < n; i++) {
+            double sum[3] = {0.0, 0.0, 0.0};
+            for (int b = 0; b < kSub; b++)
+                for (int a = 0; a < kSub; a++) {
+                    const double px = 2.0 * ((i + (a + 0.5) / kSub) / n) - 1.0, pz = 2.0 * ((j + (b + 0.5) / kSub) / n) - 1.0;
+                    double dx = px, dz = pz;
+                    const double dy = 1.0 - std::fabs(px) - std::fabs(pz);
+                    if (dy < 0.0) { dx = (1.0 - std::fabs(pz)) * std::copysign(1.0, px); dz = (1.0 - std::fabs(px)) * std::copysign(1.0, pz); }
+                    const double len = std::sqrt(dx * dx + dy * dy + dz * dz);
+                    const double theta = std::acos(std::fmin(std::fmax(dy / len, -1.0), 1.0)), phi = std::atan2(dx, -dz);
+                    const double sx = (phi / (2.0 * kPi) + 0.5) * w - 0.5, sy = theta / kPi * h - 0.5;
+                    const double fx = std::floor(sx), fy = std::floor(sy), ax = sx - fx, ay = sy - fy;
+                    const int64_t x0 = (int64_t)fx, y0 = (int64_t)fy;
+                    for (int c = 0; c < 3; c++)
+                        sum[c] += (1.0 - ay) * ((1.0 - ax) * texel(x0, y0, c) + ax * texel(x0 + 1, y0, c)) +
+                                  ay * ((1.0 - ax) * texel(x0, y0 + 1, c) + ax * texel(x0 + 1, y0 + 1, c));
+                }
+            for (int c = 0; c < 3; c++) {
+                const double v = sum[c] / (kSub * kSub) * (double)scale;
+                out[((size_t)j * n + i) * 3u + (size_t)c] = (float)std::fmin(std::fmax(v, 0.0), (double)RWR_SKY_IMAGE_COMPONENT_MAX);
+            }
+        }
+    return RWR_OK;
+}
+
 int rwr_circle_controller_update(float speed, uint32_t pressed_keys, rwr_camera *camera)
 {
     if (!camera) return set_error(RWR_ERR_INVALID_ARGUMENT, "camera is NULL");

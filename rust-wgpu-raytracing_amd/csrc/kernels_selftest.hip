@@ -212,6 +212,24 @@ hipError_t launch_selftest_sobol(hipStream_t s, const uint32_t *d_in, uint32_t n
     return hipGetLastError();
 }
 
+// RWR_FLAG_SKY_IMAGE: out[3 i ...] = sky_image_radiance of direction i (rwr_device.h), for rwr_selftest_sky_image and
+// tests/test_gpu_sky_image.py.
+__global__ void __launch_bounds__(256)
+k_selftest_sky_image(const WfSkyImage si, const float *__restrict__ dirs, uint32_t n, float *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const f3 s = sky_image_radiance(si.image, si.n, mk3(dirs[3u * i], dirs[3u * i + 1u], dirs[3u * i + 2u]));
+    out[3u * i] = s.x; out[3u * i + 1u] = s.y; out[3u * i + 2u] = s.z;
+}
+
+hipError_t launch_selftest_sky_image(hipStream_t s, const WfSkyImage &si, const float *d_dirs, uint32_t count, float *d_out)
+{
+    if (count == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_selftest_sky_image, dim3((count + 255u) / 256u), dim3(256), 0, s, si, d_dirs, count, d_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_selftest_exact_div(hipStream_t s, unsigned long long *d_out4, uint32_t count, uint32_t seed)
 {
     hipLaunchKernelGGL(k_selftest_div, dim3(8192), dim3(256), 0, s, d_out4, count, seed);

@@ -393,6 +393,14 @@ RWR_DEV void add_sky(TraceShared &sh, const WfSky &sky, uint32_t e, float dy, f3
     // (a black sky adds nothing at all: add_fixed skips zeros)
     add_fixed(sh, e, (uint32_t)(thr.x * s0 * kWfFixedScale), (uint32_t)(thr.y * s1 * kWfFixedScale), (uint32_t)(thr.z * s2 * kWfFixedScale));
 }
+// IMG forms (RWR_FLAG_SKY_IMAGE; SKY forms of their own): S = S_img(D) of the whole direction, four 16-byte taps of the context's
+// octahedral map (rwr_device.h sky_image_radiance), on the lanes whose ray missed alone; the term is formed and added as add_sky's.
+// si is the kernels' last argument (its pointer and side sit in scalar registers); no other form reads it.
+RWR_DEV void add_sky_image(TraceShared &sh, const WfSkyImage &si, uint32_t e, f3 D, f3 thr)
+{
+    const f3 s = sky_image_radiance(si.image, si.n, D);
+    add_fixed(sh, e, (uint32_t)(thr.x * s.x * kWfFixedScale), (uint32_t)(thr.y * s.y * kWfFixedScale), (uint32_t)(thr.z * s.z * kWfFixedScale));
+}
 
 // GLOW forms (RWR_FLAG_EMISSIVE): the local shading of the hit `obj` becomes E'(h) = E(h) + Le(h), Le the radiance of the hit's
 // surface (rwr_surface.h glow_record) — one f32 add per channel to the shader's value, ahead of the product with the throughput.
@@ -507,6 +515,8 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // SHADOW: RWR_FLAG_SHADOWS — a hit adds its term's ambient part and leaves a shadow record (shadow_hit); separate instantiations,
 // so that frames without the flag keep their kernels.
 // SKY: RWR_FLAG_SKY — a ray that hits nothing adds the sky's term (add_sky); separate instantiations for the same reason.
+// IMG: RWR_FLAG_SKY_IMAGE — of the SKY forms alone: the sky's term comes from the context's image (add_sky_image); separate
+// instantiations for the same reason, and so that the SKY forms under the gradient keep their registers (profiles/sky_image_kernel_resources.txt).
 // MIRROR: RWR_FLAG_MIRRORS — of the EMIT forms alone: a hit on a mirror surface sends the reflected ray on, with T * R
 // (emit_next_ray); separate instantiations for the same reason.
 // SURF: which surface models the EMIT form knows — kSurfNone, kSurfMirrors (RWR_FLAG_MIRRORS alone: the MIRROR forms), kSurfGlass
@@ -516,14 +526,15 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // counted; of the forms that end a path as of the EMIT forms; separate instantiations for the same reason.
 // Which combinations exist, and how launch_wf_bounce picks one: LaneForms and PacketForms below, behind the kernels.
 template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false, bool SKY = false,
-          int SURF = kSurfNone, bool GLOW = false>
+          int SURF = kSurfNone, bool GLOW = false, bool IMG = false>
 __global__ void __launch_bounds__(WIDE ? 1024 : 256)
 k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                 const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                 uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
-                const WfSky sky, const WfSurfaces sf, const WfGlow gl)
+                const WfSky sky, const WfSurfaces sf, const WfGlow gl, const WfSkyImage si)
 {
     static_assert(EMIT || SURF == kSurfNone, "only a kernel that emits rays has a MIRROR or a glass form");
+    static_assert(SKY || !IMG, "the sky's image is a form of the SKY forms");
     constexpr bool MIRROR = SURF != kSurfNone;
     __shared__ TraceShared sh;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
@@ -607,7 +618,8 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                 if (EMIT && MIRROR) event = emit_from_surface<SURF>(p, wf, em, sf, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, s1.albedo);
                 }
             } else if (SKY) {
-                add_sky(sh, sky, e, D.y, thr);
+                if constexpr (IMG) add_sky_image(sh, si, e, D, thr);
+                else add_sky(sh, sky, e, D.y, thr);
             }
             if (SURF == kSurfGlass || SURF == kSurfGloss) count_surface_events<SURF == kSurfGloss>(sf.events, event);
             if (GLOW) count_glow_hits(gl.hits, lit);
@@ -705,14 +717,15 @@ RWR_DEV i2 sphere_pair_intersect_t(f3 center, float radius, v3 O, v3 D, f2 &t_ou
 #ifndef RWR_GLOSS_SKY_PACKET_OCC
 #define RWR_GLOSS_SKY_PACKET_OCC 3
 #endif
-template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false, int SURF = kSurfNone, bool GLOW = false>   // EMIT, SHADOW, SKY, SURF, GLOW: see k_wf_trace_lane
+template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false, int SURF = kSurfNone, bool GLOW = false, bool IMG = false>   // EMIT, SHADOW, SKY, SURF, GLOW, IMG: see k_wf_trace_lane
 __global__ void __launch_bounds__(256, (SURF == kSurfGloss && SKY && !SHADOW) ? RWR_GLOSS_SKY_PACKET_OCC : RWR_PACKET_OCC)
 k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
                   uint32_t *__restrict__ counters, const uint32_t *__restrict__ pool_list, uint32_t n_tiles, const WfEmit em, const WfShadow sw,
-                  const WfSky sky, const WfSurfaces sf, const WfGlow gl)
+                  const WfSky sky, const WfSurfaces sf, const WfGlow gl, const WfSkyImage si)
 {
     static_assert(EMIT || SURF == kSurfNone, "only a kernel that emits rays has a MIRROR or a glass form");
+    static_assert(SKY || !IMG, "the sky's image is a form of the SKY forms");
     constexpr bool MIRROR = SURF != kSurfNone;
     __shared__ TraceShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -879,8 +892,13 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
         // (glossy forms: the sky's terms first — integer sums, any order gives the same bytes — so that the packet's ray numbers and a
         // missed ray's throughput are dead while the hits' next rays are made: the registers the disk loop and the rule need)
         if (SKY && SURF == kSurfGloss) {
+            if constexpr (IMG) {
+                if (i0 < last && !have.x) add_sky_image(sh, si, e0, lane3(R.D, 0), mk3(thr.x.x, thr.y.x, thr.z.x));
+                if (i1 < last && !have.y) add_sky_image(sh, si, e1, lane3(R.D, 1), mk3(thr.x.y, thr.y.y, thr.z.y));
+            } else {
             if (i0 < last && !have.x) add_sky(sh, sky, e0, R.D.y.x, mk3(thr.x.x, thr.y.x, thr.z.x));
             if (i1 < last && !have.y) add_sky(sh, sky, e1, R.D.y.y, mk3(thr.x.y, thr.y.y, thr.z.y));
+            }
         }
         // -- shade the second hit, add albedo(h0) * E(h1) to the pixel's sums --------------------------------------
         if (__any(any2(have))) {
@@ -979,8 +997,13 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
             }
         }
         if (SKY && SURF != kSurfGloss) {   // per ray, not per wave: every ray of the packet (not the padding of its last lanes: i0, i1 < last) that found nothing
+            if constexpr (IMG) {
+                if (i0 < last && !have.x) add_sky_image(sh, si, e0, lane3(R.D, 0), mk3(thr.x.x, thr.y.x, thr.z.x));
+                if (i1 < last && !have.y) add_sky_image(sh, si, e1, lane3(R.D, 1), mk3(thr.x.y, thr.y.y, thr.z.y));
+            } else {
             if (i0 < last && !have.x) add_sky(sh, sky, e0, R.D.y.x, mk3(thr.x.x, thr.y.x, thr.z.x));
             if (i1 < last && !have.y) add_sky(sh, sky, e1, R.D.y.y, mk3(thr.x.y, thr.y.y, thr.z.y));
+            }
         }
     }
     __syncthreads();
@@ -999,51 +1022,51 @@ struct SortForms {
     template <uint32_t I> static constexpr Kernel kernel() { return &k_wf_sort<decode(I).list>; }
 };
 struct PacketForms {
-    struct Form { bool nmap, emit, shadow, sky; int surf; bool glow; };
-    static constexpr uint32_t kRange = 16u * 4u * 2u;
-    static constexpr uint32_t encode(Form f) { return f.nmap + 2u * f.emit + 4u * f.shadow + 8u * f.sky + 16u * (uint32_t)f.surf + 64u * f.glow; }
+    struct Form { bool nmap, emit, shadow, sky; int surf; bool glow, img; };
+    static constexpr uint32_t kRange = 16u * 4u * 2u * 2u;
+    static constexpr uint32_t encode(Form f) { return f.nmap + 2u * f.emit + 4u * f.shadow + 8u * f.sky + 16u * (uint32_t)f.surf + 64u * f.glow + 128u * f.img; }
     static constexpr Form decode(uint32_t i)
     {
-        return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (int)((i >> 4) & 3u), (i & 64u) != 0};
+        return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (int)((i >> 4) & 3u), (i & 64u) != 0, (i & 128u) != 0};
     }
-    static constexpr bool valid(Form f) { return f.emit || f.surf == kSurfNone; }
+    static constexpr bool valid(Form f) { return (f.emit || f.surf == kSurfNone) && (f.sky || !f.img); }
     using Kernel = decltype(&k_wf_trace_packet<false>);
     template <uint32_t I> static constexpr Kernel kernel()
     {
         constexpr Form f = decode(I);
-        return &k_wf_trace_packet<f.nmap, f.emit, f.shadow, f.sky, f.surf, f.glow>;
+        return &k_wf_trace_packet<f.nmap, f.emit, f.shadow, f.sky, f.surf, f.glow, f.img>;
     }
 };
 // WIDE — 1 024 threads around one copy of the nodelets — only with the nodelets in LDS, 16-bit stacks and no normal map (LaneLdsPlan)
 struct LaneForms {
-    struct Form { bool nodes_in_lds, nmap, stack16, wide, emit, shadow, sky; int surf; bool glow; };
-    static constexpr uint32_t kRange = 128u * 4u * 2u;
+    struct Form { bool nodes_in_lds, nmap, stack16, wide, emit, shadow, sky; int surf; bool glow, img; };
+    static constexpr uint32_t kRange = 128u * 4u * 2u * 2u;
     static constexpr uint32_t encode(Form f)
     {
         return f.nodes_in_lds + 2u * f.nmap + 4u * f.stack16 + 8u * f.wide + 16u * f.emit + 32u * f.shadow + 64u * f.sky + 128u * (uint32_t)f.surf +
-               512u * f.glow;
+               512u * f.glow + 1024u * f.img;
     }
     static constexpr Form decode(uint32_t i)
     {
         return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (i & 16u) != 0, (i & 32u) != 0, (i & 64u) != 0, (int)((i >> 7) & 3u),
-                    (i & 512u) != 0};
+                    (i & 512u) != 0, (i & 1024u) != 0};
     }
-    static constexpr bool valid(Form f) { return (f.emit || f.surf == kSurfNone) && (!f.wide || (f.nodes_in_lds && !f.nmap && f.stack16)); }
+    static constexpr bool valid(Form f) { return (f.emit || f.surf == kSurfNone) && (f.sky || !f.img) && (!f.wide || (f.nodes_in_lds && !f.nmap && f.stack16)); }
     static constexpr bool is_wide(Form f) { return f.wide; }
     using Kernel = decltype(&k_wf_trace_lane<false, false, false>);
     template <uint32_t I> static constexpr Kernel kernel()
     {
         constexpr Form f = decode(I);
-        return &k_wf_trace_lane<f.nodes_in_lds, f.nmap, f.stack16, f.wide, f.emit, f.shadow, f.sky, f.surf, f.glow>;
+        return &k_wf_trace_lane<f.nodes_in_lds, f.nmap, f.stack16, f.wide, f.emit, f.shadow, f.sky, f.surf, f.glow, f.img>;
     }
 };
 static constexpr auto kSortForms = form_table<SortForms>();
 static constexpr auto kPacketForms = form_table<PacketForms>();
 static constexpr auto kLaneForms = form_table<LaneForms>();
 // (GLOW goes with every form and adds no condition to valid(): the rule is stated beside PrimaryForms, kernels_wf_primary.hip)
-static_assert(check_forms<SortForms>(2) && check_forms<PacketForms>(80), "packets: NMAP x (4 path-ending + 16 EMIT forms), with and without GLOW");
-static_assert(check_forms<LaneForms>(360) && count_forms<LaneForms>(LaneForms::is_wide) == 40,
-              "per lane: 8 x 20 with 256 threads, 20 wide, with and without GLOW");
+static_assert(check_forms<SortForms>(2) && check_forms<PacketForms>(120), "packets: NMAP x (4 path-ending + 16 EMIT forms), with and without GLOW; the SKY half again with IMG");
+static_assert(check_forms<LaneForms>(540) && count_forms<LaneForms>(LaneForms::is_wide) == 60,
+              "per lane: 8 x 20 with 256 threads, 20 wide, with and without GLOW; the SKY half again with IMG");
 
 // RWR_WF_STATS=1 (wf.dbg set): launches of the packet kernel, the per-lane kernel and its WIDE form, by this process
 static std::atomic<uint64_t> g_trace_launches[3];
@@ -1069,13 +1092,14 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
                        wf, info, counters, pool_list, n_tiles, sample_count, packets ? packet_min_rays : 0xffffffffu, bvh.packet_extent, bvh.packet_dense_rays);
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
     const int surf = ft.trace_surf();
+    const bool img = ft.sky_on && ft.sky_image.image != nullptr;   // RWR_FLAG_SKY_IMAGE in effect: the IMG forms
     if (packets) {
         if (wf.dbg) g_trace_launches[0].fetch_add(1u, std::memory_order_relaxed);
-        hipLaunchKernelGGL(kPacketForms[PacketForms::encode({nmap, ft.emits, ft.shadows, ft.sky_on, surf, ft.glows})], dim3(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit)),
-                           dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, ft.emit, ft.shadow, ft.sky, ft.surfaces, ft.glow);
+        hipLaunchKernelGGL(kPacketForms[PacketForms::encode({nmap, ft.emits, ft.shadows, ft.sky_on, surf, ft.glows, img})], dim3(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit)),
+                           dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, ft.emit, ft.shadow, ft.sky, ft.surfaces, ft.glow, ft.sky_image);
     }
     const LaneLdsPlan l = lane_lds_plan(bvh, fp, bvh.wide_lane && !nmap);
-    const uint32_t form = LaneForms::encode({l.nodes_in_lds, nmap, l.stack16, l.wide, ft.emits, ft.shadows, ft.sky_on, surf, ft.glows});
+    const uint32_t form = LaneForms::encode({l.nodes_in_lds, nmap, l.stack16, l.wide, ft.emits, ft.shadows, ft.sky_on, surf, ft.glows, img});
     if (wf.dbg) g_trace_launches[l.wide ? 2 : 1].fetch_add(1u, std::memory_order_relaxed);
     if (plan) *plan = LanePlanRecord{plan->launches + 1u, l.nodes_in_lds, l.stack16, l.wide};
     if (l.wide) {   // (at most 146 KiB: beyond the default limit, raised per form)
@@ -1085,7 +1109,7 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     }
     const dim3 grid(std::min(l.wide ? 512u : kWfTraceGroups, n_tiles * kWfMaxSplit));
     hipLaunchKernelGGL(kLaneForms[form], grid, dim3(l.wide ? 1024 : 256), l.bytes, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles,
-                       ft.emit, ft.shadow, ft.sky, ft.surfaces, ft.glow);
+                       ft.emit, ft.shadow, ft.sky, ft.surfaces, ft.glow, ft.sky_image);
     return hipGetLastError();
 }
 

@@ -280,6 +280,9 @@ int WfFrame::trace_groups(const AccumPlan &ap)
     }
     if (rq.sky) std::memcpy(&ft.sky, &ctx->sky, sizeof ft.sky);
     ft.sky_on = rq.sky;
+    // (the slot lets go of the image of its last frame, whose kernels ran ahead of this frame's on the slot's stream, and holds on to this one's)
+    W.sky_image = rq.sky_image ? ctx->sky_image : nullptr;
+    ft.sky_image = rq.sky_image ? WfSkyImage{W.sky_image->ptr, ctx->sky_image_n, 0u} : WfSkyImage{nullptr, 0u, 0u};
     ft.soft = rq.soft;
     const rwr_shadow_params *soft = ft.soft ? &ctx->shadow : nullptr;
     // (global sample indices: an accumulating frame traces [accum_before, accum_before + spp), keyed like one frame of them all)

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <utility>
+#include <memory>
 #include <vector>
 
 #include "rwr_internal.h"
@@ -172,6 +173,7 @@ struct WfState {
     DeviceBuffer<LightRec> d_light_recs;
     DeviceBuffer<unsigned long long> d_light_masks;
     DeviceBuffer<unsigned long long> d_light_counts;
+    std::shared_ptr<DeviceBuffer<float4>> sky_image;   // RWR_FLAG_SKY_IMAGE: the image this slot's last frame under the flag reads, kept until the slot's next
 };
 
 // Progressive accumulation (RWR_FLAG_ACCUMULATE): ONE accumulation per context.  Its sums and the first frame's sample-0 planes
@@ -314,6 +316,11 @@ struct rwr_context {
     uint32_t last_reproject_set = 0;       // ... and the history set it wrote (rwr_reproject_readback, rwr_last_reproject_stats)
     rwr_denoise_params denoise = rwr::kDenoiseDefaults;   // RWR_FLAG_DENOISE (rwr_denoise_set_params)
     rwr_sky_params sky = rwr::kSkyDefaults;               // RWR_FLAG_SKY (rwr_sky_set_params)
+    // RWR_FLAG_SKY_IMAGE (rwr_sky_set_image): the octahedral map, n x n float4 texels (null: none), and its generation.  A call makes a
+    // new buffer; a frame slot holds on to the one its frame was enqueued with (WfState::sky_image), so nothing waits for a frame.
+    std::shared_ptr<rwr::DeviceBuffer<float4>> sky_image;
+    uint32_t sky_image_n = 0;
+    uint64_t sky_image_generation = 0;
     rwr_shadow_params shadow = rwr::kShadowDefaults;      // RWR_FLAG_SOFT_SHADOWS (rwr_shadow_set_params)
     uint64_t scene_generation = 0;         // bumped by every change of the scene (an accumulation does not survive one)
     // one decoded texture per scene part (texels decoded to linear f32 at upload, Rgba8UnormSrgb semantics)

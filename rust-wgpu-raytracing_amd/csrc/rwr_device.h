@@ -261,6 +261,26 @@ RWR_DEV f3 tex_sample_bilinear(const float4 *__restrict__ tex, uint32_t pitch, f
     return tex_filter(tex, tex_taps(pitch, wmax, hmax, fxy));
 }
 
+// RWR_FLAG_SKY_IMAGE item 1: S_img(D) of the n x n octahedral map `image` (one float4 per texel) — the mapping in the header's f32
+// operations and their order (this build contracts nothing; the divisions are IEEE), then the fetch above at (u n - 0.5, v n - 0.5).
+// A NaN or zero direction gives NaN coordinates: the taps stay inside the map (tex_taps), the value is NaN and counts as 0.
+RWR_DEV f2 sky_image_uv(f3 D)
+{
+    const float a = (fabsf(D.x) + fabsf(D.y)) + fabsf(D.z);
+    float px = D.x / a, pz = D.z / a;
+    if (D.y < 0.0f) {
+        const float qx = (1.0f - fabsf(pz)) * copysignf(1.0f, px), qz = (1.0f - fabsf(px)) * copysignf(1.0f, pz);
+        px = qx; pz = qz;
+    }
+    return f2{px * 0.5f + 0.5f, pz * 0.5f + 0.5f};
+}
+RWR_DEV f3 sky_image_radiance(const float4 *__restrict__ image, uint32_t n, f3 D)
+{
+    const f2 uv = sky_image_uv(D);
+    const float fn = (float)n;
+    return tex_sample_bilinear(image, n * 16u, fn - 1.0f, fn - 1.0f, f2{uv.x * fn - 0.5f, uv.y * fn - 0.5f});
+}
+
 // The same fetch and filter from the quad form of the texture (rwr_internal.h QuadTex): the 2x2 footprint is the one
 // record at p = (med3(f0.x, -1, wmax) + 1, med3(f0.y, -1, hmax) + 1), f0 = floor(fxy), which holds exactly the taps
 // tex_taps picks (a NaN position: v_med3 returns one of its finite operands, so p stays inside the (w+1) x (h+1) grid).

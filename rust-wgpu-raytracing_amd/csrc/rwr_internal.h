@@ -363,6 +363,14 @@ struct WfSky {
     float zr, zg, zb, hr, hg, hb;   // zenith, horizon: rwr_sky_params' six floats in its order (plain members, no arrays: they stay registers)
 };
 static_assert(sizeof(WfSky) == sizeof(rwr_sky_params), "WfSky is rwr_sky_params");
+// The sky's image (RWR_FLAG_SKY_IMAGE; the IMG forms of the trace kernels' SKY forms, add_sky_image): the context's octahedral map,
+// n x n float4 texels, and n; image == nullptr: the gradient of WfSky, the SKY forms without IMG.  A kernel argument of its own
+// behind all others (cf. WfEmit): no other form reads it, and all of them keep their instructions.
+struct WfSkyImage {
+    const float4 *image;
+    uint32_t n;
+    uint32_t pad;
+};
 // The mesh light (RWR_FLAG_LIGHT_PARTS; rwr_part_lights.h): the face list, its length, the frame's shading records (a listed face's
 // part is ShadeRec::material, its radiance that part's record of WfGlow::table) and L = M + 1, the lights the stage chooses among.
 // A kernel argument of k_wf_light behind WfLights: scalar registers.
@@ -379,6 +387,7 @@ struct WfFeatures {
     WfEmit emit{nullptr, 0u, 0u};
     WfShadow shadow{nullptr, nullptr, nullptr};
     WfSky sky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    WfSkyImage sky_image{nullptr, 0u, 0u};   // RWR_FLAG_SKY_IMAGE in effect: the image the IMG forms fetch S(D) from (else null: the gradient)
     WfSurfaces surfaces{nullptr, 0u, 0u, nullptr};   // rwr_surface.h
     WfGlow glow{nullptr, 0u, 0u, nullptr, nullptr, nullptr, nullptr};   // rwr_surface.h
     bool emits = false, shadows = false, sky_on = false;
@@ -588,6 +597,8 @@ hipError_t launch_selftest_exact_math(hipStream_t s, unsigned long long *d_out4,
 hipError_t launch_selftest_exact_div(hipStream_t s, unsigned long long *d_out4, uint32_t count, uint32_t seed);
 // kernels_selftest.hip: d_out[i] = rng_sobol(d_in[i], d_in[n + i], d_in[2 n + i], d_in[3 n + i]) (RWR_FLAG_SOBOL's word)
 hipError_t launch_selftest_sobol(hipStream_t s, const uint32_t *d_in, uint32_t n, uint32_t *d_out);
+// kernels_selftest.hip: d_out[3 i ...] = sky_image_radiance(si, d_dirs[3 i ...]) (RWR_FLAG_SKY_IMAGE's S_img), count directions
+hipError_t launch_selftest_sky_image(hipStream_t s, const WfSkyImage &si, const float *d_dirs, uint32_t count, float *d_out);
 
 // kernels_selftest.hip: d_out[wave] = {shader cycles, 100 MHz ticks} around iters * 8 v_fma_f32 (mode 0) / v_pk_fma_f32 (mode 1)
 hipError_t launch_clock_probe(hipStream_t s, ulonglong2 *d_out, uint32_t ticks_100mhz);

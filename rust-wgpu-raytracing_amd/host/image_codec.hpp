@@ -11,7 +11,9 @@
 // Also a minimal PNG writer (stored deflate blocks) for the presentation step.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -826,6 +828,86 @@ inline bool decode_image(const uint8_t *bytes, size_t n, Image &img, std::string
     if (is_jpeg(bytes, n)) return decode_jpeg(bytes, n, img, err);
     err = "unrecognised image format (PNG and JPEG are supported)";
     return false;
+}
+
+// ------------------------------------------------------------ Radiance .hdr --
+// The sky's picture (rwr_render --sky-image): a Radiance RGBE file.  Header lines up to an empty one, the first "#?RADIANCE" (or
+// "#?RGBE"), one of them "FORMAT=32-bit_rle_rgbe"; then "-Y h +X w" (the one orientation: top row first, left to right); then h
+// scanlines, each either flat (four bytes r, g, b, e per pixel) or new-style RLE (2, 2, w >> 8, w & 255, then the four channels one
+// after the other as runs: a count above 128 repeats the next byte count - 128 times, a count up to 128 copies that many bytes).
+// A pixel's floats are Radiance's own (color.c colr_color): 0 when e is 0, else (m + 0.5) * 2^(e - 136) per channel.
+struct ImageF {
+    uint32_t width = 0, height = 0;
+    std::vector<float> rgb;  // width*height*3, row 0 = top row of the file
+};
+
+inline bool is_hdr(const uint8_t *b, size_t n)
+{
+    return (n >= 10 && std::memcmp(b, "#?RADIANCE", 10) == 0) || (n >= 6 && std::memcmp(b, "#?RGBE", 6) == 0);
+}
+
+inline bool decode_hdr(const uint8_t *b, size_t n, ImageF &img, std::string &err)
+{
+    if (!is_hdr(b, n)) { err = "not a Radiance picture (#?RADIANCE)"; return false; }
+    size_t pos = 0;
+    auto line = [&](std::string &out) {
+        out.clear();
+        while (pos < n && b[pos] != '\n') out.push_back((char)b[pos++]);
+        if (pos >= n) return false;
+        pos++;
+        return true;
+    };
+    std::string l;
+    bool format = false;
+    for (;;) {
+        if (!line(l)) { err = "Radiance header: no end"; return false; }
+        if (l.empty()) break;
+        if (l.rfind("FORMAT=", 0) == 0) {
+            if (l != "FORMAT=32-bit_rle_rgbe") { err = "Radiance header: " + l + " (32-bit_rle_rgbe is supported)"; return false; }
+            format = true;
+        }
+    }
+    if (!format) { err = "Radiance header: no FORMAT=32-bit_rle_rgbe"; return false; }
+    if (!line(l)) { err = "Radiance header: no resolution line"; return false; }
+    unsigned w = 0, h = 0;
+    char tail = 0;
+    if (std::sscanf(l.c_str(), "-Y %u +X %u%c", &h, &w, &tail) != 2 || w == 0 || h == 0 || w > 32768u || h > 32768u) {
+        err = "Radiance resolution '" + l + "' (-Y h +X w, each 1 ... 32768, is supported)";
+        return false;
+    }
+    std::vector<uint8_t> row((size_t)w * 4u);
+    img.width = w; img.height = h;
+    img.rgb.assign((size_t)w * h * 3u, 0.0f);
+    for (unsigned y = 0; y < h; y++) {
+        const bool rle = w >= 8u && w < 32768u && pos + 4 <= n && b[pos] == 2 && b[pos + 1] == 2 && (((unsigned)b[pos + 2] << 8) | b[pos + 3]) == w;
+        if (rle) {
+            pos += 4;
+            for (unsigned c = 0; c < 4; c++)
+                for (unsigned x = 0; x < w;) {
+                    if (pos >= n) { err = "Radiance picture: truncated scanline"; return false; }
+                    unsigned count = b[pos++];
+                    const bool run = count > 128u;
+                    if (run) count -= 128u;
+                    if (count == 0 || x + count > w) { err = "Radiance picture: a run leaves its scanline"; return false; }
+                    if (pos + (run ? 1u : count) > n) { err = "Radiance picture: truncated scanline"; return false; }
+                    for (unsigned k = 0; k < count; k++) row[(size_t)(x + k) * 4u + c] = run ? b[pos] : b[pos + k];
+                    pos += run ? 1u : count;
+                    x += count;
+                }
+        } else {
+            if (pos + (size_t)w * 4u > n) { err = "Radiance picture: truncated scanline"; return false; }
+            std::memcpy(row.data(), b + pos, (size_t)w * 4u);
+            pos += (size_t)w * 4u;
+        }
+        for (unsigned x = 0; x < w; x++) {
+            const uint8_t *p = &row[(size_t)x * 4u];
+            float *o = &img.rgb[((size_t)y * w + x) * 3u];
+            if (p[3] == 0) continue;
+            const float f = std::ldexp(1.0f, (int)p[3] - 136);
+            for (int c = 0; c < 3; c++) o[c] = ((float)p[c] + 0.5f) * f;
+        }
+    }
+    return true;
 }
 
 }  // namespace codec

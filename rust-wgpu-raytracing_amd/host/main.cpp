@@ -8,7 +8,7 @@
 //              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]...
 //              [--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]]
 //              [--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] [--sobol]
-//              [--show-params] [--out frame.png] [--time]
+//              [--sky-image FILE[:scale] [--sky-image-size N]] [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
 // (KEY in W A S D Up Down Left Right Space LShift, or '-' for no key).  After the script,
@@ -21,12 +21,14 @@
 // too — is blended with the history of the frames before it while the camera moves; the program prints `history K` for the
 // final frame.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "image_codec.hpp"
 #include "state.hpp"
 
 using namespace rwr;
@@ -173,6 +175,10 @@ int main(int argc, char **argv)
         for (int c = 0; c < 3; c++) e.le[c] = v[c];
         return true;
     };
+    // --sky-image FILE[:scale] [--sky-image-size N]: a latitude-longitude picture for RWR_FLAG_SKY_IMAGE, its scale and the map's side
+    std::string sky_image;
+    double sky_image_scale = 1.0;
+    uint32_t sky_image_size = 256u;
     struct Resize { uint64_t frame; uint32_t w, h; };
     std::vector<Resize> resizes;
     for (int i = 1; i < argc; i++) {
@@ -235,6 +241,29 @@ int main(int argc, char **argv)
             sky = true;
             (zenith ? sky_zenith_set : sky_horizon_set) = true;
         }
+        else if (a == "--sky-image") {   // "FILE" or "FILE:scale", the scale a finite number >= 0 behind the last colon
+            sky_image = next();
+            const size_t colon = sky_image.rfind(':');
+            double v = 0.0;
+            if (colon != std::string::npos && colon + 1 < sky_image.size() && sky_image.find('/', colon) == std::string::npos) {
+                if (!parse_number(sky_image.c_str() + colon + 1, v) || v < 0.0 || !((float)v - (float)v == 0.0f)) {
+                    std::fprintf(stderr, "--sky-image FILE[:scale]: the scale is a finite number >= 0\n");
+                    return 2;
+                }
+                sky_image_scale = v;
+                sky_image.resize(colon);
+            }
+            if (sky_image.empty()) { std::fprintf(stderr, "--sky-image FILE[:scale]: no file\n"); return 2; }
+            sky = true;
+        }
+        else if (a == "--sky-image-size") {
+            double v = 0.0;
+            if (!parse_number(next(), v) || v != (double)(uint32_t)v || v < 2.0 || v > (double)RWR_SKY_IMAGE_SIZE_MAX) {
+                std::fprintf(stderr, "--sky-image-size N: a whole number in [2, %u]\n", RWR_SKY_IMAGE_SIZE_MAX);
+                return 2;
+            }
+            sky_image_size = (uint32_t)v;
+        }
         else if (a == "--mirror-part" || a == "--mirror-sphere") {
             Mirror m{a == "--mirror-sphere", 0u, {1.0f, 1.0f, 1.0f}};
             if (!parse_mirror(next(), m) || (m.sphere && m.index >= RWR_MAX_SPHERES)) {
@@ -289,7 +318,7 @@ int main(int argc, char **argv)
                         "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
                         "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]... "
                         "[--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... "
-                        "[--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] [--sobol] "
+                        "[--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] [--sobol] [--sky-image FILE[:scale] [--sky-image-size N]] "
                         "[--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]] "
                         "[--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
@@ -304,6 +333,11 @@ int main(int argc, char **argv)
                         "  --sky         bounce rays that leave the scene return the sky's radiance (RWR_FLAG_SKY; needs --bounces >= 1): a "
                         "gradient from --sky-horizon (straight down) to --sky-zenith (straight up), components in [0, 16] "
                         "(rwr_sky_set_params); either colour implies --sky\n"
+                        "  --sky-image FILE[:scale]  the sky's radiance comes from a picture of a place instead of the gradient "
+                        "(RWR_FLAG_SKY_IMAGE; implies --sky): a latitude-longitude PNG or JPEG (taken to linear) or a Radiance .hdr file, top row "
+                        "straight up, the centre column towards -z; multiplied by scale (1 when left out; an 8-bit picture wants about 4 to "
+                        "light a scene), converted to an octahedral map of --sky-image-size N texels a side (256 when left out; 2 ... 2048) "
+                        "(rwr_sky_image_from_equirect, rwr_sky_set_image)\n"
                         "  --mirror-part N[:r,g,b], --mirror-sphere N[:r,g,b]  part N of the scene / sphere N is a mirror of reflectance r,g,b "
                         "in [0, 1] (1,1,1 when left out) and reflects the ray that found it (RWR_FLAG_MIRRORS, implied; needs --bounces >= 1; "
                         "rwr_scene_set_part_mirror / rwr_scene_set_sphere_mirror); repeatable\n"
@@ -349,7 +383,8 @@ int main(int argc, char **argv)
                            (glosses.empty() ? 0u : (uint32_t)RWR_FLAG_GLOSSY) | (soft_shadows ? (uint32_t)RWR_FLAG_SOFT_SHADOWS : 0u) |
                            (reproject ? (uint32_t)RWR_FLAG_REPROJECT : 0u) | (emitters.empty() ? 0u : (uint32_t)RWR_FLAG_EMISSIVE) |
                            (light_sampling ? (uint32_t)RWR_FLAG_LIGHT_SAMPLING : 0u) | (light_parts ? (uint32_t)RWR_FLAG_LIGHT_PARTS : 0u) |
-                           (light_mis ? (uint32_t)RWR_FLAG_LIGHT_MIS : 0u) | (sobol ? (uint32_t)RWR_FLAG_SOBOL : 0u);
+                           (light_mis ? (uint32_t)RWR_FLAG_LIGHT_MIS : 0u) | (sobol ? (uint32_t)RWR_FLAG_SOBOL : 0u) |
+                           (sky_image.empty() ? 0u : (uint32_t)RWR_FLAG_SKY_IMAGE);
     if (show_params) {
         if (reproject)   // (a line of its own, ahead of the line every run prints)
             std::printf("reproject 1 history %u normal %g depth %g\n", reproject_params.max_history, (double)reproject_params.normal_cos_min,
@@ -362,6 +397,8 @@ int main(int argc, char **argv)
                 std::printf(" %s %u:%g,%g,%g", e.sphere ? "sphere" : "part", e.index, (double)e.le[0], (double)e.le[1], (double)e.le[2]);
             std::printf("\n");
         }
+        if (!sky_image.empty())   // (likewise)
+            std::printf("sky image %u scale %g file %s\n", sky_image_size, sky_image_scale, sky_image.c_str());
         std::printf("spp %u bounces %u flags 0x%x sky %d zenith %g,%g,%g horizon %g,%g,%g gloss %zu", spp, bounces, flags, sky ? 1 : 0,
                     (double)sky_params.zenith[0], (double)sky_params.zenith[1], (double)sky_params.zenith[2],
                     (double)sky_params.horizon[0], (double)sky_params.horizon[1], (double)sky_params.horizon[2], glosses.size());
@@ -393,11 +430,51 @@ int main(int argc, char **argv)
         pos = comma + 1;
     }
 
+    // the sky's picture, decoded and converted ahead of the device: PNG / JPEG through the texture path's decoders and the sRGB
+    // curve, .hdr as it stands
+    std::vector<float> sky_map;
+    if (!sky_image.empty()) {
+        std::vector<uint8_t> bytes;
+        if (FILE *f = std::fopen(sky_image.c_str(), "rb")) {
+            uint8_t buf[65536];
+            for (size_t got; (got = std::fread(buf, 1, sizeof buf, f)) != 0;) bytes.insert(bytes.end(), buf, buf + got);
+            std::fclose(f);
+        } else {
+            std::fprintf(stderr, "--sky-image: cannot open %s\n", sky_image.c_str());
+            return 2;
+        }
+        codec::ImageF pic;
+        std::string err;
+        if (codec::is_hdr(bytes.data(), bytes.size())) {
+            if (!codec::decode_hdr(bytes.data(), bytes.size(), pic, err)) { std::fprintf(stderr, "--sky-image: %s: %s\n", sky_image.c_str(), err.c_str()); return 2; }
+        } else {
+            codec::Image ldr;
+            if (!codec::decode_image(bytes.data(), bytes.size(), ldr, err)) { std::fprintf(stderr, "--sky-image: %s: %s\n", sky_image.c_str(), err.c_str()); return 2; }
+            float lut[256];
+            for (int i = 0; i < 256; i++) {
+                const double c = i / 255.0;
+                lut[i] = (float)(c <= 0.04045 ? c / 12.92 : std::pow((c + 0.055) / 1.055, 2.4));
+            }
+            pic.width = ldr.width; pic.height = ldr.height;
+            pic.rgb.resize((size_t)ldr.width * ldr.height * 3u);
+            for (size_t i = 0; i < (size_t)ldr.width * ldr.height; i++)
+                for (int c = 0; c < 3; c++) pic.rgb[3u * i + c] = lut[ldr.rgba[4u * i + c]];
+        }
+        sky_map.resize((size_t)sky_image_size * sky_image_size * 3u);
+        if (rwr_sky_image_from_equirect(pic.rgb.data(), pic.width, pic.height, (float)sky_image_scale, sky_image_size, sky_map.data()) != RWR_OK) {
+            std::fprintf(stderr, "--sky-image: %s\n", rwr_last_error_string());
+            return 2;
+        }
+    }
+
     try {
         State state(w, h, res, scene);
         const rwr_render_params params{spp, bounces, 0u, flags};
         if (sky_zenith_set || sky_horizon_set) {
             if (rwr_sky_set_params(state.context(), &sky_params) != RWR_OK) { std::fprintf(stderr, "--sky: %s\n", rwr_last_error_string()); return 2; }
+        }
+        if (!sky_map.empty()) {
+            if (rwr_sky_set_image(state.context(), sky_map.data(), sky_image_size) != RWR_OK) { std::fprintf(stderr, "--sky-image: %s\n", rwr_last_error_string()); return 2; }
         }
         if (soft_shadows) state.set_shadow_params(shadow_params);   // (in range already: a failure is the library's, reported below)
         for (const Mirror &m : mirrors) {   // (the scene is loaded: a part the scene does not have is the library's refusal)
@@ -447,6 +524,7 @@ int main(int argc, char **argv)
         const Camera &c = state.camera();
         std::printf("frames %llu  eye (%.6f, %.6f, %.6f)  target (%.6f, %.6f, %.6f)  size %ux%u  aspect %.9g\n", (unsigned long long)rendered,
                     c.eye.x, c.eye.y, c.eye.z, c.target.x, c.target.y, c.target.z, state.size().width, state.size().height, (double)c.aspect);
+        if (!sky_map.empty()) std::printf("sky image %ux%u\n", sky_image_size, sky_image_size);
         if (accumulate) std::printf("samples %llu\n", (unsigned long long)state.accumulated_samples());
         if (reproject) std::printf("history %llu\n", (unsigned long long)state.reprojected_frames());
         if (!glosses.empty()) std::printf("glossy rays %llu\n", (unsigned long long)state.glossy_rays());
