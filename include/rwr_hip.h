@@ -590,7 +590,8 @@ enum {
                                        share of the two densities, so that every light term is bounded by T * Le, the cap no longer
                                        darkens receivers that touch an emitter, and both flags may stay on in any scene.  Without this
                                        flag every frame is what it was, byte for byte.  All arithmetic f32, no contraction.
-                                       1. The flag is effective only while RWR_FLAG_LIGHT_SAMPLING or RWR_FLAG_LIGHT_PARTS is effective,
+                                       1. The flag is effective only while RWR_FLAG_LIGHT_SAMPLING, RWR_FLAG_LIGHT_PARTS or (its items 5
+                                          and 6 say what is weighted there) RWR_FLAG_LIGHT_SKY is effective,
                                           each by its own rule; otherwise it is cleared before the frame's kernels are chosen and the
                                           frame is the frame without it, in the same kernels.  L: the lights the stage chooses among
                                           (RWR_FLAG_LIGHT_PARTS' item 3; M under RWR_FLAG_LIGHT_SAMPLING alone).
@@ -630,7 +631,7 @@ enum {
                                        6. The sum is the same integral: at every direction omega towards an emitter the light sample
                                           contributes with weight p_l / (p_l + p_b) = 1 - m and the bounce ray with p_b / (p_l + p_b) = m.
                                           The balance heuristic only; no power heuristic, no power-proportional light choice, no light
-                                          rays from glossy hits, no weighting of the sky.
+                                          rays from glossy hits, no weighting of the gradient sky (the sky's image: RWR_FLAG_LIGHT_SKY).
                                        7. The bit (after item 1) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
                                           effective flags.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED. */
@@ -668,7 +669,7 @@ enum {
                                        5. The bit (after item 3) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
                                           effective flags.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED. */
-    RWR_FLAG_SKY_IMAGE = 1u << 24      /* extension: sky light from an image — RWR_FLAG_SKY's radiance S(D) comes from an octahedral
+    RWR_FLAG_SKY_IMAGE = 1u << 24,     /* extension: sky light from an image — RWR_FLAG_SKY's radiance S(D) comes from an octahedral
                                        environment map (rwr_sky_set_image) instead of the two-colour gradient.  The flag implies
                                        nothing.  Off by default; without the flag every frame is what it was, byte for byte.
                                        1. With the flag in effect the S(D) of RWR_FLAG_SKY item 1 is S_img(D), f32 operations in
@@ -700,10 +701,64 @@ enum {
                                           in both: a new image starts a new history.  Without the bit, rwr_sky_set_image disturbs
                                           neither.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED. */
+    RWR_FLAG_LIGHT_SKY = 1u << 25      /* extension: light rays aimed at the sky's image — the light ray of an eligible (diffuse) hit may
+                                       aim at RWR_FLAG_SKY_IMAGE's map, drawn in proportion to the map's radiance, so that a map with
+                                       a small sun converges.  The flag implies nothing.  Off by default; without the flag every frame
+                                       is what it was, byte for byte.  All arithmetic f32, no contraction, unless it says double.
+                                       1. The distribution, made on the host once per image (by the first frame that asks for the flag
+                                          after rwr_sky_set_image; rwr_sky_get_light_info).  All sums in double, rounded to f32 once, on
+                                          storing.  For texel (row j, column i): lum = r + g + b; b_ji = the sum of lum over the 3 x 3
+                                          neighbourhood, indices clamped to [0, n - 1], rows outer, columns inner (S_img's bilinear
+                                          fetch reads exactly those texels from inside the cell: the density is positive wherever
+                                          S_img is); p_c = the point of |x| + |y| + |z| = 1 at the cell's centre, u = (i + 0.5) / n,
+                                          v = (j + 0.5) / n: px = 2u - 1, pz = 2v - 1, py = (1 - |px|) - |pz|, and where py < 0
+                                          (px, pz) <- ((1 - |pz|) copysign(1, px), (1 - |px|) copysign(1, pz)); l2 = (px px + py py) + pz pz;
+                                          w_ji = b_ji * (1 / (l2 * sqrt(l2))) — the cell du dv covers the solid angle 4 a^3 du dv, a the
+                                          L1 norm of the unit direction, a = 1 / |p|.  W_j = sum_i w_ji, W = sum_j W_j, in index order.
+                                          R_j = (float)((W_0 + ... + W_j) / W), C_ji = (float)((w_j0 + ... + w_ji) / W_j); in each cdf every
+                                          entry from the last texel (row) of non-zero weight on is 1.0f; a row with W_j = 0 holds 1.0f
+                                          throughout.  The cdf before index 0 is 0.
+                                       2. Eligible hits, O, T, n and the RNG block d = 274 + 17 k are RWR_FLAG_LIGHT_SAMPLING's: one light
+                                          ray per eligible hit, no random number moves, no dimension is added.  With M the emitting
+                                          spheres in use while RWR_FLAG_LIGHT_SAMPLING is effective (else 0) and P = 1 while
+                                          RWR_FLAG_LIGHT_PARTS is (else 0) there are L = M + P + 1 lights, the sky the last:
+                                          i = min((uint32)(rng(d) * (float)L), L - 1), drawn only when L > 1.  i < M is the sphere rule,
+                                          i == M with P = 1 the face rule, both with this L in their g; i == L - 1 is the sky lane.
+                                       3. The sky lane's draw.  Row j: the first entry with rng(d + 1) < R_j; column i: the first with
+                                          rng(d + 2) < C_ji (binary searches).  u = ((float)i + rng(d + 3)) / (float)n,
+                                          v = ((float)j + rng(d + 4)) / (float)n; px = 2u - 1, pz = 2v - 1, py = (1 - |px|) - |pz|, folded
+                                          as in item 1 where py < 0; len = sqrtf((px px + py py) + pz pz); omega = p / len per component.
+                                       4. The factor, one function for both sides: sky_light_g(omega, ndw = dot3(n, omega), L).  omega is
+                                          mapped forward with RWR_FLAG_SKY_IMAGE's item 1, giving a, u, v; the texel is
+                                          i' = min((uint32)(u * (float)n), n - 1), j' likewise with v;
+                                          P = (R_j' - R_(j'-1)) * (C_j'i' - C_j'(i'-1));
+                                          g = ((((float)L * ndw) * 0.318309886f) * (4 * ((a * a) * a))) / (((float)n * (float)n) * P),
+                                          which is p_b / p_l as in the other two rules.  !(P > 0) or !(ndw > 0): no sample, no ray.
+                                          The light side calls it on the omega it drew: a bounce ray in that direction computes the
+                                          same float.
+                                       5. The ray (O, omega) REACHES the sky when it hits nothing — no sphere at any t, no face: the
+                                          predicate by which a bounce ray counts as a miss.  The term is T.c * (S_img(omega).c * g) per
+                                          channel, m(g) in g's place under RWR_FLAG_LIGHT_MIS, converted and capped to [0, 64] like a
+                                          bounce term (NaN as 0) and added to the same sums.  A path adds no more terms than under
+                                          RWR_FLAG_LIGHT_SAMPLING.
+                                       6. No double counting: while the flag is effective a diffuse (marked) ray that leaves the scene
+                                          adds no sky term; under RWR_FLAG_LIGHT_MIS it adds T.c * (S_img(D).c * m(g')) instead,
+                                          g' = sky_light_g(D, dot3(n, D), L), n the normal of the hit that sent the ray, and where
+                                          !(P > 0) — the sampler cannot go there — all of T.c * S_img(D).c.  Such misses, silenced or
+                                          weighted, count as suppressed.  The misses of mirror, glass and glossy rays keep S.
+                                       7. The flag is effective while RWR_FLAG_SKY_IMAGE is effective and W > 0; otherwise it is cleared
+                                          and the frame is the frame without it, byte for byte, in the same kernels.  It does not need
+                                          RWR_FLAG_EMISSIVE.  RWR_FLAG_LIGHT_MIS is effective while any of the three light flags is.
+                                          The gradient sky gets no light rays: cosine-distributed bounce rays suit it.
+                                       8. rwr_last_light_stats' three totals include the sky's rays, reached rays and suppressed misses;
+                                          rwr_last_sky_light_stats reports the sky's share of each.
+                                       9. The bit (after item 7) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
+                                          effective flags; the image's generation is in both already.  With RWR_FLAG_ORTHO_RAYS,
+                                          RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
 };
 /* every flag above, and the bits between them that the library keeps for itself: a caller sets none of the latter */
 #define RWR_FLAGS_RESERVED (0xfu << 17)
-#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21) | (1u << 22) | (1u << 23) | (1u << 24))
+#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21) | (1u << 22) | (1u << 23) | (1u << 24) | (1u << 25))
 
 #define RWR_MAX_BOUNCES 8u
 
@@ -1070,6 +1125,9 @@ RWR_API int rwr_last_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_
  * item 8 silenced or RWR_FLAG_LIGHT_MIS weighted.  Zeros for a frame the flag did nothing to.  Exact counts.  Waits for the frame.  A NULL argument is
  * RWR_ERR_INVALID_ARGUMENT. */
 RWR_API int rwr_last_part_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits);
+/* RWR_FLAG_LIGHT_SKY: the sky's share of rwr_last_light_stats' three counts — the light rays aimed at the image, those that reached it,
+ * and the misses of diffuse rays that item 6 silenced or weighted.  Zeros for a frame without the flag in effect. */
+RWR_API int rwr_last_sky_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_misses);
 
 /* Progressive accumulation (RWR_FLAG_ACCUMULATE).  One context holds one accumulation.
  * rwr_accum_reset: the next accumulating frame starts over at N = 0 (host-side only, nothing waits).
@@ -1117,6 +1175,10 @@ RWR_API int rwr_sky_get_params(rwr_context *ctx, rwr_sky_params *out);
 #define RWR_SKY_IMAGE_COMPONENT_MAX 64.0f
 RWR_API int rwr_sky_set_image(rwr_context *ctx, const float *rgb, uint32_t n);
 RWR_API int rwr_sky_get_image_info(rwr_context *ctx, uint32_t *n, uint64_t *generation);
+/* RWR_FLAG_LIGHT_SKY: the sampling table a frame under the flag would use — n, the image's side (0 when there is no image or the image
+ * has no weight: the flag is not effective), and the generation of the image it was built for.  Builds the table if the image has
+ * changed since (what the first frame under the flag would do); either pointer may be NULL. */
+RWR_API int rwr_sky_get_light_info(rwr_context *ctx, uint32_t *n, uint64_t *generation);
 /* Host only, no context and no device: turns a latitude-longitude picture (w x h x 3 floats, row 0 = straight up, the centre column
  * = direction (0, 0, -1), columns increasing towards +x) into the n x n x 3 octahedral map `out` that rwr_sky_set_image takes.  Per
  * output texel the mean of 4 x 4 sub-positions; each is mapped to a direction by the inverse of the flag's mapping, the direction to
@@ -1186,6 +1248,10 @@ RWR_API int rwr_selftest_sobol(rwr_context *ctx, const uint32_t *pixel, const ui
  * function evaluates it, for `count` directions (at most 2^24 a call).  RWR_ERR_NOT_READY while the context holds no image.  A
  * value that differs from the definition's bits is a bug. */
 RWR_API int rwr_selftest_sky_image(rwr_context *ctx, const float *dirs, size_t count, float *out_rgb);
+/* Self-test of RWR_FLAG_LIGHT_SKY's items 3 and 4 as the kernels' device functions evaluate them on the context's image: for tuple i,
+ * out[8 i ...] = {omega.x, omega.y, omega.z, column, row (uint32 bits), P, g, 0} of the draw from the four uniforms u4[4 i ...] (in
+ * [0, 1)) and of sky_light_g(omega, dot3(normal, omega), n_lights).  RWR_ERR_NOT_READY without an image or with an image of no weight. */
+RWR_API int rwr_selftest_sky_light(rwr_context *ctx, const float *u4, size_t count, const float normal[3], uint32_t n_lights, float *out);
 
 /* Measurement aid for roofline accounting (bench.py): runs a short f32 VALU loop with `waves_per_simd` (1..8)
  * waves on every SIMD and stamps the shader cycle counter against the constant 100 MHz counter.

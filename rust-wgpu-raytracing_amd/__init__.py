@@ -60,6 +60,7 @@ FLAG_LIGHT_SAMPLING = 1 << 16  # every diffuse hit also sends a ray towards an e
 FLAG_LIGHT_PARTS = 1 << 21     # ... or towards a point on a face of an emitting part, the mesh light (include/rwr_hip.h; bits 17-20 are reserved)
 FLAG_LIGHT_MIS = 1 << 22       # the light ray and the diffuse bounce ray are combined by the balance heuristic: multiple importance sampling (include/rwr_hip.h)
 FLAG_SOBOL = 1 << 23           # every random number of the path tracer comes from an Owen-scrambled Sobol sequence instead of the hash (include/rwr_hip.h)
+FLAG_LIGHT_SKY = 1 << 25       # the light ray of a diffuse hit may aim at FLAG_SKY_IMAGE's map, drawn in proportion to its radiance (include/rwr_hip.h)
 FLAG_SKY_IMAGE = 1 << 24       # FLAG_SKY's radiance comes from the context's octahedral environment map (sky_set_image) instead of the gradient (include/rwr_hip.h)
 SKY_IMAGE_SIZE_MAX, SKY_IMAGE_COMPONENT_MAX = 2048, 64.0   # RWR_SKY_IMAGE_SIZE_MAX, RWR_SKY_IMAGE_COMPONENT_MAX
 MAX_EMISSION = 64.0         # RWR_MAX_EMISSION: the largest component of a radiance
@@ -136,6 +137,7 @@ def lib() -> C.CDLL:
         "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
         "rwr_sky_set_image": [vp, vp, u32], "rwr_sky_get_image_info": [vp, vp, vp],
         "rwr_sky_image_from_equirect": [vp, u32, u32, f32, u32, vp], "rwr_selftest_sky_image": [vp, vp, C.c_size_t, vp],
+        "rwr_sky_get_light_info": [vp, vp, vp], "rwr_last_sky_light_stats": [vp, vp, vp, vp], "rwr_selftest_sky_light": [vp, vp, C.c_size_t, vp, u32, vp],
         "rwr_shadow_set_params": [vp, vp], "rwr_shadow_get_params": [vp, vp],
         "rwr_reproject_set_params": [vp, vp], "rwr_reproject_get_params": [vp, vp], "rwr_reproject_reset": [vp],
         "rwr_reproject_frames": [vp, vp], "rwr_last_reproject_stats": [vp, vp, vp, vp], "rwr_reproject_readback": [vp, vp],
@@ -176,7 +178,8 @@ def lib() -> C.CDLL:
                            "rwr_scene_get_part_gloss", "rwr_scene_get_sphere_gloss", "rwr_last_gloss_stats",
                            "rwr_shadow_set_params", "rwr_shadow_get_params", "rwr_scene_set_part_emission", "rwr_scene_set_sphere_emission",
                            "rwr_scene_get_part_emission", "rwr_scene_get_sphere_emission", "rwr_last_emission_stats", "rwr_last_light_stats", "rwr_last_part_light_stats",
-                           "rwr_selftest_sobol", "rwr_sky_set_image", "rwr_sky_get_image_info", "rwr_sky_image_from_equirect", "rwr_selftest_sky_image")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_selftest_sobol", "rwr_sky_set_image", "rwr_sky_get_image_info", "rwr_sky_image_from_equirect", "rwr_selftest_sky_image",
+                           "rwr_sky_get_light_info", "rwr_last_sky_light_stats", "rwr_selftest_sky_light")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -623,6 +626,13 @@ class Context:
         _check(lib().rwr_last_part_light_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
 
+    def last_sky_light_stats(self):
+        """FLAG_LIGHT_SKY: the sky's share of last_light_stats' three counts — light rays aimed at the image, those that reached it,
+        misses of diffuse rays that were silenced or, under FLAG_LIGHT_MIS, weighted (rwr_last_sky_light_stats)."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rwr_last_sky_light_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
     def set_triangles(self, triangles):
         """Single-triangle passes (the reference's dormant models/triangle), after the spheres."""
         triangles = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE)
@@ -759,6 +769,16 @@ class Context:
         out = np.zeros_like(d)
         _check(lib().rwr_selftest_sky_image(self._h, _p(d), len(d), _p(out)))
         return out
+
+    def selftest_sky_light(self, u4, normal=(0.0, 1.0, 0.0), n_lights: int = 1) -> dict:
+        """FLAG_LIGHT_SKY's draw and factor on the context's image for every row of `u4` (float32 (N, 4), uniforms in [0, 1)), evaluated
+        by the kernels' device functions (rwr_selftest_sky_light): {"omega": float32 (N, 3), "texel": uint32 (N, 2) column and row,
+        "P": float32 (N,), "g": float32 (N,)}.  RwrError(ERR_NOT_READY) while no image is held or the image is all black."""
+        u = np.ascontiguousarray(u4, dtype=np.float32).reshape(-1, 4)
+        nrm = np.ascontiguousarray(normal, dtype=np.float32).reshape(3)
+        out = np.zeros((len(u), 8), np.float32)
+        _check(lib().rwr_selftest_sky_light(self._h, _p(u), len(u), _p(nrm), int(n_lights), _p(out)))
+        return {"omega": out[:, 0:3].copy(), "texel": out[:, 3:5].copy().view(np.uint32), "P": out[:, 5].copy(), "g": out[:, 6].copy()}
 
     def measure_valu_clock(self, waves_per_simd: int = 8) -> dict:
         """Shader clock (MHz) and cycles a SIMD spends per wave64 v_fma_f32 / v_pk_fma_f32, measured under load."""
@@ -982,6 +1002,13 @@ class Context:
         """{"n": side of the image held (0: none), "generation": how many accepted sky_set_image calls} (rwr_sky_get_image_info)."""
         n, gen = C.c_uint32(0), C.c_uint64(0)
         _check(lib().rwr_sky_get_image_info(self._h, C.byref(n), C.byref(gen)))
+        return {"n": int(n.value), "generation": int(gen.value)}
+
+    def sky_get_light_info(self) -> dict:
+        """{"n": side of the FLAG_LIGHT_SKY sampling table a frame would use (0: no image, or an all-black one), "generation": the
+        image generation it was built for} (rwr_sky_get_light_info); builds the table if the image changed since."""
+        n, gen = C.c_uint32(0), C.c_uint64(0)
+        _check(lib().rwr_sky_get_light_info(self._h, C.byref(n), C.byref(gen)))
         return {"n": int(n.value), "generation": int(gen.value)}
 
     def shadow_set_params(self, mesh=None, sphere=None):

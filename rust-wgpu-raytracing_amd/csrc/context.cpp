@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "rwr_context.h"
+#include "rwr_sky_light.h"
 
 namespace rwr {
 
@@ -116,6 +117,29 @@ void read_tunables(rwr_context *ctx)
     if (env_u64("RWR_ACCUM_MAX_SAMPLES", &ctx->accum_max)) ctx->accum_max = std::min<uint64_t>(1u << 24, std::max<uint64_t>(1u, ctx->accum_max));
 }
 }  // namespace
+
+// RWR_FLAG_LIGHT_SKY item 1: the table of the context's image, built on the host by the first frame that asks for the flag after the image
+// changed, into a buffer of its own, filled before anything can read it (as the image is: the buffer before stays with the frame
+// slots whose frames read it, WfState::sky_light).  No image, or an image without weight: no table, and the flag is not effective.
+int rwr::scene_sky_light(rwr_context *ctx, bool &have)
+{
+    if (ctx->sky_light_generation != ctx->sky_image_generation) {
+        ctx->sky_light.reset();
+        if (ctx->sky_image && !ctx->sky_image_host.empty()) {
+            const std::vector<float> table = build_sky_light(&ctx->sky_image_host[0].x, ctx->sky_image_n, 4u);
+            if (!table.empty()) {
+                DeviceGuard g(ctx->device);
+                auto buf = std::make_shared<DeviceBuffer<float>>();
+                RWR_HIP_CHECK(buf->ensure(table.size()));
+                RWR_HIP_CHECK(hipMemcpy(buf->ptr, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+                ctx->sky_light = std::move(buf);
+            }
+        }
+        ctx->sky_light_generation = ctx->sky_image_generation;
+    }
+    have = ctx->sky_light != nullptr;
+    return RWR_OK;
+}
 
 extern "C" {
 
@@ -473,14 +497,14 @@ int rwr_last_emission_stats(rwr_context *ctx, uint64_t *emissive_hits)
     return RWR_OK;
 }
 
-// the last frame's six light counts (WfGlow::light_counts): the stage's totals, then the mesh light's share; zeros for a frame without the stage
-static int last_light_counts(rwr_context *ctx, unsigned long long counts[6])
+// the last frame's nine light counts (WfGlow::light_counts): the stage's totals, then the mesh light's share, then the sky's; zeros for a frame without the stage
+static int last_light_counts(rwr_context *ctx, unsigned long long counts[9])
 {
-    for (int i = 0; i < 6; i++) counts[i] = 0ull;
+    for (int i = 0; i < 9; i++) counts[i] = 0ull;
     if (ctx->last_light && ctx->wf_state[ctx->last_wf_state].d_light_counts.ptr) {
         DeviceGuard g(ctx->device);
         RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
-        RWR_HIP_CHECK(hipMemcpy(counts, ctx->wf_state[ctx->last_wf_state].d_light_counts.ptr, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        RWR_HIP_CHECK(hipMemcpy(counts, ctx->wf_state[ctx->last_wf_state].d_light_counts.ptr, 9 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     }
     return RWR_OK;
 }
@@ -488,7 +512,7 @@ static int last_light_counts(rwr_context *ctx, unsigned long long counts[6])
 int rwr_last_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits)
 {
     if (!ctx || !light_rays || !reached || !suppressed_hits) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
-    unsigned long long counts[6];
+    unsigned long long counts[9];
     const int rc = last_light_counts(ctx, counts);
     if (rc != RWR_OK) return rc;
     *light_rays = counts[0]; *reached = counts[1]; *suppressed_hits = counts[2];
@@ -498,10 +522,20 @@ int rwr_last_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reach
 int rwr_last_part_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_hits)
 {
     if (!ctx || !light_rays || !reached || !suppressed_hits) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
-    unsigned long long counts[6];
+    unsigned long long counts[9];
     const int rc = last_light_counts(ctx, counts);
     if (rc != RWR_OK) return rc;
     *light_rays = counts[3]; *reached = counts[4]; *suppressed_hits = counts[5];
+    return RWR_OK;
+}
+
+int rwr_last_sky_light_stats(rwr_context *ctx, uint64_t *light_rays, uint64_t *reached, uint64_t *suppressed_misses)
+{
+    if (!ctx || !light_rays || !reached || !suppressed_misses) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    unsigned long long counts[9];
+    const int rc = last_light_counts(ctx, counts);
+    if (rc != RWR_OK) return rc;
+    *light_rays = counts[6]; *reached = counts[7]; *suppressed_misses = counts[8];
     return RWR_OK;
 }
 
@@ -632,6 +666,7 @@ int rwr_sky_set_image(rwr_context *ctx, const float *rgb, uint32_t n)
         ctx->sky_image.reset();
         ctx->sky_image_n = 0u;
         ctx->sky_image_generation++;
+        ctx->sky_image_host = std::vector<float4>();
         return RWR_OK;
     }
     if (n < 2u || n > RWR_SKY_IMAGE_SIZE_MAX)
@@ -650,6 +685,18 @@ int rwr_sky_set_image(rwr_context *ctx, const float *rgb, uint32_t n)
     ctx->sky_image = std::move(buf);
     ctx->sky_image_n = n;
     ctx->sky_image_generation++;
+    ctx->sky_image_host = std::move(host);   // (RWR_FLAG_LIGHT_SKY builds its table from these texels, when a frame first asks)
+    return RWR_OK;
+}
+
+int rwr_sky_get_light_info(rwr_context *ctx, uint32_t *n, uint64_t *generation)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    bool have = false;
+    const int rc = rwr::scene_sky_light(ctx, have);
+    if (rc != RWR_OK) return rc;
+    if (n) *n = have ? ctx->sky_image_n : 0u;
+    if (generation) *generation = ctx->sky_light_generation;
     return RWR_OK;
 }
 

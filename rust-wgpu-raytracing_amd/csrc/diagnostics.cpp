@@ -66,8 +66,31 @@ int rwr_selftest_sky_image(rwr_context *ctx, const float *dirs, size_t count, fl
     DeviceBuffer<float> d;   // the directions, then the values
     RWR_HIP_CHECK(d.ensure(6 * count));
     RWR_HIP_CHECK(hipMemcpyAsync(d.ptr, dirs, 3 * count * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    RWR_HIP_CHECK(launch_selftest_sky_image(ctx->stream, WfSkyImage{image->ptr, ctx->sky_image_n, 0u}, d.ptr, (uint32_t)count, d.ptr + 3 * count));
+    RWR_HIP_CHECK(launch_selftest_sky_image(ctx->stream, WfSkyImage{image->ptr, ctx->sky_image_n, 0u, nullptr}, d.ptr, (uint32_t)count, d.ptr + 3 * count));
     RWR_HIP_CHECK(hipMemcpyAsync(out_rgb, d.ptr + 3 * count, 3 * count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    RWR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return RWR_OK;
+}
+
+int rwr_selftest_sky_light(rwr_context *ctx, const float *u4, size_t count, const float normal[3], uint32_t n_lights, float *out)
+{
+    if (!ctx || !u4 || !normal || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (count > (size_t)1 << 24) return set_error(RWR_ERR_INVALID_ARGUMENT, "at most 2^24 tuples a call, not %zu", count);
+    if (!ctx->sky_image) return set_error(RWR_ERR_NOT_READY, "the context holds no sky image (rwr_sky_set_image)");
+    bool have = false;
+    const int rc = scene_sky_light(ctx, have);
+    if (rc != RWR_OK) return rc;
+    if (!have) return set_error(RWR_ERR_NOT_READY, "the sky image has no weight (every texel is black): there is no table to draw from");
+    if (count == 0) return RWR_OK;
+    DeviceGuard g(ctx->device);
+    const std::shared_ptr<DeviceBuffer<float4>> image = ctx->sky_image;
+    const std::shared_ptr<DeviceBuffer<float>> table = ctx->sky_light;
+    DeviceBuffer<float> d;   // the uniforms, then the records
+    RWR_HIP_CHECK(d.ensure(12 * count));
+    RWR_HIP_CHECK(hipMemcpyAsync(d.ptr, u4, 4 * count * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    RWR_HIP_CHECK(launch_selftest_sky_light(ctx->stream, WfSkyImage{image->ptr, ctx->sky_image_n, 0u, table->ptr}, d.ptr, (uint32_t)count, normal, n_lights,
+                                            d.ptr + 4 * count));
+    RWR_HIP_CHECK(hipMemcpyAsync(out, d.ptr + 4 * count, 8 * count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     RWR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return RWR_OK;
 }

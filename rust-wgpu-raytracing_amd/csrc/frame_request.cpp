@@ -13,7 +13,7 @@ namespace {
 // id / t planes, so RWR_FLAG_AUX_OUTPUTS is implied, and its own bit is not part of rp.flags from there on (nor of a history's key).
 // mode: a surface flag switches on the surfaces of its model (surface_mode's bit).
 struct FlagRule { uint32_t flag; const char *name, *stage, *why; uint32_t mode; };
-constexpr FlagRule kFlagRules[15] = {
+constexpr FlagRule kFlagRules[16] = {
     {RWR_FLAG_ACCUMULATE, "RWR_FLAG_ACCUMULATE", nullptr, nullptr, 0u},
     {RWR_FLAG_SHADOWS, "RWR_FLAG_SHADOWS", nullptr, nullptr, 0u},
     {RWR_FLAG_DENOISE, "RWR_FLAG_DENOISE", "filter", "its taps reach 62 pixels", 0u},
@@ -28,7 +28,8 @@ constexpr FlagRule kFlagRules[15] = {
     {RWR_FLAG_LIGHT_PARTS, "RWR_FLAG_LIGHT_PARTS", nullptr, nullptr, 0u},
     {RWR_FLAG_LIGHT_MIS, "RWR_FLAG_LIGHT_MIS", nullptr, nullptr, 0u},
     {RWR_FLAG_SOBOL, "RWR_FLAG_SOBOL", nullptr, nullptr, 0u},
-    {RWR_FLAG_SKY_IMAGE, "RWR_FLAG_SKY_IMAGE", nullptr, nullptr, 0u}};
+    {RWR_FLAG_SKY_IMAGE, "RWR_FLAG_SKY_IMAGE", nullptr, nullptr, 0u},
+    {RWR_FLAG_LIGHT_SKY, "RWR_FLAG_LIGHT_SKY", nullptr, nullptr, 0u}};
 constexpr uint32_t kSurfaceFlags = RWR_FLAG_MIRRORS | RWR_FLAG_GLASS | RWR_FLAG_GLOSSY;
 
 // What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
@@ -132,14 +133,24 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
         }
         if (n_listed == 0u) rp.flags &= ~(uint32_t)RWR_FLAG_LIGHT_PARTS;
     }
-    // Multiple importance sampling weights the light rays of the two flags above against the bounce rays: without either there is nothing to weight
-    if (!(rp.flags & (RWR_FLAG_LIGHT_SAMPLING | RWR_FLAG_LIGHT_PARTS))) rp.flags &= ~(uint32_t)RWR_FLAG_LIGHT_MIS;
+    // Light rays towards the sky's image need the image in effect and a sampling table of it (an image with weight: looked at, and
+    // built if the image changed, only when the flag is set and the image is in effect); they do not need RWR_FLAG_EMISSIVE
+    if (rp.flags & RWR_FLAG_LIGHT_SKY) {
+        bool have = false;
+        if (rp.flags & RWR_FLAG_SKY_IMAGE) {
+            const int rc = scene_sky_light(ctx, have);
+            if (rc != RWR_OK) return rc;
+        }
+        if (!have) rp.flags &= ~(uint32_t)RWR_FLAG_LIGHT_SKY;
+    }
+    // Multiple importance sampling weights the light rays of the three flags above against the bounce rays: without any there is nothing to weight
+    if (!(rp.flags & (RWR_FLAG_LIGHT_SAMPLING | RWR_FLAG_LIGHT_PARTS | RWR_FLAG_LIGHT_SKY))) rp.flags &= ~(uint32_t)RWR_FLAG_LIGHT_MIS;
     // Soft shadows change the direction of shadow rays and nothing else: without shadow rays, or with two point lights, there is nothing to change
     if (!(asked & RWR_FLAG_SHADOWS) || (ctx->shadow.mesh_light_radius == 0.0f && ctx->shadow.sphere_light_radius == 0.0f)) rp.flags &= ~(uint32_t)RWR_FLAG_SOFT_SHADOWS;
     auto has = [](uint32_t flags, uint32_t flag) { return (flags & flag) != 0; };
     rq = FrameRequest{rp, row_begin, row_end, row_pitch, has(rp.flags, RWR_FLAG_AUX_OUTPUTS), has(asked, RWR_FLAG_ACCUMULATE), has(asked, RWR_FLAG_SHADOWS),
                       has(asked, RWR_FLAG_DENOISE), has(asked, RWR_FLAG_REPROJECT), has(rp.flags, RWR_FLAG_MIRRORS), has(rp.flags, RWR_FLAG_GLASS),
-                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), has(rp.flags, RWR_FLAG_EMISSIVE), has(rp.flags, RWR_FLAG_LIGHT_SAMPLING), has(rp.flags, RWR_FLAG_LIGHT_PARTS), has(rp.flags, RWR_FLAG_LIGHT_MIS), false, false, false, false};
+                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), has(rp.flags, RWR_FLAG_EMISSIVE), has(rp.flags, RWR_FLAG_LIGHT_SAMPLING), has(rp.flags, RWR_FLAG_LIGHT_PARTS), has(rp.flags, RWR_FLAG_LIGHT_MIS), false, false, false, false, false};
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
     // with shadow rays (the integrator's stages trace them), one the filter follows (it runs behind the integrator's resolve) or one
     // with an emitter (the integrator's kernels add its light)
@@ -147,6 +158,7 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
     // The sample sequence changes the integrator's random numbers and nothing else: it sends no frame there, and a frame of the
     // reference's kernels draws none (rq.rp.flags is what the histories' keys and the kernels see)
     rq.sky_image = has(rp.flags, RWR_FLAG_SKY_IMAGE);
+    rq.light_sky = has(rp.flags, RWR_FLAG_LIGHT_SKY);
     rq.sobol = rq.wavefront && has(rp.flags, RWR_FLAG_SOBOL);
     if (!rq.sobol) rq.rp.flags &= ~(uint32_t)RWR_FLAG_SOBOL;
     rq.dormant = ctx->n_triangles != 0 || (rp.flags & RWR_FLAG_ORTHO_RAYS) != 0;

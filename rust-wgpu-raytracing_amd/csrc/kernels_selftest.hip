@@ -230,6 +230,30 @@ hipError_t launch_selftest_sky_image(hipStream_t s, const WfSkyImage &si, const 
     return hipGetLastError();
 }
 
+// RWR_FLAG_LIGHT_SKY: out[8 i ...] = the direction sky_light_draw makes of the four uniforms u4[4 i ...], its texel's column and row (as
+// uint32 bits), P and g = sky_light_g of that direction against the normal (nx, ny, nz) among n_lights lights, 0 (rwr_device.h), for
+// rwr_selftest_sky_light and tests/test_gpu_sky_light.py.
+__global__ void __launch_bounds__(256)
+k_selftest_sky_light(const WfSkyImage si, const float *__restrict__ u4, uint32_t n, float nx, float ny, float nz, uint32_t n_lights, float *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint32_t ti, tj;
+    const f3 w = sky_light_draw(si.table, si.n, u4[4u * i], u4[4u * i + 1u], u4[4u * i + 2u], u4[4u * i + 3u], true, ti, tj);
+    float P = 0.0f;
+    const float g = sky_light_g(si.table, si.n, w, dot3(mk3(nx, ny, nz), w), (float)n_lights, ti, tj, P);
+    out[8u * i] = w.x; out[8u * i + 1u] = w.y; out[8u * i + 2u] = w.z;
+    out[8u * i + 3u] = __uint_as_float(ti); out[8u * i + 4u] = __uint_as_float(tj);
+    out[8u * i + 5u] = P; out[8u * i + 6u] = g; out[8u * i + 7u] = 0.0f;
+}
+
+hipError_t launch_selftest_sky_light(hipStream_t s, const WfSkyImage &si, const float *d_u4, uint32_t count, const float nrm[3], uint32_t n_lights, float *d_out)
+{
+    if (count == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_selftest_sky_light, dim3((count + 255u) / 256u), dim3(256), 0, s, si, d_u4, count, nrm[0], nrm[1], nrm[2], n_lights, d_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_selftest_exact_div(hipStream_t s, unsigned long long *d_out4, uint32_t count, uint32_t seed)
 {
     hipLaunchKernelGGL(k_selftest_div, dim3(8192), dim3(256), 0, s, d_out4, count, seed);

@@ -402,6 +402,43 @@ RWR_DEV void add_sky_image(TraceShared &sh, const WfSkyImage &si, uint32_t e, f3
     add_fixed(sh, e, (uint32_t)(thr.x * s.x * kWfFixedScale), (uint32_t)(thr.y * s.y * kWfFixedScale), (uint32_t)(thr.z * s.z * kWfFixedScale));
 }
 
+// whether a ray record's last word carries emit_next_ray's mark
+RWR_DEV bool wf_ray_marked(float w) { return (__float_as_uint(w) >> 16) != 0u; }
+// LSKY forms (RWR_FLAG_LIGHT_SKY item 6; forms of their own of the IMG x GLOW forms): the miss of a
+// MARKED ray — w is its record's last word — adds no sky term, the light sample of the ray's origin may have aimed at the image
+// already; under RWR_FLAG_LIGHT_MIS (gl.light & 4) it adds T * S_img(D) m(g') instead, g' = sky_light_g of D and the normal the
+// ray's origin left at its queue slot — and all of S where the sampler cannot go (!(P > 0)).  Such misses, silenced or weighted, are
+// counted in light_counts[2] and [8], one atomic per wave each.  Unmarked rays add what add_sky_image adds.
+RWR_DEV void add_sky_image_lit(TraceShared &sh, const WfSkyImage &si, const WfGlow &gl, uint32_t e, f3 D, f3 thr, float w, size_t pool_base, bool &suppressed)
+{
+    f3 s = sky_image_radiance(si.image, si.n, D);
+    if (wf_ray_marked(w)) {
+        float m = 0.0f;
+        suppressed = true;
+        if (gl.light & 4u) {   // (uniform)
+            const float4 rn = *reinterpret_cast<const float4 *>(gl.light_recs + pool_base + e);
+            uint32_t ti, tj;
+            float P;
+            const float gp = sky_light_g(si.table, si.n, D, dot3(mk3(rn.x, rn.y, rn.z), D), (float)(gl.light >> 8), ti, tj, P);
+            m = mis_weight(gp);
+            if (!(P > 0.0f)) { m = 1.0f; suppressed = false; }
+        }
+        s = mk3(s.x * m, s.y * m, s.z * m);
+    }
+    add_fixed(sh, e, (uint32_t)(thr.x * s.x * kWfFixedScale), (uint32_t)(thr.y * s.y * kWfFixedScale), (uint32_t)(thr.z * s.z * kWfFixedScale));
+}
+// a wave's suppressed misses (two per lane) into the frame's total of suppressed hits and the sky's share of it; call where the
+// wave's lanes have come together again
+RWR_DEV void count_sky_suppressed(const WfGlow &gl, bool s0, bool s1 = false)
+{
+    const unsigned long long active = __ballot(true);
+    const uint32_t n = (uint32_t)__popcll(__ballot(s0)) + (uint32_t)__popcll(__ballot(s1));
+    if (n && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(active)) {
+        atomicAdd(&gl.light_counts[2], (unsigned long long)n);
+        atomicAdd(&gl.light_counts[8], (unsigned long long)n);
+    }
+}
+
 // GLOW forms (RWR_FLAG_EMISSIVE): the local shading of the hit `obj` becomes E'(h) = E(h) + Le(h), Le the radiance of the hit's
 // surface (rwr_surface.h glow_record) — one f32 add per channel to the shader's value, ahead of the product with the throughput.
 // le: that radiance, for shadow_hit's ambient part.  Returns whether the surface emits (count_glow_hits).
@@ -466,8 +503,6 @@ RWR_DEV float mis_bounce_g(const FrameParams &p, const WfGlow &gl, const ShadeRe
     const float kc = s2 / (1.0f + cmax);
     return 2.0f * Lf * kc * nd;
 }
-// whether a ray record's last word carries emit_next_ray's mark
-RWR_DEV bool wf_ray_marked(float w) { return (__float_as_uint(w) >> 16) != 0u; }
 
 // The trace kernels are PERSISTENT: kWfTraceGroups workgroups pull work items — (pool of the class, share of it)
 // — from a device counter until the class's live x split items are handed out.  Returns false when none are left.
@@ -515,6 +550,9 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // SHADOW: RWR_FLAG_SHADOWS — a hit adds its term's ambient part and leaves a shadow record (shadow_hit); separate instantiations,
 // so that frames without the flag keep their kernels.
 // SKY: RWR_FLAG_SKY — a ray that hits nothing adds the sky's term (add_sky); separate instantiations for the same reason.
+// LSKY: RWR_FLAG_LIGHT_SKY — of the IMG x GLOW forms alone: the miss of a marked ray is silenced or weighted (add_sky_image_lit);
+// separate instantiations, so that the IMG forms without the flag keep their instructions and registers: behind a run-time switch
+// thirteen packet forms spilled vector registers their parents did not (profiles/sky_light_kernel_resources.txt).
 // IMG: RWR_FLAG_SKY_IMAGE — of the SKY forms alone: the sky's term comes from the context's image (add_sky_image); separate
 // instantiations for the same reason, and so that the SKY forms under the gradient keep their registers (profiles/sky_image_kernel_resources.txt).
 // MIRROR: RWR_FLAG_MIRRORS — of the EMIT forms alone: a hit on a mirror surface sends the reflected ray on, with T * R
@@ -526,7 +564,7 @@ RWR_DEV bool next_item(TraceShared &sh, const PoolInfo *__restrict__ info, uint3
 // counted; of the forms that end a path as of the EMIT forms; separate instantiations for the same reason.
 // Which combinations exist, and how launch_wf_bounce picks one: LaneForms and PacketForms below, behind the kernels.
 template <bool NODES_IN_LDS, bool NMAP, bool STACK16, bool WIDE = false, bool EMIT = false, bool SHADOW = false, bool SKY = false,
-          int SURF = kSurfNone, bool GLOW = false, bool IMG = false>
+          int SURF = kSurfNone, bool GLOW = false, bool IMG = false, bool LSKY = false>
 __global__ void __launch_bounds__(WIDE ? 1024 : 256)
 k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                 const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
@@ -535,6 +573,7 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
 {
     static_assert(EMIT || SURF == kSurfNone, "only a kernel that emits rays has a MIRROR or a glass form");
     static_assert(SKY || !IMG, "the sky's image is a form of the SKY forms");
+    static_assert(!LSKY || (IMG && GLOW), "light rays towards the sky's image: a form of the IMG x GLOW forms");
     constexpr bool MIRROR = SURF != kSurfNone;
     __shared__ TraceShared sh;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
@@ -597,6 +636,7 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
             }
             uint32_t event = kEventNone;   // glass and glossy forms: what a counted hit did
             bool lit = false;              // GLOW forms: the hit's surface emits
+            bool quiet = false;            // LSKY forms: a marked ray's miss, silenced or weighted (RWR_FLAG_LIGHT_SKY)
             if (have) {
                 float gp = 0.0f;   // GLOW forms under RWR_FLAG_LIGHT_MIS: a marked ray's g'
                 if constexpr (GLOW)
@@ -618,11 +658,13 @@ k_wf_trace_lane(const FrameParams p, const TriRecord *__restrict__ tris, const S
                 if (EMIT && MIRROR) event = emit_from_surface<SURF>(p, wf, em, sf, tris, shade, tile, e, O, D, obj, best_t, mh.ndotd, thr, s1.albedo);
                 }
             } else if (SKY) {
-                if constexpr (IMG) add_sky_image(sh, si, e, D, thr);
+                if constexpr (LSKY) add_sky_image_lit(sh, si, gl, e, D, thr, b.w, pool_base, quiet);
+                else if constexpr (IMG) add_sky_image(sh, si, e, D, thr);
                 else add_sky(sh, sky, e, D.y, thr);
             }
             if (SURF == kSurfGlass || SURF == kSurfGloss) count_surface_events<SURF == kSurfGloss>(sf.events, event);
             if (GLOW) count_glow_hits(gl.hits, lit);
+            if constexpr (LSKY) count_sky_suppressed(gl, quiet);
             if (EMIT) {   // rays written for the next generation (lanes past the pool's end have left the iteration)
                 const unsigned long long em = __ballot(have);
                 if (em && (tid & 63u) == (uint32_t)__builtin_ctzll(em)) atomicAdd(&wf.wave_total[tile * 4u], (uint32_t)__popcll(em));
@@ -717,7 +759,7 @@ RWR_DEV i2 sphere_pair_intersect_t(f3 center, float radius, v3 O, v3 D, f2 &t_ou
 #ifndef RWR_GLOSS_SKY_PACKET_OCC
 #define RWR_GLOSS_SKY_PACKET_OCC 3
 #endif
-template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false, int SURF = kSurfNone, bool GLOW = false, bool IMG = false>   // EMIT, SHADOW, SKY, SURF, GLOW, IMG: see k_wf_trace_lane
+template <bool NMAP, bool EMIT = false, bool SHADOW = false, bool SKY = false, int SURF = kSurfNone, bool GLOW = false, bool IMG = false, bool LSKY = false>   // EMIT, SHADOW, SKY, SURF, GLOW, IMG, LSKY: see k_wf_trace_lane
 __global__ void __launch_bounds__(256, (SURF == kSurfGloss && SKY && !SHADOW) ? RWR_GLOSS_SKY_PACKET_OCC : RWR_PACKET_OCC)
 k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const ShadeRec *__restrict__ shade,
                   const BvhDevice bvh, const float4 *__restrict__ tex, const WfBuffers wf, const PoolInfo *__restrict__ info,
@@ -726,6 +768,7 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
 {
     static_assert(EMIT || SURF == kSurfNone, "only a kernel that emits rays has a MIRROR or a glass form");
     static_assert(SKY || !IMG, "the sky's image is a form of the SKY forms");
+    static_assert(!LSKY || (IMG && GLOW), "light rays towards the sky's image: a form of the IMG x GLOW forms");
     constexpr bool MIRROR = SURF != kSurfNone;
     __shared__ TraceShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -892,7 +935,12 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
         // (glossy forms: the sky's terms first — integer sums, any order gives the same bytes — so that the packet's ray numbers and a
         // missed ray's throughput are dead while the hits' next rays are made: the registers the disk loop and the rule need)
         if (SKY && SURF == kSurfGloss) {
-            if constexpr (IMG) {
+            if constexpr (LSKY) {
+                bool q0 = false, q1 = false;
+                if (i0 < last && !have.x) add_sky_image_lit(sh, si, gl, e0, lane3(R.D, 0), mk3(thr.x.x, thr.y.x, thr.z.x), b0.w, pool_base, q0);
+                if (i1 < last && !have.y) add_sky_image_lit(sh, si, gl, e1, lane3(R.D, 1), mk3(thr.x.y, thr.y.y, thr.z.y), b1.w, pool_base, q1);
+                count_sky_suppressed(gl, q0, q1);
+            } else if constexpr (IMG) {
                 if (i0 < last && !have.x) add_sky_image(sh, si, e0, lane3(R.D, 0), mk3(thr.x.x, thr.y.x, thr.z.x));
                 if (i1 < last && !have.y) add_sky_image(sh, si, e1, lane3(R.D, 1), mk3(thr.x.y, thr.y.y, thr.z.y));
             } else {
@@ -997,7 +1045,12 @@ k_wf_trace_packet(const FrameParams p, const TriRecord *__restrict__ tris, const
             }
         }
         if (SKY && SURF != kSurfGloss) {   // per ray, not per wave: every ray of the packet (not the padding of its last lanes: i0, i1 < last) that found nothing
-            if constexpr (IMG) {
+            if constexpr (LSKY) {
+                bool q0 = false, q1 = false;
+                if (i0 < last && !have.x) add_sky_image_lit(sh, si, gl, e0, lane3(R.D, 0), mk3(thr.x.x, thr.y.x, thr.z.x), b0.w, pool_base, q0);
+                if (i1 < last && !have.y) add_sky_image_lit(sh, si, gl, e1, lane3(R.D, 1), mk3(thr.x.y, thr.y.y, thr.z.y), b1.w, pool_base, q1);
+                count_sky_suppressed(gl, q0, q1);
+            } else if constexpr (IMG) {
                 if (i0 < last && !have.x) add_sky_image(sh, si, e0, lane3(R.D, 0), mk3(thr.x.x, thr.y.x, thr.z.x));
                 if (i1 < last && !have.y) add_sky_image(sh, si, e1, lane3(R.D, 1), mk3(thr.x.y, thr.y.y, thr.z.y));
             } else {
@@ -1022,51 +1075,55 @@ struct SortForms {
     template <uint32_t I> static constexpr Kernel kernel() { return &k_wf_sort<decode(I).list>; }
 };
 struct PacketForms {
-    struct Form { bool nmap, emit, shadow, sky; int surf; bool glow, img; };
-    static constexpr uint32_t kRange = 16u * 4u * 2u * 2u;
-    static constexpr uint32_t encode(Form f) { return f.nmap + 2u * f.emit + 4u * f.shadow + 8u * f.sky + 16u * (uint32_t)f.surf + 64u * f.glow + 128u * f.img; }
+    struct Form { bool nmap, emit, shadow, sky; int surf; bool glow, img, lsky; };
+    static constexpr uint32_t kRange = 16u * 4u * 2u * 2u * 2u;
+    static constexpr uint32_t encode(Form f) { return f.nmap + 2u * f.emit + 4u * f.shadow + 8u * f.sky + 16u * (uint32_t)f.surf + 64u * f.glow + 128u * f.img + 256u * f.lsky; }
     static constexpr Form decode(uint32_t i)
     {
-        return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (int)((i >> 4) & 3u), (i & 64u) != 0, (i & 128u) != 0};
+        return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (int)((i >> 4) & 3u), (i & 64u) != 0, (i & 128u) != 0, (i & 256u) != 0};
     }
-    static constexpr bool valid(Form f) { return (f.emit || f.surf == kSurfNone) && (f.sky || !f.img); }
+    static constexpr bool valid(Form f) { return (f.emit || f.surf == kSurfNone) && (f.sky || !f.img) && (!f.lsky || (f.img && f.glow)); }
     using Kernel = decltype(&k_wf_trace_packet<false>);
     template <uint32_t I> static constexpr Kernel kernel()
     {
         constexpr Form f = decode(I);
-        return &k_wf_trace_packet<f.nmap, f.emit, f.shadow, f.sky, f.surf, f.glow, f.img>;
+        return &k_wf_trace_packet<f.nmap, f.emit, f.shadow, f.sky, f.surf, f.glow, f.img, f.lsky>;
     }
 };
 // WIDE — 1 024 threads around one copy of the nodelets — only with the nodelets in LDS, 16-bit stacks and no normal map (LaneLdsPlan)
 struct LaneForms {
-    struct Form { bool nodes_in_lds, nmap, stack16, wide, emit, shadow, sky; int surf; bool glow, img; };
-    static constexpr uint32_t kRange = 128u * 4u * 2u * 2u;
+    struct Form { bool nodes_in_lds, nmap, stack16, wide, emit, shadow, sky; int surf; bool glow, img, lsky; };
+    static constexpr uint32_t kRange = 128u * 4u * 2u * 2u * 2u;
     static constexpr uint32_t encode(Form f)
     {
         return f.nodes_in_lds + 2u * f.nmap + 4u * f.stack16 + 8u * f.wide + 16u * f.emit + 32u * f.shadow + 64u * f.sky + 128u * (uint32_t)f.surf +
-               512u * f.glow + 1024u * f.img;
+               512u * f.glow + 1024u * f.img + 2048u * f.lsky;
     }
     static constexpr Form decode(uint32_t i)
     {
         return Form{(i & 1u) != 0, (i & 2u) != 0, (i & 4u) != 0, (i & 8u) != 0, (i & 16u) != 0, (i & 32u) != 0, (i & 64u) != 0, (int)((i >> 7) & 3u),
-                    (i & 512u) != 0, (i & 1024u) != 0};
+                    (i & 512u) != 0, (i & 1024u) != 0, (i & 2048u) != 0};
     }
-    static constexpr bool valid(Form f) { return (f.emit || f.surf == kSurfNone) && (f.sky || !f.img) && (!f.wide || (f.nodes_in_lds && !f.nmap && f.stack16)); }
+    static constexpr bool valid(Form f)
+    {
+        return (f.emit || f.surf == kSurfNone) && (f.sky || !f.img) && (!f.lsky || (f.img && f.glow)) && (!f.wide || (f.nodes_in_lds && !f.nmap && f.stack16));
+    }
     static constexpr bool is_wide(Form f) { return f.wide; }
     using Kernel = decltype(&k_wf_trace_lane<false, false, false>);
     template <uint32_t I> static constexpr Kernel kernel()
     {
         constexpr Form f = decode(I);
-        return &k_wf_trace_lane<f.nodes_in_lds, f.nmap, f.stack16, f.wide, f.emit, f.shadow, f.sky, f.surf, f.glow, f.img>;
+        return &k_wf_trace_lane<f.nodes_in_lds, f.nmap, f.stack16, f.wide, f.emit, f.shadow, f.sky, f.surf, f.glow, f.img, f.lsky>;
     }
 };
 static constexpr auto kSortForms = form_table<SortForms>();
 static constexpr auto kPacketForms = form_table<PacketForms>();
 static constexpr auto kLaneForms = form_table<LaneForms>();
 // (GLOW goes with every form and adds no condition to valid(): the rule is stated beside PrimaryForms, kernels_wf_primary.hip)
-static_assert(check_forms<SortForms>(2) && check_forms<PacketForms>(120), "packets: NMAP x (4 path-ending + 16 EMIT forms), with and without GLOW; the SKY half again with IMG");
-static_assert(check_forms<LaneForms>(540) && count_forms<LaneForms>(LaneForms::is_wide) == 60,
-              "per lane: 8 x 20 with 256 threads, 20 wide, with and without GLOW; the SKY half again with IMG");
+static_assert(check_forms<SortForms>(2) && check_forms<PacketForms>(140),
+              "packets: NMAP x (4 path-ending + 16 EMIT forms), with and without GLOW; the SKY half again with IMG; the IMG x GLOW forms again with LSKY");
+static_assert(check_forms<LaneForms>(630) && count_forms<LaneForms>(LaneForms::is_wide) == 70,
+              "per lane: 8 x 20 with 256 threads, 20 wide, with and without GLOW; the SKY half again with IMG; the IMG x GLOW forms again with LSKY");
 
 // RWR_WF_STATS=1 (wf.dbg set): launches of the packet kernel, the per-lane kernel and its WIDE form, by this process
 static std::atomic<uint64_t> g_trace_launches[3];
@@ -1093,13 +1150,14 @@ hipError_t launch_wf_bounce(hipStream_t s, const FrameParams &fp, const TriRecor
     const bool nmap = (fp.flags & RWR_FLAG_NORMAL_MAP) != 0;
     const int surf = ft.trace_surf();
     const bool img = ft.sky_on && ft.sky_image.image != nullptr;   // RWR_FLAG_SKY_IMAGE in effect: the IMG forms
+    const bool lsky = img && ft.glows && (ft.glow.light & 8u) != 0u;   // RWR_FLAG_LIGHT_SKY in effect: their LSKY forms
     if (packets) {
         if (wf.dbg) g_trace_launches[0].fetch_add(1u, std::memory_order_relaxed);
-        hipLaunchKernelGGL(kPacketForms[PacketForms::encode({nmap, ft.emits, ft.shadows, ft.sky_on, surf, ft.glows, img})], dim3(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit)),
+        hipLaunchKernelGGL(kPacketForms[PacketForms::encode({nmap, ft.emits, ft.shadows, ft.sky_on, surf, ft.glows, img, lsky})], dim3(std::min(kWfTraceGroups, n_tiles * kWfMaxSplit)),
                            dim3(256), 0, s, fp, tris, shade, bvh, tex, wf, info, counters, pool_list, n_tiles, ft.emit, ft.shadow, ft.sky, ft.surfaces, ft.glow, ft.sky_image);
     }
     const LaneLdsPlan l = lane_lds_plan(bvh, fp, bvh.wide_lane && !nmap);
-    const uint32_t form = LaneForms::encode({l.nodes_in_lds, nmap, l.stack16, l.wide, ft.emits, ft.shadows, ft.sky_on, surf, ft.glows, img});
+    const uint32_t form = LaneForms::encode({l.nodes_in_lds, nmap, l.stack16, l.wide, ft.emits, ft.shadows, ft.sky_on, surf, ft.glows, img, lsky});
     if (wf.dbg) g_trace_launches[l.wide ? 2 : 1].fetch_add(1u, std::memory_order_relaxed);
     if (plan) *plan = LanePlanRecord{plan->launches + 1u, l.nodes_in_lds, l.stack16, l.wide};
     if (l.wide) {   // (at most 146 KiB: beyond the default limit, raised per form)

@@ -213,10 +213,13 @@ int WfFrame::surface_table()
 // count of emitting hits, from zero.
 int WfFrame::glow_table()
 {
-    ft.glows = rq.glow;
-    if (!rq.glow) return RWR_OK;
+    // (RWR_FLAG_LIGHT_SKY without RWR_FLAG_EMISSIVE in effect: the GLOW forms — they carry the marks, the normals and the ballots —
+    // over a table that emits nothing)
+    ft.glows = rq.glow || rq.light_sky;
+    if (!ft.glows) return RWR_OK;
+    const bool dark = !rq.glow;
     const size_t n_parts = ctx->part_glow.size(), n_recs = n_parts + RWR_MAX_SPHERES;
-    if (W.glow_version != ctx->glow_version || W.d_glow.count < n_recs) {
+    if (W.glow_version != ctx->glow_version || W.glow_dark != dark || W.d_glow.count < n_recs) {
         if (W.glow_version != 0u) RWR_HIP_CHECK(hipEventSynchronize(W.glow_copied));   // the image's last copy has been read
         if (W.h_glow_count < n_recs) {
             W.h_glow = PinnedSurface();
@@ -232,27 +235,31 @@ int WfFrame::glow_table()
             if (i < ctx->part_inv_pdf.size()) W.h_glow.h[i].on = ctx->part_inv_pdf[i];
         }
         for (size_t i = 0; i < RWR_MAX_SPHERES; i++) W.h_glow.h[n_parts + i] = ctx->sphere_glow[i];
+        if (dark)
+            for (size_t i = 0; i < n_recs; i++) W.h_glow.h[i] = SurfaceRec{0.0f, 0.0f, 0.0f, 0.0f};
         RWR_HIP_CHECK(hipMemcpyAsync(W.d_glow.ptr, W.h_glow.h, n_recs * sizeof(SurfaceRec), hipMemcpyHostToDevice, stream));
         RWR_HIP_CHECK(hipEventRecord(W.glow_copied, stream));
         W.glow_version = ctx->glow_version;
+        W.glow_dark = dark;
     }
     RWR_HIP_CHECK(W.d_glow_hits.ensure(1));
     RWR_HIP_CHECK(hipMemsetAsync(W.d_glow_hits.ptr, 0, sizeof(unsigned long long), stream));
     ft.glow = WfGlow{W.d_glow.ptr, (uint32_t)n_parts, 0u, W.d_glow_hits.ptr, nullptr, nullptr, nullptr};
     // RWR_FLAG_LIGHT_SAMPLING, RWR_FLAG_LIGHT_PARTS: a normal per queue slot and the light ballots, per queue like the rays and kept like
-    // them (allocated by the first frame that needs them); the frame's six counts start from zero.  trace_groups points ft.glow at a
+    // them (allocated by the first frame that needs them); the frame's nine counts start from zero.  trace_groups points ft.glow at a
     // queue's share.  glow.light: 1 the spheres, 2 the mesh light (validate made its list and device copy current), 4
-    // RWR_FLAG_LIGHT_MIS (mask values, as rwr_surface.h states them), bits 8-15 L, the lights the stage chooses among.
-    ft.lights_on = rq.light || rq.light_parts;
+    // RWR_FLAG_LIGHT_MIS, 8 RWR_FLAG_LIGHT_SKY (mask values, as rwr_surface.h states them), bits 8-15 L, the lights the stage chooses among.
+    ft.lights_on = rq.light || rq.light_parts || rq.light_sky;
     if (ft.lights_on) {
         if (rq.light) ft.lights = scene_lights(ctx);
         if (rq.light_parts)
             ft.part_lights = WfPartLights{ctx->d_part_lights.ptr, ctx->d_shade.ptr, (uint32_t)ctx->part_lights.size(), ft.lights.m + 1u};
         RWR_HIP_CHECK(W.d_light_recs.ensure(n_queues * slots));
         RWR_HIP_CHECK(W.d_light_masks.ensure(n_queues * n_tiles * group * 8u));
-        RWR_HIP_CHECK(W.d_light_counts.ensure(6));
-        RWR_HIP_CHECK(hipMemsetAsync(W.d_light_counts.ptr, 0, 6 * sizeof(unsigned long long), stream));
-        ft.glow.light = (rq.light ? 1u : 0u) | (rq.light_parts ? 2u : 0u) | (rq.light_mis ? 4u : 0u) | ((ft.lights.m + (rq.light_parts ? 1u : 0u)) << 8);
+        RWR_HIP_CHECK(W.d_light_counts.ensure(9));
+        RWR_HIP_CHECK(hipMemsetAsync(W.d_light_counts.ptr, 0, 9 * sizeof(unsigned long long), stream));
+        ft.glow.light = (rq.light ? 1u : 0u) | (rq.light_parts ? 2u : 0u) | (rq.light_mis ? 4u : 0u) | (rq.light_sky ? 8u : 0u) |
+                        ((ft.lights.m + (rq.light_parts ? 1u : 0u) + (rq.light_sky ? 1u : 0u)) << 8);
         ft.glow.light_counts = W.d_light_counts.ptr;
     }
     return RWR_OK;
@@ -282,7 +289,8 @@ int WfFrame::trace_groups(const AccumPlan &ap)
     ft.sky_on = rq.sky;
     // (the slot lets go of the image of its last frame, whose kernels ran ahead of this frame's on the slot's stream, and holds on to this one's)
     W.sky_image = rq.sky_image ? ctx->sky_image : nullptr;
-    ft.sky_image = rq.sky_image ? WfSkyImage{W.sky_image->ptr, ctx->sky_image_n, 0u} : WfSkyImage{nullptr, 0u, 0u};
+    W.sky_light = rq.light_sky ? ctx->sky_light : nullptr;   // (validate made it current; held as the image is)
+    ft.sky_image = rq.sky_image ? WfSkyImage{W.sky_image->ptr, ctx->sky_image_n, 0u, W.sky_light ? W.sky_light->ptr : nullptr} : WfSkyImage{nullptr, 0u, 0u, nullptr};
     ft.soft = rq.soft;
     const rwr_shadow_params *soft = ft.soft ? &ctx->shadow : nullptr;
     // (global sample indices: an accumulating frame traces [accum_before, accum_before + spp), keyed like one frame of them all)
@@ -303,7 +311,7 @@ int WfFrame::trace_groups(const AccumPlan &ap)
             RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere, 0u,
                                            (uint32_t)ap.before + s0, soft, &shadow_plan));
         if (ft.lights_on)   // h0's light samples: ray 1 sits in the queue, the first sort has not run
-            RWR_HIP_CHECK(launch_wf_light(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.glow, ft.lights, ft.part_lights, n_tiles, shadow_tiles, cnt, 0u, (uint32_t)ap.before + s0));
+            RWR_HIP_CHECK(launch_wf_light(gs, fp, ctx->d_tris.ptr, bvh, wfq[q], ft.glow, ft.lights, ft.part_lights, ft.sky_image, n_tiles, shadow_tiles, cnt, 0u, (uint32_t)ap.before + s0));
         // the bounce stage: one generation of rays per bounce (RWR_FLAG_MULTI_BOUNCE: up to RWR_MAX_BOUNCES).  Generation k traces
         // ray k of every path that is still alive — the sort and trace kernels run again over the same fixed slots — and, unless
         // it is the last, writes ray k + 1 back into the slot of every hit, with its bit in the other ballot array.
@@ -325,7 +333,7 @@ int WfFrame::trace_groups(const AccumPlan &ap)
                 RWR_HIP_CHECK(launch_wf_shadow(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.shadow, n_tiles, shadow_tiles, cnt, light_mesh, light_sphere, gen,
                                                (uint32_t)ap.before + s0, soft, &shadow_plan));
             if (ft.lights_on && emit)   // the light samples of this generation's hits, from the rays it just wrote, ahead of the next sort
-                RWR_HIP_CHECK(launch_wf_light(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.glow, ft.lights, ft.part_lights, n_tiles, shadow_tiles, cnt, gen, (uint32_t)ap.before + s0));
+                RWR_HIP_CHECK(launch_wf_light(gs, fp, ctx->d_tris.ptr, bvh, wg, ft.glow, ft.lights, ft.part_lights, ft.sky_image, n_tiles, shadow_tiles, cnt, gen, (uint32_t)ap.before + s0));
             if (emit) std::swap(wg.masks, masks_next);
         }
         if (rp.max_bounces && s0 + group >= rp.spp) last_counters = wfq[q].counters;

@@ -166,14 +166,16 @@ struct WfState {
     size_t h_glow_count = 0;
     OwnedEvent glow_copied;
     uint64_t glow_version = 0;
+    bool glow_dark = false;   // the copy holds zeros: a frame that runs the GLOW forms for RWR_FLAG_LIGHT_SKY without RWR_FLAG_EMISSIVE in effect
     DeviceBuffer<unsigned long long> d_glow_hits;
     // RWR_FLAG_LIGHT_SAMPLING, allocated by the first frame that samples its lights: per ray queue a 16-byte record per slot (the
-    // hit's normal, WfGlow::light_recs) and the light ballots (layout of d_masks), kept like the queues; the frame's six counts
-    // {light rays, reached, silenced hits} and the mesh light's share of each (WfGlow::light_counts), zeroed per frame
+    // hit's normal, WfGlow::light_recs) and the light ballots (layout of d_masks), kept like the queues; the frame's nine counts
+    // {light rays, reached, silenced hits}, the mesh light's share of each and the sky's (WfGlow::light_counts), zeroed per frame
     DeviceBuffer<LightRec> d_light_recs;
     DeviceBuffer<unsigned long long> d_light_masks;
     DeviceBuffer<unsigned long long> d_light_counts;
     std::shared_ptr<DeviceBuffer<float4>> sky_image;   // RWR_FLAG_SKY_IMAGE: the image this slot's last frame under the flag reads, kept until the slot's next
+    std::shared_ptr<DeviceBuffer<float>> sky_light;    // RWR_FLAG_LIGHT_SKY: likewise the image's sampling table (rwr_sky_light.h)
 };
 
 // Progressive accumulation (RWR_FLAG_ACCUMULATE): ONE accumulation per context.  Its sums and the first frame's sample-0 planes
@@ -321,6 +323,12 @@ struct rwr_context {
     std::shared_ptr<rwr::DeviceBuffer<float4>> sky_image;
     uint32_t sky_image_n = 0;
     uint64_t sky_image_generation = 0;
+    // RWR_FLAG_LIGHT_SKY: the image's texels as the host handed them over (kept: the table is built lazily, by the first frame that asks
+    // for the flag after the image changed — scene_sky_light), the table's device copy (null: none, or W = 0) and the image
+    // generation it was built for (0: never)
+    std::vector<float4> sky_image_host;
+    std::shared_ptr<rwr::DeviceBuffer<float>> sky_light;
+    uint64_t sky_light_generation = 0;
     rwr_shadow_params shadow = rwr::kShadowDefaults;      // RWR_FLAG_SOFT_SHADOWS (rwr_shadow_set_params)
     uint64_t scene_generation = 0;         // bumped by every change of the scene (an accumulation does not survive one)
     // one decoded texture per scene part (texels decoded to linear f32 at upload, Rgba8UnormSrgb semantics)
@@ -371,7 +379,7 @@ struct rwr_context {
     bool last_shadows = false;      // the last render call traced shadow rays (RWR_FLAG_SHADOWS): their counters are in its WfState
     bool last_gloss = false;        // the last render call ran the glossy forms (RWR_FLAG_GLOSSY): their counter is d_surface_events[kEventGlossy]
     bool last_glass = false;        // the last render call ran the glass forms (RWR_FLAG_GLASS): their counters are in its WfState
-    bool last_light = false;        // the last render call sampled its lights (RWR_FLAG_LIGHT_SAMPLING, RWR_FLAG_LIGHT_PARTS): the counts are its WfState's d_light_counts
+    bool last_light = false;        // the last render call sampled its lights (RWR_FLAG_LIGHT_SAMPLING, RWR_FLAG_LIGHT_PARTS, RWR_FLAG_LIGHT_SKY): the counts are its WfState's d_light_counts
     bool last_glow = false;         // the last render call ran the GLOW forms (RWR_FLAG_EMISSIVE): their counter is its WfState's d_glow_hits
     // optional per-kernel timing (rwr_ctx_set_kernel_timing)
     uint32_t timing_every = 0;
@@ -443,6 +451,9 @@ inline WfLights scene_lights(const rwr_context *ctx) { return ctx->lights; }
 // scene.cpp: the mesh light's length, after rebuilding and uploading the list if the scene changed it (RWR_FLAG_LIGHT_PARTS item 1);
 // waits for the frames in flight only when it has to upload.  Called for frames that ask for the flag, so no other frame pays.
 int scene_part_lights(rwr_context *ctx, uint32_t &n);
+// context.cpp: whether the sky's image has a sampling table (RWR_FLAG_LIGHT_SKY item 1: an image, and W > 0), after building and
+// uploading it if the image changed since the last one was built.  Called for frames that ask for the flag, so no other frame pays.
+int scene_sky_light(rwr_context *ctx, bool &have);
 
 // context.cpp: per-frame buffers of every active slot for the current scene and screen
 hipError_t ensure_frame_buffers(rwr_context *ctx);

@@ -281,6 +281,53 @@ RWR_DEV f3 sky_image_radiance(const float4 *__restrict__ image, uint32_t n, f3 D
     return tex_sample_bilinear(image, n * 16u, fn - 1.0f, fn - 1.0f, f2{uv.x * fn - 0.5f, uv.y * fn - 0.5f});
 }
 
+// RWR_FLAG_LIGHT_SKY (rwr_sky_light.h: the table — n floats of the row cdf, then n per row of the conditional cdfs).
+// Item 3, for both sides: the factor g = p_b / p_l of the unit direction w with n . w = ndw among Lf lights — w mapped forward
+// with S_img's own operations, its texel (ti, tj), the texel's probability P from the two cdfs (the entry before index 0 is 0).
+// The caller takes no sample where !(P > 0) or !(ndw > 0).
+RWR_DEV float sky_light_g(const float *__restrict__ table, uint32_t n, f3 w, float ndw, float Lf, uint32_t &ti, uint32_t &tj, float &P)
+{
+    const float a = (fabsf(w.x) + fabsf(w.y)) + fabsf(w.z);
+    const f2 uv = sky_image_uv(w);
+    const float fn = (float)n;
+    ti = min((uint32_t)(uv.x * fn), n - 1u);   // (the conversion saturates: a NaN or negative coordinate takes texel 0)
+    tj = min((uint32_t)(uv.y * fn), n - 1u);
+    const float *__restrict__ C = table + n + (size_t)tj * n;
+    const float r1 = table[tj], r0 = tj ? table[tj - 1u] : 0.0f;
+    const float c1 = C[ti], c0 = ti ? C[ti - 1u] : 0.0f;
+    P = (r1 - r0) * (c1 - c0);
+    return (((Lf * ndw) * 0.318309886f) * (4.0f * ((a * a) * a))) / ((fn * fn) * P);
+}
+// Item 2, the sky lane's draw from four uniforms: row tj, the first entry with u.x < R_j; column ti, the first with u.y < C_ji (binary
+// searches: the last entry of either cdf is 1 > u, so they end inside it); the point (ti + u.z, tj + u.w) / n of the square; the
+// inverse of S_img's mapping; the unit direction by three divisions.  `on`: a lane that draws (the others search nothing).
+RWR_DEV f3 sky_light_draw(const float *__restrict__ table, uint32_t n, float u0, float u1, float u2, float u3, bool on, uint32_t &ti, uint32_t &tj)
+{
+    uint32_t lo = 0u, hi = on ? n - 1u : 0u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (u0 < table[mid]) hi = mid; else lo = mid + 1u;
+    }
+    tj = lo;
+    const float *__restrict__ C = table + n + (size_t)tj * n;
+    lo = 0u; hi = on ? n - 1u : 0u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (u1 < C[mid]) hi = mid; else lo = mid + 1u;
+    }
+    ti = lo;
+    const float fn = (float)n;
+    const float u = ((float)ti + u2) / fn, v = ((float)tj + u3) / fn;
+    float px = 2.0f * u - 1.0f, pz = 2.0f * v - 1.0f;
+    const float py = (1.0f - fabsf(px)) - fabsf(pz);
+    if (py < 0.0f) {
+        const float qx = (1.0f - fabsf(pz)) * copysignf(1.0f, px), qz = (1.0f - fabsf(px)) * copysignf(1.0f, pz);
+        px = qx; pz = qz;
+    }
+    const float len = sqrtf((px * px + py * py) + pz * pz);
+    return mk3(px / len, py / len, pz / len);
+}
+
 // The same fetch and filter from the quad form of the texture (rwr_internal.h QuadTex): the 2x2 footprint is the one
 // record at p = (med3(f0.x, -1, wmax) + 1, med3(f0.y, -1, hmax) + 1), f0 = floor(fxy), which holds exactly the taps
 // tex_taps picks (a NaN position: v_med3 returns one of its finite operands, so p stays inside the (w+1) x (h+1) grid).

@@ -23,6 +23,7 @@ struct FrameRequest {
     bool light_parts; // RWR_FLAG_LIGHT_PARTS with RWR_FLAG_EMISSIVE effective, a bounce and a mesh light that is not empty: k_wf_light's PARTS forms (else the bit is cleared from rp.flags)
     bool light_mis;   // RWR_FLAG_LIGHT_MIS with one of the two light flags effective: the light stage and add_glow weight their values (else the bit is cleared from rp.flags)
     bool sky_image;   // RWR_FLAG_SKY_IMAGE with RWR_FLAG_SKY in effect and an image in the context: add_sky fetches S(D) from it (else the bit is cleared from rp.flags)
+    bool light_sky;   // RWR_FLAG_LIGHT_SKY with RWR_FLAG_SKY_IMAGE in effect and an image with weight: k_wf_light's SKY forms, and the GLOW forms whatever rq.glow says (else the bit is cleared from rp.flags)
     bool sobol;       // RWR_FLAG_SOBOL in a frame the wavefront integrator renders: its kernels read the bit in FrameParams::flags, beside the seed (else the bit is cleared from rp.flags)
     bool wavefront;   // the wavefront integrator renders it (several samples, a bounce, or an accumulation)
     bool dormant;     // the reference's dormant parts (single-triangle passes, orthographic rays) have their own plain kernel

@@ -366,10 +366,14 @@ static_assert(sizeof(WfSky) == sizeof(rwr_sky_params), "WfSky is rwr_sky_params"
 // The sky's image (RWR_FLAG_SKY_IMAGE; the IMG forms of the trace kernels' SKY forms, add_sky_image): the context's octahedral map,
 // n x n float4 texels, and n; image == nullptr: the gradient of WfSky, the SKY forms without IMG.  A kernel argument of its own
 // behind all others (cf. WfEmit): no other form reads it, and all of them keep their instructions.
+// table: RWR_FLAG_LIGHT_SKY in effect — the image's sampling distribution (rwr_sky_light.h), read by k_wf_light's SKY forms and, behind
+// WfGlow::light & 8, at the miss sites of the trace kernels' IMG x GLOW forms; null otherwise.  (The last member of the last
+// argument: no other argument moves.)
 struct WfSkyImage {
     const float4 *image;
     uint32_t n;
     uint32_t pad;
+    const float *table;
 };
 // The mesh light (RWR_FLAG_LIGHT_PARTS; rwr_part_lights.h): the face list, its length, the frame's shading records (a listed face's
 // part is ShadeRec::material, its radiance that part's record of WfGlow::table) and L = M + 1, the lights the stage chooses among.
@@ -387,13 +391,13 @@ struct WfFeatures {
     WfEmit emit{nullptr, 0u, 0u};
     WfShadow shadow{nullptr, nullptr, nullptr};
     WfSky sky{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    WfSkyImage sky_image{nullptr, 0u, 0u};   // RWR_FLAG_SKY_IMAGE in effect: the image the IMG forms fetch S(D) from (else null: the gradient)
+    WfSkyImage sky_image{nullptr, 0u, 0u, nullptr};   // RWR_FLAG_SKY_IMAGE in effect: the image the IMG forms fetch S(D) from (else null: the gradient)
     WfSurfaces surfaces{nullptr, 0u, 0u, nullptr};   // rwr_surface.h
     WfGlow glow{nullptr, 0u, 0u, nullptr, nullptr, nullptr, nullptr};   // rwr_surface.h
     bool emits = false, shadows = false, sky_on = false;
     bool glows = false;   // RWR_FLAG_EMISSIVE with an emitter in the scene: the GLOW forms of all three kernels, which read `glow`
     bool soft = false;   // RWR_FLAG_SOFT_SHADOWS: k_wf_shadow's SOFT forms (no other kernel looks)
-    bool lights_on = false;   // RWR_FLAG_LIGHT_SAMPLING or RWR_FLAG_LIGHT_PARTS: glow.light is set, k_wf_light runs (kernels_wf_light.hip) with `lights`
+    bool lights_on = false;   // RWR_FLAG_LIGHT_SAMPLING, RWR_FLAG_LIGHT_PARTS or RWR_FLAG_LIGHT_SKY: glow.light is set, k_wf_light runs (kernels_wf_light.hip) with `lights`
     WfLights lights{};        // rwr_surface.h (m = 0 while RWR_FLAG_LIGHT_SAMPLING is not effective)
     WfPartLights part_lights{nullptr, nullptr, 0u, 0u};   // RWR_FLAG_LIGHT_PARTS: the mesh light (n = 0 while the flag is not effective: the forms without PARTS)
     int surf = kSurfNone;   // the surface models of the frame's flags (kSurfGlass: the table may hold glass records; kSurfGloss: glossy ones too)
@@ -472,10 +476,11 @@ hipError_t launch_wf_shadow(hipStream_t s, const FrameParams &fp, const TriRecor
                             LanePlanRecord *plan = nullptr);
 // kernels_wf_light.hip (RWR_FLAG_LIGHT_SAMPLING, RWR_FLAG_LIGHT_PARTS): the light samples of the hits whose diffuse rays generation
 // `gen` emitted (0: the primary stage), from glow's records and ballots, added to wf's sums; the rays traced and reached into
-// glow.light_counts.  parts.n != 0: the PARTS forms, which aim at the mesh light too.
+// glow.light_counts.  parts.n != 0: the PARTS forms, which aim at the mesh light too.  sky.table != null (RWR_FLAG_LIGHT_SKY): the
+// SKY forms, which aim at the sky's image too.
 hipError_t launch_wf_light(hipStream_t s, const FrameParams &fp, const TriRecord *tris, const BvhDevice &bvh, const WfBuffers &wf,
-                           const WfGlow &glow, const WfLights &lights, const WfPartLights &parts, uint32_t n_tiles, uint32_t expected_tiles,
-                           uint32_t sample_count, uint32_t gen, uint32_t sample_base);
+                           const WfGlow &glow, const WfLights &lights, const WfPartLights &parts, const WfSkyImage &sky, uint32_t n_tiles,
+                           uint32_t expected_tiles, uint32_t sample_count, uint32_t gen, uint32_t sample_base);
 size_t wf_pool_info_bytes();
 // RWR_WF_STATS=1: trace launches of this process so far {packet kernel, per-lane kernel, its 1 024-thread form}
 void wf_trace_launch_counts(uint64_t out[3]);
@@ -599,6 +604,9 @@ hipError_t launch_selftest_exact_div(hipStream_t s, unsigned long long *d_out4, 
 hipError_t launch_selftest_sobol(hipStream_t s, const uint32_t *d_in, uint32_t n, uint32_t *d_out);
 // kernels_selftest.hip: d_out[3 i ...] = sky_image_radiance(si, d_dirs[3 i ...]) (RWR_FLAG_SKY_IMAGE's S_img), count directions
 hipError_t launch_selftest_sky_image(hipStream_t s, const WfSkyImage &si, const float *d_dirs, uint32_t count, float *d_out);
+// d_out[8 i ...] = {w.x, w.y, w.z, texel column, texel row (as uint32 bits), P, g, -} of sky_light_draw and sky_light_g (RWR_FLAG_LIGHT_SKY)
+// for the four uniforms d_u4[4 i ...], the normal nrm and L lights, count tuples
+hipError_t launch_selftest_sky_light(hipStream_t s, const WfSkyImage &si, const float *d_u4, uint32_t count, const float nrm[3], uint32_t n_lights, float *d_out);
 
 // kernels_selftest.hip: d_out[wave] = {shader cycles, 100 MHz ticks} around iters * 8 v_fma_f32 (mode 0) / v_pk_fma_f32 (mode 1)
 hipError_t launch_clock_probe(hipStream_t s, ulonglong2 *d_out, uint32_t ticks_100mhz);

@@ -129,6 +129,9 @@ struct WfSurfaces {
 // the hits it silenced Le m(g') in place of 0 (mis_weight below; g' from the ray, the hit and the slot's LightRec, which the hit's own
 // emit_next_ray has not overwritten yet).  Bits 8-15 hold L, the lights the stage chooses among (M + 1 with the mesh light, else M),
 // which g' needs; a part's record of `table` carries the inv_pdf of the part's listed faces in its fourth component (0: none listed).
+// A fourth bit, mask value 8 — RWR_FLAG_LIGHT_SKY is effective: the sky's image is the last of the L lights (k_wf_light's SKY forms), the
+// trace kernels run the LSKY forms, whose marked misses are silenced or weighted, and light_counts holds nine: [6], [7], [8] are the
+// sky's share of [0], [1], [2] ([8]: the suppressed misses).  The table may then hold zeros alone (no RWR_FLAG_EMISSIVE in effect).
 struct LightRec { float n[3]; uint32_t pad; };
 static_assert(sizeof(LightRec) == 16, "LightRec is 16 B");
 struct WfGlow {

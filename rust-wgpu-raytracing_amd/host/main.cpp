@@ -8,7 +8,7 @@
 //              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]...
 //              [--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]]
 //              [--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] [--sobol]
-//              [--sky-image FILE[:scale] [--sky-image-size N]] [--show-params] [--out frame.png] [--time]
+//              [--sky-image FILE[:scale] [--sky-image-size N]] [--light-sky] [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
 // (KEY in W A S D Up Down Left Right Space LShift, or '-' for no key).  After the script,
@@ -160,6 +160,7 @@ int main(int argc, char **argv)
     bool light_sampling = false;   // --light-sampling
     bool light_parts = false;      // --light-parts
     bool light_mis = false;        // --light-mis
+    bool light_sky = false;        // --light-sky
     bool sobol = false;            // --sobol
     auto parse_emitter = [](const char *text, Emitter &e) {
         char *end = nullptr;
@@ -301,6 +302,7 @@ int main(int argc, char **argv)
         else if (a == "--light-sampling") light_sampling = true;
         else if (a == "--light-parts") light_parts = true;
         else if (a == "--light-mis") light_mis = true;
+        else if (a == "--light-sky") light_sky = true;
         else if (a == "--sobol") sobol = true;
         else if (a == "--show-params") show_params = true;
         else if (a == "--resize") {
@@ -318,7 +320,7 @@ int main(int argc, char **argv)
                         "[--denoise [--denoise-iterations N] [--denoise-sigma S]] [--sky [--sky-zenith r,g,b] [--sky-horizon r,g,b]] "
                         "[--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]... "
                         "[--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... "
-                        "[--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] [--sobol] [--sky-image FILE[:scale] [--sky-image-size N]] "
+                        "[--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] [--sobol] [--sky-image FILE[:scale] [--sky-image-size N]] [--light-sky] "
                         "[--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]] "
                         "[--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
@@ -362,6 +364,10 @@ int main(int argc, char **argv)
                         "  --light-mis  the light ray and the diffuse bounce ray that finds the same emitter are combined by the balance heuristic "
                         "(RWR_FLAG_LIGHT_MIS, multiple importance sampling; implies nothing: it needs --light-sampling or --light-parts in effect to do "
                         "anything); with it both may stay on in a scene that glows all over; prints `weighted hits N` for the final frame\n"
+                        "  --light-sky   every diffuse hit's light ray may aim at the sky's image, drawn in proportion to its radiance "
+                        "(RWR_FLAG_LIGHT_SKY; implies nothing: it needs --sky-image, --sky and --bounces >= 1 to do anything; with the other light "
+                        "flags one ray per hit chooses among the spheres, the parts and the sky; best with --light-mis): a picture with a small sun "
+                        "converges; prints `sky light rays N, reached M` for the final frame\n"
                         "  --sobol       every random number of the path tracer comes from an Owen-scrambled Sobol sequence instead of the "
                         "independent hash (RWR_FLAG_SOBOL; implies nothing: it does something in frames with --spp > 1, --bounces >= 1, "
                         "--accumulate or --soft-shadows): a pixel's samples are stratified against each other, so that 16 samples "
@@ -384,7 +390,7 @@ int main(int argc, char **argv)
                            (reproject ? (uint32_t)RWR_FLAG_REPROJECT : 0u) | (emitters.empty() ? 0u : (uint32_t)RWR_FLAG_EMISSIVE) |
                            (light_sampling ? (uint32_t)RWR_FLAG_LIGHT_SAMPLING : 0u) | (light_parts ? (uint32_t)RWR_FLAG_LIGHT_PARTS : 0u) |
                            (light_mis ? (uint32_t)RWR_FLAG_LIGHT_MIS : 0u) | (sobol ? (uint32_t)RWR_FLAG_SOBOL : 0u) |
-                           (sky_image.empty() ? 0u : (uint32_t)RWR_FLAG_SKY_IMAGE);
+                           (sky_image.empty() ? 0u : (uint32_t)RWR_FLAG_SKY_IMAGE) | (light_sky ? (uint32_t)RWR_FLAG_LIGHT_SKY : 0u);
     if (show_params) {
         if (reproject)   // (a line of its own, ahead of the line every run prints)
             std::printf("reproject 1 history %u normal %g depth %g\n", reproject_params.max_history, (double)reproject_params.normal_cos_min,
@@ -538,6 +544,11 @@ int main(int argc, char **argv)
             uint64_t rays = 0, reached = 0;
             state.part_light_rays(rays, reached);
             std::printf("part light rays %llu, reached %llu\n", (unsigned long long)rays, (unsigned long long)reached);
+        }
+        if (light_sky) {
+            uint64_t rays = 0, reached = 0;
+            state.sky_light_rays(rays, reached);
+            std::printf("sky light rays %llu, reached %llu\n", (unsigned long long)rays, (unsigned long long)reached);
         }
         if (light_mis) std::printf("weighted hits %llu\n", (unsigned long long)state.light_weighted_hits());
         if (timing) std::printf("%.3f ms/frame over %llu frames (update + render, host wall clock)\n", sec * 1e3 / (double)rendered,

@@ -176,6 +176,13 @@ public:
         rays = reached = 0;
         check(rwr_last_part_light_stats(ctx_, &rays, &reached, &silenced));
     }
+    // extension (RWR_FLAG_LIGHT_SKY): the sky's share of them
+    void sky_light_rays(uint64_t &rays, uint64_t &reached)
+    {
+        uint64_t silenced = 0;
+        rays = reached = 0;
+        check(rwr_last_sky_light_stats(ctx_, &rays, &reached, &silenced));
+    }
     // extension (RWR_FLAG_GLOSSY): the rays the glossy hits of the frame rendered last sent on
     uint64_t glossy_rays()
     {
