@@ -701,7 +701,7 @@ enum {
                                           in both: a new image starts a new history.  Without the bit, rwr_sky_set_image disturbs
                                           neither.  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle passes:
                                           RWR_ERR_UNSUPPORTED. */
-    RWR_FLAG_LIGHT_SKY = 1u << 25      /* extension: light rays aimed at the sky's image — the light ray of an eligible (diffuse) hit may
+    RWR_FLAG_LIGHT_SKY = 1u << 25,     /* extension: light rays aimed at the sky's image — the light ray of an eligible (diffuse) hit may
                                        aim at RWR_FLAG_SKY_IMAGE's map, drawn in proportion to the map's radiance, so that a map with
                                        a small sun converges.  The flag implies nothing.  Off by default; without the flag every frame
                                        is what it was, byte for byte.  All arithmetic f32, no contraction, unless it says double.
@@ -755,10 +755,46 @@ enum {
                                        9. The bit (after item 7) is part of RWR_FLAG_ACCUMULATE's key and of RWR_FLAG_REPROJECT's
                                           effective flags; the image's generation is in both already.  With RWR_FLAG_ORTHO_RAYS,
                                           RWR_FLAG_USE_BVH or single-triangle passes: RWR_ERR_UNSUPPORTED. */
+    RWR_FLAG_TONEMAP = 1u << 26        /* extension: tone mapping and exposure — the frame's rgba8 plane becomes curve(E * colour) instead
+                                       of the mean saturated at 1.0, so that a lamp, the sun of a sky image and the wall beside the
+                                       lamp keep apart.  The third stage behind the resolve, after RWR_FLAG_REPROJECT's and
+                                       RWR_FLAG_DENOISE's; parameters: rwr_tonemap_set_params.  Off by default; without the flag every
+                                       frame is what it was, byte for byte.  All arithmetic f32, in exactly this order, no contraction,
+                                       IEEE division.
+                                       1. The frame path.  A frame with the flag always takes the path integrator and is rendered as if
+                                          RWR_FLAG_AUX_OUTPUTS were set, like RWR_FLAG_DENOISE.  The stage runs last on the frame's
+                                          stream: after either resolve, after the reprojection stage and after the filter.  Its bit is
+                                          part neither of the effective flags nor of RWR_FLAG_ACCUMULATE's or RWR_FLAG_REPROJECT's key,
+                                          and neither are its parameters: changing them between accumulating or reprojecting frames
+                                          restarts nothing.  The histories never see the stage.
+                                       2. The depth, id, t and color_f32 planes, every count and every history are those of the frame
+                                          without the flag, bit for bit: color_f32 stays the linear radiance.
+                                       3. The measure, only with auto_exposure.  A pixel counts when its alpha in color_f32 is not 0.
+                                          For each counted pixel Y = (0.2126f r + 0.7152f g) + 0.0722f b,
+                                          Yc = fminf(fmaxf(Y, 2^-16), 2^16) (a NaN Y gives 2^-16) and L = (int32)bits(Yc) - 0x3f800000:
+                                          the piecewise-linear log2 in units of 2^-23, an exact integer.  log_sum is the sum of L as
+                                          int64, count the number of counted pixels: the same bits in any order.
+                                       4. The exposure.  M = floor(log_sum / count) — floor division, not C's truncation —,
+                                          G = float_from_bits(0x3f800000 + M) and E = (key / G) * exposure.  With count == 0, or
+                                          without auto_exposure, E = exposure.
+                                       5. The map.  For every pixel and each of r, g, b: x = c * E, then
+                                          RWR_TONEMAP_CLAMP     y = x
+                                          RWR_TONEMAP_REINHARD  y = (x * (1.0f + x * iw2)) / (1.0f + x), iw2 = 1.0f / (white * white),
+                                                                computed once on the host
+                                          RWR_TONEMAP_ACES      y = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f)
+                                                                (Narkowicz's fit)
+                                          and the byte is the rgba8 store's rule on y: times 255, saturated to [0, 255], nearest, ties
+                                          to even, NaN gives 0.  The alpha byte is the one the resolve wrote.  Background pixels are 0
+                                          under every curve.  There is no sRGB transfer function in the stage.
+                                       6. rwr_render_rows and rwr_render_strips with a part of the frame: RWR_ERR_UNSUPPORTED (the measure
+                                          is over the whole frame).  With RWR_FLAG_ORTHO_RAYS, RWR_FLAG_USE_BVH or single-triangle
+                                          passes: RWR_ERR_UNSUPPORTED.
+                                       7. rwr_last_tonemap_stats: log_sum, count and E of the frame rendered last; a manual frame gives
+                                          0, 0 and exposure, a frame without the flag 0, 0 and 0. */
 };
 /* every flag above, and the bits between them that the library keeps for itself: a caller sets none of the latter */
 #define RWR_FLAGS_RESERVED (0xfu << 17)
-#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21) | (1u << 22) | (1u << 23) | (1u << 24) | (1u << 25))
+#define RWR_FLAGS_PUBLIC (((1u << 17) - 1u) | (1u << 21) | (1u << 22) | (1u << 23) | (1u << 24) | (1u << 25) | (1u << 26))
 
 #define RWR_MAX_BOUNCES 8u
 
@@ -1147,6 +1183,28 @@ typedef struct rwr_denoise_params {
 } rwr_denoise_params;
 RWR_API int rwr_denoise_set_params(rwr_context *ctx, const rwr_denoise_params *params);
 RWR_API int rwr_denoise_get_params(rwr_context *ctx, rwr_denoise_params *out);
+
+/* RWR_FLAG_TONEMAP: the stage's parameters, per context.  curve: one of RWR_TONEMAP_* (default RWR_TONEMAP_ACES); auto_exposure 0
+ * (default): E = exposure, 1: E = (key / G) * exposure with G, the log-average luminance, measured from the frame on the GPU (the
+ * flag's items 3 and 4); exposure, a linear factor (default 1) and key (default 0.18), each finite and in [2^-16, 2^16]; white,
+ * Reinhard's white point — the input that maps to 1 — (default 4), finite and in [2^-8, 2^16].  Anything else, NaN included,
+ * curve > 2 or auto_exposure > 1: RWR_ERR_INVALID_ARGUMENT, and the parameters stay as they were.  params = NULL restores the
+ * defaults.  Host-side, waits for nothing; frames rendered after the call use the new values.  An accumulation and a reprojection
+ * history go on.
+ * rwr_last_tonemap_stats: the measure's log_sum and count and the exposure E of the frame rendered last (the flag's item 7; E is
+ * computed on the host from the two sums, by the function the GPU uses).  Waits for the frame, as rwr_last_render_stats does. */
+enum { RWR_TONEMAP_CLAMP = 0, RWR_TONEMAP_REINHARD = 1, RWR_TONEMAP_ACES = 2 };
+typedef struct rwr_tonemap_params {
+    uint32_t curve;
+    uint32_t auto_exposure;
+    float exposure;
+    float key;
+    float white;
+} rwr_tonemap_params;        /* 20 bytes */
+#define RWR_TONEMAP_DEFAULTS {RWR_TONEMAP_ACES, 0u, 1.0f, 0.18f, 4.0f}   /* an initialiser of rwr_tonemap_params: what NULL restores */
+RWR_API int rwr_tonemap_set_params(rwr_context *ctx, const rwr_tonemap_params *params);
+RWR_API int rwr_tonemap_get_params(rwr_context *ctx, rwr_tonemap_params *out);
+RWR_API int rwr_last_tonemap_stats(rwr_context *ctx, int64_t *log_sum, uint32_t *count, float *exposure);
 
 /* RWR_FLAG_SKY: the sky's two colours, per context.  In S(D) at the flag u is 1 straight up, 1/2 along the geometric horizon and 0
  * straight down: `zenith` is the radiance at u = 1, `horizon` the radiance at u = 0, the mean of the two along the horizon.

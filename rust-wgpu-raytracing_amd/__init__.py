@@ -62,7 +62,10 @@ FLAG_LIGHT_MIS = 1 << 22       # the light ray and the diffuse bounce ray are co
 FLAG_SOBOL = 1 << 23           # every random number of the path tracer comes from an Owen-scrambled Sobol sequence instead of the hash (include/rwr_hip.h)
 FLAG_LIGHT_SKY = 1 << 25       # the light ray of a diffuse hit may aim at FLAG_SKY_IMAGE's map, drawn in proportion to its radiance (include/rwr_hip.h)
 FLAG_SKY_IMAGE = 1 << 24       # FLAG_SKY's radiance comes from the context's octahedral environment map (sky_set_image) instead of the gradient (include/rwr_hip.h)
-SKY_IMAGE_SIZE_MAX, SKY_IMAGE_COMPONENT_MAX = 2048, 64.0   # RWR_SKY_IMAGE_SIZE_MAX, RWR_SKY_IMAGE_COMPONENT_MAX
+FLAG_TONEMAP = 1 << 26         # exposure and a tone curve over the frame's rgba8 plane, the last stage behind the resolve; implies FLAG_AUX_OUTPUTS (include/rwr_hip.h)
+TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2   # RWR_TONEMAP_*
+TONEMAP_PARAMS_DTYPE = np.dtype([("curve", "<u4"), ("auto_exposure", "<u4"), ("exposure", "<f4"), ("key", "<f4"), ("white", "<f4")])
+SKY_IMAGE_SIZE_MAX, SKY_IMAGE_COMPONENT_MAX = 2048, 64.0  # RWR_SKY_IMAGE_SIZE_MAX, RWR_SKY_IMAGE_COMPONENT_MAX
 MAX_EMISSION = 64.0         # RWR_MAX_EMISSION: the largest component of a radiance
 SHADOW_PARAMS_DTYPE = np.dtype([("mesh_light_radius", "<f4"), ("sphere_light_radius", "<f4")])
 REPROJECT_PARAMS_DTYPE = np.dtype([("max_history", "<u4"), ("normal_cos_min", "<f4"), ("depth_rel", "<f4")])
@@ -134,6 +137,7 @@ def lib() -> C.CDLL:
         "rwr_last_traversal_plan": [vp, vp, vp],
         "rwr_accum_reset": [vp], "rwr_accum_samples": [vp, vp],
         "rwr_denoise_set_params": [vp, vp], "rwr_denoise_get_params": [vp, vp],
+        "rwr_tonemap_set_params": [vp, vp], "rwr_tonemap_get_params": [vp, vp], "rwr_last_tonemap_stats": [vp, vp, vp, vp],
         "rwr_sky_set_params": [vp, vp], "rwr_sky_get_params": [vp, vp],
         "rwr_sky_set_image": [vp, vp, u32], "rwr_sky_get_image_info": [vp, vp, vp],
         "rwr_sky_image_from_equirect": [vp, u32, u32, f32, u32, vp], "rwr_selftest_sky_image": [vp, vp, C.c_size_t, vp],
@@ -179,7 +183,8 @@ def lib() -> C.CDLL:
                            "rwr_shadow_set_params", "rwr_shadow_get_params", "rwr_scene_set_part_emission", "rwr_scene_set_sphere_emission",
                            "rwr_scene_get_part_emission", "rwr_scene_get_sphere_emission", "rwr_last_emission_stats", "rwr_last_light_stats", "rwr_last_part_light_stats",
                            "rwr_selftest_sobol", "rwr_sky_set_image", "rwr_sky_get_image_info", "rwr_sky_image_from_equirect", "rwr_selftest_sky_image",
-                           "rwr_sky_get_light_info", "rwr_last_sky_light_stats", "rwr_selftest_sky_light")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
+                           "rwr_sky_get_light_info", "rwr_last_sky_light_stats", "rwr_selftest_sky_light",
+                           "rwr_tonemap_set_params", "rwr_tonemap_get_params", "rwr_last_tonemap_stats")   # what a library named by RWR_HIP_LIB may lack; any other gap is an error
     for name, argtypes in sigs.items():
         fn = getattr(L, name, None)
         if fn is None and name in _NEWER_ENTRY_POINTS and os.environ.get("RWR_HIP_LIB"):
@@ -927,6 +932,31 @@ class Context:
         _check(lib().rwr_denoise_get_params(self._h, _p(p)))
         return {"iterations": int(p["iterations"][0]), "sigma_color": float(p["sigma_color"][0]),
                 "normal_cos_min": float(p["normal_cos_min"][0]), "depth_rel": float(p["depth_rel"][0])}
+
+    def set_tonemap_params(self, curve=None, auto_exposure=None, exposure=None, key=None, white=None):
+        """The FLAG_TONEMAP stage's parameters (rwr_tonemap_set_params); an argument left out keeps its value, no argument at all
+        restores the defaults.  Out of range or NaN: RwrError(ERR_INVALID_ARGUMENT), and the parameters stay.  No history restarts."""
+        given = {"curve": curve, "auto_exposure": auto_exposure, "exposure": exposure, "key": key, "white": white}
+        if all(v is None for v in given.values()):
+            _check(lib().rwr_tonemap_set_params(self._h, None))
+            return
+        p = np.zeros(1, dtype=TONEMAP_PARAMS_DTYPE)
+        for k, v in self.tonemap_params().items():
+            p[k] = v if given[k] is None else given[k]
+        _check(lib().rwr_tonemap_set_params(self._h, _p(p)))
+
+    def tonemap_params(self) -> dict:
+        p = np.zeros(1, dtype=TONEMAP_PARAMS_DTYPE)
+        _check(lib().rwr_tonemap_get_params(self._h, _p(p)))
+        return {"curve": int(p["curve"][0]), "auto_exposure": int(p["auto_exposure"][0]), "exposure": float(p["exposure"][0]),
+                "key": float(p["key"][0]), "white": float(p["white"][0])}
+
+    def last_tonemap_stats(self) -> tuple[int, int, float]:
+        """(log_sum, count, exposure) of the last render call (rwr_last_tonemap_stats): the measure's two sums and the frame's E as a
+        float32 value; (0, 0, exposure) for a manual frame, (0, 0, 0.0) for a frame without the flag.  Waits for the frame."""
+        a, b, e = C.c_int64(0), C.c_uint32(0), C.c_float(0.0)
+        _check(lib().rwr_last_tonemap_stats(self._h, C.byref(a), C.byref(b), C.byref(e)))
+        return int(a.value), int(b.value), float(e.value)
 
     def set_reproject_params(self, max_history=None, normal_cos_min=None, depth_rel=None):
         """The FLAG_REPROJECT stage's parameters (rwr_reproject_set_params); an argument left out keeps its value, no argument at all

@@ -15,6 +15,7 @@
 
 #include "rwr_context.h"
 #include "rwr_sky_light.h"
+#include "rwr_tonemap.h"
 
 namespace rwr {
 
@@ -562,6 +563,50 @@ int rwr_denoise_get_params(rwr_context *ctx, rwr_denoise_params *out)
 {
     if (!ctx || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
     *out = ctx->denoise;
+    return RWR_OK;
+}
+
+// RWR_FLAG_TONEMAP: no history holds these — an accumulation and a reprojection history go on across a call
+int rwr_tonemap_set_params(rwr_context *ctx, const rwr_tonemap_params *params)
+{
+    if (!ctx) return set_error(RWR_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (!params) {
+        ctx->tonemap = kTonemapDefaults;
+        return RWR_OK;
+    }
+    const rwr_tonemap_params p = *params;
+    const float lo = 1.0f / 65536.0f, hi = 65536.0f;
+    auto within = [](float v, float a, float b) { return v >= a && v <= b; };   // (false for NaN)
+    if (p.curve > (uint32_t)RWR_TONEMAP_ACES) return set_error(RWR_ERR_INVALID_ARGUMENT, "tonemap curve %u: 0 (clamp), 1 (Reinhard), 2 (ACES)", p.curve);
+    if (p.auto_exposure > 1u) return set_error(RWR_ERR_INVALID_ARGUMENT, "tonemap auto_exposure %u: 0 or 1", p.auto_exposure);
+    if (!within(p.exposure, lo, hi)) return set_error(RWR_ERR_INVALID_ARGUMENT, "tonemap exposure %g: finite, 2^-16 ... 2^16", (double)p.exposure);
+    if (!within(p.key, lo, hi)) return set_error(RWR_ERR_INVALID_ARGUMENT, "tonemap key %g: finite, 2^-16 ... 2^16", (double)p.key);
+    if (!within(p.white, 1.0f / 256.0f, hi)) return set_error(RWR_ERR_INVALID_ARGUMENT, "tonemap white %g: finite, 2^-8 ... 2^16", (double)p.white);
+    ctx->tonemap = p;
+    return RWR_OK;
+}
+
+int rwr_tonemap_get_params(rwr_context *ctx, rwr_tonemap_params *out)
+{
+    if (!ctx || !out) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = ctx->tonemap;
+    return RWR_OK;
+}
+
+// the last frame's sums from its slot's record; E on the host, by the function k_tm_exposure calls
+int rwr_last_tonemap_stats(rwr_context *ctx, int64_t *log_sum, uint32_t *count, float *exposure)
+{
+    if (!ctx || !log_sum || !count || !exposure) return set_error(RWR_ERR_INVALID_ARGUMENT, "NULL argument");
+    TonemapRecord rec{0, 0u, 0.0f};
+    const rwr_tonemap_params &tp = ctx->last_tonemap_params;
+    if (ctx->last_tonemap && tp.auto_exposure && ctx->slots[ctx->cur].d_tm_record.ptr) {
+        DeviceGuard g(ctx->device);
+        RWR_HIP_CHECK(hipStreamSynchronize(ctx->slots[ctx->cur].stream));
+        RWR_HIP_CHECK(hipMemcpy(&rec, ctx->slots[ctx->cur].d_tm_record.ptr, sizeof rec, hipMemcpyDeviceToHost));
+    }
+    *log_sum = rec.log_sum;
+    *count = rec.count;
+    *exposure = ctx->last_tonemap ? tonemap_exposure(rec.log_sum, rec.count, tp.auto_exposure, tp.key, tp.exposure) : 0.0f;
     return RWR_OK;
 }
 

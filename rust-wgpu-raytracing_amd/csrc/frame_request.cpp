@@ -13,7 +13,7 @@ namespace {
 // id / t planes, so RWR_FLAG_AUX_OUTPUTS is implied, and its own bit is not part of rp.flags from there on (nor of a history's key).
 // mode: a surface flag switches on the surfaces of its model (surface_mode's bit).
 struct FlagRule { uint32_t flag; const char *name, *stage, *why; uint32_t mode; };
-constexpr FlagRule kFlagRules[16] = {
+constexpr FlagRule kFlagRules[17] = {
     {RWR_FLAG_ACCUMULATE, "RWR_FLAG_ACCUMULATE", nullptr, nullptr, 0u},
     {RWR_FLAG_SHADOWS, "RWR_FLAG_SHADOWS", nullptr, nullptr, 0u},
     {RWR_FLAG_DENOISE, "RWR_FLAG_DENOISE", "filter", "its taps reach 62 pixels", 0u},
@@ -29,7 +29,8 @@ constexpr FlagRule kFlagRules[16] = {
     {RWR_FLAG_LIGHT_MIS, "RWR_FLAG_LIGHT_MIS", nullptr, nullptr, 0u},
     {RWR_FLAG_SOBOL, "RWR_FLAG_SOBOL", nullptr, nullptr, 0u},
     {RWR_FLAG_SKY_IMAGE, "RWR_FLAG_SKY_IMAGE", nullptr, nullptr, 0u},
-    {RWR_FLAG_LIGHT_SKY, "RWR_FLAG_LIGHT_SKY", nullptr, nullptr, 0u}};
+    {RWR_FLAG_LIGHT_SKY, "RWR_FLAG_LIGHT_SKY", nullptr, nullptr, 0u},
+    {RWR_FLAG_TONEMAP, "RWR_FLAG_TONEMAP", "stage", "the exposure is measured over all of it", 0u}};
 constexpr uint32_t kSurfaceFlags = RWR_FLAG_MIRRORS | RWR_FLAG_GLASS | RWR_FLAG_GLOSSY;
 
 // What an accumulating frame must share with the frame before for the accumulation to go on (rwr_hip.h RWR_FLAG_ACCUMULATE): the
@@ -53,7 +54,7 @@ std::vector<unsigned char> accum_key_of(const rwr_context *ctx, const rwr_camera
 }
 
 // What a reprojecting frame must share with the one before for the history to go on (rwr_hip.h RWR_FLAG_REPROJECT item 2): the
-// screen, spp, bounces, seed, the effective flags (the DENOISE and REPROJECT bits are not among them), frames in flight, the scene,
+// screen, spp, bounces, seed, the effective flags (the DENOISE, REPROJECT and TONEMAP bits are not among them), frames in flight, the scene,
 // the stage's parameters and, while the sky lights the frame, the sky's, while the lights have a size, theirs.  NOT the camera.
 std::vector<unsigned char> reproject_key_of(const rwr_context *ctx, const FrameRequest &rq)
 {
@@ -150,11 +151,12 @@ int validate(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const rwr_r
     auto has = [](uint32_t flags, uint32_t flag) { return (flags & flag) != 0; };
     rq = FrameRequest{rp, row_begin, row_end, row_pitch, has(rp.flags, RWR_FLAG_AUX_OUTPUTS), has(asked, RWR_FLAG_ACCUMULATE), has(asked, RWR_FLAG_SHADOWS),
                       has(asked, RWR_FLAG_DENOISE), has(asked, RWR_FLAG_REPROJECT), has(rp.flags, RWR_FLAG_MIRRORS), has(rp.flags, RWR_FLAG_GLASS),
-                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), has(rp.flags, RWR_FLAG_EMISSIVE), has(rp.flags, RWR_FLAG_LIGHT_SAMPLING), has(rp.flags, RWR_FLAG_LIGHT_PARTS), has(rp.flags, RWR_FLAG_LIGHT_MIS), false, false, false, false, false};
+                      has(rp.flags, RWR_FLAG_GLOSSY), has(rp.flags, RWR_FLAG_SKY), has(rp.flags, RWR_FLAG_SOFT_SHADOWS), has(rp.flags, RWR_FLAG_EMISSIVE), has(rp.flags, RWR_FLAG_LIGHT_SAMPLING), has(rp.flags, RWR_FLAG_LIGHT_PARTS), has(rp.flags, RWR_FLAG_LIGHT_MIS), false, false, false, false, false,
+                      has(asked, RWR_FLAG_TONEMAP)};
     // an accumulating frame always takes the wavefront integrator (its samples are jittered even at spp 1), and so does a frame
     // with shadow rays (the integrator's stages trace them), one the filter follows (it runs behind the integrator's resolve) or one
-    // with an emitter (the integrator's kernels add its light)
-    rq.wavefront = rp.spp != 1 || rp.max_bounces != 0 || rq.accumulate || rq.shadows || rq.denoise || rq.reproject || rq.glow;
+    // with an emitter (the integrator's kernels add its light), and one the tone-mapping stage follows (as the filter)
+    rq.wavefront = rp.spp != 1 || rp.max_bounces != 0 || rq.accumulate || rq.shadows || rq.denoise || rq.reproject || rq.glow || rq.tonemap;
     // The sample sequence changes the integrator's random numbers and nothing else: it sends no frame there, and a frame of the
     // reference's kernels draws none (rq.rp.flags is what the histories' keys and the kernels see)
     rq.sky_image = has(rp.flags, RWR_FLAG_SKY_IMAGE);

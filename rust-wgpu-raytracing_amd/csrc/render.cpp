@@ -82,6 +82,8 @@ int render_frame(rwr_context *ctx, const rwr_camera_inv_uniform *camera, const r
     ctx->last_gloss = rq.wavefront && rq.gloss && ap.trace_spp != 0u;
     ctx->last_glow = rq.wavefront && rq.glow && ap.trace_spp != 0u;
     ctx->last_light = rq.wavefront && (rq.light || rq.light_parts || rq.light_sky) && ap.trace_spp != 0u;
+    ctx->last_tonemap = rq.tonemap;
+    if (rq.tonemap) ctx->last_tonemap_params = ctx->tonemap;
     ctx->last_bounce = 0;  // filled in lazily by rwr_last_render_stats from the pass counters
     return RWR_OK;
 }

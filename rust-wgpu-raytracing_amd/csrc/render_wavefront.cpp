@@ -51,6 +51,7 @@ struct WfFrame {
     int resolve(AccumPlan &ap);
     int reproject_stage(ReprojectPlan &pp);
     int denoise_stage();
+    int tonemap_stage();
 };
 
 // The frame's sums, queues, streams, events and pinned words; the refusal of a frame whose queues cannot be held.
@@ -419,6 +420,16 @@ int WfFrame::denoise_stage()
     return RWR_OK;
 }
 
+// RWR_FLAG_TONEMAP: the last stage on the slot's stream, behind either resolve, the reprojection stage and the filter (and behind the
+// events the next accumulating resolve and the next reprojection stage wait for: the histories never see it).  It rewrites the
+// frame's rgba8 plane from its colour_f32 plane; the record is the slot's, zeroed on the stream — the host waits for nothing.
+int WfFrame::tonemap_stage()
+{
+    RWR_HIP_CHECK(sl.d_tm_record.ensure(1));
+    RWR_HIP_CHECK(launch_wf_tonemap(stream, fp.width, fp.height, tg, ctx->tonemap, sl.d_tm_record.ptr));
+    return RWR_OK;
+}
+
 }  // namespace
 
 // A frame of the wavefront integrator: the samples are traced in launch groups; per group the primary stage (all of the
@@ -441,6 +452,7 @@ int enqueue_wavefront(rwr_context *ctx, FrameSlot &sl, const FrameRequest &rq, A
     if ((rc = F.trace_groups(ap)) != RWR_OK || (rc = F.resolve(ap)) != RWR_OK) return rc;
     if (rq.reproject && (rc = F.reproject_stage(pp)) != RWR_OK) return rc;
     if (rq.denoise && (rc = F.denoise_stage()) != RWR_OK) return rc;
+    if (rq.tonemap && (rc = F.tonemap_stage()) != RWR_OK) return rc;
     ctx->last_segments = F.n_tiles;
     ctx->last_trace_plan = F.trace_plan;
     ctx->last_shadow_plan = F.shadow_plan;

@@ -89,6 +89,9 @@ struct FrameSlot {
     // RWR_FLAG_DENOISE, allocated by the slot's first denoised frame: the guide records and the two colour planes the iterations
     // alternate between (kernels_wf_denoise.hip)
     DeviceBuffer<float4> d_dn_guide, d_dn_a, d_dn_b;
+    // RWR_FLAG_TONEMAP, allocated by the slot's first tone-mapped frame: the measure's sums and the exposure (kernels_wf_tonemap.hip),
+    // zeroed on the stream by every frame that measures
+    DeviceBuffer<TonemapRecord> d_tm_record;
     // RWR_FRAME_GRAPH (A/B knob): the reference frame's two launches (k_frame_setup -> k_primary_p2) as a
     // hipGraph of this slot — replayed as it is while camera and parameters stay the same, updated in place when they change
     OwnedGraphExec frame_graph;
@@ -122,6 +125,7 @@ struct FrameSlot {
 constexpr uint32_t kMaxFramesInFlight = 3;
 constexpr rwr_denoise_params kDenoiseDefaults{5u, 0.04f, 0.95f, 0.05f};   // RWR_FLAG_DENOISE: DESIGN.md §6 says why these
 constexpr rwr_reproject_params kReprojectDefaults{32u, 0.95f, 0.05f};   // RWR_FLAG_REPROJECT: the tap tests are the denoiser's
+constexpr rwr_tonemap_params kTonemapDefaults = RWR_TONEMAP_DEFAULTS;   // RWR_FLAG_TONEMAP
 constexpr rwr_sky_params kSkyDefaults = RWR_SKY_DEFAULTS;   // RWR_FLAG_SKY
 constexpr rwr_shadow_params kShadowDefaults = RWR_SHADOW_DEFAULTS;   // RWR_FLAG_SOFT_SHADOWS
 constexpr uint32_t kWfMaxQueues = 4;
@@ -317,6 +321,9 @@ struct rwr_context {
     uint64_t last_reproject_frames = 0;    // rwr_reproject_frames: of the frame rendered last, 0 when it did not reproject
     uint32_t last_reproject_set = 0;       // ... and the history set it wrote (rwr_reproject_readback, rwr_last_reproject_stats)
     rwr_denoise_params denoise = rwr::kDenoiseDefaults;   // RWR_FLAG_DENOISE (rwr_denoise_set_params)
+    rwr_tonemap_params tonemap = rwr::kTonemapDefaults;   // RWR_FLAG_TONEMAP (rwr_tonemap_set_params)
+    bool last_tonemap = false;                            // the last render call ran the stage, with these parameters (rwr_last_tonemap_stats;
+    rwr_tonemap_params last_tonemap_params = rwr::kTonemapDefaults;   // its record is its slot's d_tm_record)
     rwr_sky_params sky = rwr::kSkyDefaults;               // RWR_FLAG_SKY (rwr_sky_set_params)
     // RWR_FLAG_SKY_IMAGE (rwr_sky_set_image): the octahedral map, n x n float4 texels (null: none), and its generation.  A call makes a
     // new buffer; a frame slot holds on to the one its frame was enqueued with (WfState::sky_image), so nothing waits for a frame.

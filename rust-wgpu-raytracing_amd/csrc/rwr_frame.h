@@ -27,6 +27,7 @@ struct FrameRequest {
     bool sobol;       // RWR_FLAG_SOBOL in a frame the wavefront integrator renders: its kernels read the bit in FrameParams::flags, beside the seed (else the bit is cleared from rp.flags)
     bool wavefront;   // the wavefront integrator renders it (several samples, a bounce, or an accumulation)
     bool dormant;     // the reference's dormant parts (single-triangle passes, orthographic rays) have their own plain kernel
+    bool tonemap;     // RWR_FLAG_TONEMAP: the tone-mapping stage runs last, behind the filter (AUX implied, this bit cleared)
 };
 
 // Progressive accumulation: what this frame does with the context's history.

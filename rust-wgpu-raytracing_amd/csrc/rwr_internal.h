@@ -528,6 +528,18 @@ hipError_t launch_wf_reproject(hipStream_t s, uint32_t width, uint32_t height, c
                                const rwr_camera_inv_uniform &cam, const RpCamera *prev, const rwr_reproject_params &rp,
                                const RpHistory &from, const RpHistory &to, unsigned long long *counts);
 
+// RWR_FLAG_TONEMAP (kernels_wf_tonemap.hip).  The frame slot's record: the measure's two sums, added atomically, and the exposure
+// k_tm_exposure makes of them (rwr_tonemap.h tonemap_exposure).
+struct TonemapRecord {
+    long long log_sum;
+    uint32_t count;
+    float exposure;
+};
+static_assert(sizeof(TonemapRecord) == 16, "the slot's record is 16 bytes");
+// The stage, behind everything else of the frame: tg holds the frame with its colour_f32 plane, whose rgba8 plane it rewrites.  rec
+// is zeroed here, on the stream, and used with tp.auto_exposure alone (manual mode: one launch, E = tp.exposure).
+hipError_t launch_wf_tonemap(hipStream_t s, uint32_t width, uint32_t height, const Targets &tg, const rwr_tonemap_params &tp, TonemapRecord *rec);
+
 // per-frame records and tables (kernels_primary.hip): FrameTri + tnum per face, ray tables per column pair / row
 struct FrameSetupOut {
     FrameTri *ftris;   // n_tris

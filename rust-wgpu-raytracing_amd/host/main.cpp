@@ -8,7 +8,8 @@
 //              [--mirror-part N[:r,g,b]]... [--mirror-sphere N[:r,g,b]]... [--glass-part N[:ior[:r,g,b]]]...
 //              [--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... [--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]]
 //              [--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] [--sobol]
-//              [--sky-image FILE[:scale] [--sky-image-size N]] [--light-sky] [--show-params] [--out frame.png] [--time]
+//              [--sky-image FILE[:scale] [--sky-image-size N]] [--light-sky]
+//              [--tonemap [clamp|reinhard|aces]] [--exposure STOPS] [--auto-exposure [KEY]] [--white W] [--show-params] [--out frame.png] [--time]
 //
 // --keys: comma separated KEY*COUNT; each entry holds KEY down for COUNT frames
 // (KEY in W A S D Up Down Left Right Space LShift, or '-' for no key).  After the script,
@@ -182,10 +183,19 @@ int main(int argc, char **argv)
     uint32_t sky_image_size = 256u;
     struct Resize { uint64_t frame; uint32_t w, h; };
     std::vector<Resize> resizes;
+    // --tonemap [CURVE], --exposure STOPS, --auto-exposure [KEY], --white W: RWR_FLAG_TONEMAP and its parameters (the library's defaults)
+    bool tonemap = false;
+    rwr_tonemap_params tonemap_params = RWR_TONEMAP_DEFAULTS;
+    const char *const curve_names[3] = {"clamp", "reinhard", "aces"};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
             if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); }
+            return argv[++i];
+        };
+        // the value of an option that may stand without one: the next argument unless it is an option itself (null: none)
+        auto next_optional = [&]() -> const char * {
+            if (i + 1 >= argc || std::strncmp(argv[i + 1], "--", 2) == 0) return nullptr;
             return argv[++i];
         };
         if (a == "--res") res = next();
@@ -216,6 +226,36 @@ int main(int argc, char **argv)
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-iterations") { denoise = true; denoise_iterations = std::atoi(next()); }
         else if (a == "--denoise-sigma") { denoise = true; denoise_sigma = (float)std::atof(next()); }
+        else if (a == "--tonemap") {
+            tonemap = true;
+            if (const char *v = next_optional()) {
+                uint32_t c = 0;
+                while (c < 3u && std::strcmp(v, curve_names[c]) != 0) c++;
+                if (c == 3u) { std::fprintf(stderr, "--tonemap [clamp|reinhard|aces]: '%s' is none of them\n", v); return 2; }
+                tonemap_params.curve = c;
+            }
+        }
+        else if (a == "--exposure") {   // stops: the factor is 2^STOPS, computed in double
+            double v = 0.0;
+            if (!parse_number(next(), v) || v < -16.0 || v > 16.0) { std::fprintf(stderr, "--exposure STOPS: a number in [-16, 16]\n"); return 2; }
+            tonemap_params.exposure = (float)std::exp2(v);
+            tonemap = true;
+        }
+        else if (a == "--auto-exposure") {
+            tonemap = true;
+            tonemap_params.auto_exposure = 1u;
+            if (const char *text = next_optional()) {
+                double v = 0.0;
+                if (!parse_number(text, v) || v < 1.0 / 65536.0 || v > 65536.0) { std::fprintf(stderr, "--auto-exposure [KEY]: a number in [2^-16, 2^16]\n"); return 2; }
+                tonemap_params.key = (float)v;
+            }
+        }
+        else if (a == "--white") {
+            double v = 0.0;
+            if (!parse_number(next(), v) || v < 1.0 / 256.0 || v > 65536.0) { std::fprintf(stderr, "--white W: a number in [2^-8, 2^16]\n"); return 2; }
+            tonemap_params.white = (float)v;
+            tonemap = true;
+        }
         else if (a == "--reproject") reproject = true;
         else if (a == "--reproject-history" || a == "--reproject-normal" || a == "--reproject-depth") {
             double v = 0.0;
@@ -322,6 +362,7 @@ int main(int argc, char **argv)
                         "[--glass-sphere N[:ior[:r,g,b]]]... [--gloss-part N:rough[:r,g,b]]... [--gloss-sphere N:rough[:r,g,b]]... "
                         "[--emissive-part N:r,g,b]... [--emissive-sphere N:r,g,b]... [--light-sampling] [--light-parts] [--light-mis] [--sobol] [--sky-image FILE[:scale] [--sky-image-size N]] [--light-sky] "
                         "[--reproject [--reproject-history N] [--reproject-normal C] [--reproject-depth X]] "
+                        "[--tonemap [clamp|reinhard|aces]] [--exposure STOPS] [--auto-exposure [KEY]] [--white W] "
                         "[--show-params] [--out frame.png] [--time]\n"
                         "  --accumulate  every frame adds its samples to those of the frames before while nothing changes "
                         "(RWR_FLAG_ACCUMULATE); prints `samples N` for the final frame\n"
@@ -376,6 +417,12 @@ int main(int argc, char **argv)
                         "last frame, while the camera moves (RWR_FLAG_REPROJECT; with --keys every key step's frame feeds the next one's history): "
                         "at most N frames of history per pixel (1-1024), taps of faces whose normals' cosine is at least C and whose distance "
                         "differs by at most X of itself (rwr_reproject_set_params); a value implies --reproject; prints `history K` for the final frame\n"
+                        "  --tonemap [clamp|reinhard|aces]  the picture is curve(exposure x radiance) instead of the radiance cut off at 1, so that a "
+                        "lamp and the wall beside it keep apart (RWR_FLAG_TONEMAP; aces when left out; rwr_tonemap_set_params).  --exposure STOPS: "
+                        "the factor 2^STOPS, STOPS in [-16, 16]; --auto-exposure [KEY]: the exposure that brings the frame's log-average luminance, "
+                        "measured on the GPU, to KEY (0.18 when left out), times --exposure's factor; --white W: the radiance Reinhard's curve maps "
+                        "to 1 (4 when left out).  Each of the three implies --tonemap; prints `exposure E (log-average G over N pixels)` for the "
+                        "final frame\n"
                         "  --show-params prints the render parameters the arguments give and exits, without a device\n");
             return 0;
         } else {
@@ -390,8 +437,12 @@ int main(int argc, char **argv)
                            (reproject ? (uint32_t)RWR_FLAG_REPROJECT : 0u) | (emitters.empty() ? 0u : (uint32_t)RWR_FLAG_EMISSIVE) |
                            (light_sampling ? (uint32_t)RWR_FLAG_LIGHT_SAMPLING : 0u) | (light_parts ? (uint32_t)RWR_FLAG_LIGHT_PARTS : 0u) |
                            (light_mis ? (uint32_t)RWR_FLAG_LIGHT_MIS : 0u) | (sobol ? (uint32_t)RWR_FLAG_SOBOL : 0u) |
-                           (sky_image.empty() ? 0u : (uint32_t)RWR_FLAG_SKY_IMAGE) | (light_sky ? (uint32_t)RWR_FLAG_LIGHT_SKY : 0u);
+                           (sky_image.empty() ? 0u : (uint32_t)RWR_FLAG_SKY_IMAGE) | (light_sky ? (uint32_t)RWR_FLAG_LIGHT_SKY : 0u) |
+                           (tonemap ? (uint32_t)RWR_FLAG_TONEMAP : 0u);
     if (show_params) {
+        if (tonemap)   // (a line of its own, ahead of the line every run prints)
+            std::printf("tonemap 1 curve %s auto-exposure %u exposure %g key %g white %g\n", curve_names[tonemap_params.curve], tonemap_params.auto_exposure,
+                        (double)tonemap_params.exposure, (double)tonemap_params.key, (double)tonemap_params.white);
         if (reproject)   // (a line of its own, ahead of the line every run prints)
             std::printf("reproject 1 history %u normal %g depth %g\n", reproject_params.max_history, (double)reproject_params.normal_cos_min,
                         (double)reproject_params.depth_rel);
@@ -510,6 +561,9 @@ int main(int argc, char **argv)
         if (reproject_set) {
             if (rwr_reproject_set_params(state.context(), &reproject_params) != RWR_OK) { std::fprintf(stderr, "--reproject: %s\n", rwr_last_error_string()); return 2; }
         }
+        if (tonemap) {
+            if (rwr_tonemap_set_params(state.context(), &tonemap_params) != RWR_OK) { std::fprintf(stderr, "--tonemap: %s\n", rwr_last_error_string()); return 2; }
+        }
         uint64_t rendered = 0;
         const auto t0 = std::chrono::steady_clock::now();
         auto frame = [&]() {  // [Resized: resize()] then RedrawRequested: update() then render() (lib.rs:1323-1337)
@@ -549,6 +603,19 @@ int main(int argc, char **argv)
             uint64_t rays = 0, reached = 0;
             state.sky_light_rays(rays, reached);
             std::printf("sky light rays %llu, reached %llu\n", (unsigned long long)rays, (unsigned long long)reached);
+        }
+        if (tonemap) {   // G from the two sums as the flag's item 4 has it; a manual frame measured nothing
+            int64_t log_sum = 0;
+            uint32_t counted = 0;
+            float E = 0.0f, G = 0.0f;
+            check(rwr_last_tonemap_stats(state.context(), &log_sum, &counted, &E));
+            if (counted) {
+                int64_t m = log_sum / (int64_t)counted;
+                if (log_sum % (int64_t)counted != 0 && log_sum < 0) m -= 1;
+                const int32_t bits = 0x3f800000 + (int32_t)m;
+                std::memcpy(&G, &bits, sizeof G);
+            }
+            std::printf("exposure %g (log-average %g over %u pixels)\n", (double)E, (double)G, counted);
         }
         if (light_mis) std::printf("weighted hits %llu\n", (unsigned long long)state.light_weighted_hits());
         if (timing) std::printf("%.3f ms/frame over %llu frames (update + render, host wall clock)\n", sec * 1e3 / (double)rendered,
